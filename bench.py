@@ -11,6 +11,7 @@ in HBM before the timed region.
     python bench.py --gpus N --steps K --warmup W          # spawns its own N ranks (fresh processes, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + DIR/*.npy: what the last timed step computed
 
 Rank 0 prints ONE JSON line.  ``roofline`` covers the dominant kernels (the
 MFMA implicit-GEMM conv family: forward, dgrad, wgrad): algorithmic conv FLOPs
@@ -102,6 +103,23 @@ def measure_train(yolo, strategy, inputs, steps, warmup, barrier):
         loss = yolo.dist_train_step(strategy, inputs)
     barrier()
     return time.perf_counter() - t0, loss
+
+
+DUMP_SAMPLE = 1 << 22      # --dump-outputs: entries of the 61.8 M-float weight / gradient arenas written (16 MB per array)
+
+
+def dump_outputs(out_dir, yolo, loss):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float32 .npy files (about 34 MB in all): the loss
+    train_step returns, its four parts (the metric updates), the BN moving statistics, and the updated weights and the step's
+    gradients at a fixed, seeded sample of arena positions (the sample depends on the arena size only, so two builds of the
+    project line up entry for entry).  Called after the timed region, before any further step changes the state."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(yolo.arena_floats, min(DUMP_SAMPLE, yolo.arena_floats), replace=False))
+    arrays = {'loss': loss, 'loss_parts': yolo._plan(BATCH, True).loss4, 'moving_stats': yolo.moving,
+              'weights_sample': yolo.params, 'grads_sample': yolo.grads}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, name + '.npy'), a[idx] if name.endswith('_sample') else a)
 
 
 def conv_family_roofline(yolo, plan, busy_s):
@@ -302,7 +320,10 @@ def main():
     ap.add_argument('--check-replicas', action='store_true', help='after the run, verify that every rank holds identical weights')
     ap.add_argument('--transport', default='torch', choices=['torch', 'native'], help="gradient all-reduce through torch.distributed (default) or RCCL called directly through the C ABI (y3_comm_*)")
     ap.add_argument('--force-collective', action='store_true', help='(rehearsal) with one rank: initialise the process group anyway and all-reduce every bucket')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last one computed (loss, weights, gradients: dump_outputs) as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.tiled_only:
         torch.cuda.set_device(0)
         print(json.dumps(tiled_4k(True)), flush=True)
@@ -366,6 +387,8 @@ def main():
         torch.cuda.synchronize()
 
     dt, loss = measure_train(yolo, strategy, inputs, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, yolo, loss)
     # host cost of one step: queue drained first, so that the figure is launch work and not back-pressure from a full queue
     # (outside the timed region; tools/host_profile.py: ~3.1 ms, i.e. the host could feed a step six times as fast)
     t1 = time.perf_counter()
