@@ -374,6 +374,50 @@ int y3_tile_gather_zscore_nhwc(const void* img, int dtype, int height, int width
                                int ntiles, int tile_h, int tile_w, float* out, int channel_pitch, void* workspace,
                                y3_stream_t stream);
 
+/* ---- training augmentation on the device: augment.py:30-125, 275-297 at the severities of imagereader.py:369-391 ----------
+ * The random decisions of augment_image_box_pair are drawn on the host (yolo3/augment.py draw_augmentation, same np.random
+ * order up to the noise draw) into one record per image; the pixels never leave the device.  Per image i, with
+ * H = h_out, W = w_out:
+ *   1. resample + crop + flips.  Output pixel (r, c) reads the rescaled image (rows x cols) at row rr + dy, column cc + dx,
+ *      rr = reflect_y ? H-1-r : r, cc = reflect_x ? W-1-c : c (the crop is taken before the flips, augment.py:289-296).
+ *      Rescaled row q samples the source at ((2q+1) h_in - rows) / (2 rows) (skimage.transform.rescale's pixel centres),
+ *      evaluated as an exact integer floor of that numerator plus an fp32 fraction of the remainder; columns alike.
+ *      Bilinear; samples outside the source mirror without repeating the edge (scipy mode='mirror' = numpy 'reflect').
+ *      rows == h_in and cols == w_in give an exact copy (uint8 / uint16 -> float32 exactly).
+ *   2. noise (noise_severity > 0): x += s_i * N(0,1), s_i = noise_severity * (2 u_noise - 1) * (max_i - min_i), max / min over
+ *      all channels of the crop after step 1 (the sign is kept, as augment.py does).  N(0,1) of element e = (ch*H + y)*W + x:
+ *      Philox4x32-10, key = (seed low 32 bits, seed high 32 bits), counter = (e, 0, 0, 0); Box-Muller on the first two output
+ *      words u1 = ((w0 >> 8) + 1) 2^-24, u2 = (w1 >> 8) 2^-24: sqrt(-2 ln u1) cos(2 pi u2).  The same record gives the same bits
+ *      on every launch; it is NOT the host path's noise stream (np.random.standard_normal).
+ *   3. blur (blur_sigma > 0): scipy.ndimage.gaussian_filter(img_hwc, blur_sigma, mode='reflect') -- truncate 4.0, radius
+ *      int(4 sigma + 0.5) <= 8, weights exp(-k^2 / 2 sigma^2) normalised over -radius..radius -- on ALL THREE axes, the channel
+ *      axis included (augment.py:122 passes a scalar sigma for an HWC image).  mode='reflect' repeats the edge (half-sample
+ *      symmetric); on the channel axis the 1-D filter folds into a fixed C x C mix (for C = 3 the reflections wrap more than
+ *      once; for C = 1 the fold is the identity).  radius 0 (sigma < 0.125) is the identity.
+ *   4. out: float32 [n][C][H][W] (format_image's layout), ready for y3_zscore.
+ * src: DEVICE [n][h_in][w_in][c], dtype 0 = uint8, 1 = uint16, 2 = float32 (as y3_tile_gather); c = 1 or 3; 2 source rows must
+ * fit the LDS row stage (w_in * c * element size <= 30 KiB).  records: HOST array of n y3_aug_record, validated before any launch
+ * (Y3_EINVAL + message: src_h / src_w != h_in / w_in, rows or cols < 1, dy + h_out > rows or dx + w_out > cols, negative
+ * offsets, reflect flags not 0/1, non-finite or negative severity, u_noise outside [0, 1], non-finite blur_sigma or radius > 8,
+ * bad dtype or c) and handed to the kernels as kernel arguments.  Passes: resample (+ min / max); noise + blur along W +
+ * channel mix; blur along H -- the last two only for images that need them.  workspace: y3_augment_workspace_bytes(n, h_out,
+ * w_out, c); after the call its first 2n uint32 words hold image i's max and -min as order-preserving keys (u = float bits;
+ * key = sign ? ~u : u | 2^31). */
+typedef struct y3_aug_record {
+    int32_t src_h, src_w;        /* source image size (= h_in, w_in) */
+    int32_t rows, cols;          /* rescaled size int(np.round(scale * src)) */
+    int32_t dy, dx;              /* crop offset in the rescaled image */
+    int32_t reflect_x, reflect_y;
+    float noise_severity;        /* 0 = no noise */
+    float u_noise;               /* the uniform of augment.py's noise sign / size draw */
+    float blur_sigma;            /* <= 0 = no blur */
+    int32_t reserved;            /* 0 */
+    uint64_t seed;               /* Philox key of the noise */
+} y3_aug_record;                 /* 56 bytes */
+int y3_augment_batch(const void* src, int dtype, int n, int h_in, int w_in, int c, const y3_aug_record* records, int h_out, int w_out,
+                     float* out, void* workspace, y3_stream_t stream);
+size_t y3_augment_workspace_bytes(int n, int h_out, int w_out, int c);
+
 /* ---- gradient exchange: tf.distribute.MirroredStrategy's all-reduce (train.py:38-39, model.py:500,510-515) -------
  * One process per GPU; SUM over the replicas (the loss is already divided by the global batch, model.py:492).  RCCL over
  * xGMI underneath (librccl.so is opened on first use).  Rank 0 calls y3_comm_unique_id and hands the 128 bytes to the

@@ -1,0 +1,368 @@
+// Training augmentation on the device (augment.py:30-125, 275-297; imagereader.py:369-391): bilinear rescale + crop + flips,
+// Gaussian noise scaled by the crop's range, 3-axis Gaussian blur, HWC -> CHW float32.  The random decisions are drawn on
+// the host (yolo3/augment.py draw_augmentation) and arrive as one y3_aug_record per image; semantics in yolo3hip.h.
+//
+// Passes (one launch each per chunk of up to Y3_AUG_CHUNK images):
+//   aug_resample  one workgroup per output row: the two source rows the row interpolates between are staged in LDS with
+//                 4-byte loads, every output column is two LDS lookups per row; writes CHW float32 into `out` and folds the
+//                 row's min / max into two order-preserving words per image (atomicMax).
+//   aug_row       only for images with noise or blur: one workgroup per (row, 256-column segment).  Loads the segment and its
+//                 reflect halo, adds the noise on the load (the halo gets the same counter-based draws as the element it
+//                 mirrors), filters along W and mixes the channels with the folded C x C matrix.  Without blur it writes
+//                 back in place, with blur into the workspace.
+//   aug_col       only for images with blur: 64-column x 32-row tiles with a row halo in LDS, filter along H -> `out`.
+#include "common.h"
+#include <math.h>
+#include <algorithm>
+
+#define Y3_AUG_CHUNK 32        // images per launch: the per-image table travels as a kernel argument (32 x 48 B)
+#define Y3_AUG_MAX_RADIUS 8    // int(4 sigma + 0.5) <= 8, i.e. sigma < 2.125 (the reader draws |sigma| <= 2)
+#define Y3_AUG_STAGE_BYTES 61440   // dynamic LDS for the two staged source rows (+ static scratch < 64 KiB)
+
+struct AugImg {                // 48 bytes
+    int rows, cols, dy, dx;
+    int flags;                 // 1 = reflect_x, 2 = reflect_y
+    int radius;                // blur radius, 0 = no blur
+    float sigma;               // blur sigma (radius > 0)
+    float noise;               // severity * (2 u_noise - 1): noise sigma = noise * (max - min); 0 = no noise
+    unsigned seed_lo, seed_hi;
+    int pad0, pad1;
+};
+struct AugTable {
+    AugImg img[Y3_AUG_CHUNK];
+};
+
+// order-preserving float <-> uint (x < y <=> enc(x) < enc(y)); 0 is below every encoded value, so a zeroed word is "empty"
+__device__ __forceinline__ unsigned aug_enc(float f) {
+    const unsigned u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float aug_dec(unsigned u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
+// scipy mode='mirror' (= numpy 'reflect'): whole-sample symmetric, period 2(n-1), no edge repeat
+__device__ __forceinline__ int aug_mirror(int p, int n) {
+    if (n == 1) return 0;
+    const int period = 2 * (n - 1);
+    int q = p % period;
+    if (q < 0) q += period;
+    return q < n ? q : period - q;
+}
+// scipy mode='reflect' (= numpy 'symmetric'): half-sample symmetric, period 2n, the edge repeats
+__device__ __forceinline__ int aug_reflect(int p, int n) {
+    const int period = 2 * n;
+    int q = p % period;
+    if (q < 0) q += period;
+    return q < n ? q : period - 1 - q;
+}
+
+// Source coordinate of rescaled index o: ((2o + 1) n_in - n_res) / (2 n_res), as an exact integer floor i0 and the fraction
+// of the remainder (numerator < 2^31 is checked on the host)
+__device__ __forceinline__ void aug_coord(int o, int n_in, int n_res, int& i0, float& f) {
+    const int num = (2 * o + 1) * n_in - n_res, den = 2 * n_res;
+    i0 = num >= 0 ? num / den : -((den - 1 - num) / den);
+    f = (float)(num - i0 * den) / (float)den;
+}
+
+__device__ __forceinline__ float aug_lerp(float a, float b, float f) { return f == 0.f ? a : (1.f - f) * a + f * b; }
+
+// Philox4x32-10 (Salmon et al., SC'11): counter (e, 0, 0, 0), key (seed_lo, seed_hi); Box-Muller on the first two words
+__device__ __forceinline__ float aug_normal(unsigned e, unsigned k0, unsigned k1) {
+    unsigned c0 = e, c1 = 0u, c2 = 0u, c3 = 0u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0;
+        c1 = lo1;
+        c2 = hi0 ^ c3 ^ k1;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    const float u1 = (float)((c0 >> 8) + 1u) * 5.9604644775390625e-8f;    // (0, 1]
+    const float u2 = (float)(c1 >> 8) * 5.9604644775390625e-8f;           // [0, 1)
+    return sqrtf(-2.f * logf(u1)) * cosf(6.2831853071795865f * u2);
+}
+
+// Normalised Gaussian weights w[0..radius] (scipy _gaussian_kernel1d: exp(-x^2 / 2 sigma^2) / sum over -r..r, in double) and,
+// when mix != nullptr, the C x C channel matrix of the same 1-D filter folded through mode='reflect' on an axis of length C.
+// Called by the whole workgroup (two barriers).
+__device__ void aug_weights(const AugImg& a, float* wgt, float* mix, int C) {
+    __shared__ double phi[Y3_AUG_MAX_RADIUS + 1];
+    const int r = a.radius;
+    if ((int)threadIdx.x <= r) {
+        const double s = (double)a.sigma, x = (double)threadIdx.x;
+        phi[threadIdx.x] = exp(-0.5 / (s * s) * x * x);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double sum = phi[0];
+        for (int k = 1; k <= r; ++k) sum += 2.0 * phi[k];
+        double w[Y3_AUG_MAX_RADIUS + 1];
+        for (int k = 0; k <= r; ++k) {
+            w[k] = phi[k] / sum;
+            wgt[k] = (float)w[k];
+        }
+        if (mix)
+            for (int co = 0; co < C; ++co) {
+                double m[3] = {0.0, 0.0, 0.0};
+                for (int k = -r; k <= r; ++k) m[aug_reflect(co + k, C)] += w[k < 0 ? -k : k];
+                for (int ci = 0; ci < C; ++ci) mix[co * C + ci] = (float)m[ci];
+            }
+    }
+    __syncthreads();
+}
+
+// ---- pass 1: resample + crop + flips -> CHW, per-image min / max ---------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ void aug_stage_row(const T* __restrict__ src, int elems, unsigned char* dst) {
+    const unsigned char* s = (const unsigned char*)src;
+    const int bytes = elems * (int)sizeof(T);
+    if ((((size_t)s) & 3) == 0 && (bytes & 3) == 0) {
+        const unsigned* s4 = (const unsigned*)s;
+        unsigned* d4 = (unsigned*)dst;
+        for (int i = threadIdx.x; i < (bytes >> 2); i += blockDim.x) d4[i] = s4[i];
+    } else {
+        T* d = (T*)dst;
+        for (int i = threadIdx.x; i < elems; i += blockDim.x) d[i] = src[i];
+    }
+}
+
+template <typename T, int C>
+__global__ __launch_bounds__(256) void aug_resample_kernel(const T* __restrict__ src, int Hin, int Win, AugTable tab, int Hout, int Wout,
+                                                           float* __restrict__ out, unsigned* __restrict__ minmax) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage[];
+    __shared__ float red[2][4];
+    const AugImg& a = tab.img[blockIdx.y];
+    const int r = blockIdx.x;
+    const int rr = (a.flags & 2) ? Hout - 1 - r : r;
+    int y0;
+    float fy;
+    aug_coord(rr + a.dy, Hin, a.rows, y0, fy);
+    const int ya = aug_mirror(y0, Hin), yb = fy == 0.f ? ya : aug_mirror(y0 + 1, Hin);
+    const int rowElems = Win * C;
+    const T* img = src + (size_t)blockIdx.y * Hin * rowElems;
+    const size_t rowBytes = ((size_t)rowElems * sizeof(T) + 15) & ~(size_t)15;
+    const T* la = (const T*)stage;
+    const T* lb = (const T*)(stage + rowBytes);
+    aug_stage_row(img + (size_t)ya * rowElems, rowElems, stage);
+    if (yb != ya) aug_stage_row(img + (size_t)yb * rowElems, rowElems, stage + rowBytes);
+    else lb = la;
+    __syncthreads();
+    const size_t plane = (size_t)Hout * Wout;
+    float* o = out + (size_t)blockIdx.y * C * plane + (size_t)r * Wout;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int c = threadIdx.x; c < Wout; c += blockDim.x) {
+        const int cc = (a.flags & 1) ? Wout - 1 - c : c;
+        int x0;
+        float fx;
+        aug_coord(cc + a.dx, Win, a.cols, x0, fx);
+        const int xa = aug_mirror(x0, Win) * C, xb = (fx == 0.f ? aug_mirror(x0, Win) : aug_mirror(x0 + 1, Win)) * C;
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch) {
+            const float top = aug_lerp((float)la[xa + ch], (float)la[xb + ch], fx);
+            const float bot = aug_lerp((float)lb[xa + ch], (float)lb[xb + ch], fx);
+            const float v = aug_lerp(top, bot, fy);
+            o[ch * plane + c] = v;
+            lo = fminf(lo, v);
+            hi = fmaxf(hi, v);
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, s));
+        hi = fmaxf(hi, __shfl_xor(hi, s));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = lo;
+        red[1][threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) {
+            lo = fminf(lo, red[0][w]);
+            hi = fmaxf(hi, red[1][w]);
+        }
+        atomicMax(minmax + 2 * blockIdx.y, aug_enc(hi));
+        atomicMax(minmax + 2 * blockIdx.y + 1, aug_enc(-lo));
+    }
+}
+
+// ---- pass 2: noise + blur along W + channel mix ---------------------------------------------------------------------------
+template <int C>
+__global__ __launch_bounds__(256) void aug_row_kernel(float* __restrict__ io, float* __restrict__ tmp, AugTable tab, int Hout, int Wout, int nseg,
+                                                      const unsigned* __restrict__ minmax) {
+    __shared__ float row[C][256 + 2 * Y3_AUG_MAX_RADIUS];
+    __shared__ float wgt[Y3_AUG_MAX_RADIUS + 1];
+    __shared__ float mix[C * C];
+    const AugImg& a = tab.img[blockIdx.y];
+    if (a.noise == 0.f && a.radius == 0) return;
+    const int R = a.radius;
+    if (R > 0) aug_weights(a, wgt, C > 1 ? mix : nullptr, C);
+    const int h = blockIdx.x / nseg, x0 = (blockIdx.x - h * nseg) * 256;
+    const size_t plane = (size_t)Hout * Wout;
+    const float* s = io + (size_t)blockIdx.y * C * plane + (size_t)h * Wout;
+    const float sig = a.noise * (aug_dec(minmax[2 * blockIdx.y]) + aug_dec(minmax[2 * blockIdx.y + 1]));   // noise * (max - min)
+    const bool noisy = a.noise != 0.f;
+    const int span = min(256, Wout - x0) + 2 * R;
+    for (int ch = 0; ch < C; ++ch)
+        for (int i = threadIdx.x; i < span; i += blockDim.x) {
+            const int x = aug_reflect(x0 - R + i, Wout);
+            float v = s[ch * plane + x];
+            if (noisy) v += sig * aug_normal((unsigned)(((size_t)ch * Hout + h) * Wout + x), a.seed_lo, a.seed_hi);
+            row[ch][i] = v;
+        }
+    __syncthreads();
+    const int x = x0 + threadIdx.x;
+    if (x >= Wout) return;
+    float b[C];
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+        const float* p = &row[ch][threadIdx.x + R];
+        if (R == 0) {
+            b[ch] = p[0];
+        } else {
+            float acc = wgt[0] * p[0];
+            for (int k = 1; k <= R; ++k) acc += wgt[k] * (p[-k] + p[k]);      // scipy correlate1d's symmetric form
+            b[ch] = acc;
+        }
+    }
+    float* d = (R > 0 ? tmp : io) + (size_t)blockIdx.y * C * plane + (size_t)h * Wout + x;
+#pragma unroll
+    for (int co = 0; co < C; ++co) {
+        float v = b[co];
+        if (C > 1 && R > 0) {
+            v = 0.f;
+#pragma unroll
+            for (int ci = 0; ci < C; ++ci) v += mix[co * C + ci] * b[ci];
+        }
+        d[co * plane] = v;
+    }
+}
+
+// ---- pass 3: blur along H --------------------------------------------------------------------------------------------------
+#define AUG_COL_TW 64
+#define AUG_COL_TH 32
+__global__ __launch_bounds__(256) void aug_col_kernel(const float* __restrict__ tmp, float* __restrict__ out, AugTable tab, int C, int Hout, int Wout,
+                                                      int tilesx, int tilesy) {
+    __shared__ float col[AUG_COL_TH + 2 * Y3_AUG_MAX_RADIUS][AUG_COL_TW];
+    __shared__ float wgt[Y3_AUG_MAX_RADIUS + 1];
+    const AugImg& a = tab.img[blockIdx.y];
+    if (a.radius == 0) return;
+    const int R = a.radius;
+    aug_weights(a, wgt, nullptr, C);
+    const int t = blockIdx.x, tx = t % tilesx, ty = (t / tilesx) % tilesy, ch = t / (tilesx * tilesy);
+    const int lane = threadIdx.x & (AUG_COL_TW - 1), grp = threadIdx.x / AUG_COL_TW;
+    const int x = tx * AUG_COL_TW + lane, y0 = ty * AUG_COL_TH;
+    const size_t plane = (size_t)Hout * Wout;
+    const float* s = tmp + ((size_t)blockIdx.y * C + ch) * plane;
+    const int rowsIn = min(AUG_COL_TH, Hout - y0) + 2 * R;
+    for (int i = grp; i < rowsIn; i += 256 / AUG_COL_TW) col[i][lane] = x < Wout ? s[(size_t)aug_reflect(y0 - R + i, Hout) * Wout + x] : 0.f;
+    __syncthreads();
+    if (x >= Wout) return;
+    float* d = out + ((size_t)blockIdx.y * C + ch) * plane + x;
+    for (int i = grp; i < AUG_COL_TH && y0 + i < Hout; i += 256 / AUG_COL_TW) {
+        float acc = wgt[0] * col[i + R][lane];
+        for (int k = 1; k <= R; ++k) acc += wgt[k] * (col[i + R - k][lane] + col[i + R + k][lane]);
+        d[(size_t)(y0 + i) * Wout] = acc;
+    }
+}
+
+// ---- host entry ------------------------------------------------------------------------------------------------------------
+static size_t aug_minmax_bytes(int n) { return ((size_t)n * 2 * sizeof(unsigned) + 255) & ~(size_t)255; }
+
+extern "C" size_t y3_augment_workspace_bytes(int n, int h_out, int w_out, int c) {
+    if (n <= 0 || h_out <= 0 || w_out <= 0 || c <= 0) return 0;
+    return aug_minmax_bytes(n) + (size_t)n * c * h_out * w_out * sizeof(float);
+}
+
+static int aug_blur_radius(float sigma) { return sigma > 0.f ? (int)(4.0 * (double)sigma + 0.5) : 0; }
+
+template <typename T, int C>
+static void aug_launch_resample(const void* src, int h_in, int w_in, const AugTable& tab, int nb, int h_out, int w_out, float* out,
+                                unsigned* mm, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((aug_resample_kernel<T, C>), dim3(h_out, nb), dim3(256), lds, st, (const T*)src, h_in, w_in, tab, h_out, w_out, out, mm);
+}
+
+extern "C" int y3_augment_batch(const void* src, int dtype, int n, int h_in, int w_in, int c, const y3_aug_record* records, int h_out,
+                                int w_out, float* out, void* workspace, y3_stream_t stream) {
+    Y3_CHECK_ARG(src && records && out && workspace, "augment_batch: null pointer");
+    Y3_CHECK_ARG(dtype >= 0 && dtype <= 2, "augment_batch: dtype %d (0 = u8, 1 = u16, 2 = f32)", dtype);
+    Y3_CHECK_ARG(c == 1 || c == 3, "augment_batch: channels %d (1 or 3)", c);
+    Y3_CHECK_ARG(n > 0 && h_in > 0 && w_in > 0 && h_out > 0 && w_out > 0, "augment_batch: bad dims n %d in %dx%d out %dx%d", n, h_in, w_in, h_out, w_out);
+    Y3_CHECK_ARG((long long)h_out * w_out * c < (1LL << 31) && h_out <= 65535, "augment_batch: output %dx%dx%d too large", h_out, w_out, c);
+    const size_t esize = dtype == 0 ? 1 : dtype == 1 ? 2 : 4;
+    const size_t rowBytes = ((size_t)w_in * c * esize + 15) & ~(size_t)15;
+    Y3_CHECK_ARG(2 * rowBytes <= Y3_AUG_STAGE_BYTES, "augment_batch: source rows of %d x %d x %zu bytes exceed the LDS row stage", w_in, c, esize);
+    for (int i = 0; i < n; ++i) {
+        const y3_aug_record& r = records[i];
+        Y3_CHECK_ARG(r.src_h == h_in && r.src_w == w_in, "augment_batch: record %d: source %dx%d, batch %dx%d", i, r.src_h, r.src_w, h_in, w_in);
+        Y3_CHECK_ARG(r.rows >= 1 && r.cols >= 1, "augment_batch: record %d: rescaled size %dx%d", i, r.rows, r.cols);
+        Y3_CHECK_ARG((long long)2 * r.rows * h_in < (1LL << 31) && (long long)2 * r.cols * w_in < (1LL << 31), "augment_batch: record %d: rescaled size %dx%d too large",
+                     i, r.rows, r.cols);
+        Y3_CHECK_ARG(r.dy >= 0 && r.dx >= 0 && (long long)r.dy + h_out <= r.rows && (long long)r.dx + w_out <= r.cols,
+                     "augment_batch: record %d: crop %d+%d x %d+%d outside the rescaled %dx%d", i, r.dy, h_out, r.dx, w_out, r.rows, r.cols);
+        Y3_CHECK_ARG((r.reflect_x == 0 || r.reflect_x == 1) && (r.reflect_y == 0 || r.reflect_y == 1), "augment_batch: record %d: reflect flags %d %d", i,
+                     r.reflect_x, r.reflect_y);
+        Y3_CHECK_ARG(isfinite(r.noise_severity) && r.noise_severity >= 0.f && isfinite(r.u_noise) && r.u_noise >= 0.f && r.u_noise <= 1.f,
+                     "augment_batch: record %d: noise severity %g, u_noise %g", i, (double)r.noise_severity, (double)r.u_noise);
+        Y3_CHECK_ARG(isfinite(r.blur_sigma) && aug_blur_radius(r.blur_sigma) <= Y3_AUG_MAX_RADIUS, "augment_batch: record %d: blur sigma %g (radius <= %d)", i,
+                     (double)r.blur_sigma, Y3_AUG_MAX_RADIUS);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* mm = (unsigned*)workspace;
+    float* tmp = (float*)((char*)workspace + aug_minmax_bytes(n));
+    const hipError_t e = hipMemsetAsync(mm, 0, (size_t)n * 2 * sizeof(unsigned), st);
+    if (e != hipSuccess) {
+        y3_set_error("augment_batch: memset: %s", hipGetErrorString(e));
+        return Y3_ELAUNCH;
+    }
+    const size_t plane = (size_t)h_out * w_out;
+    for (int base = 0; base < n; base += Y3_AUG_CHUNK) {
+        const int nb = std::min(Y3_AUG_CHUNK, n - base);
+        AugTable tab = {};
+        bool any_row = false, any_blur = false;
+        for (int i = 0; i < nb; ++i) {
+            const y3_aug_record& r = records[base + i];
+            AugImg& a = tab.img[i];
+            a.rows = r.rows;
+            a.cols = r.cols;
+            a.dy = r.dy;
+            a.dx = r.dx;
+            a.flags = (r.reflect_x ? 1 : 0) | (r.reflect_y ? 2 : 0);
+            a.radius = aug_blur_radius(r.blur_sigma);
+            a.sigma = r.blur_sigma;
+            a.noise = (float)((double)r.noise_severity * (2.0 * (double)r.u_noise - 1.0));
+            a.seed_lo = (unsigned)(r.seed & 0xffffffffu);
+            a.seed_hi = (unsigned)(r.seed >> 32);
+            any_row |= a.noise != 0.f || a.radius > 0;
+            any_blur |= a.radius > 0;
+        }
+        const void* s = (const char*)src + (size_t)base * h_in * w_in * c * esize;
+        float* o = out + (size_t)base * c * plane;
+        float* t = tmp + (size_t)base * c * plane;
+        unsigned* m = mm + 2 * base;
+        const size_t lds = 2 * rowBytes;
+        switch (dtype * 4 + c) {
+            case 0 * 4 + 1: aug_launch_resample<unsigned char, 1>(s, h_in, w_in, tab, nb, h_out, w_out, o, m, lds, st); break;
+            case 0 * 4 + 3: aug_launch_resample<unsigned char, 3>(s, h_in, w_in, tab, nb, h_out, w_out, o, m, lds, st); break;
+            case 1 * 4 + 1: aug_launch_resample<unsigned short, 1>(s, h_in, w_in, tab, nb, h_out, w_out, o, m, lds, st); break;
+            case 1 * 4 + 3: aug_launch_resample<unsigned short, 3>(s, h_in, w_in, tab, nb, h_out, w_out, o, m, lds, st); break;
+            case 2 * 4 + 1: aug_launch_resample<float, 1>(s, h_in, w_in, tab, nb, h_out, w_out, o, m, lds, st); break;
+            default: aug_launch_resample<float, 3>(s, h_in, w_in, tab, nb, h_out, w_out, o, m, lds, st); break;
+        }
+        Y3_CHECK_LAUNCH("augment_batch: resample");
+        if (any_row) {
+            const int nseg = y3_cdiv(w_out, 256);
+            if (c == 1) hipLaunchKernelGGL(aug_row_kernel<1>, dim3(nseg * h_out, nb), dim3(256), 0, st, o, t, tab, h_out, w_out, nseg, (const unsigned*)m);
+            else hipLaunchKernelGGL(aug_row_kernel<3>, dim3(nseg * h_out, nb), dim3(256), 0, st, o, t, tab, h_out, w_out, nseg, (const unsigned*)m);
+            Y3_CHECK_LAUNCH("augment_batch: noise / row blur");
+        }
+        if (any_blur) {
+            const int tilesx = y3_cdiv(w_out, AUG_COL_TW), tilesy = y3_cdiv(h_out, AUG_COL_TH);
+            hipLaunchKernelGGL(aug_col_kernel, dim3(tilesx * tilesy * c, nb), dim3(256), 0, st, (const float*)t, o, tab, c, h_out, w_out, tilesx, tilesy);
+            Y3_CHECK_LAUNCH("augment_batch: column blur");
+        }
+    }
+    return Y3_OK;
+}

@@ -58,7 +58,7 @@ def effective_reader_count(requested, cpus, local_world):
 
 
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
-                learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl'):
+                learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu'):
     os.makedirs(output_folder, exist_ok=True)
     anchors = [(64, 384), (384, 64)]
 
@@ -78,11 +78,11 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     # one reader per rank: the unshuffled test reader takes this rank's stride of the key list (the reference splits one
     # global test batch over its replicas, train.py:64-66)
     test_reader = imagereader.ImageReader(test_database_filepath, anchors, use_augmentation=False, shuffle=False, num_workers=reader_count,
-                                          num_shards=world, shard_index=rank)
+                                          num_shards=world, shard_index=rank, augmentation_device=augmentation_device)
     print('Test Reader has {} images'.format(test_reader.get_image_count()))
     print('Setting up training image reader')
     train_reader = imagereader.ImageReader(train_database_filepath, anchors, use_augmentation=use_augmentation, shuffle=True,
-                                           num_workers=reader_count, balance_classes=True)
+                                           num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device)
     print('Train Reader has {} images'.format(train_reader.get_image_count()))
     training_checkpoint_filepath = None
     try:
@@ -240,9 +240,13 @@ if __name__ == "__main__":
     parser.add_argument('--reader_count', dest='reader_count', type=int, default=None, help='(addition) reader processes per GPU; default: 3 (as the reference) up to 12 when the host has the cores')
     parser.add_argument('--max_epochs', dest='max_epochs', type=int, default=None, help='(addition) stop after this many epochs')
     parser.add_argument('--backend', dest='backend', type=str, default='nccl', help='(addition) torch.distributed backend under torch.distributed.run: nccl (= RCCL, one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
+    parser.add_argument('--augmentation_device', dest='augmentation_device', choices=('cpu', 'gpu'), default='cpu',
+                        help='(addition) where the readers\' images are augmented: cpu = in the reader processes (as the reference), gpu = drawn '
+                             'there, applied to each batch by HIP kernels; the test reader (no augmentation) uploads its pixels unconverted either way round')
     a = parser.parse_args()
     print('Arguments:')
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
-                a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend)
+                a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
+                a.augmentation_device)

@@ -109,6 +109,8 @@ SIGNATURES = {
     'y3_comm_destroy': (i32, [vp]),
     'y3_zscore': (i32, [fp, fp, i32, sz, vp, vp]),
     'y3_zscore_workspace_bytes': (sz, [i32]),
+    'y3_augment_batch': (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, fp, vp, vp]),     # records: HOST pointer (augment.AUG_RECORD)
+    'y3_augment_workspace_bytes': (sz, [i32, i32, i32, i32]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -7,11 +7,20 @@ the reference's order) and outside the measured path.  scikit-ima
 the rescale of augment.py:277-280 is restated on scipy.ndimage.map_coordinates (rescale_bilinear).  Pinned by
 tests/golden/augment.npz, produced by running the reference's augment.py under seeded np.random: boxes and crop
 offsets identical, pixels to 1e-4 of the 8-bit range.  Boxes are [n,5] = x, y, w, h, class (top-left corner).
+
+draw_augmentation is the device path's half of augment_image_box_pair: the same random decisions, boxes transformed here,
+the pixels left to y3_augment_batch (csrc/augment.hip) through one AUG_RECORD per image.
 """
 import numpy as np
 import scipy.ndimage
 
 MIN_VISIBLE = 12      # boxes with less than 12 px inside the crop are dropped (augment.py:228-237)
+
+# y3_aug_record (include/yolo3hip.h), one per image of a y3_augment_batch call
+AUG_RECORD = np.dtype([('src_h', '<i4'), ('src_w', '<i4'), ('rows', '<i4'), ('cols', '<i4'), ('dy', '<i4'), ('dx', '<i4'),
+                       ('reflect_x', '<i4'), ('reflect_y', '<i4'), ('noise_severity', '<f4'), ('u_noise', '<f4'),
+                       ('blur_sigma', '<f4'), ('reserved', '<i4'), ('seed', '<u8')])
+assert AUG_RECORD.itemsize == 56
 
 
 def jitter_boxes(boxes, location_jitter, size_jitter, img_shape):
@@ -138,3 +147,58 @@ def augment_image_box_pair(img, boxes, rotation_flag=False, reflection_flag=Fals
         if sigma > 0:
             img = scipy.ndimage.gaussian_filter(img, sigma, mode='reflect')
     return np.asarray(img, dtype=np.float32), boxes
+
+
+def identity_record(img_shape, crop_to=None):
+    """The record of crop_to_size (augment.py:20-27): scale 1, no flips, no noise, no blur.  Draws the crop offsets from
+    np.random exactly as crop_to_size does (none when the image already has the crop's size)."""
+    rec, _ = draw_augmentation(img_shape, None, crop_to=crop_to)
+    return rec
+
+
+def draw_augmentation(img_shape, boxes, rotation_flag=False, reflection_flag=False, crop_to=None, noise_augmentation_severity=0,
+                      scale_augmentation_severity=0, blur_augmentation_max_sigma=0, box_size_augmentation_severity=0,
+                      box_location_jitter_severity=0):
+    """The random decisions of augment_image_box_pair (same keyword arguments) without touching pixels -> (record, boxes).
+
+    Draws from the global np.random in augment_image_box_pair's order: reflect_x, reflect_y, scale_x, scale_y, the box
+    jitter normals, dy, dx, the noise uniform; everything up to there -- boxes, flips, rescaled size, crop offsets -- is
+    what augment_image_box_pair gives under the same seed.  Then, where the host path spends H*W*C normals on the noise
+    (which the device draws from its own counter-based stream keyed by `seed`), this draws the blur uniform and the 64-bit
+    noise seed: the blur sigma has the host path's distribution but not its seed-for-seed value.  record: AUG_RECORD
+    array of shape [1]; boxes: transformed on the host (None when none survive), as augment_image_box_pair returns them."""
+    assert not rotation_flag, 'Rotation not implemented for image and boxes pair'
+    assert len(img_shape) in (2, 3)
+    noise = noise_augmentation_severity or 0
+    scale = scale_augmentation_severity or 0
+    blur = blur_augmentation_max_sigma or 0
+    assert 0 <= noise < 1 and 0 <= scale < 1 and 0 <= (box_size_augmentation_severity or 0) < 1 and 0 <= (box_location_jitter_severity or 0) < 1
+    H, W = int(img_shape[0]), int(img_shape[1])
+    if crop_to is None:
+        crop_to = (H, W)
+    reflect_x = reflect_y = False
+    scale_x = scale_y = 1
+    if reflection_flag:
+        reflect_x = np.random.rand() > 0.5
+        reflect_y = np.random.rand() > 0.5
+    if scale > 0:
+        hi = 1.0 + scale
+        lo = max(max(crop_to[0] / H, crop_to[1] / W), 1.0 - scale)
+        scale_x = lo + (hi - lo) * np.random.rand()
+        scale_y = lo + (hi - lo) * np.random.rand()
+    boxes = jitter_boxes(boxes, box_location_jitter_severity or 0, box_size_augmentation_severity or 0, img_shape)
+    rows, cols = H, W
+    if scale_x != 1 or scale_y != 1:                     # rescale_bilinear's output size
+        rows, cols = int(np.round(scale_y * H)), int(np.round(scale_x * W))
+    dy = dx = 0                                          # transform_image's crop offsets
+    if rows - crop_to[0] > 0:
+        dy = int(np.random.randint(0, rows - crop_to[0]))
+    if cols - crop_to[1] > 0:
+        dx = int(np.random.randint(0, cols - crop_to[1]))
+    boxes = transform_boxes(boxes, crop_to, reflect_x, reflect_y, scale_x, scale_y, dx, dy)
+    u_noise = np.random.rand() if noise > 0 else 0.0
+    sigma = (-blur + 2 * blur * np.random.rand()) if blur > 0 else 0.0
+    seed = np.random.randint(0, 2**64, dtype=np.uint64) if noise > 0 else 0
+    rec = np.zeros(1, AUG_RECORD)
+    rec[0] = (H, W, rows, cols, dy, dx, int(reflect_x), int(reflect_y), noise, u_noise, sigma, 0, seed)
+    return rec, boxes

@@ -4,6 +4,7 @@ ground-truth label layout the loss consumes.
 
 ImageReader       imagereader.py:79-460  (lmdb + protobuf datasets, worker processes, bounded queue)
 zscore_normalize  imagereader.py:34-46   (csrc/pointwise.hip, fp64 partial sums)
+augment_device    augment.py:30-125 on the device (csrc/augment.hip) for ImageReader(..., augmentation_device='gpu')
 format_image      imagereader.py:57-60
 format_boxes      ImageReader.__format_boxes, imagereader.py:252-324 (host NumPy,
                   as in the reference: it runs in the reader processes)
@@ -23,6 +24,10 @@ from . import lmdbio
 from .isg_ai_pb import ImageYoloBoxesPair
 
 NETWORK_DOWNSAMPLE_FACTOR = 32   # model.YoloV3.NETWORK_DOWNSAMPLE_FACTOR (model.py:25)
+# augment_image_box_pair's arguments in the training reader (imagereader.py:369-391)
+TRAIN_AUGMENTATION = dict(reflection_flag=True, rotation_flag=False, noise_augmentation_severity=0.03, scale_augmentation_severity=0.1,
+                          blur_augmentation_max_sigma=2, box_size_augmentation_severity=0.03, box_location_jitter_severity=0.03)
+_AUG_DTYPES = {torch.uint8: 0, torch.uint16: 1, torch.float32: 2}
 
 
 def zscore_normalize_device(x):
@@ -37,6 +42,31 @@ def zscore_normalize_device(x):
     st = torch.cuda.current_stream(x.device).cuda_stream
     check(lib.y3_zscore(x.data_ptr(), out.data_ptr(), b, count, ws.data_ptr(), st), 'y3_zscore')
     return out
+
+
+def augment_device(src, records, crop_to, ranges=False):
+    """y3_augment_batch: src CUDA [B, H, W, C] (uint8, uint16 or float32, HWC as stored), records AUG_RECORD [B] (host; see
+    augment.draw_augmentation) -> float32 [B, C, crop_h, crop_w], resampled / cropped / flipped / noised / blurred, NOT z-scored.
+    Enqueued on the current stream.  ranges=True also returns the per-image (min, max) of the resampled crop the noise was
+    scaled by (CUDA float32 [B] each)."""
+    assert src.is_cuda and src.dim() == 4 and src.dtype in _AUG_DTYPES, (src.dtype, tuple(src.shape))
+    src = src.contiguous()
+    records = np.ascontiguousarray(records, dtype=augment.AUG_RECORD)
+    b, h, w, c = src.shape
+    assert records.shape == (b,)
+    ho, wo = int(crop_to[0]), int(crop_to[1])
+    out = torch.empty((b, c, ho, wo), dtype=torch.float32, device=src.device)
+    ws = torch.empty(int(lib.y3_augment_workspace_bytes(b, ho, wo, c)), dtype=torch.uint8, device=src.device)
+    st = torch.cuda.current_stream(src.device).cuda_stream
+    check(lib.y3_augment_batch(src.data_ptr(), _AUG_DTYPES[src.dtype], b, h, w, c, records.ctypes.data, ho, wo, out.data_ptr(),
+                               ws.data_ptr(), st), 'y3_augment_batch')
+    if not ranges:
+        return out
+    enc = ws[:8 * b].view(torch.int32).view(b, 2).to(torch.int64) & 0xffffffff      # yolo3hip.h: encoded max, encoded -min
+    bits = torch.where(enc >= 2**31, enc - 2**31, 2**32 - 1 - enc)
+    bits = torch.where(bits >= 2**31, bits - 2**32, bits).to(torch.int32)
+    val = bits.view(torch.float32)
+    return out, -val[:, 1], val[:, 0]
 
 
 def zscore_normalize(image_data):
@@ -154,10 +184,14 @@ class Dataset:
             yield from self.reader.generator()           # z-scored examples, as the reference's unbatched dataset yields them
             return
         dev = self.device or torch.device('cuda', torch.cuda.current_device())
+        on_gpu = self.reader.augmentation_device == 'gpu'     # examples carry raw HWC pixels + an AUG_RECORD (ImageReader)
+        crop = self.reader.image_size[:2]
         if not self.prefetch_depth:
             for ex in self._examples():
                 imgs = torch.from_numpy(np.stack([e[0] for e in ex])).to(dev, non_blocking=True)
                 labels = [torch.from_numpy(np.stack([e[i] for e in ex])).to(dev, non_blocking=True) for i in (1, 2, 3)]
+                if on_gpu:
+                    imgs = augment_device(imgs, np.concatenate([e[4] for e in ex]), crop)
                 yield (zscore_normalize_device(imgs), *labels)
             return
         import queue
@@ -188,6 +222,8 @@ class Dataset:
                                         for j in range(4)]
                     for j in range(4):
                         np.stack([e[j] for e in ex], out=slot['bufs'][j].numpy())
+                    if on_gpu:
+                        slot['records'] = np.concatenate([e[4] for e in ex])   # host side: read by the y3_augment_batch call
                     if not hand_over(slot):
                         return
             finally:
@@ -203,7 +239,8 @@ class Dataset:
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(dev))
                 slot['event'] = ev
-                yield (zscore_normalize_device(dev_t[0]), dev_t[1], dev_t[2], dev_t[3])
+                imgs = augment_device(dev_t[0], slot['records'], crop) if on_gpu else dev_t[0]
+                yield (zscore_normalize_device(imgs), dev_t[1], dev_t[2], dev_t[3])
         finally:
             stop.set()          # the consumer walked away (epoch boundary): the producer exits at its next hand-over
 
@@ -212,10 +249,16 @@ class ImageReader:
     """imagereader.ImageReader (imagereader.py:79-460): same constructor, startup / shutdown / get_image_size /
     get_number_classes / get_image_count / get_example / generator; get_tf_dataset() returns a ``Dataset``."""
 
-    def __init__(self, img_db, anchors, use_augmentation=True, balance_classes=False, shuffle=True, num_workers=1, num_shards=1, shard_index=0):
+    def __init__(self, img_db, anchors, use_augmentation=True, balance_classes=False, shuffle=True, num_workers=1, num_shards=1, shard_index=0,
+                 augmentation_device='cpu'):
         """num_shards / shard_index (addition): with one process per GPU every rank owns a reader; an unshuffled reader
         (the test set) then serves every num_shards-th stride of the key list, so the ranks evaluate disjoint images like
-        the replicas of the reference's one distributed test batch."""
+        the replicas of the reference's one distributed test batch.
+        augmentation_device (addition): 'cpu' augments in the worker processes (augment.augment_image_box_pair, the
+        reference's design); 'gpu' has the workers draw only the random decisions (augment.draw_augmentation) and hand out
+        the stored pixels, which the batches then augment on the device (augment_device, csrc/augment.hip)."""
+        assert augmentation_device in ('cpu', 'gpu'), augmentation_device
+        self.augmentation_device = augmentation_device
         self.num_shards, self.shard_index = int(num_shards), int(shard_index)
         assert 0 <= self.shard_index < self.num_shards
         self.image_db = img_db
@@ -327,18 +370,23 @@ class ImageReader:
         return fn
 
     def load_example(self, key, env):
-        """One example as the workers produce it: (image[C,H,W] float32 NOT yet z-scored, label_1, label_2, label_3)."""
+        """One example as the workers produce it: (image[C,H,W] float32 NOT yet z-scored, label_1, label_2, label_3); with
+        augmentation_device='gpu': (image[H,W,C] as stored, label_1, label_2, label_3, AUG_RECORD [1])."""
         datum = ImageYoloBoxesPair().ParseFromString(env.get(key))
         img, boxes = datum.to_arrays()
         if list(img.shape) != list(self.image_size):
             raise RuntimeError("Encountered unexpected image shape from database. Expected {}. Found {}.".format(self.image_size, img.shape))
         boxes = boxes.copy()
         crop_to = [self.image_size[0], self.image_size[1]]
+        if self.augmentation_device == 'gpu':
+            if self.use_augmentation:
+                rec, boxes = augment.draw_augmentation(img.shape, boxes, crop_to=crop_to, **TRAIN_AUGMENTATION)
+            else:
+                rec = augment.identity_record(img.shape, crop_to)
+            labels = format_boxes(boxes, self.image_size, self.anchors, self.number_classes)
+            return (np.ascontiguousarray(img), labels[0], labels[1], labels[2], rec)
         if self.use_augmentation:                               # severities of imagereader.py:369-391
-            img, boxes = augment.augment_image_box_pair(img.astype(np.float32), boxes, reflection_flag=True, rotation_flag=False, crop_to=crop_to,
-                                                        noise_augmentation_severity=0.03, scale_augmentation_severity=0.1,
-                                                        blur_augmentation_max_sigma=2, box_size_augmentation_severity=0.03,
-                                                        box_location_jitter_severity=0.03)
+            img, boxes = augment.augment_image_box_pair(img.astype(np.float32), boxes, crop_to=crop_to, **TRAIN_AUGMENTATION)
         if img.shape[0] != self.image_size[0] or img.shape[1] != self.image_size[1]:
             img, boxes = augment.crop_to_size(img, boxes, crop_to)
         img = np.ascontiguousarray(format_image(img)).astype(np.float32)
@@ -383,6 +431,10 @@ class ImageReader:
         example = self._get_raw()
         if example is None:
             return None
+        if self.augmentation_device == 'gpu':                  # a batch of one through the device path
+            src = torch.from_numpy(example[0][None]).cuda()
+            img = zscore_normalize_device(augment_device(src, example[4], self.image_size[:2]))[0].cpu().numpy()
+            return (img,) + tuple(example[1:4])
         return (zscore_normalize(example[0]),) + tuple(example[1:])
 
     def generator(self):

@@ -1,6 +1,8 @@
 """End-to-end training throughput with the real data plane: synthetic lmdb (64 uint8 416x416x3 images, 1-4
 boxes) -> ImageReader worker processes (lmdb + protobuf decode, augmentation, z-score, label layout) -> batches ->
-YoloV3.train_step.  Compare with bench.py (inputs resident).  python tools/train_throughput.py [workers] [augment 0/1]"""
+YoloV3.train_step.  Compare with bench.py (inputs resident).
+python tools/train_throughput.py [workers] [augment 0/1] [cpu|gpu]: the third argument is ImageReader's augmentation_device.
+Also prints a reader's CPU time per example (ImageReader.load_example timed in this process before the workers start)."""
 import os
 import sys
 import tempfile
@@ -13,6 +15,7 @@ import numpy as np   # noqa: E402
 
 workers = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 augment = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+device = sys.argv[3] if len(sys.argv) > 3 else 'cpu'
 import build_lmdb                         # noqa: E402
 from yolo3 import lmdbio, imagereader     # noqa: E402
 
@@ -30,7 +33,14 @@ for i in range(64):
 path = os.path.join(tmp, 'train-syn.lmdb')
 lmdbio.write_environment(path, items)
 anchors = [(64, 384), (384, 64)]
-reader = imagereader.ImageReader(path, anchors, use_augmentation=bool(augment), shuffle=True, num_workers=workers, balance_classes=True)
+reader = imagereader.ImageReader(path, anchors, use_augmentation=bool(augment), shuffle=True, num_workers=workers, balance_classes=True,
+                                   augmentation_device=device)
+with lmdbio.Environment(path) as env:      # what one worker spends per example (lmdb + decode + augmentation or its draws + labels)
+    np.random.seed(0)
+    c0 = time.process_time()
+    for key in reader.keys_flat[:32]:
+        reader.load_example(key, env)
+    cpu_per_example = (time.process_time() - c0) / 32
 reader.startup()                          # worker processes are forked before this process touches the GPU
 import torch                              # noqa: E402
 from yolo3.model import YoloV3            # noqa: E402
@@ -52,6 +62,7 @@ for step in range(60):
         t_data += t1 - t0
         t_step += t2 - t1
         n += 1
-print('workers %d augment %d: %.1f images/s end to end (waiting for data %.1f ms, step %.1f ms per batch)'
-      % (workers, augment, 8 * n / (t_data + t_step), 1e3 * t_data / n, 1e3 * t_step / n))
 reader.shutdown()
+print('workers %d augment %d device %s: %.1f images/s end to end (waiting for data %.1f ms, step %.1f ms per batch); '
+      'reader CPU %.1f ms per example'
+      % (workers, augment, device, 8 * n / (t_data + t_step), 1e3 * t_data / n, 1e3 * t_step / n, 1e3 * cpu_per_example))
