@@ -7,6 +7,11 @@ calling an entry point that fails, raises.  Build with
 import ctypes as C
 import os
 
+# torch's HIP runtime first, always: torch ships its own libamdhip64 / libhsa-runtime64, and the library below links the system
+# ROCm's.  Loaded in the other order (`python __graft_entry__.py smoke`: build() imports this module before anything imports
+# torch) the library's first launch failed with "no ROCm-capable device is detected" while torch itself ran.
+import torch  # noqa: F401,E402
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('Y3_LIB') or os.path.join(_HERE, '_lib', 'libyolo3hip.so')     # Y3_LIB: A/B two builds (tools/)
 

@@ -1,6 +1,7 @@
 """Development helper (not a test): the model-level gradient errors of one training step against the fp64 oracle, per tensor,
 for both convolution arithmetics -- to tell sporadic leaky-relu / ignore-mask flips (a few tensors, different ones per arithmetic)
-from a systematic error of one arithmetic (many tensors, one of them).   python tests/grad_err_report.py [img] [batch]"""
+from a systematic error of one arithmetic (many tensors, one of them).   python tests/grad_err_report.py [img] [batch] [order]
+order: the arithmetic whose model is built first, then the other (default f32,x3)."""
 import os
 import sys
 
@@ -12,8 +13,11 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, 'object-detection-yolov3_amd'), os.path
 import test_gpu_model as T      # noqa: E402
 
 img, n = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (96, 4)
+order = sys.argv[3].split(',') if len(sys.argv) > 3 else ['f32', 'x3']
+assert sorted(order) == ['f32', 'x3'], order
+print('%d x %d, models built in the order %s' % (img, n, ', '.join(order)))
 out = {}
-for arith in ('f32', 'x3'):
+for arith in order:
     om, params, yolo, images, gts = T._setup(img, n, 11, False, conv_arithmetic=arith)
     if 'ref' not in out:
         res = {}
