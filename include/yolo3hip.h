@@ -418,6 +418,36 @@ int y3_augment_batch(const void* src, int dtype, int n, int h_in, int w_in, int 
                      float* out, void* workspace, y3_stream_t stream);
 size_t y3_augment_workspace_bytes(int n, int h_out, int w_out, int c);
 
+/* ---- detection accuracy: matching + 101-point AP (not in the reference; yolo3/metrics.py, evaluate.py) ----
+ * Detections are the keep lists of y3_nms_per_class: per (image, class) segment s = img * K + c the first
+ * min(keep_cnt[s], max_keep, max_det) entries of keep_idx / keep_score, in keep order (descending score, ties: higher row
+ * index).  A segment's pool entries start at offsets[s] (exclusive prefix over the segments, image-major) and run in keep
+ * order, so the pool order is (image, class, keep rank) and does not depend on how the images were batched.
+ *
+ * y3_eval_offsets: offsets[0..nseg) = that prefix, offsets[nseg] = the total (the one count the host reads per batch to
+ * size the pool).  One workgroup. */
+int y3_eval_offsets(const int* keep_cnt, int nseg, int max_keep, int max_det, int* offsets, y3_stream_t stream);
+/* y3_eval_match: rows [n, nb, ld floats] with corners x0,y0,x1,y1 first (the decode rows, ld = 5+K; or bare boxes, ld = 4),
+ * clipped to [0,clip_w]x[0,clip_h] as y3_nms_per_class clips them (clip_w <= 0: no clip).  gt [n, max_gt, 5] = corners x0,y0,
+ * x1,y1 + class (float), the first gt_cnt[i] rows valid.  max_gt_per_class: the host's bound on the GT boxes of one
+ * (image, class); they are staged in LDS, at most 4096 (Y3_EINVAL + message above that, nothing launched).  Per segment
+ * and threshold t (iou_thr_host: HOST array of num_thr in 1..32 values in (0, 1]): in keep order each detection takes the
+ * unmatched GT box of its class with the largest IoU if that IoU >= t (IoU: y3_compute_iou's fp32 arithmetic, detection
+ * first; equal IoU: the highest GT index) and is then a TP.  Writes, at pool position offsets[s] + j (< pool_capacity),
+ * pool_key = (class << 32) | ~order_key(score) (int64; ascending = class ascending, score descending; order_key maps fp32
+ * bits monotonically onto uint32) and pool_tp = TP mask (bit t).  One workgroup per segment, one wave per threshold. */
+int y3_eval_match(const float* rows, int n, int nb, int ld, int num_classes, float clip_w, float clip_h, const int* keep_idx,
+                  const int* keep_cnt, const float* keep_score, int max_keep, int max_det, const float* gt, const int* gt_cnt,
+                  int max_gt, int max_gt_per_class, const float* iou_thr_host, int num_thr, const int* offsets,
+                  long long* pool_key, unsigned* pool_tp, long long pool_capacity, y3_stream_t stream);
+/* y3_eval_ap: keys / tp [m] = the pool stably sorted by key (so ties keep the (image, keep rank) order), npos [K] = GT boxes
+ * per class.  Per (class c, threshold t): precision = tp_cum / (rank+1), its suffix maximum (envelope), AP = mean over
+ * j = 0..100 of the envelope at the first rank with 100 tp_cum >= j npos (0 if none); npos == 0 -> AP and recall NaN.
+ * ap, recall (final tp / npos), tp_count, fp_count: [K][T].  workspace: y3_eval_ap_workspace_bytes(m, num_thr). */
+int y3_eval_ap(const long long* keys, const unsigned* tp, long long m, int num_classes, int num_thr, const int* npos,
+               void* workspace, size_t workspace_bytes, float* ap, float* recall, int* tp_count, int* fp_count, y3_stream_t stream);
+size_t y3_eval_ap_workspace_bytes(long long m, int num_thr);
+
 /* ---- gradient exchange: tf.distribute.MirroredStrategy's all-reduce (train.py:38-39, model.py:500,510-515) -------
  * One process per GPU; SUM over the replicas (the loss is already divided by the global batch, model.py:492).  RCCL over
  * xGMI underneath (librccl.so is opened on first use).  Rank 0 calls y3_comm_unique_id and hands the 128 bytes to the

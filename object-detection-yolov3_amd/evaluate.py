@@ -1,0 +1,150 @@
+#!/usr/bin/env python3
+"""evaluate.py -- detection accuracy of a saved model: AP per class and IoU threshold, mAP@0.5 and mAP@0.5:0.95.
+
+Not in the reference.  The images go through inference.py's path (per-image z-score -> network -> clip -> small-box
+filter -> class-wise NMS, same defaults) and the NMS keep lists are matched against the ground truth on the GPU
+(yolo3.metrics.DetectionEvaluator; the metric is defined in DESIGN §3.6).  Ground truth comes from either
+  --database      an lmdb written by build_lmdb.py (the records as stored: no augmentation), or
+  --image-folder + --csv-folder   images and X,Y,W,H,C csv files of the same basename (build_lmdb.py's input).
+"""
+import argparse
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from yolo3 import bbox_utils, imagereader, lmdbio, metrics
+from yolo3.isg_ai_pb import ImageYoloBoxesPair
+from yolo3.model import YoloV3
+
+
+def load_model(path):
+    if os.path.isdir(path):
+        path = os.path.join(path, 'yolov3.npz')
+    return YoloV3.from_file(path)
+
+
+def database_examples(path):
+    """(name, HWC uint8 image, [G,5] X,Y,W,H,C) of every record, in key order."""
+    env = lmdbio.Environment(path)
+    try:
+        for key in env.keys():
+            img, boxes = ImageYoloBoxesPair().ParseFromString(env.get(key)).to_arrays()
+            yield key.decode('ascii'), img, np.asarray(boxes).reshape(-1, 5)
+    finally:
+        env.close()
+
+
+def folder_examples(image_folder, csv_folder, image_format):
+    """(name, HWC image, [G,5] X,Y,W,H,C) of every image of the folder, sorted by file name; the csv of image a.tif is
+    <csv_folder>/a.csv (build_lmdb.py); a missing csv means no ground truth."""
+    ext = '.' + image_format.lstrip('.')
+    for fn in sorted(f for f in os.listdir(image_folder) if f.endswith(ext)):
+        img = imagereader.imread(os.path.join(image_folder, fn))
+        stem = fn[:-len(ext)]
+        yield fn, (img[:, :, None] if img.ndim == 2 else img), bbox_utils.load_boxes_to_xywhc(os.path.join(csv_folder, stem + '.csv'))
+
+
+def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
+             max_detections=None):
+    """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds)."""
+    yolo = load_model(saved_model_filepath)
+    yolo.inference_precision = precision
+    model = yolo.get_keras_model()
+    ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
+    t0 = time.perf_counter()
+    batch = []
+
+    def flush():
+        imgs = [b[1] for b in batch]
+        if any(im.shape != imgs[0].shape for im in imgs):
+            raise RuntimeError('images must share one size (the model input is fixed): {}'.format({im.shape for im in imgs}))
+        height, width = imgs[0].shape[:2]
+        x = torch.from_numpy(np.stack([np.ascontiguousarray(im.astype(np.float32).transpose((2, 0, 1))) for im in imgs])).cuda()
+        rows = model(imagereader.zscore_normalize_device(x), training=False)
+        ev.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height))
+        batch.clear()
+
+    for ex in examples:
+        batch.append(ex)
+        if len(batch) == batch_size:
+            flush()
+    if batch:
+        flush()
+    res = ev.result()
+    torch.cuda.synchronize()
+    return res, ev.num_images, time.perf_counter() - t0
+
+
+def _fmt(v):
+    return '' if isinstance(v, float) and math.isnan(v) else repr(float(v))
+
+
+def write_csv(res, path):
+    """One row per class, then a 'mean' row (mean over the classes with ground truth; NaN cells are empty)."""
+    thr = res['iou_thresholds']
+    with open(path, 'w') as fh:
+        fh.write(','.join(['class', 'npos', 'tp', 'fp', 'precision', 'recall', 'f1', 'ap'] + ['ap@%.2f' % t for t in thr]) + '\n')
+        valid = res['npos'] > 0
+        for c in range(res['ap'].shape[0]):
+            ap_mean = float(res['ap'][c].mean()) if valid[c] else float('nan')
+            cells = [str(c), str(int(res['npos'][c])), str(int(res['tp50'][c])), str(int(res['fp50'][c])), _fmt(res['precision50'][c]),
+                     _fmt(res['recall50'][c]), _fmt(res['f1_50'][c]), _fmt(ap_mean)] + [_fmt(v) for v in res['ap'][c]]
+            fh.write(','.join(cells) + '\n')
+        fh.write(','.join(['mean', str(int(res['npos'].sum())), '', '', '', '', '', _fmt(res['map_all'])] + [_fmt(v) for v in res['map']]) + '\n')
+
+
+def print_table(res):
+    thr = res['iou_thresholds']
+    op = res['op_threshold']
+    print('{:>6} {:>7} {:>7} {:>7} {:>9} {:>9} {:>9} {:>9} {:>9}'.format('class', 'npos', 'tp', 'fp', 'precision', 'recall', 'f1',
+                                                                          'AP@%.2f' % op, 'AP'))
+    col = int(np.nonzero(thr == np.float32(op))[0][0])
+    for c in range(res['ap'].shape[0]):
+        print('{:>6} {:>7d} {:>7d} {:>7d} {:>9.4f} {:>9.4f} {:>9.4f} {:>9.4f} {:>9.4f}'.format(
+            c, int(res['npos'][c]), int(res['tp50'][c]), int(res['fp50'][c]), res['precision50'][c], res['recall50'][c], res['f1_50'][c],
+            res['ap'][c, col], float(np.mean(res['ap'][c]))))
+    print('tp / fp / precision / recall / f1 at IoU {:.2f}; AP = mean over IoU {}'.format(op, ', '.join('%.2f' % t for t in thr)))
+    print('mAP50 = {:.4f}  mAP50:95 = {:.4f}  mAP (all thresholds) = {:.4f}'.format(res['map50'], res['map50_95'], res['map_all']))
+
+
+if __name__ == '__main__':
+    parser = argparse.ArgumentParser(prog='evaluate', description='Script to measure the detection accuracy (AP / mAP) of the selected model')
+    parser.add_argument('--saved-model-filepath', type=str, help='Filepath to the saved model to use', required=True)
+    parser.add_argument('--database', type=str, default=None, help='lmdb written by build_lmdb.py (e.g. test-<name>.lmdb)')
+    parser.add_argument('--image-folder', dest='image_folder', type=str, default=None)
+    parser.add_argument('--csv-folder', dest='csv_folder', type=str, default=None, help='X,Y,W,H,C csv per image, same basename')
+    parser.add_argument('--image-format', dest='image_format', type=str, default='tif')
+    parser.add_argument('--min-box-size', type=int, default=32, help='Smallest detection to consider. Default (32, 32).')
+    parser.add_argument('--precision', choices=['fp32', 'bf16'], default='fp32', help='conv arithmetic')
+    parser.add_argument('--batch-size', type=int, default=8, help='images per model call')
+    parser.add_argument('--iou-thresholds', type=float, nargs='+', default=None,
+                        help='IoU thresholds (1..32 values in (0, 1]); default 0.50:0.05:0.95')
+    parser.add_argument('--max-detections', type=int, default=None, help='detections kept per image and class (default: all NMS keeps)')
+    parser.add_argument('--output-file', type=str, default=None, help='per-class csv')
+    a = parser.parse_args()
+    if (a.database is None) == (a.image_folder is None and a.csv_folder is None):
+        parser.error('give exactly one data source: --database, or --image-folder with --csv-folder')
+    if a.database is None and (a.image_folder is None or a.csv_folder is None):
+        parser.error('--image-folder and --csv-folder go together')
+    if a.batch_size < 1:
+        parser.error('--batch-size must be >= 1')
+    if a.max_detections is not None and a.max_detections < 1:
+        parser.error('--max-detections must be >= 1')
+    thresholds = metrics.COCO_IOU_THRESHOLDS if a.iou_thresholds is None else a.iou_thresholds
+    if not 1 <= len(thresholds) <= 32 or not all(0 < t <= 1 for t in thresholds):
+        parser.error('--iou-thresholds: 1..32 values in (0, 1]')
+    print('Arguments:')
+    for k, v in vars(a).items():
+        print('{} = {}'.format(k, v))
+    if a.database is not None:
+        examples = database_examples(a.database)
+    else:
+        examples = folder_examples(a.image_folder, a.csv_folder, a.image_format)
+    res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections)
+    print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
+    print_table(res)
+    if a.output_file:
+        write_csv(res, a.output_file)

@@ -1,0 +1,252 @@
+"""Detection accuracy: COCO-style 101-point AP / mAP of the ``detect`` path against ground truth, on the GPU.
+
+Not in the reference.  The metric (yolo3hip.h ``y3_eval_*``):
+
+- ground truth X,Y,W,H,C (build_lmdb.py / bbox_utils.load_boxes_to_xywhc) -> corners (X, Y, X+W, Y+H);
+- detections = the NMS keep lists (descending score, ties: higher row index), optionally cut to ``max_detections``
+  per (image, class);
+- per image, class and IoU threshold t, in keep order, a detection takes the unmatched GT box of its class with the
+  largest fp32 IoU (``y3_compute_iou``'s arithmetic; equal IoU: highest GT index) if that IoU >= t: a TP;
+- per (class, t) over all images, sorted by score descending (ties: image order, then keep rank): the 101-point
+  interpolated AP; a class without GT has AP NaN and is left out of every mean.
+
+Matching runs on the device (``y3_eval_match``) straight on ``nms_device``'s keep lists; each batch appends its
+(key, TP mask) entries to device pools at positions fixed by an exclusive prefix over the keep counts
+(``y3_eval_offsets``: the one count the host reads per batch).  ``result()`` sorts the pools once (torch.sort,
+stable) and runs ``y3_eval_ap``.
+"""
+import numpy as np
+import torch
+
+from ._hip import lib, check, float_array
+from . import bbox_utils
+
+COCO_IOU_THRESHOLDS = tuple(float(np.float32(0.5) + np.float32(0.05) * np.float32(k)) for k in range(10))
+MAX_GT_PER_CLASS = 4096     # Y3_EVAL_MAX_GT: the GT boxes of one (image, class) are staged in LDS
+
+
+def gt_corners(boxes_xywhc):
+    """[G,5] X,Y,W,H,C -> float32 [G,5] x0,y0,x1,y1,C."""
+    b = np.asarray(boxes_xywhc, np.float64).reshape(-1, 5)
+    out = np.empty((b.shape[0], 5), np.float32)
+    out[:, 0] = b[:, 0]
+    out[:, 1] = b[:, 1]
+    out[:, 2] = b[:, 0] + b[:, 2]
+    out[:, 3] = b[:, 1] + b[:, 3]
+    out[:, 4] = b[:, 4]
+    return out
+
+
+def decode_pool_key(keys):
+    """int64 pool keys -> (class int32, score float32) (inverse of the key y3_eval_match writes)."""
+    keys = np.asarray(keys, np.int64)
+    cls = (keys >> 32).astype(np.int32)
+    mono = (~(keys & 0xffffffff)) & 0xffffffff
+    bits = np.where(mono >= 2**31, mono - 2**31, (~mono) & 0xffffffff).astype(np.uint32)
+    return cls, bits.view(np.float32)
+
+
+class DetectionEvaluator:
+    """Accumulates matches over batches of images; ``result()`` gives AP / recall / TP / FP per (class, threshold).
+
+    iou_thresholds: 1..32 values in (0, 1], fp32 (default: COCO's 0.50:0.05:0.95).  max_detections: keep at most this
+    many detections per (image, class) in score order (default: every entry NMS kept)."""
+
+    def __init__(self, num_classes, iou_thresholds=COCO_IOU_THRESHOLDS, max_detections=None, device=None):
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError('num_classes must be >= 1')
+        thr = np.asarray(iou_thresholds, np.float32).reshape(-1)
+        if not 1 <= thr.size <= 32 or not np.all((thr > 0) & (thr <= 1)):
+            raise ValueError('iou_thresholds: 1..32 values in (0, 1], got {}'.format(list(thr)))
+        self.iou_thresholds = thr
+        if max_detections is not None and int(max_detections) < 1:
+            raise ValueError('max_detections must be >= 1')
+        self.max_detections = None if max_detections is None else int(max_detections)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._thr_host = float_array(thr)
+        self.reset()
+
+    def reset(self):
+        self._keys = torch.empty(0, dtype=torch.int64, device=self.device)
+        self._tp = torch.empty(0, dtype=torch.int32, device=self.device)
+        self._used = 0
+        self._npos = np.zeros(self.num_classes, np.int64)
+        self.num_images = 0
+
+    # ---- input paths ----------------------------------------------------------------------------------------------
+    def add_batch(self, rows, gt_boxes_per_image, min_box_size, clip_wh=None, iou_threshold=0.3, score_threshold=0.1):
+        """rows: CUDA float32 [N, Nb, 5+K] (the network's decode rows); gt_boxes_per_image: N arrays [G,5] X,Y,W,H,C.
+        Runs the ``detect`` path's NMS (``bbox_utils.nms_device``, same clip / small-box filter / thresholds) and matches
+        its keep lists on the device; no detection leaves the GPU."""
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3
+        n, nb, d = rows.shape
+        if d - 5 != self.num_classes:
+            raise ValueError('rows carry {} classes, the evaluator {}'.format(d - 5, self.num_classes))
+        gt = self._gt_batch(gt_boxes_per_image, n)
+        rows = rows.contiguous()
+        keep_idx, keep_cnt, keep_score = bbox_utils.nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh)
+        cw, chh = (float(clip_wh[0]), float(clip_wh[1])) if clip_wh is not None else (-1.0, -1.0)
+        self._match(rows, n, nb, d, cw, chh, keep_idx, keep_cnt, keep_score, nb, gt)
+
+    def add_detections(self, boxes, scores, labels, gt, row_index=None):
+        """Host detections from any source, one entry per image: boxes [M,4] corners x0,y0,x1,y1, scores [M], labels [M]
+        int class ids, gt [G,5] X,Y,W,H,C; an image's boxes may be None (no detections, as ``bbox_utils.detect`` returns).
+        Sorted on the host into keep order (score descending, ties: higher row index; row_index: per image [M] ints, e.g.
+        ``detect``'s keep rows, default the position in the array) and matched by the same kernels as ``add_batch``
+        (no clip)."""
+        n = len(boxes)
+        if row_index is None:
+            row_index = [None] * n
+        if not (len(scores) == len(labels) == len(gt) == len(row_index) == n) or n == 0:
+            raise ValueError('boxes, scores, labels and gt need one entry per image (at least one image)')
+        K = self.num_classes
+        per = []
+        for i in range(n):
+            if boxes[i] is None:                  # bbox_utils.detect's (None,)*4 for an image without detections
+                per.append((np.zeros((0, 4), np.float32), np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64)))
+                continue
+            b = np.asarray(boxes[i], np.float32).reshape(-1, 4)
+            s = np.asarray(scores[i], np.float32).reshape(-1)
+            lab = np.asarray(labels[i]).reshape(-1)
+            if not (b.shape[0] == s.shape[0] == lab.shape[0]):
+                raise ValueError('image {}: {} boxes, {} scores, {} labels'.format(i, b.shape[0], s.shape[0], lab.shape[0]))
+            if not (np.all(np.isfinite(b)) and np.all(np.isfinite(s))):
+                raise ValueError('image {}: non-finite box or score'.format(i))
+            if lab.size and (lab.min() < 0 or lab.max() >= K or np.any(lab != np.round(lab))):
+                raise ValueError('image {}: labels outside 0..{}'.format(i, K - 1))
+            rid = np.arange(b.shape[0]) if row_index[i] is None else np.asarray(row_index[i], np.int64).reshape(-1)
+            if rid.shape[0] != b.shape[0]:
+                raise ValueError('image {}: {} row indices for {} boxes'.format(i, rid.shape[0], b.shape[0]))
+            per.append((b, s, lab.astype(np.int64), rid))
+        mb = max(1, max(p[0].shape[0] for p in per))
+        rows = np.zeros((n, mb, 4), np.float32)
+        keep_idx = np.zeros((n, K, mb), np.int32)
+        keep_cnt = np.zeros((n, K), np.int32)
+        keep_score = np.zeros((n, K, mb), np.float32)
+        for i, (b, s, lab, rid) in enumerate(per):
+            rows[i, :b.shape[0]] = b
+            for c in range(K):
+                idx = np.nonzero(lab == c)[0]
+                order = idx[np.lexsort((-rid[idx], -s[idx].astype(np.float64)))]     # score desc, then higher row index first
+                keep_idx[i, c, :order.size] = order
+                keep_score[i, c, :order.size] = s[order]
+                keep_cnt[i, c] = order.size
+        gtb = self._gt_batch(gt, n)
+        dev = self.device
+        self._match(torch.from_numpy(rows).to(dev), n, mb, 4, -1.0, -1.0, torch.from_numpy(keep_idx).to(dev),
+                    torch.from_numpy(keep_cnt).to(dev), torch.from_numpy(keep_score).to(dev), mb, gtb)
+
+    # ---- device plumbing ------------------------------------------------------------------------------------------
+    def _gt_batch(self, gt_list, n):
+        if len(gt_list) != n:
+            raise ValueError('{} ground-truth entries for {} images'.format(len(gt_list), n))
+        K = self.num_classes
+        corners = [gt_corners(g) for g in gt_list]
+        npos = np.zeros(K, np.int64)
+        worst = 0
+        for i, g in enumerate(corners):
+            if not np.all(np.isfinite(g)):
+                raise ValueError('image {}: non-finite ground truth'.format(i))
+            c = g[:, 4]
+            if c.size and (c.min() < 0 or c.max() >= K or np.any(c != np.round(c))):
+                raise ValueError('image {}: ground-truth classes outside 0..{}'.format(i, K - 1))
+            per = np.bincount(c.astype(np.int64), minlength=K)
+            npos += per
+            worst = max(worst, int(per.max()) if per.size else 0)
+        max_gt = max(1, max(g.shape[0] for g in corners))
+        buf = np.zeros((n, max_gt, 5), np.float32)
+        cnt = np.zeros(n, np.int32)
+        for i, g in enumerate(corners):
+            buf[i, :g.shape[0]] = g
+            cnt[i] = g.shape[0]
+        return buf, cnt, max_gt, worst, npos
+
+    def _match(self, rows, n, nb, ld, clip_w, clip_h, keep_idx, keep_cnt, keep_score, max_keep, gt):
+        buf, cnt, max_gt, worst, npos = gt
+        dev = self.device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        K = self.num_classes
+        max_det = max_keep if self.max_detections is None else min(self.max_detections, max_keep)
+        offsets = torch.empty(n * K + 1, dtype=torch.int32, device=dev)
+        check(lib.y3_eval_offsets(keep_cnt.data_ptr(), n * K, max_keep, max_det, offsets.data_ptr(), st), 'y3_eval_offsets')
+        gt_dev = torch.from_numpy(buf).to(dev)
+        cnt_dev = torch.from_numpy(cnt).to(dev)
+        total = int(offsets[n * K].item())                                # the one host read of the batch
+        self._reserve(self._used + total)             # only grows capacity: a refused batch below (GT over the LDS cap) adds nothing
+        used = self._used
+        check(lib.y3_eval_match(rows.data_ptr(), n, nb, ld, K, clip_w, clip_h, keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(),
+                                max_keep, max_det, gt_dev.data_ptr(), cnt_dev.data_ptr(), max_gt, worst, self._thr_host,
+                                len(self.iou_thresholds), offsets.data_ptr(), self._keys.data_ptr() + 8 * used,
+                                self._tp.data_ptr() + 4 * used, self._keys.numel() - used, st), 'y3_eval_match')
+        self._used += total
+        self._npos += npos
+        self.num_images += n
+
+    def _reserve(self, need):
+        cap = self._keys.numel()
+        if need <= cap and cap > 0:                   # never empty: y3_eval_match takes the pool even for a batch without detections
+            return
+        cap = max(need, 2 * cap, 1024)
+        keys = torch.empty(cap, dtype=torch.int64, device=self.device)
+        tp = torch.empty(cap, dtype=torch.int32, device=self.device)
+        keys[:self._used] = self._keys[:self._used]
+        tp[:self._used] = self._tp[:self._used]
+        self._keys, self._tp = keys, tp
+
+    # ---- output ---------------------------------------------------------------------------------------------------
+    def matches(self):
+        """Pool entries in (image, class, keep rank) order: (class int32 [M], score float32 [M], TP mask uint32 [M])."""
+        keys = self._keys[:self._used].cpu().numpy()
+        cls, score = decode_pool_key(keys)
+        return cls, score, self._tp[:self._used].cpu().numpy().view(np.uint32)
+
+    def result(self):
+        """dict of NumPy arrays (K = classes, T = thresholds):
+        ap, recall [K,T] (NaN where npos == 0), tp, fp [K,T], npos [K], iou_thresholds [T], map [T] (mean AP over classes
+        with npos > 0), map50 (t = 0.5; NaN if 0.5 is not a threshold), map50_95 (mean over classes and the ten COCO
+        thresholds; NaN unless those are the thresholds), map_all (mean over classes and all thresholds), and at the
+        operating-point threshold op_threshold (0.5, else the first one): tp50, fp50, precision50 (TP / (TP+FP), 0 without
+        detections), recall50 (TP / npos, NaN without GT), f1_50 (0 when precision + recall is 0)."""
+        dev = self.device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        K, T, m = self.num_classes, len(self.iou_thresholds), self._used
+        keys, order = torch.sort(self._keys[:m], stable=True)
+        tp = self._tp[:m][order].contiguous()
+        keys = keys.contiguous()
+        npos = torch.from_numpy(self._npos.astype(np.int32)).to(dev)
+        ws_bytes = int(lib.y3_eval_ap_workspace_bytes(m, T))
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
+        ap = torch.empty(K, T, dtype=torch.float32, device=dev)
+        rec = torch.empty(K, T, dtype=torch.float32, device=dev)
+        tpc = torch.empty(K, T, dtype=torch.int32, device=dev)
+        fpc = torch.empty(K, T, dtype=torch.int32, device=dev)
+        check(lib.y3_eval_ap(keys.data_ptr() if m else None, tp.data_ptr() if m else None, m, K, T, npos.data_ptr(), ws.data_ptr(),
+                             ws_bytes, ap.data_ptr(), rec.data_ptr(), tpc.data_ptr(), fpc.data_ptr(), st), 'y3_eval_ap')
+        return summarize(ap.cpu().numpy().astype(np.float64), rec.cpu().numpy().astype(np.float64), tpc.cpu().numpy().astype(np.int64),
+                         fpc.cpu().numpy().astype(np.int64), self._npos.copy(), self.iou_thresholds)
+
+
+def summarize(ap, recall, tp, fp, npos, iou_thresholds):
+    """The result dict of DetectionEvaluator.result() from the per-(class, threshold) numbers."""
+    thr = np.asarray(iou_thresholds, np.float32)
+    valid = npos > 0
+    with np.errstate(invalid='ignore', divide='ignore'):
+        per_t = ap[valid].mean(axis=0) if valid.any() else np.full(thr.size, np.nan)
+        hits = np.nonzero(thr == np.float32(0.5))[0]
+        op = int(hits[0]) if hits.size else 0
+        t50, f50 = tp[:, op], fp[:, op]
+        prec = np.where(t50 + f50 > 0, t50 / np.maximum(t50 + f50, 1), 0.0)
+        rec = np.where(valid, t50 / np.maximum(npos, 1), np.nan)
+        s = prec + rec
+        ok = valid & (s > 0)
+        f1 = np.where(valid, 0.0, np.nan)
+        f1[ok] = 2 * prec[ok] * rec[ok] / s[ok]
+    coco = thr.size == 10 and np.array_equal(thr, np.asarray(COCO_IOU_THRESHOLDS, np.float32))
+    return {
+        'ap': ap, 'recall': recall, 'tp': tp, 'fp': fp, 'npos': npos, 'iou_thresholds': thr, 'map': per_t,
+        'map50': float(per_t[hits[0]]) if hits.size else float('nan'),
+        'map50_95': float(ap[valid].mean()) if coco and valid.any() else float('nan'),
+        'map_all': float(ap[valid].mean()) if valid.any() else float('nan'),
+        'op_threshold': float(thr[op]), 'tp50': t50, 'fp50': f50, 'precision50': prec, 'recall50': rec, 'f1_50': f1,
+    }
