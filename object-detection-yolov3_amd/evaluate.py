@@ -6,6 +6,8 @@ filter -> class-wise NMS, same defaults) and the NMS keep lists are matched agai
 (yolo3.metrics.DetectionEvaluator; the metric is defined in DESIGN §3.6).  Ground truth comes from either
   --database      an lmdb written by build_lmdb.py (the records as stored: no augmentation), or
   --image-folder + --csv-folder   images and X,Y,W,H,C csv files of the same basename (build_lmdb.py's input).
+Under `python -m torch.distributed.run --nproc-per-node N` every rank evaluates every N-th example (keys[rank::N]) and
+the ranks' evaluators are merged (yolo3.metrics.all_gather_evaluator, a collective); rank 0 prints and writes the csv.
 """
 import argparse
 import math
@@ -15,8 +17,7 @@ import time
 import numpy as np
 import torch
 
-from yolo3 import bbox_utils, imagereader, lmdbio, metrics
-from yolo3.isg_ai_pb import ImageYoloBoxesPair
+from yolo3 import bbox_utils, imagereader, metrics
 from yolo3.model import YoloV3
 
 
@@ -26,53 +27,33 @@ def load_model(path):
     return YoloV3.from_file(path)
 
 
-def database_examples(path):
-    """(name, HWC uint8 image, [G,5] X,Y,W,H,C) of every record, in key order."""
-    env = lmdbio.Environment(path)
-    try:
-        for key in env.keys():
-            img, boxes = ImageYoloBoxesPair().ParseFromString(env.get(key)).to_arrays()
-            yield key.decode('ascii'), img, np.asarray(boxes).reshape(-1, 5)
-    finally:
-        env.close()
+def database_examples(path, num_shards=1, shard_index=0):
+    """(name, HWC uint8 image, [G,5] X,Y,W,H,C) of every num_shards-th record from shard_index on, in key order."""
+    return metrics.database_examples(path, num_shards, shard_index)
 
 
-def folder_examples(image_folder, csv_folder, image_format):
-    """(name, HWC image, [G,5] X,Y,W,H,C) of every image of the folder, sorted by file name; the csv of image a.tif is
-    <csv_folder>/a.csv (build_lmdb.py); a missing csv means no ground truth."""
+def folder_examples(image_folder, csv_folder, image_format, num_shards=1, shard_index=0):
+    """(name, HWC image, [G,5] X,Y,W,H,C) of every image of the folder, sorted by file name (every num_shards-th from
+    shard_index on); the csv of image a.tif is <csv_folder>/a.csv (build_lmdb.py); a missing csv means no ground truth."""
     ext = '.' + image_format.lstrip('.')
-    for fn in sorted(f for f in os.listdir(image_folder) if f.endswith(ext)):
+    for fn in sorted(f for f in os.listdir(image_folder) if f.endswith(ext))[shard_index::num_shards]:
         img = imagereader.imread(os.path.join(image_folder, fn))
         stem = fn[:-len(ext)]
         yield fn, (img[:, :, None] if img.ndim == 2 else img), bbox_utils.load_boxes_to_xywhc(os.path.join(csv_folder, stem + '.csv'))
 
 
 def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
-             max_detections=None):
-    """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds)."""
+             max_detections=None, distributed=False):
+    """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds).
+    distributed: a collective over the default process group; every rank passes its keys[rank::world] share of the
+    examples and gets the result over all of them."""
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision
-    model = yolo.get_keras_model()
     ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
     t0 = time.perf_counter()
-    batch = []
-
-    def flush():
-        imgs = [b[1] for b in batch]
-        if any(im.shape != imgs[0].shape for im in imgs):
-            raise RuntimeError('images must share one size (the model input is fixed): {}'.format({im.shape for im in imgs}))
-        height, width = imgs[0].shape[:2]
-        x = torch.from_numpy(np.stack([np.ascontiguousarray(im.astype(np.float32).transpose((2, 0, 1))) for im in imgs])).cuda()
-        rows = model(imagereader.zscore_normalize_device(x), training=False)
-        ev.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height))
-        batch.clear()
-
-    for ex in examples:
-        batch.append(ex)
-        if len(batch) == batch_size:
-            flush()
-    if batch:
-        flush()
+    metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size)
+    if distributed:
+        ev = metrics.all_gather_evaluator(ev)
     res = ev.result()
     torch.cuda.synchronize()
     return res, ev.num_images, time.perf_counter() - t0
@@ -124,6 +105,8 @@ if __name__ == '__main__':
                         help='IoU thresholds (1..32 values in (0, 1]); default 0.50:0.05:0.95')
     parser.add_argument('--max-detections', type=int, default=None, help='detections kept per image and class (default: all NMS keeps)')
     parser.add_argument('--output-file', type=str, default=None, help='per-class csv')
+    parser.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend under torch.distributed.run: nccl (= RCCL, '
+                        'one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
     a = parser.parse_args()
     if (a.database is None) == (a.image_folder is None and a.csv_folder is None):
         parser.error('give exactly one data source: --database, or --image-folder with --csv-folder')
@@ -136,15 +119,30 @@ if __name__ == '__main__':
     thresholds = metrics.COCO_IOU_THRESHOLDS if a.iou_thresholds is None else a.iou_thresholds
     if not 1 <= len(thresholds) <= 32 or not all(0 < t <= 1 for t in thresholds):
         parser.error('--iou-thresholds: 1..32 values in (0, 1]')
-    print('Arguments:')
-    for k, v in vars(a).items():
-        print('{} = {}'.format(k, v))
+    world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
+    if world > 1:
+        import torch.distributed as dist
+        device = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')) % torch.cuda.device_count())
+        torch.cuda.set_device(device)
+        if a.backend == 'nccl':
+            dist.init_process_group('nccl', device_id=device)
+        else:
+            dist.init_process_group(a.backend)
+    if rank == 0:
+        print('Arguments:')
+        for k, v in vars(a).items():
+            print('{} = {}'.format(k, v))
     if a.database is not None:
-        examples = database_examples(a.database)
+        examples = database_examples(a.database, world, rank)
     else:
-        examples = folder_examples(a.image_folder, a.csv_folder, a.image_format)
-    res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections)
-    print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
-    print_table(res)
-    if a.output_file:
-        write_csv(res, a.output_file)
+        examples = folder_examples(a.image_folder, a.csv_folder, a.image_format, world, rank)
+    res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
+                                distributed=world > 1)
+    if rank == 0:
+        print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
+        print_table(res)
+        if a.output_file:
+            write_csv(res, a.output_file)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()

@@ -9,6 +9,8 @@ global batch = batch_size x replicas (:41), Adam warm-up at lr/10 for min(1000, 
 "step > N: break" loop bound (N+1 steps, Q16), NaN-loss abort (:124-125), per-step metric print, test loop of
 image_count/batch_size(+1) batches (:76,:144), test_loss.csv (:170-173), best checkpoint on a new minimum (:178-182),
 early stopping with CONVERGENCE_TOLERANCE 1e-4 (:185-197), final export of the best checkpoint (:208-221).
+Added (opt-in, off by default): --test_map 1 runs a test-set mAP pass after every test epoch (<out>/test_map.csv), and
+--model_selection map50 / map50_95 checkpoints and stops early on that mAP instead of the test loss.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -40,6 +42,64 @@ def is_new_minimum(test_loss):
     return (len(test_loss) - 1) == int(np.argmin(test_loss))
 
 
+def best_epoch_of_max(scores, tolerance=CONVERGENCE_TOLERANCE):
+    """best_epoch_of for a score where higher is better (mAP): the FIRST epoch within `tolerance` of the maximum.  NaN
+    epochs (no ground truth) never count."""
+    v = np.asarray(scores, np.float64)
+    if np.all(np.isnan(v)):
+        raise ValueError('no epoch has a finite score')
+    with np.errstate(invalid='ignore'):
+        error_from_best = np.abs(v - np.nanmax(v))
+        error_from_best[error_from_best < tolerance] = 0
+    return int(np.where(error_from_best == 0)[0][0])
+
+
+def should_stop_max(scores, early_stopping_count, tolerance=CONVERGENCE_TOLERANCE):
+    """should_stop for a higher-is-better score: more than `early_stopping_count` epochs since the best one."""
+    return len(scores) - best_epoch_of_max(scores, tolerance) > early_stopping_count
+
+
+def is_new_maximum(scores):
+    """is_new_minimum for a higher-is-better score: the newest value is the (first) maximum; a NaN never is."""
+    v = np.asarray(scores, np.float64)
+    return not np.isnan(v[-1]) and (len(v) - 1) == int(np.argmax(np.where(np.isnan(v), -np.inf, v)))
+
+
+MODEL_SELECTIONS = ('loss', 'map50', 'map50_95')
+
+
+def effective_test_map(test_map, model_selection):
+    """--test_map as it takes effect: a mAP model selection needs the mAP pass, so it implies --test_map 1."""
+    if model_selection not in MODEL_SELECTIONS:
+        raise ValueError('model_selection must be one of {}, got {!r}'.format(MODEL_SELECTIONS, model_selection))
+    return bool(test_map) or model_selection != 'loss'
+
+
+def evaluate_test_map(yolo, strategy, database, batch_size, min_box_size, world, rank):
+    """One mAP pass over the test lmdb (COCO thresholds): this rank reads its keys[rank::world] share in this process and runs
+    it through the live model's fp32 predict plan (the plan test_step uses), then the ranks' evaluators are merged.  With
+    world > 1 the model evaluated is the one a checkpoint would save: the MEAN of the replicas' BN moving statistics
+    (App. C4) is swapped in for the pass and every replica's own values are put back after.  A collective: every rank
+    calls it.  Returns (DetectionEvaluator.result() over the whole test set, images, seconds)."""
+    from yolo3 import metrics
+    t0 = time.time()
+    own = None
+    if strategy is not None:
+        mean = strategy.mean_moving_stats(yolo.moving)
+        own = yolo.moving.clone()
+        yolo.moving.copy_(mean)
+    try:
+        ev = metrics.DetectionEvaluator(yolo.number_classes)
+        metrics.evaluate_examples(yolo, metrics.database_examples(database, world, rank), ev, min_box_size, batch_size, precision='fp32')
+    finally:
+        if own is not None:
+            yolo.moving.copy_(own)
+    if world > 1:
+        ev = metrics.all_gather_evaluator(ev)
+    res = ev.result()
+    return res, ev.num_images, time.time() - t0
+
+
 def abort_on_nan(loss_value, message):
     """train.py:124-125,151-152."""
     if np.isnan(float(loss_value)):
@@ -58,7 +118,9 @@ def effective_reader_count(requested, cpus, local_world):
 
 
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
-                learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu'):
+                learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
+                test_map=False, model_selection='loss', test_map_min_box_size=32):
+    test_map = effective_test_map(test_map, model_selection)
     os.makedirs(output_folder, exist_ok=True)
     anchors = [(64, 384), (384, 64)]
 
@@ -127,6 +189,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         train_epoch_size = test_every_n_steps
         test_epoch_size = test_reader.get_image_count() / batch_size
         test_loss = list()
+        map_rows = list()          # test_map.csv: epoch, map50, map50_95, tp50, fp50, npos
+        map_scores = list()        # the --model_selection mAP per epoch
         names = ['loss', 'loss_xy', 'loss_wh', 'loss_obj', 'loss_class']
         train_metrics = [model.Mean('train_' + n) for n in names]
         test_metrics = [model.Mean('test_' + n) for n in names]
@@ -182,6 +246,21 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             for m in test_metrics:
                 m.reset_states()
 
+            if test_map:
+                res, map_images, map_secs = evaluate_test_map(yolo, strategy, test_database_filepath, batch_size, test_map_min_box_size, world, rank)
+                print('Test Epoch: {}: mAP50 = {}, mAP50:95 = {} ({} images, mAP pass took {:.3f} s)'.format(
+                    epoch, res['map50'], res['map50_95'], map_images, map_secs))
+                if model_selection != 'loss':
+                    if not map_scores and int(res['npos'].sum()) == 0:
+                        raise RuntimeError('--model_selection {}: the test set holds no ground-truth boxes, so its mAP is undefined'.format(model_selection))
+                    map_scores.append(res[model_selection])
+                map_rows.append((epoch, res['map50'], res['map50_95'], int(res['tp50'].sum()), int(res['fp50'].sum()), int(res['npos'].sum())))
+                if rank == 0:
+                    with open(os.path.join(output_folder, 'test_map.csv'), 'w') as csvfile:
+                        csvfile.write('epoch,map50,map50_95,tp50,fp50,npos\n')
+                        for row in map_rows:
+                            csvfile.write('{},{!r},{!r},{},{},{}\n'.format(*row))
+
             if rank == 0:
                 with open(os.path.join(output_folder, 'test_loss.csv'), 'w') as csvfile:
                     for v in test_loss:
@@ -189,8 +268,15 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                         csvfile.write('\n')
             print('Epoch took: {} s'.format(time.time() - start_time))
 
-            if is_new_minimum(test_loss):
-                print('Test loss improved: {}, saving checkpoint'.format(np.min(test_loss)))
+            if model_selection == 'loss':
+                improved = is_new_minimum(test_loss)
+                if improved:
+                    print('Test loss improved: {}, saving checkpoint'.format(np.min(test_loss)))
+            else:
+                improved = is_new_maximum(map_scores)
+                if improved:
+                    print('Test {} improved: {}, saving checkpoint'.format(model_selection, map_scores[-1]))
+            if improved:
                 # BN moving statistics are sync-on-read: the checkpoint stores their MEAN over the replicas (App. C4); every
                 # replica keeps its own running values (a collective: all ranks take part, rank 0 writes)
                 saved_moving = strategy.mean_moving_stats(yolo.moving) if strategy is not None else None
@@ -200,11 +286,18 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                     yolo.save_weights(training_checkpoint_filepath, moving=saved_moving)
 
             print('Best Current Epoch Selection:')
-            print('Test Loss:')
-            print(test_loss)
-            print('Best epoch: {}'.format(best_epoch_of(test_loss)))
-            if should_stop(test_loss, early_stopping_count):
-                break
+            if model_selection == 'loss':
+                print('Test Loss:')
+                print(test_loss)
+                print('Best epoch: {}'.format(best_epoch_of(test_loss)))
+                if should_stop(test_loss, early_stopping_count):
+                    break
+            else:
+                print('Test {}:'.format(model_selection))
+                print(map_scores)
+                print('Best epoch: {}'.format(best_epoch_of_max(map_scores)))
+                if should_stop_max(map_scores, early_stopping_count):
+                    break
             epoch = epoch + 1
             if max_epochs is not None and epoch >= max_epochs:
                 break
@@ -243,10 +336,17 @@ if __name__ == "__main__":
     parser.add_argument('--augmentation_device', dest='augmentation_device', choices=('cpu', 'gpu'), default='cpu',
                         help='(addition) where the readers\' images are augmented: cpu = in the reader processes (as the reference), gpu = drawn '
                              'there, applied to each batch by HIP kernels; the test reader (no augmentation) uploads its pixels unconverted either way round')
+    parser.add_argument('--test_map', dest='test_map', type=int, choices=(0, 1), default=0,
+                        help='(addition) 1: after every test epoch, one mAP pass over the test lmdb (COCO thresholds), printed and written to <output_dir>/test_map.csv')
+    parser.add_argument('--test_map_min_box_size', dest='test_map_min_box_size', type=int, default=32,
+                        help='(addition) smallest detection the mAP pass considers (as evaluate.py --min-box-size)')
+    parser.add_argument('--model_selection', dest='model_selection', choices=MODEL_SELECTIONS, default='loss',
+                        help='(addition) what picks the checkpoint and drives early stopping: the test loss (first minimum, as the reference) '
+                             'or the test-set mAP50 / mAP50:95 (first maximum; implies --test_map 1)')
     a = parser.parse_args()
     print('Arguments:')
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
-                a.augmentation_device)
+                a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size)

@@ -14,12 +14,18 @@ Matching runs on the device (``y3_eval_match``) straight on ``nms_device``'s kee
 (key, TP mask) entries to device pools at positions fixed by an exclusive prefix over the keep counts
 (``y3_eval_offsets``: the one count the host reads per batch).  ``result()`` sorts the pools once (torch.sort,
 stable) and runs ``y3_eval_ap``.
+
+Across processes: ``state()`` exports the pools with the number of entries each image added, ``merge``
+concatenates several states' per-image blocks in global image order (the single-process pool order, so the merged
+result is bit-identical to one evaluator that saw every image), and ``all_gather_evaluator`` does that over a
+torch.distributed group.  ``evaluate_examples`` is the batching loop evaluate.py and train.py --test_map share.
 """
 import numpy as np
 import torch
 
 from ._hip import lib, check, float_array
-from . import bbox_utils
+from . import bbox_utils, imagereader, lmdbio
+from .isg_ai_pb import ImageYoloBoxesPair
 
 COCO_IOU_THRESHOLDS = tuple(float(np.float32(0.5) + np.float32(0.05) * np.float32(k)) for k in range(10))
 MAX_GT_PER_CLASS = 4096     # Y3_EVAL_MAX_GT: the GT boxes of one (image, class) are staged in LDS
@@ -71,6 +77,7 @@ class DetectionEvaluator:
         self._keys = torch.empty(0, dtype=torch.int64, device=self.device)
         self._tp = torch.empty(0, dtype=torch.int32, device=self.device)
         self._used = 0
+        self._counts = []         # per batch: int32 device [n] = pool entries each image added (image order)
         self._npos = np.zeros(self.num_classes, np.int64)
         self.num_images = 0
 
@@ -180,6 +187,7 @@ class DetectionEvaluator:
                                 len(self.iou_thresholds), offsets.data_ptr(), self._keys.data_ptr() + 8 * used,
                                 self._tp.data_ptr() + 4 * used, self._keys.numel() - used, st), 'y3_eval_match')
         self._used += total
+        self._counts.append(torch.diff(offsets[0::K]))               # image i's entries: offsets[(i+1)K] - offsets[iK]
         self._npos += npos
         self.num_images += n
 
@@ -193,6 +201,61 @@ class DetectionEvaluator:
         keys[:self._used] = self._keys[:self._used]
         tp[:self._used] = self._tp[:self._used]
         self._keys, self._tp = keys, tp
+
+    # ---- state across processes -----------------------------------------------------------------------------------
+    def image_counts(self):
+        """int32 device [num_images]: pool entries each image added, in image order (they sum to the pool size)."""
+        if len(self._counts) != 1:
+            self._counts = [torch.cat(self._counts) if self._counts else torch.empty(0, dtype=torch.int32, device=self.device)]
+        return self._counts[0]
+
+    def state(self):
+        """What ``merge`` / ``all_gather_evaluator`` combine (device tensors are copies): keys int64 [M], tp int32 [M] = the
+        pools in (image, class, keep rank) order, image_counts int32 [num_images], npos int64 [K] (NumPy), num_images,
+        iou_thresholds (float32), num_classes, max_detections."""
+        return {'keys': self._keys[:self._used].clone(), 'tp': self._tp[:self._used].clone(), 'image_counts': self.image_counts().clone(),
+                'npos': self._npos.copy(), 'num_images': self.num_images, 'iou_thresholds': self.iou_thresholds.copy(),
+                'num_classes': self.num_classes, 'max_detections': self.max_detections}
+
+    @classmethod
+    def merge(cls, states, order='strided', device=None):
+        """A new evaluator holding the images of every state, its pool in GLOBAL image order.  order: 'strided' (W states:
+        global image g is local image g // W of state g % W, the keys[rank::world] split of ImageReader(num_shards=W) and
+        inference.py), or an explicit sequence of (state, local image) pairs naming every image once.  ``result()`` sorts
+        stably, so equal scores rank by pool position: rebuilding the single-process order makes the merged result
+        bit-identical to one evaluator fed all images in that order.  States must share thresholds, classes and
+        max_detections."""
+        states = list(states)
+        if not states:
+            raise ValueError('merge needs at least one state')
+        s0 = states[0]
+        thr0 = np.asarray(s0['iou_thresholds'], np.float32)
+        for i, s in enumerate(states[1:], 1):
+            thr = np.asarray(s['iou_thresholds'], np.float32)
+            if s['num_classes'] != s0['num_classes'] or s['max_detections'] != s0['max_detections'] or not np.array_equal(thr, thr0):
+                raise ValueError('state {} does not match state 0: classes {} / {}, max_detections {} / {}, iou_thresholds {} / {}'.format(
+                    i, s['num_classes'], s0['num_classes'], s['max_detections'], s0['max_detections'], list(thr), list(thr0)))
+        state_index, local_index = global_image_order([int(s['num_images']) for s in states], order)
+        ev = cls(s0['num_classes'], thr0, s0['max_detections'], device)
+        dev = ev.device
+        counts = []
+        for i, s in enumerate(states):
+            c = s['image_counts'].to(dev, torch.int64)
+            if c.numel() != int(s['num_images']) or int(c.sum()) != s['keys'].numel() or s['tp'].numel() != s['keys'].numel():
+                raise ValueError('state {}: {} image counts summing to {} for {} images and {} keys / {} TP masks'.format(
+                    i, c.numel(), int(c.sum()), s['num_images'], s['keys'].numel(), s['tp'].numel()))
+            counts.append(c)
+        total = sum(s['keys'].numel() for s in states)
+        idx, cnt = pool_gather_index(counts, state_index, local_index, total)
+        ev._reserve(total)
+        if total:
+            ev._keys[:total] = torch.cat([s['keys'].to(dev) for s in states])[idx]
+            ev._tp[:total] = torch.cat([s['tp'].to(dev) for s in states])[idx]
+        ev._used = total
+        ev._counts = [cnt.to(torch.int32)]
+        ev._npos = np.sum([np.asarray(s['npos'], np.int64) for s in states], axis=0)
+        ev.num_images = int(state_index.size)
+        return ev
 
     # ---- output ---------------------------------------------------------------------------------------------------
     def matches(self):
@@ -250,3 +313,130 @@ def summarize(ap, recall, tp, fp, npos, iou_thresholds):
         'map_all': float(ap[valid].mean()) if valid.any() else float('nan'),
         'op_threshold': float(thr[op]), 'tp50': t50, 'fp50': f50, 'precision50': prec, 'recall50': rec, 'f1_50': f1,
     }
+
+
+def global_image_order(num_images, order='strided'):
+    """(state index, local image index): int64 arrays [N], entry g = where global image g lives.  num_images: images per
+    state.  'strided': W states, global image g = local image g // W of state g % W; state s must hold ceil((N - s) / W)
+    of the N images.  Otherwise ``order`` is a sequence of (state, local image) pairs naming every image exactly once."""
+    counts = [int(v) for v in num_images]
+    W, N = len(counts), sum(counts)
+    if W == 0:
+        raise ValueError('no states')
+    if isinstance(order, str):
+        if order != 'strided':
+            raise ValueError("order must be 'strided' or a sequence of (state, local image) pairs, got {!r}".format(order))
+        want = [(N - s + W - 1) // W for s in range(W)]
+        if counts != want:
+            raise ValueError('image counts {} are not a strided split of {} images over {} states ({})'.format(counts, N, W, want))
+        g = np.arange(N, dtype=np.int64)
+        return g % W, g // W
+    pairs = np.asarray(list(order), np.int64).reshape(-1, 2)
+    s, loc = pairs[:, 0].copy(), pairs[:, 1].copy()
+    if pairs.shape[0] != N or np.any((s < 0) | (s >= W)) or np.any(loc < 0) or np.any(loc >= np.asarray(counts, np.int64)[np.clip(s, 0, W - 1)]):
+        raise ValueError('order must name each of the {} images of {} states (counts {}) once'.format(N, W, counts))
+    base = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    if np.unique(base[s] + loc).size != N:
+        raise ValueError('order names an image twice')
+    return s, loc
+
+
+def pool_gather_index(image_counts, state_index, local_index, total):
+    """Index plumbing of ``merge``: image_counts = per state int64 tensor [images of the state] (pool entries per image);
+    state_index / local_index = global_image_order.  Returns (index int64 [total] into the state-major concatenation of the
+    pools that puts the per-image blocks in global order, entries per image int64 [N] in global order)."""
+    dev = image_counts[0].device
+    flat = torch.cat(image_counts)                                     # every image, state-major
+    base = np.concatenate([[0], np.cumsum([c.numel() for c in image_counts])[:-1]]).astype(np.int64)
+    img = torch.from_numpy(base[np.asarray(state_index, np.int64)] + np.asarray(local_index, np.int64)).to(dev)
+    starts = torch.cumsum(flat, 0) - flat                              # each image's first entry in the concatenated pool
+    cnt, first = flat[img], starts[img]
+    within = torch.arange(total, dtype=torch.int64, device=dev) - torch.repeat_interleave(torch.cumsum(cnt, 0) - cnt, cnt, output_size=total)
+    return torch.repeat_interleave(first, cnt, output_size=total) + within, cnt
+
+
+def all_gather_evaluator(ev, group=None):
+    """COLLECTIVE over ``group`` (default: the default process group): EVERY rank must call it, with its own evaluator,
+    and every rank gets back the merged evaluator (``merge`` of the ranks' states in rank order, order='strided': rank r
+    evaluated images r, r + W, ... of the global order).  Never call it from rank 0 alone: the other ranks would never
+    join and rank 0 waits forever.  Sizes are gathered first, then the zero-padded pools, trimmed after.  Works on nccl
+    (device tensors) and gloo (staged through host memory)."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    st = ev.state()
+    dev = ev.device if dist.get_backend(group) == 'nccl' else torch.device('cpu')
+
+    def gather(t):
+        out = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(out, t.contiguous(), group=group)
+        return out
+
+    thr = np.zeros(32, np.float32)
+    T = st['iou_thresholds'].size
+    thr[:T] = st['iou_thresholds']
+    md = -1 if st['max_detections'] is None else st['max_detections']
+    meta = torch.tensor([st['keys'].numel(), st['num_images'], st['num_classes'], md, T] + thr.view(np.int32).tolist(), dtype=torch.int64, device=dev)
+    metas = [m.cpu().numpy() for m in gather(meta)]
+    for r, m in enumerate(metas):                    # every rank sees every meta row: all raise together, before shapes diverge
+        if not np.array_equal(m[2:], metas[0][2:]):
+            raise ValueError('rank {} evaluates with classes / max_detections / thresholds {} against rank 0\'s {}'.format(r, m[2:5], metas[0][2:5]))
+    max_m = max(1, max(int(m[0]) for m in metas))
+    max_n = max(1, max(int(m[1]) for m in metas))
+
+    def padded(t, size):
+        p = torch.zeros(size, dtype=t.dtype, device=dev)
+        p[:t.numel()] = t.to(dev)
+        return p
+
+    keys = gather(padded(st['keys'], max_m))
+    tp = gather(padded(st['tp'], max_m))
+    counts = gather(padded(st['image_counts'], max_n))
+    npos = gather(torch.from_numpy(st['npos']).to(dev))
+    states = [{'keys': keys[r][:int(m[0])], 'tp': tp[r][:int(m[0])], 'image_counts': counts[r][:int(m[1])], 'npos': npos[r].cpu().numpy(),
+               'num_images': int(m[1]), 'iou_thresholds': st['iou_thresholds'], 'num_classes': st['num_classes'],
+               'max_detections': st['max_detections']} for r, m in enumerate(metas)]
+    return DetectionEvaluator.merge(states, 'strided', device=ev.device)
+
+
+# ---- the evaluation loop shared by evaluate.py and train.py --test_map -----------------------------------------------
+def database_examples(path, num_shards=1, shard_index=0):
+    """(name, HWC image, [G,5] X,Y,W,H,C) of the records keys[shard_index::num_shards] of an lmdb written by build_lmdb.py,
+    in env.keys() order (= ImageReader.keys_flat); the records as stored, no augmentation, no image decode."""
+    env = lmdbio.Environment(path)
+    try:
+        for i, key in enumerate(env.keys()):
+            if i % num_shards != shard_index:
+                continue
+            img, boxes = ImageYoloBoxesPair().ParseFromString(env.get(key)).to_arrays()
+            yield key.decode('ascii'), img, np.asarray(boxes).reshape(-1, 5)
+    finally:
+        env.close()
+
+
+def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, precision=None):
+    """Feeds (name, HWC image, [G,5] X,Y,W,H,C) examples through ``yolo`` (a YoloV3: per-image z-score -> predict ->
+    clip -> small-box filter -> NMS, inference.py's path) into ``evaluator``, ``batch_size`` images per call, the short
+    tail as one smaller call.  precision: predict()'s ('fp32' / 'bf16'; default yolo.inference_precision).  Returns the
+    number of images added."""
+    if batch_size < 1:
+        raise ValueError('batch_size must be >= 1')
+    batch, count = [], 0
+
+    def flush():
+        imgs = [b[1] for b in batch]
+        if any(im.shape != imgs[0].shape for im in imgs):
+            raise RuntimeError('images must share one size (the model input is fixed): {}'.format({im.shape for im in imgs}))
+        height, width = imgs[0].shape[:2]
+        x = torch.from_numpy(np.stack([np.ascontiguousarray(im.astype(np.float32).transpose((2, 0, 1))) for im in imgs])).to(yolo.device)
+        rows = yolo.predict(imagereader.zscore_normalize_device(x), precision=precision)
+        evaluator.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height))
+        batch.clear()
+
+    for ex in examples:
+        batch.append(ex)
+        count += 1
+        if len(batch) == batch_size:
+            flush()
+    if batch:
+        flush()
+    return count
