@@ -322,6 +322,20 @@ size_t y3_loss_workspace_bytes(void);
 int y3_adam_step(float* param, const float* grad, float* m, float* v, size_t count,
                  const float* lr_t_dev, float beta1, float beta2, float eps, y3_stream_t stream);
 
+/* ---- y3_adam_step + an exponential moving average of the weights, one launch
+ * (replaces a trainer's separate EMA pass after the optimiser step, e.g.
+ * ultralytics' ModelEMA.update; no counterpart in the reference).  param, m, v
+ * come out bit-identical to y3_adam_step; then, with omd = *omd_dev (1 - decay,
+ * DEVICE memory like lr_t_dev):
+ *   ema_param[i]  += (param_new[i] - ema_param[i]) * omd     i < count
+ *   ema_moving[j] += (moving[j] - ema_moving[j]) * omd       j < moving_count
+ * moving: the BatchNorm moving statistics of this step's forward pass.  Every
+ * array 16-byte aligned; counts need not be multiples of 4. */
+int y3_adam_step_ema(float* param, const float* grad, float* m, float* v, size_t count,
+                     const float* lr_t_dev, float beta1, float beta2, float eps,
+                     float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
+                     const float* omd_dev, y3_stream_t stream);
+
 /* ---- class-wise NMS (bbox_utils.py:200-281; inference.py:72-79) ------------
  * rows [N,Nb,5+K].  A row is a candidate of class c if w > min_box and
  * h > min_box (strict) and sqrt(cls_c*obj) >= score_thr; greedy suppression

@@ -775,6 +775,11 @@ extern "C" int y3_colsum(const y3_tensor* src, float* out, y3_stream_t stream) {
 // ---------------------------------------------------------------------------
 // Keras Adam (App. C5), fused over the whole parameter arena
 // ---------------------------------------------------------------------------
+// one element of one float4 lane f: the update of adam_kernel and adam_ema_kernel (one text, so the two give the same bits)
+#define Y3_ADAM1(f)                              \
+    mm.f += (gg.f - mm.f) * o1;                  \
+    vv.f += (gg.f * gg.f - vv.f) * o2;           \
+    pp.f -= (mm.f * lr_t) / (sqrtf(vv.f) + eps);
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t count4,
                             size_t count, const float* __restrict__ lr_t_dev, float b1, float b2, float eps) {
     const float lr_t = *lr_t_dev;
@@ -785,10 +790,6 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
         const float4 gg = reinterpret_cast<const float4*>(g)[i];
         float4 mm = reinterpret_cast<float4*>(m)[i];
         float4 vv = reinterpret_cast<float4*>(v)[i];
-#define Y3_ADAM1(f)                              \
-    mm.f += (gg.f - mm.f) * o1;                  \
-    vv.f += (gg.f * gg.f - vv.f) * o2;           \
-    pp.f -= (mm.f * lr_t) / (sqrtf(vv.f) + eps);
         Y3_ADAM1(x) Y3_ADAM1(y) Y3_ADAM1(z) Y3_ADAM1(w)
         reinterpret_cast<float4*>(p)[i] = pp;
         reinterpret_cast<float4*>(m)[i] = mm;
@@ -813,6 +814,76 @@ extern "C" int y3_adam_step(float* param, const float* grad, float* m, float* v,
     hipLaunchKernelGGL(adam_kernel, dim3(stream_blocks((long long)(count / 4 + 1), 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v,
                        count / 4, count, lr_t_dev, beta1, beta2, eps);
     Y3_CHECK_LAUNCH("adam_step");
+    return Y3_OK;
+}
+
+// adam_kernel + the exponential moving average of the weights in the same pass: p, m, v come out with the bits
+// adam_kernel gives; then ema_p += (p_new - ema_p) * omd over the arena, and the same update of ema_mv towards the BatchNorm
+// moving statistics mv (a second, small segment, written by this step's forward pass).  omd = 1 - decay is read from device
+// memory, like lr_t, so a replayed graph picks up each step's value.  Two more fp32 streams than Adam alone: 9 per element.
+__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t count4,
+                                size_t count, const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float* __restrict__ ema_p,
+                                const float* __restrict__ mv, float* __restrict__ ema_mv, size_t mcount4, size_t mcount,
+                                const float* __restrict__ omd_dev) {
+    const float lr_t = *lr_t_dev;
+    const float omd = *omd_dev;
+    const float o1 = 1.f - b1, o2 = 1.f - b2;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (size_t i = tid; i < count4; i += stride) {
+        float4 pp = reinterpret_cast<float4*>(p)[i];
+        const float4 gg = reinterpret_cast<const float4*>(g)[i];
+        float4 mm = reinterpret_cast<float4*>(m)[i];
+        float4 vv = reinterpret_cast<float4*>(v)[i];
+        float4 ee = reinterpret_cast<float4*>(ema_p)[i];
+        Y3_ADAM1(x) Y3_ADAM1(y) Y3_ADAM1(z) Y3_ADAM1(w)
+        ee.x += (pp.x - ee.x) * omd;
+        ee.y += (pp.y - ee.y) * omd;
+        ee.z += (pp.z - ee.z) * omd;
+        ee.w += (pp.w - ee.w) * omd;
+        reinterpret_cast<float4*>(p)[i] = pp;
+        reinterpret_cast<float4*>(m)[i] = mm;
+        reinterpret_cast<float4*>(v)[i] = vv;
+        reinterpret_cast<float4*>(ema_p)[i] = ee;
+    }
+    for (size_t i = tid; i < mcount4; i += stride) {
+        const float4 s = reinterpret_cast<const float4*>(mv)[i];
+        float4 ee = reinterpret_cast<float4*>(ema_mv)[i];
+        ee.x += (s.x - ee.x) * omd;
+        ee.y += (s.y - ee.y) * omd;
+        ee.z += (s.z - ee.z) * omd;
+        ee.w += (s.w - ee.w) * omd;
+        reinterpret_cast<float4*>(ema_mv)[i] = ee;
+    }
+    // tails: lane x of a float4 through the same update text
+    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {
+        const size_t i = (count4 << 2) + threadIdx.x;
+        float4 pp, gg, mm, vv;
+        pp.x = p[i], gg.x = g[i], mm.x = m[i], vv.x = v[i];
+        Y3_ADAM1(x)
+        p[i] = pp.x;
+        m[i] = mm.x;
+        v[i] = vv.x;
+        ema_p[i] += (pp.x - ema_p[i]) * omd;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < (mcount & 3)) {
+        const size_t i = (mcount4 << 2) + threadIdx.x;
+        ema_mv[i] += (mv[i] - ema_mv[i]) * omd;
+    }
+}
+extern "C" int y3_adam_step_ema(float* param, const float* grad, float* m, float* v, size_t count, const float* lr_t_dev, float beta1,
+                                float beta2, float eps, float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
+                                const float* omd_dev, y3_stream_t stream) {
+    Y3_CHECK_ARG(param && grad && m && v && lr_t_dev && ema_param && omd_dev, "adam_step_ema: null pointer");
+    Y3_CHECK_ARG(moving_count == 0 || (moving && ema_moving), "adam_step_ema: null moving-statistics pointer");
+    Y3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema_param | (uintptr_t)moving |
+                   (uintptr_t)ema_moving) & 15) == 0,
+                 "adam_step_ema: arenas must be 16-byte aligned");
+    if (count == 0 && moving_count == 0) return Y3_OK;
+    const long long items = (long long)((count > moving_count ? count : moving_count) / 4 + 1);
+    hipLaunchKernelGGL(adam_ema_kernel, dim3(stream_blocks(items, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, count / 4, count,
+                       lr_t_dev, beta1, beta2, eps, ema_param, moving, ema_moving, moving_count / 4, moving_count, omd_dev);
+    Y3_CHECK_LAUNCH("adam_step_ema");
     return Y3_OK;
 }
 

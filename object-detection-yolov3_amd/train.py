@@ -10,11 +10,14 @@ global batch = batch_size x replicas (:41), Adam warm-up at lr/10 for min(1000, 
 image_count/batch_size(+1) batches (:76,:144), test_loss.csv (:170-173), best checkpoint on a new minimum (:178-182),
 early stopping with CONVERGENCE_TOLERANCE 1e-4 (:185-197), final export of the best checkpoint (:208-221).
 Added (opt-in, off by default): --test_map 1 runs a test-set mAP pass after every test epoch (<out>/test_map.csv), and
---model_selection map50 / map50_95 checkpoints and stops early on that mAP instead of the test loss.
+--model_selection map50 / map50_95 checkpoints and stops early on that mAP instead of the test loss, and
+--ema_decay D keeps an exponential moving average of the weights whose copy the test loss, the mAP pass and the checkpoint
+(hence the export) use.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
 import argparse
+import contextlib
 import datetime
 import os
 import time
@@ -119,8 +122,9 @@ def effective_reader_count(requested, cpus, local_world):
 
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
-                test_map=False, model_selection='loss', test_map_min_box_size=32):
+                test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0):
     test_map = effective_test_map(test_map, model_selection)
+    ema_decay = float(ema_decay) if ema_decay else None
     os.makedirs(output_folder, exist_ok=True)
     anchors = [(64, 384), (384, 64)]
 
@@ -180,11 +184,20 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
 
         print('Creating model')
         number_classes = train_reader.get_number_classes()
-        yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate)
+        yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay)
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
             yolo._refresh_transposed()
+            yolo.reset_ema()            # every replica starts the average from rank 0's weights
+        if ema_decay is not None:
+            print('Using an exponential moving average of the weights (decay {}, warm-up {:g} steps) for the test loss, the mAP pass '
+                  'and the checkpoint'.format(ema_decay, yolo.ema_warmup))
+
+        def averaged():
+            """The model the loop judges and keeps: the EMA copy when there is one (each replica's own EMA moving statistics,
+            which evaluate_test_map and the checkpoint replace by their mean over the replicas), else the live weights."""
+            return yolo.ema_weights() if ema_decay is not None else contextlib.nullcontext()
 
         train_epoch_size = test_every_n_steps
         test_epoch_size = test_reader.get_image_count() / batch_size
@@ -233,13 +246,14 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                     m.reset_states()
 
             epoch_test_loss = list()
-            for step, (batch_images, l1, l2, l3) in enumerate(test_dataset):
-                if step > test_epoch_size:
-                    break
-                inputs = (batch_images, (l1, l2, l3), *test_metrics)
-                loss_value = yolo.dist_test_step(strategy, inputs)
-                abort_on_nan(loss_value, 'Test Loss went to NaN')
-                epoch_test_loss.append(float(loss_value))
+            with averaged():
+                for step, (batch_images, l1, l2, l3) in enumerate(test_dataset):
+                    if step > test_epoch_size:
+                        break
+                    inputs = (batch_images, (l1, l2, l3), *test_metrics)
+                    loss_value = yolo.dist_test_step(strategy, inputs)
+                    abort_on_nan(loss_value, 'Test Loss went to NaN')
+                    epoch_test_loss.append(float(loss_value))
             test_loss.append(np.mean(epoch_test_loss))
             print('Test Epoch: {}: Loss = {}'.format(epoch, test_metrics[0].result()))
             log_scalars('test', int((epoch + 1) * train_epoch_size), test_metrics)
@@ -247,7 +261,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 m.reset_states()
 
             if test_map:
-                res, map_images, map_secs = evaluate_test_map(yolo, strategy, test_database_filepath, batch_size, test_map_min_box_size, world, rank)
+                with averaged():
+                    res, map_images, map_secs = evaluate_test_map(yolo, strategy, test_database_filepath, batch_size, test_map_min_box_size, world, rank)
                 print('Test Epoch: {}: mAP50 = {}, mAP50:95 = {} ({} images, mAP pass took {:.3f} s)'.format(
                     epoch, res['map50'], res['map50_95'], map_images, map_secs))
                 if model_selection != 'loss':
@@ -279,11 +294,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             if improved:
                 # BN moving statistics are sync-on-read: the checkpoint stores their MEAN over the replicas (App. C4); every
                 # replica keeps its own running values (a collective: all ranks take part, rank 0 writes)
-                saved_moving = strategy.mean_moving_stats(yolo.moving) if strategy is not None else None
-                training_checkpoint_filepath = os.path.join(output_folder, 'checkpoint', 'ckpt.npz')
-                if rank == 0:
-                    os.makedirs(os.path.dirname(training_checkpoint_filepath), exist_ok=True)
-                    yolo.save_weights(training_checkpoint_filepath, moving=saved_moving)
+                with averaged():
+                    saved_moving = strategy.mean_moving_stats(yolo.moving) if strategy is not None else None
+                    training_checkpoint_filepath = os.path.join(output_folder, 'checkpoint', 'ckpt.npz')
+                    if rank == 0:
+                        os.makedirs(os.path.dirname(training_checkpoint_filepath), exist_ok=True)
+                        yolo.save_weights(training_checkpoint_filepath, moving=saved_moving)
 
             print('Best Current Epoch Selection:')
             if model_selection == 'loss':
@@ -320,7 +336,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         dist.destroy_process_group()
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser(prog='train_yolo', description='Script which trains a yolo_v3 model')
     parser.add_argument('--batch_size', dest='batch_size', type=int, help='training batch size', default=8)
     parser.add_argument('--learning_rate', dest='learning_rate', type=float, default=1e-4)
@@ -343,10 +359,17 @@ if __name__ == "__main__":
     parser.add_argument('--model_selection', dest='model_selection', choices=MODEL_SELECTIONS, default='loss',
                         help='(addition) what picks the checkpoint and drives early stopping: the test loss (first minimum, as the reference) '
                              'or the test-set mAP50 / mAP50:95 (first maximum; implies --test_map 1)')
-    a = parser.parse_args()
+    parser.add_argument('--ema_decay', dest='ema_decay', type=float, default=0.0,
+                        help='(addition) 0 (default): off; in (0, 1): keep an exponential moving average of the weights (decay ramped up '
+                             'over the first few thousand steps) and use it for the test loss, the mAP pass, the checkpoint and the export')
+    return parser
+
+
+if __name__ == "__main__":
+    a = build_parser().parse_args()
     print('Arguments:')
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
-                a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size)
+                a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay)

@@ -98,6 +98,7 @@ SIGNATURES = {
     'y3_loss_fwd_bwd': (i32, [TP, fp, C.POINTER(C.c_float), i32, i32, i32, i32, f32, fp, TP, vp, vp]),
     'y3_loss_workspace_bytes': (sz, []),
     'y3_adam_step': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, vp]),
+    'y3_adam_step_ema': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, fp, fp, sz, fp, vp]),
     'y3_nms_per_class': (i32, [fp, i32, i32, i32, f32, f32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
     'y3_nms_workspace_bytes': (sz, [i32, i32, i32]),
     'y3_nms_single_class': (i32, [fp, i32, f32, ip, ip, fp, vp, sz, vp]),

@@ -11,6 +11,7 @@ order, and each step is a static list of kernel launches (replayable as one
 HIP graph).  torch is used for device memory, streams and the RCCL all-reduce
 only; there is no torch.nn / autograd / CPU fallback on this path.
 """
+import contextlib
 import math
 import os
 
@@ -28,6 +29,14 @@ BN_EPILOGUE_WIDE = os.environ.get('Y3_BN_EPI_WIDE', '1') != '0'   # ... also whe
 LRELU_ALPHA = 0.2      # tf.nn.leaky_relu default (App. C3)
 BF16_PATCH_MIN_BYTES = 300e6   # bf16 path: a 3x3 layer that moves less (input + residual + output) stays off the patch kernels
 ALIGN = 64             # arena alignment in floats (256 B)
+
+
+def ema_one_minus_decay(ema_decay, ema_warmup, t):
+    """1 - d_t of the weight average after step t (1-based), with the warm-up ramp of the common YOLO trainers:
+    d_t = ema_decay * (1 - exp(-t / ema_warmup)).  Computed in fp64 and rounded once to fp32, the value the fused Adam + EMA
+    kernel reads (y3_adam_step_ema)."""
+    d = float(ema_decay) * (1.0 - math.exp(-float(t) / float(ema_warmup)))
+    return np.float32(1.0 - d)
 
 
 def _round_up(v, a):
@@ -676,7 +685,12 @@ class YoloV3:
     WEIGHT_DECAY = 5e-4      # declared by the reference but never applied (Q9)
 
     def __init__(self, global_batch_size, img_size, number_classes, anchors=None, learning_rate=1e-4, device=None, seed=None,
-                 use_graph=False, inference_precision='fp32', conv_arithmetic=None):
+                 use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000):
+        # exponential moving average of the weights: None / 0 = off; checked before the device is needed
+        if ema_decay is not None and ema_decay != 0 and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError('ema_decay must be None (off) or in (0, 1), got %r' % (ema_decay,))
+        if ema_decay and not float(ema_warmup) > 0.0:
+            raise ValueError('ema_warmup must be > 0, got %r' % (ema_warmup,))
         if not torch.cuda.is_available():
             raise RuntimeError('yolo3.model.YoloV3 needs an MI355X (HIP) device: there is no CPU path')
         self.device = torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
@@ -712,6 +726,17 @@ class YoloV3:
         self.lr_t_dev = z(1)
         self.beta1, self.beta2, self.adam_eps = 0.9, 0.999, 1e-7   # Keras Adam defaults (App. C5)
         self.iterations = 0
+        # the average (ema_params, ema_moving) and the stash ema_weights() parks the live arenas in; None when off
+        self.ema_decay = float(ema_decay) if ema_decay else None
+        self.ema_warmup = float(ema_warmup)
+        self.ema_params = self.ema_moving = self.ema_omd_dev = None
+        self._ema_stash = None
+        self._ema_swapped = False
+        if self.ema_decay is not None:
+            self.ema_params = z(self.arena_floats)
+            self.ema_moving = z(2 * self.moving_stride)
+            self.ema_omd_dev = z(1)
+            self._ema_stash = (z(self.arena_floats), z(2 * self.moving_stride))
         self.use_graph = bool(use_graph)
         if inference_precision not in ('fp32', 'bf16'):
             raise ValueError("inference_precision must be 'fp32' or 'bf16'")
@@ -814,6 +839,46 @@ class YoloV3:
         self.params.copy_(torch.from_numpy(host))
         self.moving.copy_(torch.from_numpy(mov))
         self._refresh_transposed()
+        self.reset_ema()
+
+    # ---- exponential moving average of the weights ---------------------------
+    def reset_ema(self):
+        """Restart the average from the current weights and moving statistics (no-op when the EMA is off).  set_weights does
+        it; a data-parallel trainer calls it again after broadcasting rank 0's weights."""
+        if self.ema_decay is None:
+            return
+        if self._ema_swapped:
+            raise RuntimeError('reset_ema inside ema_weights()')
+        self.ema_params.copy_(self.params)
+        self.ema_moving.copy_(self.moving)
+
+    def _ema_omd(self):
+        return ema_one_minus_decay(self.ema_decay, self.ema_warmup, self.iterations)
+
+    @contextlib.contextmanager
+    def ema_weights(self, moving=None):
+        """Within the block the model IS the average: ema_params in params, ema_moving (or `moving`, e.g. the cross-replica
+        mean) in moving, derived weight copies refreshed; predict / predict_tiles / test_step / get_weights / save_weights
+        all see it.  The arenas are copied in place (plans and captured graphs hold their raw pointers) and restored on
+        exit, with the derived copies rebuilt from the restored weights (the same bits as before).  No training inside."""
+        if self.ema_decay is None:
+            raise RuntimeError('ema_weights(): this model keeps no average (ema_decay=None)')
+        if self._ema_swapped:
+            raise RuntimeError('ema_weights() does not nest')
+        sp, sm = self._ema_stash
+        sp.copy_(self.params)
+        sm.copy_(self.moving)
+        self.params.copy_(self.ema_params)
+        self.moving.copy_(self.ema_moving if moving is None else moving)
+        self._refresh_transposed()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self.params.copy_(sp)
+            self.moving.copy_(sm)
+            self._refresh_transposed()
+            self._ema_swapped = False
 
     def _unpack(self, arena):
         host = arena.detach().cpu().numpy()
@@ -1068,8 +1133,15 @@ class YoloV3:
         plan.run_backward(st, hook)
 
     def _adam(self, st):
-        check(lib.y3_adam_step(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
-                               self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps, st), 'y3_adam_step')
+        if self.ema_decay is None:
+            check(lib.y3_adam_step(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                   self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps, st), 'y3_adam_step')
+        else:
+            # the same Adam step + the weight / moving-statistics average in the same pass
+            check(lib.y3_adam_step_ema(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                       self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps,
+                                       self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr(), self.moving.numel(),
+                                       self.ema_omd_dev.data_ptr(), st), 'y3_adam_step_ema')
         self._refresh_transposed()
 
     def train_step(self, inputs):
@@ -1079,11 +1151,15 @@ class YoloV3:
         images, gt_data = inputs[0], inputs[1]
         metrics = list(inputs[2:]) + [None] * 5
         n = int(images.shape[0])
+        if self._ema_swapped:
+            raise RuntimeError('train_step inside ema_weights(): the live weights are parked')
         plan = self._plan(n, True)
         self._load_inputs(plan, images, gt_data)
         self.iterations += 1
         self._bf16_stale = True
         self.lr_t_dev.fill_(self._lr_t())
+        if self.ema_decay is not None:
+            self.ema_omd_dev.fill_(float(self._ema_omd()))
         st = self._stream()
         if self.use_graph and self.dist is None:
             if plan.graph is None:
