@@ -953,34 +953,7 @@ struct TileCfg {
     int bm, bn, bk;
 };
 
-// Tuning switches.  The product library reads exactly one environment variable on this path, Y3_NO_FAST (generic kernel for
-// every launch; exercised by the GPU tests).  Everything else -- tile override, split-K targets, kernel-gradient plan -- is a
-// development knob of tools/: compiled in with -DY3_DEV only (make DEV=1 -> libyolo3hip_dev.so), constants otherwise.
-#ifdef Y3_DEV
-// Y3_TILE="bm,bn,bk" forces one configuration for every launch.
-static bool tile_override(TileCfg* t) {
-    static int state = 0;  // 0 unknown, 1 none, 2 set
-    static TileCfg forced;
-    if (state == 0) {
-        const char* e = getenv("Y3_TILE");
-        state = 1;
-        if (e && sscanf(e, "%d,%d,%d", &forced.bm, &forced.bn, &forced.bk) == 3) state = 2;
-    }
-    if (state == 2) *t = forced;
-    return state == 2;
-}
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static const char* env_str(const char* name) { return getenv(name); }
-#else
-static bool tile_override(TileCfg*) { return false; }
-static int env_int(const char*, int dflt) { return dflt; }
-static const char* env_str(const char*) { return nullptr; }
-#endif
-
-// Tile choice from the measured sweep (tools/conv_tune.py, MI355X): a launch wants >= ~600 workgroups
+// Tile choice from a measured sweep over the tile sizes (MI355X): a launch wants >= ~600 workgroups
 // (256 CUs x 2-3 resident); prefer the largest tile that still gives that many, else 64x64 (+ split-K).
 static TileCfg pick_tile(int M, int Nout) {
     TileCfg t;
@@ -998,13 +971,12 @@ static TileCfg pick_tile(int M, int Nout) {
         else
             t = {64, 64, 16};
     }
-    TileCfg f;
-    if (tile_override(&f) && f.bn <= ((Nout + 31) / 32) * 32) t = f;
     return t;
 }
 
 #define Y3_WS_HEADER (256 * 1024)   // bytes of tile tickets in front of the slabs (65 536 tiles)
 #define Y3_MAX_TICKETS (Y3_WS_HEADER / 4)
+static constexpr int x3_slots = 512;   // workgroup slots the x3 launches fill once: two workgroups of the patch kernel per CU
 struct ConvPlan {
     TileCfg t;
     int f, s0, s1, chunk0, chunk1;   // FastArgs::sk_*: tiles [0,f) in s0 slices of chunk0 K steps, the rest in s1 of chunk1
@@ -1024,23 +996,16 @@ static bool x3_shape_ok(int C, int Nout, int K, int ntaps) {
 static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
     ConvPlan pl;
     pl.t = {128, Nout <= 64 ? 64 : 128, 16};
-    {
-        static const int force_bn = env_int("Y3_X3_BN", 0);      // development: 64 = 128 x 64 tiles everywhere
-        if (force_bn == 64 || force_bn == 128) pl.t.bn = Nout <= 64 ? 64 : force_bn;
-    }
     const int tiles = y3_cdiv(M, pl.t.bm) * y3_cdiv(Nout, pl.t.bn);
     const int nk = K / 16;
     pl.tiles = pl.f = tiles;
     pl.s0 = pl.s1 = 1;
     pl.chunk0 = pl.chunk1 = even_steps(nk);
-    static const int min_steps = env_int("Y3_X3_MINSTEPS", 12);
+    constexpr int min_steps = 12;
     // slices are whole units of K steps: 3x3 launches in units of 18 (two 16-channel chunks of nine taps: the patch kernel's loop
     // body, conv_x3.hip), the others in pairs of steps
     const int unit = ntaps == 9 ? 18 : 2;
-    static const int rsplit_on = env_int("Y3_X3_RSPLIT", 2);      // 0 off, 1 only where the uniform split does not apply, 2 preferred above 256 tiles
-    static const int force_ks = env_int("Y3_X3_KS", 0);           // development: this many K slices for every split launch
-    static const int slots = env_int("Y3_X3_SLOTS", 512);         // two workgroups of the patch kernel per CU
-    if (tiles <= Y3_MAX_TICKETS && tiles > 256 && rsplit_on && !force_ks) {
+    if (tiles <= Y3_MAX_TICKETS && tiles > 256) {
         // more tiles than CUs but too few to balance by themselves (338 tiles: a third of the CUs would carry two): whole rounds of
         // tiles stay whole -- no slabs for them -- and only the remainder round is cut, so that its pieces spread evenly
         const int F = tiles / 256 * 256, R = tiles - F;
@@ -1063,7 +1028,7 @@ static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
     } else if (tiles <= Y3_MAX_TICKETS && tiles <= 256) {
         // Fewer tiles than CUs: cut along K so that the launch fills the chip's workgroup slots ONCE, two per CU -- a lone workgroup
         // (one wave per SIMD) runs its loop at a third of the MFMA rate, and a second, partly filled round costs a whole round
-        // (measured, tools/probe/x3_ks_sweep.sh / x3_ks_sweep2.sh: 507 pieces 78 us, 338 pieces 97 us, 676 pieces 103 us on the same launch).
+        // (measured with a K-slice sweep: 507 pieces 78 us, 338 pieces 97 us, 676 pieces 103 us on the same launch).
         // The slice counts a launch can have are ceil(nk / c) for c a multiple of the unit; take the largest count s_lo with
         // tiles * s_lo <= slots and give the next larger one, s_hi, to as many tiles as fill the rest of the slots.
         auto count_for = [&](int c) { return y3_cdiv(nk, c); };
@@ -1071,10 +1036,9 @@ static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
         for (int c = y3_cdiv(nk, unit) * unit; c >= unit && c >= min_steps; c -= unit) {      // slice counts grow as c shrinks
             const int sc = count_for(c);
             if (sc > 16) break;
-            const bool fits = force_ks ? sc <= force_ks : (long long)tiles * sc <= slots;
-            if (fits)
+            if ((long long)tiles * sc <= x3_slots)
                 c_lo = c;
-            else if (c_hi == 0 && !force_ks && (c_lo == 0 || sc > count_for(c_lo)))
+            else if (c_hi == 0 && (c_lo == 0 || sc > count_for(c_lo)))
                 c_hi = c;
         }
         const int s_lo = c_lo > 0 ? count_for(c_lo) : 1;
@@ -1087,10 +1051,9 @@ static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
         // blocks END with short slices (conv_fast_decode<SHORTLAST>), i.e. the blocks beyond the slots are short ones that start as
         // the first short ones finish -- and no tile needs the longer slices of s_lo (13x13 forward: 88 x 6 = 528 pieces of 54 / 18
         // steps instead of 80 x 6 + 8 x 4 with 72-step pieces: 92 -> 82 us).
-        static const int overflow_on = env_int("Y3_X3_OVERFLOW", 1);
-        if (c_hi > 0 && overflow_on && !force_ks && ntaps == 9) {
+        if (c_hi > 0 && ntaps == 9) {
             const int s_hi = count_for(c_hi), last = nk - (s_hi - 1) * c_hi;
-            if ((long long)tiles * s_hi <= slots + slots / 16 && 3 * last <= c_hi) {
+            if ((long long)tiles * s_hi <= x3_slots + x3_slots / 16 && 3 * last <= c_hi) {
                 pl.f = tiles;
                 pl.s0 = pl.s1 = s_hi;
                 pl.chunk0 = pl.chunk1 = c_hi;
@@ -1100,7 +1063,7 @@ static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
         }
         if (c_hi > 0) {      // tiles [0, f) take the next larger count: f * s_hi + (tiles - f) * s_lo <= slots
             const int s_hi = count_for(c_hi);
-            const int f = (int)((slots - (long long)tiles * s_lo) / (s_hi - s_lo));
+            const int f = (int)((x3_slots - (long long)tiles * s_lo) / (s_hi - s_lo));
             if (f > 0) {
                 pl.f = f < tiles ? f : tiles;
                 pl.s0 = s_hi;
@@ -1132,13 +1095,12 @@ static ConvPlan plan_conv(int M, int Nout, int K, bool fast_ok, bool x3 = false,
     pl.f = tiles;
     pl.s0 = pl.s1 = 1;
     pl.chunk0 = pl.chunk1 = nk > 0 ? nk : 1;
-    static const int want = env_int("Y3_SPLITK_WGS", 2000);   // workgroups to aim for (swept with tools/fwd_time.py: 1000 / 1400 / 2000 / 2800)
-    static const int min_k = env_int("Y3_SPLITK_MINK", 256);  // shortest K slice worth a launch
-    static const int cus = env_int("Y3_CUS", 256);
-    static const int rsplit_on = env_int("Y3_RSPLIT", 1);
+    constexpr int want = 2000;    // workgroups to aim for (swept with tools/fwd_time.py: 1000 / 1400 / 2000 / 2800)
+    constexpr int min_k = 256;    // shortest K slice worth a launch
+    constexpr int cus = 256;
     // measured (tools/fixed_cost.py, layer_times.py): a 676-tile launch (2.6 workgroups per CU) is better left whole unless
     // K is long; at <= 512 tiles the extra workgroups win over the slab round trip
-    static const int few_max = env_int("Y3_FEWTILES", 512);
+    constexpr int few_max = 512;
     const bool few_tiles = tiles <= few_max || ((long long)tiles * 2 <= want && K >= 2048);
     if (fast_ok && tiles <= Y3_MAX_TICKETS && few_tiles && K >= 2 * min_k) {
         int ks = (int)((want + tiles / 2) / tiles);
@@ -1149,7 +1111,7 @@ static ConvPlan plan_conv(int M, int Nout, int K, bool fast_ok, bool x3 = false,
             pl.chunk0 = even_steps(y3_cdiv(nk, ks));
             pl.s0 = y3_cdiv(nk, pl.chunk0);
         }
-    } else if (fast_ok && rsplit_on && tiles <= Y3_MAX_TICKETS && tiles > cus && nk >= 8) {
+    } else if (fast_ok && tiles <= Y3_MAX_TICKETS && tiles > cus && nk >= 8) {
         // whole rounds of tiles stay whole; the remainder round is cut along K so that its pieces spread evenly over the CUs:
         // load per CU = full rounds + ceil(R * S / CUs) / S tiles against tiles / CUs ideal
         const int F = tiles / cus * cus, R = tiles - F;
@@ -1284,8 +1246,7 @@ static bool make_fast(const ConvArgs& a, int ntaps, int bk, FastArgs* f) {
     if (a.x3) {      // three bf16 piece planes of the K-contiguous copy (y3_x3_split_weights): 6 bytes per element, same 2 GiB limit
         if (wtotal * 6 >= 0x7fffffffLL) return false;
         p.wt_bytes = (unsigned)(wtotal * 6);
-        static const int mode = env_int("Y3_X3_MODE", 1);
-        p.x3_mode = mode;
+        p.x3_mode = 1;      // non-temporal activation loads
     }
     for (int t = 0; t < ntaps; ++t) {
         p.tap_dh[t] = dh[t];
@@ -1294,8 +1255,7 @@ static bool make_fast(const ConvArgs& a, int ntaps, int bk, FastArgs* f) {
         p.tap_wrow[t] = (int)((a.tap_wsel >> (4 * t)) & 15ull) * a.C;
     }
     p.ntaps = ntaps;
-    static const int korder = env_int("Y3_KORDER", 2);      // development: 0 = taps outermost, 1 = 16-channel chunks outermost
-    p.korder = ntaps > 1 ? (korder == 2 && a.C % 32 != 0 ? 1 : korder) : 0;
+    p.korder = ntaps > 1 ? (a.C % 32 != 0 ? 1 : 2) : 0;
     p.dv_taps = y3_make_div(p.korder == 2 ? 2 * ntaps : ntaps);
     p.ohw = a.OH * a.OW;
     p.dv_ohw = y3_make_div(p.ohw);
@@ -1387,8 +1347,7 @@ static int launch_igemm(const ConvArgs& a, void* workspace, size_t workspace_byt
     if (fast_ok && make_fast(p, ntaps, t.bk, &f)) {
         f.nbn = p.nbn;
         f.nbm = y3_cdiv(p.M, t.bm);
-        static const int colmajor_kb = env_int("Y3_COLMAJOR_KB", 2048);     // kernel matrix larger than this: column-major tile ids
-        f.col_major = ((long long)p.K * p.Nout * 4 > (long long)colmajor_kb * 1024) ? 1 : 0;
+        f.col_major = ((long long)p.K * p.Nout * 4 > 2048LL * 1024) ? 1 : 0;     // kernel matrix larger than 2 MiB: column-major tile ids
         f.nb_fast = f.col_major ? f.nbm : f.nbn;
         f.dv_nb = y3_make_div(f.nb_fast);
         f.dv_s0 = y3_make_div(pl.s0);
@@ -1578,7 +1537,6 @@ static bool plan_dgrad_multi_x3(const ConvArgs* cls, int ncls, MultiX3Plan* pl) 
     const int Nout = cls[0].Nout;
     if (Nout < 64) return false;
     pl->bn = Nout >= 128 ? 128 : 64;
-    static const int slots = env_int("Y3_X3_SLOTS", 512);
     int steps[4], tsum = 0, smax = 0;
     long long total = 0;
     pl->rows = 0;
@@ -1594,13 +1552,13 @@ static bool plan_dgrad_multi_x3(const ConvArgs* cls, int ncls, MultiX3Plan* pl) 
         total += (long long)pl->tiles[c] * steps[c];
         smax = steps[c] > smax ? steps[c] : smax;
     }
-    if (tsum < slots && tsum <= Y3_MAX_TICKETS) {
-        int L = even_steps(y3_cdiv(total, slots));
+    if (tsum < x3_slots && tsum <= Y3_MAX_TICKETS) {
+        int L = even_steps(y3_cdiv(total, x3_slots));
         if (L < 12) L = 12;
         for (; L < smax; L += 2) {
             long long g = 0;
             for (int c = 0; c < ncls; ++c) g += (long long)pl->tiles[c] * y3_cdiv(steps[c], L);
-            if (g <= slots) break;
+            if (g <= x3_slots) break;
         }
         for (int c = 0; c < ncls; ++c) {
             const int sc = y3_cdiv(steps[c], L);
@@ -1676,8 +1634,7 @@ static bool launch_dgrad_multi_x3(const ConvArgs* cls, int ncls, hipStream_t st,
 // dry != nullptr: nothing is launched, *dry receives the number of partial-statistics rows (row tiles over all classes)
 static bool launch_dgrad_multi(const ConvArgs* cls, int ncls, hipStream_t st, int* dry = nullptr, size_t* dry_ws = nullptr, void* workspace = nullptr,
                               size_t workspace_bytes = 0) {
-    static const int off = env_int("Y3_NO_DGRAD_MULTI", 0);
-    if (off || ncls < 2 || ncls > 4) return false;
+    if (ncls < 2 || ncls > 4) return false;
     if (cls[0].x3) return launch_dgrad_multi_x3(cls, ncls, st, dry, dry_ws, workspace, workspace_bytes);
     if (dry_ws) *dry_ws = 0;
     FastArgs4 m = {};
@@ -1914,11 +1871,10 @@ static WgradPlan plan_wgrad(int K, int Nout, int M, int taps) {
     WgradPlan w;
     w.bkr = (K <= 64) ? 64 : 128;
     w.bn = (Nout <= 32) ? 32 : (Nout <= 64 ? 64 : 128);
-    // Measured per shape (tools/conv_tune.py with Y3_WGRAD_TILE, batch 8 at 416^2): the 1x1 layers (8-11 K steps per split, slab
+    // Measured per shape (a sweep over the tile sizes, batch 8 at 416^2): the 1x1 layers (8-11 K steps per split, slab
     // traffic as large as the operands) run 20-25 % faster on 64x64 tiles; the 3x3 layers with large kernel matrices (26x26 and
     // 13x13 grids: K*Nout >= 1M) 5-10 % faster on 128x64, the 104x104 layer (K = 576) 6 % faster on 64x128.
-    static const int shape_rules = env_int("Y3_WGRAD_SHAPE_RULES", 1);
-    if (shape_rules && w.bkr == 128 && w.bn == 128) {
+    if (w.bkr == 128 && w.bn == 128) {
         if (taps == 1) {
             w.bkr = 64;
             w.bn = 64;
@@ -1928,19 +1884,9 @@ static WgradPlan plan_wgrad(int K, int Nout, int M, int taps) {
             w.bkr = 64;
         }
     }
-    {
-        // experiments: Y3_WGRAD_TILE=bkr,bn (64|128, 32|64|128) for the layers with K <= Y3_WGRAD_TILE_MAXK (default 1024)
-        static const char* ov = env_str("Y3_WGRAD_TILE");
-        static const int maxk = env_int("Y3_WGRAD_TILE_MAXK", 1024);
-        int a = 0, b = 0;
-        if (ov && K <= maxk && sscanf(ov, "%d,%d", &a, &b) == 2 && (a == 64 || a == 128) && (b == 32 || b == 64 || b == 128) && b <= ((Nout + 31) / 32) * 32) {
-            w.bkr = a;
-            w.bn = b;
-        }
-    }
     w.tiles = y3_cdiv(K, w.bkr) * y3_cdiv(Nout, w.bn);
     // aim at ~16 waves per CU overall (these launches are latency / HBM bound per workgroup), at least 128 pixels per split
-    static const int want_waves = env_int("Y3_WGRAD_WAVES", 4096);
+    constexpr int want_waves = 4096;
     const int waves_per_wg = (w.bkr == 64 && w.bn == 32) ? 2 : 4;
     int splits = y3_cdiv(want_waves, w.tiles * waves_per_wg);
     const int maxs = y3_cdiv(M, 128);
@@ -1964,7 +1910,7 @@ static WgradPlan plan_wgrad_x3(int K, int Nout, int M) {
     w.bkr = 128;
     w.bn = 128;
     w.tiles = y3_cdiv(K, 128) * y3_cdiv(Nout, 128);
-    static const int want = env_int("Y3_WGX3_WGS", 480);
+    constexpr int want = 480;
     int splits = want / w.tiles;
     if (splits < 1) splits = 1;
     // more tiles than CUs (13x13 3x3 layers: 288): one pixel run per tile leaves most CUs with a lone workgroup; two runs are a
@@ -1984,8 +1930,7 @@ static WgradPlan plan_wgrad_x3(int K, int Nout, int M) {
 // more splits: natural-layout slabs [split][K][Nout] + slab_reduce_kernel (measured: a multi-level in-kernel tree costs more
 // than the streaming reduce when every split is only a few K steps long)
 static bool wgrad_in_kernel(const WgradPlan& w) {
-    static const int mode = env_int("Y3_WGRAD_INKERNEL", 1);
-    return mode != 0 && w.splits > 1 && w.splits <= Y3_WG_FANIN && w.tiles <= Y3_MAX_TICKETS;
+    return w.splits > 1 && w.splits <= Y3_WG_FANIN && w.tiles <= Y3_MAX_TICKETS;
 }
 static size_t wgrad_ws_bytes(const WgradPlan& w, int K, int Nout) {
     if (w.splits <= 1) return 0;
@@ -2094,9 +2039,9 @@ extern "C" int y3_conv2d_wgrad_x(const y3_tensor* src, const y3_tensor* ddst, in
     // BatchNorm-backward kernels of the compute stream, and the 128x64 / 64x128 variants otherwise fill all
     // 160 KB of a CU with 4 workgroups -- the 12 KB bn_bwd_finalize_tiles kernel on the critical path then waits for one of
     // them to retire (20 us per launch in the overlapped step against 9.7 us alone).  8 KB of pad caps them at 3 workgroups
-    // per CU (the occupancy their register budget aims at): step 18.21 -> 18.03 ms (tools/ab_wgrad_pad.sh, two rounds;
-    // padding the 32 KB 64x64 variant as well: no further change).
-    static const int pad40 = env_int("Y3_WGRAD_PAD40", 8192), pad32 = env_int("Y3_WGRAD_PAD32", 0);
+    // per CU (the occupancy their register budget aims at): step 18.21 -> 18.03 ms (A/B, two rounds; padding
+    // the 32 KB 64x64 variant as well: no further change).
+    constexpr int pad40 = 8192;
     if (x3) {
         if (!y3_wgrad_x3_launch(p, w.bkr, w.bn, grid.x, st)) {
             y3_set_error("conv2d_wgrad: no x3 kernel for tile %dx%d", w.bkr, w.bn);
@@ -2111,7 +2056,7 @@ extern "C" int y3_conv2d_wgrad_x(const y3_tensor* src, const y3_tensor* ddst, in
     else if (w.bkr == 64 && w.bn == 128)
         hipLaunchKernelGGL((conv_wgrad_kernel<64, 128, 2, 2, 16>), grid, dim3(256), pad40, st, p);
     else if (w.bkr == 64 && w.bn == 64)
-        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, 16>), grid, dim3(256), pad32, st, p);
+        hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, 16>), grid, dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL((conv_wgrad_kernel<64, 32, 2, 1, 16>), grid, dim3(128), 0, st, p);
     Y3_CHECK_LAUNCH("conv_wgrad");

@@ -83,7 +83,7 @@ constexpr int stage_rows(int bm, int tm, int cap) {
     return best;
 }
 
-template <int BM, int BN, int WM, int WN, bool STAGED, int BK = 32, int NBUF = 3, bool SK = false>
+template <int BM, int BN, int WM, int WN, int BK = 32, bool SK = false>
 __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128) ? 3 : 1) void conv_bf16_kernel(const Bf16Args p) {
     constexpr int THREADS = 64 * WM * WN;
     constexpr int Q = BK / 8;             // 16-byte quads per row and K step (BK = 32: 64-byte rows, 64: 128-byte rows)
@@ -95,6 +95,7 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128) ? 3 : 1) voi
     constexpr int TM = BM / WM, TN = BN / WN, MB = TM / 32, NB = TN / 32;
     constexpr int A_LOADS = BM * Q / THREADS, B_LOADS = (BN * Q + THREADS - 1) / THREADS;
     static_assert(BM * Q % THREADS == 0 && TM % 32 == 0 && TN % 32 == 0 && (BK == 32 || BK == 64), "tile shape");
+    constexpr int NBUF = 3;               // ring depth (2 and 4 measured and removed)
 
     // ONE LDS block (a second __shared__ object beside an LDS-DMA staging array makes hipcc drain vmcnt before every
     // ds_read, cdna_hip_programming.md 5): a ring of NBUF operand stages {A rows | B rows} in the main loop, re-used as the
@@ -297,45 +298,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 128 && BN == 128) ? 3 : 1) voi
     }
 
     Y3_TSTAMP(2);
-    if constexpr (!STAGED) {
-        // direct epilogue (no residual, 128x128 tiles): a lane stores its own channel of 16 x MB rows, 2 bytes at a time in
-        // 64-byte runs; cheaper than staging when there is nothing to load and keeps the main loop at 3 waves / SIMD
-        const bool do_lrelu = p.flags & Y3_EPI_LRELU;
-        const bool has_scale = p.scale != nullptr;
-        const __amdgpu_buffer_rsrc_t rs_dst = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, p.dst_bytes, 0x00020000);
-        const int mrow = m0 + wm * TM + 4 * lh;
-        const unsigned esz = p.out_f32 ? 4u : 2u;
-        const unsigned ldb = (unsigned)p.dst_ld * esz;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int n = n0 + wn * TN + j * 32 + l31;
-            const bool nok = n < p.Nout;
-            const float bias = (p.bias && nok) ? p.bias[n] : 0.f;
-            const float sc = (has_scale && nok) ? p.scale[n] : 1.f;
-            const float sf = (has_scale && nok) ? p.shift[n] : 0.f;
-            const unsigned vbase = (unsigned)mrow * ldb + (unsigned)n * esz;
-#pragma unroll
-            for (int i = 0; i < MB; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int dr = i * 32 + (r & 3) + 8 * (r >> 2);
-                    const bool ok = nok && mrow + dr < p.M;
-                    float v = acc[i][j][r] + bias;
-                    if (do_lrelu) v = v > 0.f ? v : p.alpha * v;
-                    if (has_scale) v = v * sc + sf;
-                    if (p.out_f32)
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs_dst, ok ? vbase : Y3_OOB, (unsigned)dr * ldb, 0);
-                    else
-                        __builtin_amdgcn_raw_buffer_store_b16(f32_to_bf16(v), rs_dst, ok ? vbase : Y3_OOB, (unsigned)dr * ldb, 0);
-                }
-            }
-        }
-#ifdef Y3_TIMING
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        Y3_TSTAMP(3);
-        return;
-    }
     // ---- epilogue.  D layout: col = lane & 31 (channel), row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
     // A lane owns single channels of scattered rows, so storing from registers would be 2-byte accesses in 64-byte
     // runs.  Instead the tile goes through LDS as fp32 (bias / lrelu / BN affine already applied) in passes of RPP rows,
@@ -1414,36 +1376,14 @@ static int check_bf16_tensor(const y3_tensor* t, const char* name) {
     return 0;
 }
 
-// Experiment switches: read from the environment only in the developer build (make DEV=1); the product library uses the defaults.
-static inline int dev_int(const char* name, int dflt) {
-#ifdef Y3_DEV
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
-
-template <int BM, int BN, int WM, int WN, bool STAGED = true, int BK = 32>
+template <int BM, int BN, int WM, int WN, int BK = 32>
 static void launch_bf16(const Bf16Args& args, int grid, hipStream_t st) {
     Bf16Args p = args;
     p.ohw = p.OH * p.OW;
     p.dv_nbn = y3_make_div(p.nbn);
     p.dv_ohw = y3_make_div(p.ohw);
     p.dv_ow = y3_make_div(p.OW);
-    static const int nbuf = dev_int("Y3_BF16_NBUF", 3);     // ring depth (experiments): 2, 3 or 4
-    if constexpr (BK == 32 && BM * BN <= 128 * 128) {
-        if (nbuf == 4) {
-            hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, STAGED, BK, 4>), dim3(grid), dim3(64 * WM * WN), 0, st, p);
-            return;
-        }
-        if (nbuf == 2) {
-            hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, STAGED, BK, 2>), dim3(grid), dim3(64 * WM * WN), 0, st, p);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, STAGED, BK, 3>), dim3(grid), dim3(64 * WM * WN), 0, st, p);
+    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, BK>), dim3(grid), dim3(64 * WM * WN), 0, st, p);
 }
 
 // Split-K plan of the 64 x 64-tile path (the small-M layers: 13x13 / 26x26 grids at batch 8, 19x19 at 8 x 608^2): without it a
@@ -1455,13 +1395,10 @@ struct Bf16Split {
 };
 static Bf16Split plan_bf16_split(long long M, int Nout, int K) {
     Bf16Split s = {1, K / 32, 0};
-    static const int on = dev_int("Y3_BF16_SPLITK", 1);
+    constexpr int maxtiles = 512, wgs = 1024, minsteps = 16;
     const long long tiles = (long long)y3_cdiv(M, 64) * y3_cdiv(Nout, 64);
     const int nk = K / 32;
-    static const int maxtiles = dev_int("Y3_BF16_SK_MAXTILES", 512);
-    if (!on || tiles > maxtiles || tiles * 4 > Y3_BF16_SK_HEADER || nk < 32) return s;
-    static const int wgs = dev_int("Y3_BF16_SK_WGS", 1024);
-    static const int minsteps = dev_int("Y3_BF16_SK_MINSTEPS", 16);
+    if (tiles > maxtiles || tiles * 4 > Y3_BF16_SK_HEADER || nk < 32) return s;
     int want = (int)(wgs / tiles);                     // aim at <= wgs workgroups
     if (want > 8) want = 8;
     if (want > nk / minsteps) want = nk / minsteps;    // at least minsteps K steps per slice
@@ -1587,13 +1524,11 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
     // the matrix pipe, so the best shape follows the grid size: 256x128 tiles (8 waves, K steps of 64) where that gives
     // 150-300 workgroups, 128x128 for larger grids, many small 64x64 workgroups (8+ waves / SIMD) for the small-M layers.
     const bool k64 = p.K % 64 == 0 && (p.ntaps == 1 || p.C % 64 == 0);
-    static const int force = dev_int("Y3_BF16_TILE", 0);   // experiments: 1 = 64x64, 2 = 128x128, 3 = 256x128
     const long long t256 = (long long)y3_cdiv(p.M, 256) * y3_cdiv(p.Nout, 128);
     const long long t128 = (long long)y3_cdiv(p.M, 128) * y3_cdiv(p.Nout, 128);
     // the 256 x 256 ping-pong kernel: whole 64-deep K tiles inside one tap, 16-byte rows for the epilogue, Cout in eights
-    static const int pp_mode = dev_int("Y3_BF16_PP", 1);     // 0 = off (A/B against conv_bf16_kernel)
     const long long tpp = (long long)y3_cdiv(p.M, 256) * y3_cdiv(p.Nout, 256);
-    if (pp_mode && p.C % 64 == 0 && p.Nout >= 256 && p.Nout % 8 == 0 && p.vec_ok && tpp >= (pp_mode == 2 ? 1 : 96)) {
+    if (p.C % 64 == 0 && p.Nout >= 256 && p.Nout % 8 == 0 && p.vec_ok && tpp >= 96) {
         p.nbn = y3_cdiv(p.Nout, 256);
         p.ohw = p.OH * p.OW;
         p.dv_nbn = y3_make_div(p.nbn);
@@ -1604,9 +1539,8 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
         return Y3_OK;
     }
     // the patch kernel for the 32 -> 64 3x3 layers (conv_bf16_c32_kernel)
-    static const int patch_on = dev_int("Y3_BF16_PATCH", 1);   // 0 = off (A/B against conv_bf16_kernel<128, 64>)
     const bool patch_epi_ok = !(flags & Y3_BF16_NO_PATCH) && (!(flags & Y3_EPI_LRELU) || (alpha >= 0.f && alpha <= 1.f));   // their leaky-relu is max(x, alpha x)
-    if (patch_on && patch_epi_ok && ksize == 3 && p.C == 32 && p.Nout == 64 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0 &&
+    if (patch_epi_ok && ksize == 3 && p.C == 32 && p.Nout == 64 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0 &&
         (!bias || ((uintptr_t)bias & 3) == 0)) {
         PatchArgs q = {};
         q.src = (const u16*)src->ptr;
@@ -1649,7 +1583,7 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
         Y3_CHECK_LAUNCH("conv_bf16_c32");
         return Y3_OK;
     }
-    if (patch_on && patch_epi_ok && ksize == 3 && p.C == 64 && p.Nout == 128 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0) {
+    if (patch_epi_ok && ksize == 3 && p.C == 64 && p.Nout == 128 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0) {
         PatchArgs q = {};
         q.src = (const u16*)src->ptr;
         q.wt = (const u16*)wt_t_bf16;
@@ -1693,25 +1627,17 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
     } else if (p.Nout <= 64) {
         p.nbn = 1;
         launch_bf16<128, 64, 4, 1>(p, y3_cdiv(p.M, 128), st);
-    } else if (k64 && (force == 3 || (force == 0 && t256 >= 150 && t256 <= 300))) {
+    } else if (k64 && t256 >= 150 && t256 <= 300) {
         p.nbn = y3_cdiv(p.Nout, 128);
         // (staged epilogue without a residual too, as for the 128 x 128 launches below: same box 8 x 608^2 2.552 -> 2.530 ms, 8 x 416^2
         // 1.729 -> 1.722, 25 / 45 tiles unchanged)
-        static const int direct256 = dev_int("Y3_BF16_DIRECT256", 0);   // 1 = the direct epilogue again (A/B)
-        if (p.resid || !direct256)
-            launch_bf16<256, 128, 4, 2, true, 64>(p, y3_cdiv(p.M, 256) * p.nbn, st);
-        else
-            launch_bf16<256, 128, 4, 2, false, 64>(p, y3_cdiv(p.M, 256) * p.nbn, st);
-    } else if (force == 2 || (force == 0 && t128 >= 512)) {
+        launch_bf16<256, 128, 4, 2, 64>(p, y3_cdiv(p.M, 256) * p.nbn, st);
+    } else if (t128 >= 512) {
         p.nbn = y3_cdiv(p.Nout, 128);
-        // with or without a residual through the staged epilogue (16-byte stores over whole tile rows).  Round 2 preferred the direct
+        // with or without a residual through the staged epilogue (16-byte stores over whole tile rows).  Round 2 preferred a direct
         // one (2-byte stores from registers, 3 waves per SIMD) where there is nothing to load; re-measured at the batches the tiled path
         // plans (45 x 608^2, same box): the ten 256 -> 128 1x1 launches of the 76^2 stage 60 -> 55 us, 512 -> 128 88 -> 76
-        static const int direct128 = dev_int("Y3_BF16_DIRECT128", 0);   // 1 = the direct epilogue again (A/B)
-        if (p.resid || !direct128)
-            launch_bf16<128, 128, 2, 2, true>(p, y3_cdiv(p.M, 128) * p.nbn, st);
-        else
-            launch_bf16<128, 128, 2, 2, false>(p, y3_cdiv(p.M, 128) * p.nbn, st);
+        launch_bf16<128, 128, 2, 2>(p, y3_cdiv(p.M, 128) * p.nbn, st);
     } else {
         p.nbn = y3_cdiv(p.Nout, 64);
         const int tiles = y3_cdiv(p.M, 64) * p.nbn;
@@ -1726,7 +1652,7 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
             p.dv_nbn = y3_make_div(p.nbn);
             p.dv_ohw = y3_make_div(p.ohw);
             p.dv_ow = y3_make_div(p.OW);
-            hipLaunchKernelGGL((conv_bf16_kernel<64, 64, 2, 2, true, 32, 3, true>), dim3(tiles * sk.splits), dim3(256), 0, st, p);
+            hipLaunchKernelGGL((conv_bf16_kernel<64, 64, 2, 2, 32, true>), dim3(tiles * sk.splits), dim3(256), 0, st, p);
         } else {
             launch_bf16<64, 64, 2, 2>(p, tiles, st);
         }
@@ -1745,7 +1671,7 @@ extern "C" int y3_conv2d_first_bf16(const y3_tensor* src, const float* wt, const
     Y3_CHECK_ARG((scale == nullptr) == (shift == nullptr), "conv2d_first_bf16: scale/shift must both be given");
     const long long npix = (long long)src->n * src->h * src->w;
     Y3_CHECK_ARG(npix * src->ld * 4 < 0x7fffffffLL, "conv2d_first_bf16: input of 2 GiB or more (split the batch)");
-    static const int groups = dev_int("Y3_BF16_FIRST_GROUPS", 16);
+    constexpr int groups = 16;
     const int xtiles = y3_cdiv(src->w, 32), rchunks = y3_cdiv(src->h, 4 * groups);
     const long long wgs = (long long)src->n * rchunks * xtiles;
     Y3_CHECK_ARG(wgs < 0x7fffffffLL, "conv2d_first_bf16: too many tiles");

@@ -20,12 +20,12 @@ struct FastArgs {
     const float* wt;   // [tap][C][Nout]; the x3 kernels (conv_x3.hip): the bf16 piece planes y3_x3_split_weights makes of the K-contiguous copy
     int Cper;          // channels per tap (K = ntaps * Cper)
     int x3_mode;       // x3 kernels: bit 0 = non-temporal activation loads, bit 3 = short-last deal of the items (conv_fast_decode)
-    // Order of the K steps of a multi-tap launch.  korder 2: 32-channel group (one 128-byte line per pixel) outermost, taps inside,
-    // the two 16-channel halves of the line innermost: the taps of a group re-read the same few image rows, and so do the
-    // neighbouring row tiles -- all within 2 * ntaps steps, while the rows are still in L2.  korder 0 (taps outermost) spaces the
-    // three uses of an image row a third of a workgroup's life apart: the big early layers fetched their input 3-4x (rocprofv3
-    // FETCH_SIZE, profiles/r04_traffic_by_kernel.txt).  korder 1 (16-channel chunks outermost; C % 32 != 0) splits the two halves
-    // of a line by ntaps steps: worse than 0 for the 32-channel layers.  dv_taps divides by the steps of a group (ntaps << (korder - 1)).
+    // Order of the K steps of a multi-tap launch (0 for one tap).  korder 2: 32-channel group (one 128-byte line per pixel)
+    // outermost, taps inside, the two 16-channel halves of the line innermost: the taps of a group re-read the same few image rows,
+    // and so do the neighbouring row tiles -- all within 2 * ntaps steps, while the rows are still in L2.  Taps outermost, measured
+    // and removed, spaced the three uses of an image row a third of a workgroup's life apart: the big early layers fetched their
+    // input 3-4x (rocprofv3 FETCH_SIZE, profiles/r04_traffic_by_kernel.txt).  korder 1 (16-channel chunks outermost) is for
+    // C % 32 != 0, which has no 32-channel groups.  dv_taps divides by the steps of a group (ntaps << (korder - 1)).
     int korder;
     Y3Div dv_taps;
     float* dst;

@@ -1173,12 +1173,7 @@ bool y3_x3p_ok(const FastArgs& p, int bm, int bn, bool dense) {
 }
 
 bool y3_x3_launch(const FastArgs& p, int bm, int bn, bool dense, int grid, hipStream_t st) {
-#ifdef Y3_DEV
-    static const int no_patch = getenv("Y3_X3_NO_PATCH") ? atoi(getenv("Y3_X3_NO_PATCH")) : 0;      // development: the im2col-order kernel for every launch
-#else
-    const int no_patch = 0;
-#endif
-    if (!no_patch && y3_x3p_ok(p, bm, bn, dense)) {
+    if (y3_x3p_ok(p, bm, bn, dense)) {
         const dim3 g(grid), b(256);
         if (p.bn_a)
             hipLaunchKernelGGL((conv_x3p_kernel<128, 128, 2, 2, true>), g, b, 0, st, p);

@@ -72,7 +72,6 @@ def tile_table(height, width, tile_size):
     return np.asarray(rows, np.int32), xs, ys
 
 
-_BANDS = os.environ.get('Y3_TILED_BANDS', '1') != '0'      # (development: 0 = the whole image before the first batch)
 _GATHER_DTYPES = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2}
 
 
@@ -231,7 +230,6 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
     # bands travel on a copy stream while it runs (a 50 MB image takes ~1 ms over PCIe).
     cur = torch.cuda.current_stream()
     slots = 2 if getattr(yolo_model, 'supports_slots', False) else 1
-    slots = min(slots, int(os.environ.get('Y3_TILED_SLOTS', slots)))      # (development: 1 = batches one after the other)
     streams = [torch.cuda.Stream() for _ in range(slots)] if slots > 1 else [cur]
     copy_stream = torch.cuda.Stream() if len(sizes) > 1 else cur
     img_dev = torch.empty(img_host.shape, dtype=img_host.dtype, device='cuda')
@@ -242,8 +240,8 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
             table_dev.record_stream(s)
     queued = []
     rows_up = 0
-    bands = upload_bands(table, sizes, img_size[0]) if _BANDS else [img_size[0]] * len(sizes)
-    fused = hasattr(yolo_model, 'run_tiles') and not getattr(yolo_model, '_fm', False) and os.environ.get('Y3_TILED_FUSED', '1') != '0'
+    bands = upload_bands(table, sizes, img_size[0])
+    fused = hasattr(yolo_model, 'run_tiles') and not getattr(yolo_model, '_fm', False)
     for bi, (b0, nb) in enumerate(zip(starts, sizes)):
         need = bands[bi]
         if need > rows_up:

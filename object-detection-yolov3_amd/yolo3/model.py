@@ -24,8 +24,6 @@ from ._hip import lib, check, view, EPI_LRELU, EPI_ACCUM, CONV_X3, BF16_NO_PATCH
 
 BN_EPS = 1e-3          # Keras BatchNormalization defaults
 BN_MOMENTUM = 0.99
-BN_EPILOGUE_STATS = os.environ.get('Y3_BN_EPI', '1') != '0'   # BatchNorm-backward statistics from the epilogue of the data gradient that completes dy
-BN_EPILOGUE_WIDE = os.environ.get('Y3_BN_EPI_WIDE', '1') != '0'   # ... also when the consumer is a stride-2 convolution or reads a concat slice
 LRELU_ALPHA = 0.2      # tf.nn.leaky_relu default (App. C3)
 BF16_PATCH_MIN_BYTES = 300e6   # bf16 path: a 3x3 layer that moves less (input + residual + output) stays off the patch kernels
 ALIGN = 64             # arena alignment in floats (256 B)
@@ -458,40 +456,37 @@ class _Plan:
         # the producer only needs y3_bn_bwd_finalize_tiles; every other layer keeps y3_bn_bwd_stats.
         epi_of = {}            # id(consumer op) -> (producer activation a, partial buffer, tiles)
         epi_for = {}           # id(producer op) -> (partial buffer, tiles)
-        if BN_EPILOGUE_STATS:
-            first_consumer = {}
-            for op in self.ops:
-                reads = []
-                if op[0] == 'conv_layer':
-                    reads = [op[2]] + ([op[5]] if op[5] is not None else [])
-                elif op[0] == 'head':
-                    reads = [op[2]]
-                elif op[0] == 'upsample':
-                    reads = [op[1]]
-                for t in reads:
-                    first_consumer.setdefault(id(t), op)
-                    if t.parent is not None:
-                        first_consumer.setdefault(id(t.parent), op)
-                    for ch in t.children:
-                        first_consumer.setdefault(id(ch), op)
-            for op in self.ops:
-                if op[0] != 'conv_layer':
-                    continue
-                _, i, src, a, y, resid, _ = op
-                cons = first_consumer.get(id(y))
-                if cons is None or cons[0] != 'conv_layer' or cons[2] is not y or y.children or y is self.x0:
-                    continue      # (a concat SLICE qualifies: later readers of the whole concat are visited earlier by the reversed walk)
-                if not BN_EPILOGUE_WIDE and (y.parent is not None or specs[cons[1]].s != 1):
-                    continue
-                csp = specs[cons[1]]
-                ca = cons[3]
-                dd = view(self.dz, ca.n, ca.h, ca.w, csp.cout)
-                tiles = int(lib.y3_conv2d_dgrad_bn_tiles_x(dd, csp.k, csp.s, y.v, CONV_X3 if mdl.x3_dgrad(csp, y.m) else 0))
-                if tiles <= 0:
-                    continue
-                part = torch.empty(tiles * 6 * y.c, dtype=torch.float32, device=mdl.device)
-                epi_of[id(cons)] = (a, part, tiles)
-                epi_for[id(op)] = (part, tiles)
+        first_consumer = {}
+        for op in self.ops:
+            reads = []
+            if op[0] == 'conv_layer':
+                reads = [op[2]] + ([op[5]] if op[5] is not None else [])
+            elif op[0] == 'head':
+                reads = [op[2]]
+            elif op[0] == 'upsample':
+                reads = [op[1]]
+            for t in reads:
+                first_consumer.setdefault(id(t), op)
+                if t.parent is not None:
+                    first_consumer.setdefault(id(t.parent), op)
+                for ch in t.children:
+                    first_consumer.setdefault(id(ch), op)
+        for op in self.ops:
+            if op[0] != 'conv_layer':
+                continue
+            _, i, src, a, y, resid, _ = op
+            cons = first_consumer.get(id(y))
+            if cons is None or cons[0] != 'conv_layer' or cons[2] is not y or y.children or y is self.x0:
+                continue      # (a concat SLICE qualifies: later readers of the whole concat are visited earlier by the reversed walk)
+            csp = specs[cons[1]]
+            ca = cons[3]
+            dd = view(self.dz, ca.n, ca.h, ca.w, csp.cout)
+            tiles = int(lib.y3_conv2d_dgrad_bn_tiles_x(dd, csp.k, csp.s, y.v, CONV_X3 if mdl.x3_dgrad(csp, y.m) else 0))
+            if tiles <= 0:
+                continue
+            part = torch.empty(tiles * 6 * y.c, dtype=torch.float32, device=mdl.device)
+            epi_of[id(cons)] = (a, part, tiles)
+            epi_for[id(op)] = (part, tiles)
         self.epilogue_stats_layers = len(epi_for)
         first_src = self.x0
         # The kernel gradient of a layer and its data gradient both start from dz and are independent.  Each is a single

@@ -1,5 +1,6 @@
-"""Time y3_conv2d_fwd / dgrad / wgrad on the network's main shapes under the tile forced by Y3_TILE (development tool).
-    Y3_TILE=128,128,32 python tools/conv_tune.py"""
+"""Time y3_conv2d_fwd / dgrad / wgrad on the network's main shapes with the planned tiles (also the per-shape driver of the
+fp32 conv counter pass in tools/profile_round.sh).
+    python tools/conv_tune.py"""
 import os
 import sys
 
@@ -20,7 +21,6 @@ SHAPES = [  # n, h, w, cin, cout, k, s
     (8, 13, 13, 1024, 512, 1, 1),
 ]
 st = torch.cuda.current_stream().cuda_stream
-tile = os.environ.get('Y3_TILE', 'default')
 for (n, h, w, cin, cout, k, s) in SHAPES:
     oh, ow = -(-h // s), -(-w // s)
     x = torch.randn(n * h * w * cin, device='cuda')
@@ -54,4 +54,4 @@ for (n, h, w, cin, cout, k, s) in SHAPES:
         torch.cuda.synchronize()
         t = a.elapsed_time(e) / 10 * 1e-3
         res.append('%s %7.1f us %6.1f TF' % (mode, t * 1e6, 2.0 * n * oh * ow * k * k * cin * cout / t / 1e12))
-    print('tile %-11s M=%7d cin=%4d cout=%4d k=%d | %s' % (tile, n * oh * ow, cin, cout, k, ' | '.join(res)), flush=True)
+    print('M=%7d cin=%4d cout=%4d k=%d | %s' % (n * oh * ow, cin, cout, k, ' | '.join(res)), flush=True)

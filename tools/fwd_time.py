@@ -1,4 +1,4 @@
-"""fp32 inference forward + decode at batch 8, 416x416 and one training step, timed (development: planner sweeps via env)."""
+"""fp32 inference forward + decode at batch 8, 416x416 and one training step, timed (development; the Y3_ variables set are printed with the result)."""
 import os
 import sys
 import time

@@ -1,7 +1,7 @@
-"""Development tool: capture one training step as a HIP graph with the loss entry's flag clear as
-hipMemsetAsync (the round-3 form: DEV library, Y3_LOSS_MEMSET=1) and with the shipped clear kernel, dump both graphs
-(hipGraphDebugDotPrint through torch.cuda.CUDAGraph.debug_dump) and report what every memset / memcpy node is wired to.
-    Y3_LIB=object-detection-yolov3_amd/yolo3/_lib/libyolo3hip_dev.so Y3_LOSS_MEMSET=1 python tools/graph_dump.py out_prefix [img] [batch]"""
+"""Development tool: capture one training step as a HIP graph, dump it (hipGraphDebugDotPrint) and
+report what every memset / memcpy node is wired to.  (Round 3 compared the loss entry's flag clear as hipMemsetAsync against
+the shipped clear kernel with it; the memset form has since been removed.)
+    python tools/graph_dump.py out_prefix [img] [batch]"""
 import os
 import re
 import sys
