@@ -110,17 +110,33 @@ def same_pad(size, k, s):
 # ----------------------------------------------------------------------------
 # forward
 # ----------------------------------------------------------------------------
+class _ForcedLeakyRelu(torch.autograd.Function):
+    """Teacher-forced training: the forward returns the implementation's own post-leaky-relu tensor `a_forced` in place of
+    leaky_relu(z); the backward applies the slope read from `a_forced` (1 where a > 0, LRELU_ALPHA elsewhere).  The backward is
+    then a smooth function of the forced tensors: no slope decision can differ between the checker and the checked."""
+
+    @staticmethod
+    def forward(ctx, z, a_forced):
+        ctx.save_for_backward(torch.where(a_forced > 0, 1.0, LRELU_ALPHA).to(z.dtype))
+        return a_forced.to(z.dtype).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        slope, = ctx.saved_tensors
+        return g * slope, None
+
+
 class Net:
     """Functional network over a list of per-layer tensors."""
 
-    def __init__(self, params, in_channels, num_anchors, num_classes, dtype=torch.float32, requires_grad=False):
+    def __init__(self, params, in_channels, num_anchors, num_classes, dtype=torch.float32, requires_grad=False, device=None):
         self.specs = layer_specs(in_channels, num_anchors, num_classes)
         self.dtype = dtype
         self.p = []
         for sp, p in zip(self.specs, params):
             q = {}
             for name, v in p.items():
-                t = torch.tensor(np.asarray(v), dtype=dtype)
+                t = v.detach().to(device=device, dtype=dtype).clone() if torch.is_tensor(v) else torch.tensor(np.asarray(v), dtype=dtype, device=device)
                 if requires_grad and name in ('W', 'b', 'gamma', 'beta'):
                     t.requires_grad_(True)
                 q[name] = t
@@ -134,6 +150,12 @@ class Net:
         self.up_trace = None    # optional list of the two upsample outputs (before rounding)
         self.bf16 = False       # emulate the bf16 inference path: operands of every conv after the first rounded to
                                 # bf16 (round-to-nearest-even), fp32 accumulate / epilogue, one rounding per stored activation
+        self.teacher = None     # teacher-forced TRAINING (with `force`): {'a': [per BatchNorm layer: the implementation's post-leaky-relu
+                                # tensor]}.  Each conv still computes z = conv(forced input) + b, but BatchNorm normalises the forced `a`
+                                # (_ForcedLeakyRelu).  A training forward fills in 'act' (leaky_relu(z) per BatchNorm layer, detached: the
+                                # forward check), 'y' and 'up' (every layer's / upsample's LIVE output, for a surrogate backward that
+                                # seeds each with the implementation's gradient -- tests/teacher_forced.py).  Without 'a' nothing is
+                                # forced and the dict only records.
 
     def _r(self, t):
         return t.to(torch.bfloat16).to(t.dtype) if self.bf16 else t
@@ -160,6 +182,10 @@ class Net:
         if not sp['bn']:
             return z                               # detection_layer model.py:108-120 (linear)
         a = F.leaky_relu(z, LRELU_ALPHA)
+        if self.teacher is not None and training:
+            self.teacher['act'].append(a.detach())
+            if 'a' in self.teacher:
+                a = _ForcedLeakyRelu.apply(z, self.teacher['a'][len(self.batch_stats)])
         if training:
             mean = a.mean(dim=(0, 2, 3))
             var = a.var(dim=(0, 2, 3), unbiased=False)
@@ -174,12 +200,14 @@ class Net:
         """model.py:94-105: frozen all-ones Conv2DTranspose k2 s2 (Q3): every
         output channel = sum over input channels, nearest 2x."""
         C = x.shape[1]
-        w = torch.ones(C, C, 2, 2, dtype=x.dtype)
+        w = torch.ones(C, C, 2, 2, dtype=x.dtype, device=x.device)
         return F.conv_transpose2d(x, w, stride=2)
 
     def feature_maps(self, x, training):
         """model.py:356-421 -> (fm1, fm2, fm3) NCHW [N, A*(5+K), G, G]."""
         self.batch_stats = []
+        if self.teacher is not None:
+            self.teacher.update(act=[], y=[], up=[])
         it = iter(range(len(self.specs)))
         raw = lambda t: self._conv_layer(t, next(it), training)
         count = [0, 0]
@@ -190,6 +218,8 @@ class Net:
             count[0] += 1
             if self.trace_exact is not None:
                 self.trace_exact.append(y.detach())
+            if self.teacher is not None:
+                self.teacher['y'].append(y)
             y = self._r(y)
             if self.trace is not None:
                 self.trace.append(y.detach())
@@ -206,6 +236,8 @@ class Net:
             count[1] += 1
             if self.up_trace is not None:
                 self.up_trace.append(y.detach())      # before rounding, like trace_exact
+            if self.teacher is not None:
+                self.teacher['up'].append(y)
             y = self._r(y)
             return self.force['up'][j].to(y.dtype) if self.force is not None else y
 
@@ -285,8 +317,9 @@ def _sigmoid_ce(labels, logits):
     return torch.clamp(logits, min=0) - logits * labels + torch.log1p(torch.exp(-torch.abs(logits)))
 
 
-def loss_layer(fm, gt, img_size, anchors, num_classes):
-    """model.py:230-354 -> (xy, wh, obj, class) losses, each / local batch."""
+def loss_layer(fm, gt, img_size, anchors, num_classes, info=None):
+    """model.py:230-354 -> (xy, wh, obj, class) losses, each / local batch.  ``info`` (optional dict) receives 'best_iou'
+    [N, Gh, Gw, A]: each prediction's best IoU against the ignore-mask boxes (None when there are none)."""
     N, _, Gh, Gw = fm.shape
     dt = fm.dtype
     stride = torch.tensor([img_size[0] // Gh, img_size[1] // Gw], dtype=dt)
@@ -303,6 +336,8 @@ def loss_layer(fm, gt, img_size, anchors, num_classes):
     true_wh = (torch.ones_like(gt[..., 2:4]) * anc)[sel]            # [V,2]
     if true_wh.shape[0] == 0:
         ignore = torch.ones_like(object_mask)                       # reduce_max over empty = -inf < .5
+        if info is not None:
+            info['best_iou'] = None
     else:
         true_xy = torch.zeros_like(true_wh)
         pxy = pred_xy.unsqueeze(-2)
@@ -313,6 +348,8 @@ def loss_layer(fm, gt, img_size, anchors, num_classes):
         inter = iwh[..., 0] * iwh[..., 1]
         iou = inter / (pwh[..., 0] * pwh[..., 1] + true_wh[..., 0] * true_wh[..., 1] - inter)
         ignore = (iou.max(dim=-1).values < 0.5).to(dt).unsqueeze(-1)
+        if info is not None:
+            info['best_iou'] = iou.max(dim=-1).values.detach()
     ignore = ignore.detach()
     valid = (object_mask + (1 - object_mask) * ignore).detach()
     object_mask = object_mask.detach()
