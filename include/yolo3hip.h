@@ -350,6 +350,45 @@ int y3_nms_per_class(const float* rows, int n, int nb, int num_classes, float mi
                      int* keep_idx, int* keep_cnt, float* keep_score, int max_keep,
                      void* workspace, size_t workspace_bytes, y3_stream_t stream);
 size_t y3_nms_workspace_bytes(int n, int nb, int num_classes);
+
+/* ---- opt-in NMS variants (not in the reference) ----------------------------------------------------
+ * y3_nms_per_class_ex: y3_nms_per_class with a method.  Candidates are selected exactly as y3_nms_per_class selects
+ * them (one device function): optional clip, strict > small-box filter, score = sqrtf(cls * obj) >= score_thr.  The
+ * order key is (score bits << 32) | row: larger score first, equal scores -> higher row index first.  Outputs keep the
+ * layout and truncation rule of y3_nms_per_class: keep_idx [N,K,max_keep], keep_cnt [N,K] = min(count, max_keep),
+ * keep_score [N,K,max_keep], in emission order.  All fp32 below is evaluated in the order written, no contraction
+ * (-ffp-contract=off), so a NumPy float32 restatement reproduces it bit for bit (except expf, see gaussian).
+ * iou(k, j) is y3_nms_per_class's: xl = max(kx0,x0), yt = max(ky0,y0), xr = min(kx1,x1), yb = min(ky1,y1),
+ *   inter = max(yb - yt, 0) * max(xr - xl, 0), iou = inter / ((karea + area) - inter), area = (x1 - x0) * (y1 - y0).
+ *
+ * Y3_NMS_HARD: exactly the launch of y3_nms_per_class (sigma ignored).
+ * Y3_NMS_DIOU (Zheng et al. 2020): the greedy rounds of y3_nms_per_class; candidate j survives kept box k iff
+ *     d = iou - rho2 / c2 <= iou_thr, with
+ *     dx = (x0 + x1) * 0.5f - (kx0 + kx1) * 0.5f,  dy = (y0 + y1) * 0.5f - (ky0 + ky1) * 0.5f,  rho2 = dx * dx + dy * dy,
+ *     ex = max(kx1, x1) - min(kx0, x0),  ey = max(ky1, y1) - min(ky0, y0),  c2 = ex * ex + ey * ey.
+ *     A NaN d (zero union, or c2 == 0) drops the candidate.  sigma ignored.
+ * Y3_NMS_SOFT_LINEAR / Y3_NMS_SOFT_GAUSSIAN (Bodla et al. 2017): s = the candidate scores; until no live candidate is left:
+ *     1. pick the live candidate with the largest key (score bits = its CURRENT score s);
+ *     2. emit its row and s (keep_score holds the decayed score);
+ *     3. every other live candidate j: iou = iou(pick, j) and
+ *          linear:   if (iou > iou_thr) s = s * (1.0f - iou)
+ *          gaussian: s = s * expf(-(iou * iou) / sigma)
+ *     4. drop j when iou is NaN or !(s >= score_thr).
+ *     Emitted scores never increase, so the output is in keep order.  Requires score_thr > 0 and, for gaussian,
+ *     sigma > 0 (else Y3_EINVAL + message, nothing launched).  expf is the device library's (within about 1 ulp of the
+ *     exact value), so gaussian scores agree with a float64 restatement to rounding, not bit for bit.
+ * workspace: y3_nms_workspace_bytes_ex(n, nb, num_classes, method) bytes (hard / diou: y3_nms_workspace_bytes; soft:
+ * 0 for nb <= 8192, the candidate state then lives in registers; workspace may be NULL when 0 bytes are needed). */
+#define Y3_NMS_HARD 0
+#define Y3_NMS_DIOU 1
+#define Y3_NMS_SOFT_LINEAR 2
+#define Y3_NMS_SOFT_GAUSSIAN 3
+int y3_nms_per_class_ex(const float* rows, int n, int nb, int num_classes, int method, float min_box,
+                        float score_thr, float iou_thr, float sigma, float clip_w, float clip_h,
+                        int* keep_idx, int* keep_cnt, float* keep_score, int max_keep,
+                        void* workspace, size_t workspace_bytes, y3_stream_t stream);
+size_t y3_nms_workspace_bytes_ex(int n, int nb, int num_classes, int method);
+
 /* bbox_utils.single_class_nms (bbox_utils.py:217-237): rows5 [M,5] = x0,y0,x1,y1,score; every row is
  * a candidate, the score is used as is.  keep_idx/keep_score [M], keep_cnt [1].
  * workspace: y3_nms_workspace_bytes(1, M, 1). */

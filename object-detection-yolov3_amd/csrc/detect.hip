@@ -285,6 +285,8 @@ struct NmsArgs {
     int cap;  // capacity (power of two) of the per-block key array
     unsigned char* ws;
     size_t ws_per_block;
+    int soft_gauss;  // soft_nms_kernel: 1 = Gaussian decay, 0 = linear
+    float sigma;     // Gaussian decay parameter
 };
 
 // IoU in the reference's operation order (bbox_utils.py:200-214), float32, no contraction
@@ -296,6 +298,36 @@ __device__ __forceinline__ bool nms_suppressed(float kx0, float ky0, float kx1, 
     const float uni = (karea + area) - inter;
     const float iou = inter / uni;
     return !(iou <= thr);  // survivors satisfy iou <= thr; NaN is dropped, as np.where(iou <= thr) drops it
+}
+
+// The same IoU as nms_suppressed, returned (soft-NMS decays by it); k is the picked box
+__device__ __forceinline__ float nms_iou(float kx0, float ky0, float kx1, float ky1, float karea, float x0, float y0, float x1, float y1,
+                                        float area) {
+    const float xl = fmaxf(kx0, x0), yt = fmaxf(ky0, y0);
+    const float xr = fminf(kx1, x1), yb = fminf(ky1, y1);
+    const float inter = fmaxf(yb - yt, 0.f) * fmaxf(xr - xl, 0.f);
+    const float uni = (karea + area) - inter;
+    return inter / uni;
+}
+
+// DIoU-NMS survival test (Y3_NMS_DIOU, yolo3hip.h): iou - rho2 / c2 <= thr survives, NaN is dropped
+__device__ __forceinline__ bool nms_suppressed_diou(float kx0, float ky0, float kx1, float ky1, float karea, float x0, float y0, float x1,
+                                                    float y1, float area, float thr) {
+    const float iou = nms_iou(kx0, ky0, kx1, ky1, karea, x0, y0, x1, y1, area);
+    const float dx = (x0 + x1) * 0.5f - (kx0 + kx1) * 0.5f;
+    const float dy = (y0 + y1) * 0.5f - (ky0 + ky1) * 0.5f;
+    const float rho2 = dx * dx + dy * dy;
+    const float ex = fmaxf(kx1, x1) - fminf(kx0, x0);
+    const float ey = fmaxf(ky1, y1) - fminf(ky0, y0);
+    const float c2 = ex * ex + ey * ey;
+    return !(iou - rho2 / c2 <= thr);
+}
+
+template <int CRIT>
+__device__ __forceinline__ bool nms_test(float kx0, float ky0, float kx1, float ky1, float karea, float x0, float y0, float x1, float y1,
+                                         float area, float thr) {
+    if (CRIT == Y3_NMS_DIOU) return nms_suppressed_diou(kx0, ky0, kx1, ky1, karea, x0, y0, x1, y1, area, thr);
+    return nms_suppressed(kx0, ky0, kx1, ky1, karea, x0, y0, x1, y1, area, thr);
 }
 
 // bbox_utils.filter_small_boxes (bbox_utils.py:274-281): indices of the rows with (x1 - x0) > min AND (y1 - y0) > min (strict),
@@ -357,7 +389,31 @@ extern "C" int y3_compute_iou(const float* box4, const float* boxes, int m, int 
     return Y3_OK;
 }
 
-template <bool LDS_KEYS>
+// A row's box, clipped to [0,clip_w]x[0,clip_h] when clip_w > 0
+__device__ __forceinline__ void nms_load_box(const NmsArgs& p, const float* r, float& x0, float& y0, float& x1, float& y1) {
+    x0 = r[0];
+    y0 = r[1];
+    x1 = r[2];
+    y1 = r[3];
+    if (p.clip_w > 0.f) {
+        x0 = fminf(fmaxf(x0, 0.f), p.clip_w);
+        x1 = fminf(fmaxf(x1, 0.f), p.clip_w);
+        y0 = fminf(fmaxf(y0, 0.f), p.clip_h);
+        y1 = fminf(fmaxf(y1, 0.f), p.clip_h);
+    }
+}
+
+// The candidate test every NMS method shares: clip, small-box filter (strict >), score = sqrt(cls*obj) >= thr
+__device__ __forceinline__ bool nms_candidate(const NmsArgs& p, const float* r, int cls, float& x0, float& y0, float& x1, float& y1,
+                                              float& score) {
+    nms_load_box(p, r, x0, y0, x1, y1);
+    const float w = x1 - x0, h = y1 - y0;
+    score = p.raw ? r[4] : sqrtf(r[5 + cls] * r[4]);
+    return w > p.min_box && h > p.min_box && score >= p.score_thr;
+}
+
+// CRIT: Y3_NMS_HARD (nms_suppressed) or Y3_NMS_DIOU (nms_suppressed_diou); the greedy rounds are the same
+template <bool LDS_KEYS, int CRIT>
 __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int s_count, s_kept, s_nk;
@@ -383,19 +439,9 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
     __syncthreads();
 
     // 1. candidates: small-box filter (strict >), score = sqrt(cls*obj) >= thr
-    const bool clip = p.clip_w > 0.f;
     for (int i = tid; i < p.nb; i += 1024) {
-        const float* r = rows + (long long)i * p.D;
-        float x0 = r[0], y0 = r[1], x1 = r[2], y1 = r[3];
-        if (clip) {
-            x0 = fminf(fmaxf(x0, 0.f), p.clip_w);
-            x1 = fminf(fmaxf(x1, 0.f), p.clip_w);
-            y0 = fminf(fmaxf(y0, 0.f), p.clip_h);
-            y1 = fminf(fmaxf(y1, 0.f), p.clip_h);
-        }
-        const float w = x1 - x0, h = y1 - y0;
-        const float score = p.raw ? r[4] : sqrtf(r[5 + cls] * r[4]);
-        if (w > p.min_box && h > p.min_box && score >= p.score_thr) {
+        float x0, y0, x1, y1, score;
+        if (nms_candidate(p, rows + (long long)i * p.D, cls, x0, y0, x1, y1, score)) {
             const int slot = atomicAdd(&s_count, 1);
             keys[slot] = ((unsigned long long)__float_as_uint(score) << 32) | (unsigned)i;
         }
@@ -427,14 +473,8 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
 
     // 3. gather the sorted boxes (SoA) and their areas
     for (int i = tid; i < count; i += 1024) {
-        const float* r = rows + (long long)(unsigned)(keys[i] & 0xffffffffull) * p.D;
-        float x0 = r[0], y0 = r[1], x1 = r[2], y1 = r[3];
-        if (clip) {
-            x0 = fminf(fmaxf(x0, 0.f), p.clip_w);
-            x1 = fminf(fmaxf(x1, 0.f), p.clip_w);
-            y0 = fminf(fmaxf(y0, 0.f), p.clip_h);
-            y1 = fminf(fmaxf(y1, 0.f), p.clip_h);
-        }
+        float x0, y0, x1, y1;
+        nms_load_box(p, rows + (long long)(unsigned)(keys[i] & 0xffffffffull) * p.D, x0, y0, x1, y1);
         bx0[i] = x0;
         by0[i] = y0;
         bx1[i] = x1;
@@ -465,7 +505,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
                 const int k = __ffsll((long long)mask) - 1;
                 kept |= 1ull << k;
                 const float kx0 = __shfl(x0, k), ky0 = __shfl(y0, k), kx1 = __shfl(x1, k), ky1 = __shfl(y1, k), kar = __shfl(ar, k);
-                if (alive && tid > k && nms_suppressed(kx0, ky0, kx1, ky1, kar, x0, y0, x1, y1, ar, p.iou_thr)) alive = false;
+                if (alive && tid > k && nms_test<CRIT>(kx0, ky0, kx1, ky1, kar, x0, y0, x1, y1, ar, p.iou_thr)) alive = false;
                 mask = __ballot(alive) & ~((2ull << k) - 1ull);
             }
             const int nk = __popcll(kept);
@@ -492,7 +532,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
                 if (dead[j]) continue;
                 const float x0 = bx0[j], y0 = by0[j], x1 = bx1[j], y1 = by1[j], ar = bar[j];
                 for (int q = 0; q < nk; ++q)
-                    if (nms_suppressed(s_kb[0][q], s_kb[1][q], s_kb[2][q], s_kb[3][q], s_kb[4][q], x0, y0, x1, y1, ar, p.iou_thr)) {
+                    if (nms_test<CRIT>(s_kb[0][q], s_kb[1][q], s_kb[2][q], s_kb[3][q], s_kb[4][q], x0, y0, x1, y1, ar, p.iou_thr)) {
                         dead[j] = 1;
                         break;
                     }
@@ -503,22 +543,215 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
     if (tid == 0) p.keep_cnt[blockIdx.x] = s_kept < p.max_keep ? s_kept : p.max_keep;
 }
 
+// ---------------------------------------------------------------------------
+// Soft-NMS (Y3_NMS_SOFT_LINEAR / Y3_NMS_SOFT_GAUSSIAN, yolo3hip.h): one 1024-thread workgroup per (image, class), no sort.
+// Candidate state (box, current score) of R > 0: thread t owns rows t + 1024 r (r < R) in registers, rows that are no
+// candidate start dead (nb <= 1024 R).  R == 0: the candidates are compacted into the workspace, SoA x0,y0,x1,y1,score,row
+// [cap] each, and thread t owns slots t + 1024 r; the slot order does not matter, the key carries the row.
+// One emission = the previous pick's decay and prune fused with each thread's argmax of its live keys, a wave max, one LDS
+// entry per wave in the half chosen by the emission's parity, ONE barrier, and every thread reducing the 16 wave entries
+// itself.  (A wave writes half e&1 at emission e; it can only write that half again at e+2, after the barrier of e+1, which
+// every thread reaches only once it has read half e&1 of emission e.)  A dead candidate has score 0: a live one is >= score_thr > 0.
+// ---------------------------------------------------------------------------
+#define Y3_SOFT_REG_ROWS 8192  // rows above this: candidate state in the workspace (16 rows per thread in registers spill)
+
+__device__ __forceinline__ float soft_decay(float s, float iou, const NmsArgs& p) {
+    float t;
+    if (p.soft_gauss)
+        t = s * expf(-(iou * iou) / p.sigma);
+    else
+        t = iou > p.iou_thr ? s * (1.0f - iou) : s;
+    return (iou != iou || !(t >= p.score_thr)) ? 0.f : t;
+}
+
+__device__ __forceinline__ unsigned long long soft_key(float s, int row) {
+    return s > 0.f ? ((unsigned long long)__float_as_uint(s) << 32) | (unsigned)row : 0ull;
+}
+
+template <int R>
+__global__ __launch_bounds__(1024) void soft_nms_kernel(const NmsArgs p) {
+    __shared__ unsigned long long s_key[2][16];
+    __shared__ float s_box[2][16][4];
+    __shared__ int s_count;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int img = blockIdx.x / p.K, cls = blockIdx.x % p.K;
+    const float* rows = p.rows + (long long)img * p.nb * p.D;
+    constexpr int NR = R > 0 ? R : 1;
+    float cx0[NR], cy0[NR], cx1[NR], cy1[NR], cs[NR];
+    // R == 0: workspace SoA
+    unsigned char* wsb = p.ws + (size_t)blockIdx.x * p.ws_per_block;
+    float* gx0 = (float*)wsb;
+    float* gy0 = gx0 + p.cap;
+    float* gx1 = gy0 + p.cap;
+    float* gy1 = gx1 + p.cap;
+    float* gs = gy1 + p.cap;
+    int* grow = (int*)(gs + p.cap);
+    int count = 0;
+
+    if (R > 0) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const int i = tid + 1024 * r;
+            float sc = 0.f;
+            cx0[r] = cy0[r] = cx1[r] = cy1[r] = 0.f;
+            if (i < p.nb && !nms_candidate(p, rows + (long long)i * p.D, cls, cx0[r], cy0[r], cx1[r], cy1[r], sc)) sc = 0.f;
+            cs[r] = sc;
+        }
+    } else {
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+        for (int i = tid; i < p.nb; i += 1024) {
+            float x0, y0, x1, y1, sc;
+            if (nms_candidate(p, rows + (long long)i * p.D, cls, x0, y0, x1, y1, sc)) {
+                const int slot = atomicAdd(&s_count, 1);
+                gx0[slot] = x0;
+                gy0[slot] = y0;
+                gx1[slot] = x1;
+                gy1[slot] = y1;
+                gs[slot] = sc;
+                grow[slot] = i;
+            }
+        }
+        __syncthreads();
+        count = s_count;
+    }
+
+    int* out_idx = p.keep_idx + (long long)blockIdx.x * p.max_keep;
+    float* out_sc = p.keep_score + (long long)blockIdx.x * p.max_keep;
+    float px0 = 0.f, py0 = 0.f, px1 = 0.f, py1 = 0.f, parea = 0.f;
+    int prow = -1, emitted = 0;
+    for (int e = 0;; ++e) {
+        unsigned long long best = 0ull;
+        float bx0 = 0.f, by0 = 0.f, bx1 = 0.f, by1 = 0.f;
+        if (R > 0) {
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const int row = tid + 1024 * r;
+                float sc = cs[r];
+                if (sc > 0.f) {
+                    if (row == prow)
+                        sc = 0.f;
+                    else if (prow >= 0)
+                        sc = soft_decay(sc, nms_iou(px0, py0, px1, py1, parea, cx0[r], cy0[r], cx1[r], cy1[r], (cx1[r] - cx0[r]) * (cy1[r] - cy0[r])), p);
+                    cs[r] = sc;
+                }
+                const unsigned long long key = soft_key(sc, row);
+                if (key > best) {
+                    best = key;
+                    bx0 = cx0[r];
+                    by0 = cy0[r];
+                    bx1 = cx1[r];
+                    by1 = cy1[r];
+                }
+            }
+        } else {
+            for (int j = tid; j < count; j += 1024) {
+                float sc = gs[j];
+                if (!(sc > 0.f)) continue;
+                const int row = grow[j];
+                const float x0 = gx0[j], y0 = gy0[j], x1 = gx1[j], y1 = gy1[j];
+                if (row == prow)
+                    sc = 0.f;
+                else if (prow >= 0)
+                    sc = soft_decay(sc, nms_iou(px0, py0, px1, py1, parea, x0, y0, x1, y1, (x1 - x0) * (y1 - y0)), p);
+                gs[j] = sc;
+                const unsigned long long key = soft_key(sc, row);
+                if (key > best) {
+                    best = key;
+                    bx0 = x0;
+                    by0 = y0;
+                    bx1 = x1;
+                    by1 = y1;
+                }
+            }
+        }
+        unsigned long long wmax = best;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long v = __shfl_xor(wmax, o);
+            wmax = v > wmax ? v : wmax;
+        }
+        const int par = e & 1;
+        if (wmax != 0ull ? best == wmax : lane == 0) {  // live keys are unique (they carry the row)
+            s_key[par][wave] = wmax;
+            s_box[par][wave][0] = bx0;
+            s_box[par][wave][1] = by0;
+            s_box[par][wave][2] = bx1;
+            s_box[par][wave][3] = by1;
+        }
+        __syncthreads();
+        unsigned long long k = s_key[par][0];
+        int w = 0;
+#pragma unroll
+        for (int q = 1; q < 16; ++q) {
+            const unsigned long long v = s_key[par][q];
+            if (v > k) {
+                k = v;
+                w = q;
+            }
+        }
+        if (k == 0ull) break;  // no live candidate left
+        px0 = s_box[par][w][0];
+        py0 = s_box[par][w][1];
+        px1 = s_box[par][w][2];
+        py1 = s_box[par][w][3];
+        parea = (px1 - px0) * (py1 - py0);
+        prow = (int)(unsigned)(k & 0xffffffffull);
+        if (tid == 0) {
+            out_idx[emitted] = prow;
+            out_sc[emitted] = __uint_as_float((unsigned)(k >> 32));
+        }
+        if (++emitted == p.max_keep) break;  // later emissions would be truncated anyway
+    }
+    if (tid == 0) p.keep_cnt[blockIdx.x] = emitted;
+}
+
 static int nms_cap(int nb) {
     int c = 64;
     while (c < nb) c <<= 1;
     return c;
 }
+static bool nms_soft(int method) { return method == Y3_NMS_SOFT_LINEAR || method == Y3_NMS_SOFT_GAUSSIAN; }
+static size_t nms_ws_per_block(int nb, int method) {
+    return nms_soft(method) ? (((size_t)nms_cap(nb) * 24 + 255) & ~(size_t)255) : (((size_t)nms_cap(nb) * 29 + 255) & ~(size_t)255);
+}
 extern "C" size_t y3_nms_workspace_bytes(int n, int nb, int num_classes) {
-    const size_t per = ((size_t)nms_cap(nb) * 29 + 255) & ~(size_t)255;
-    return per * (size_t)n * (size_t)num_classes;
+    return nms_ws_per_block(nb, Y3_NMS_HARD) * (size_t)n * (size_t)num_classes;
+}
+extern "C" size_t y3_nms_workspace_bytes_ex(int n, int nb, int num_classes, int method) {
+    if (nms_soft(method) && nb <= Y3_SOFT_REG_ROWS) return 0;  // candidate state in registers
+    return nms_ws_per_block(nb, method) * (size_t)n * (size_t)num_classes;
 }
 
-static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw, float min_box, float score_thr, float iou_thr,
-                      float clip_w, float clip_h, int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace,
+template <int CRIT>
+static void nms_greedy_launch(const NmsArgs& p, int blocks, hipStream_t st, bool* attr_failed) {
+    if (p.cap <= 16384) {
+        const size_t lds = (size_t)p.cap * 9;  // keys + dead flags, <= 144 KiB of the CU's 160 KiB
+        static bool attr_set = false;
+        if (!attr_set) {
+            if (hipFuncSetAttribute((const void*)nms_kernel<true, CRIT>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 9) != hipSuccess) {
+                *attr_failed = true;
+                return;
+            }
+            attr_set = true;
+        }
+        hipLaunchKernelGGL((nms_kernel<true, CRIT>), dim3(blocks), dim3(1024), lds, st, p);
+    } else {
+        hipLaunchKernelGGL((nms_kernel<false, CRIT>), dim3(blocks), dim3(1024), 0, st, p);
+    }
+}
+
+static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw, int method, float min_box, float score_thr, float iou_thr,
+                      float sigma, float clip_w, float clip_h, int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace,
                       size_t workspace_bytes, y3_stream_t stream) {
-    Y3_CHECK_ARG(rows && keep_idx && keep_cnt && keep_score && workspace, "nms: null pointer");
+    Y3_CHECK_ARG(method >= Y3_NMS_HARD && method <= Y3_NMS_SOFT_GAUSSIAN, "nms: unknown method %d", method);
+    Y3_CHECK_ARG(!nms_soft(method) || score_thr > 0.f, "nms: soft-NMS needs score_thr > 0 (got %g)", (double)score_thr);
+    Y3_CHECK_ARG(method != Y3_NMS_SOFT_GAUSSIAN || sigma > 0.f, "nms: Gaussian soft-NMS needs sigma > 0 (got %g)", (double)sigma);
+    const size_t need = y3_nms_workspace_bytes_ex(n, nb, num_classes, method);
+    Y3_CHECK_ARG(rows && keep_idx && keep_cnt && keep_score && (workspace || need == 0), "nms: null pointer");
     Y3_CHECK_ARG(n > 0 && nb > 0 && num_classes > 0 && max_keep > 0, "nms: bad sizes");
-    Y3_CHECK_ARG(workspace_bytes >= y3_nms_workspace_bytes(n, nb, num_classes), "nms: workspace too small");
+    Y3_CHECK_ARG(workspace_bytes >= need, "nms: workspace too small");
     NmsArgs p = {};
     p.rows = rows;
     p.nb = nb;
@@ -536,22 +769,23 @@ static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw
     p.max_keep = max_keep;
     p.cap = nms_cap(nb);
     p.ws = (unsigned char*)workspace;
-    p.ws_per_block = ((size_t)p.cap * 29 + 255) & ~(size_t)255;
+    p.ws_per_block = nms_ws_per_block(nb, method);
+    p.soft_gauss = method == Y3_NMS_SOFT_GAUSSIAN;
+    p.sigma = sigma;
     hipStream_t st = (hipStream_t)stream;
     const int blocks = n * num_classes;
-    if (p.cap <= 16384) {
-        const size_t lds = (size_t)p.cap * 9;  // keys + dead flags, <= 144 KiB of the CU's 160 KiB
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)nms_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 16384 * 9) != hipSuccess) {
-                y3_set_error("nms_per_class: cannot raise dynamic LDS limit");
-                return Y3_ELAUNCH;
-            }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((nms_kernel<true>), dim3(blocks), dim3(1024), lds, st, p);
-    } else {
-        hipLaunchKernelGGL((nms_kernel<false>), dim3(blocks), dim3(1024), 0, st, p);
+    bool attr_failed = false;
+    if (method == Y3_NMS_HARD)
+        nms_greedy_launch<Y3_NMS_HARD>(p, blocks, st, &attr_failed);
+    else if (method == Y3_NMS_DIOU)
+        nms_greedy_launch<Y3_NMS_DIOU>(p, blocks, st, &attr_failed);
+    else if (nb <= Y3_SOFT_REG_ROWS)
+        hipLaunchKernelGGL((soft_nms_kernel<Y3_SOFT_REG_ROWS / 1024>), dim3(blocks), dim3(1024), 0, st, p);
+    else
+        hipLaunchKernelGGL((soft_nms_kernel<0>), dim3(blocks), dim3(1024), 0, st, p);
+    if (attr_failed) {
+        y3_set_error("nms_per_class: cannot raise dynamic LDS limit");
+        return Y3_ELAUNCH;
     }
     Y3_CHECK_LAUNCH("nms");
     return Y3_OK;
@@ -560,12 +794,19 @@ static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw
 extern "C" int y3_nms_per_class(const float* rows, int n, int nb, int num_classes, float min_box, float score_thr, float iou_thr,
                                 float clip_w, float clip_h, int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace,
                                 size_t workspace_bytes, y3_stream_t stream) {
-    return nms_launch(rows, n, nb, num_classes, 0, min_box, score_thr, iou_thr, clip_w, clip_h, keep_idx, keep_cnt, keep_score, max_keep,
-                      workspace, workspace_bytes, stream);
+    return nms_launch(rows, n, nb, num_classes, 0, Y3_NMS_HARD, min_box, score_thr, iou_thr, 0.f, clip_w, clip_h, keep_idx, keep_cnt,
+                      keep_score, max_keep, workspace, workspace_bytes, stream);
+}
+
+extern "C" int y3_nms_per_class_ex(const float* rows, int n, int nb, int num_classes, int method, float min_box, float score_thr,
+                                   float iou_thr, float sigma, float clip_w, float clip_h, int* keep_idx, int* keep_cnt, float* keep_score,
+                                   int max_keep, void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    return nms_launch(rows, n, nb, num_classes, 0, method, min_box, score_thr, iou_thr, sigma, clip_w, clip_h, keep_idx, keep_cnt,
+                      keep_score, max_keep, workspace, workspace_bytes, stream);
 }
 
 extern "C" int y3_nms_single_class(const float* rows5, int m, float iou_thr, int* keep_idx, int* keep_cnt, float* keep_score, void* workspace,
                                    size_t workspace_bytes, y3_stream_t stream) {
-    return nms_launch(rows5, 1, m, 1, 1, -INFINITY, -INFINITY, iou_thr, -1.f, -1.f, keep_idx, keep_cnt, keep_score, m, workspace,
-                      workspace_bytes, stream);
+    return nms_launch(rows5, 1, m, 1, 1, Y3_NMS_HARD, -INFINITY, -INFINITY, iou_thr, 0.f, -1.f, -1.f, keep_idx, keep_cnt, keep_score, m,
+                      workspace, workspace_bytes, stream);
 }

@@ -43,15 +43,17 @@ def folder_examples(image_folder, csv_folder, image_format, num_shards=1, shard_
 
 
 def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
-             max_detections=None, distributed=False):
+             max_detections=None, distributed=False, nms='hard', nms_sigma=0.5):
     """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds).
     distributed: a collective over the default process group; every rank passes its keys[rank::world] share of the
-    examples and gets the result over all of them."""
+    examples and gets the result over all of them.  nms / nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its
+    Gaussian parameter."""
+    bbox_utils.check_nms_args(nms, nms_sigma)
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision
     ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
     t0 = time.perf_counter()
-    metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size)
+    metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size, nms=nms, nms_sigma=nms_sigma)
     if distributed:
         ev = metrics.all_gather_evaluator(ev)
     res = ev.result()
@@ -105,6 +107,9 @@ if __name__ == '__main__':
                         help='IoU thresholds (1..32 values in (0, 1]); default 0.50:0.05:0.95')
     parser.add_argument('--max-detections', type=int, default=None, help='detections kept per image and class (default: all NMS keeps)')
     parser.add_argument('--output-file', type=str, default=None, help='per-class csv')
+    parser.add_argument('--nms', choices=list(bbox_utils.NMS_METHODS), default='hard',
+                        help='NMS method (extension): hard (the reference\'s greedy NMS, default), diou, soft-linear or soft-gaussian')
+    parser.add_argument('--nms-sigma', dest='nms_sigma', type=float, default=0.5, help='sigma of --nms soft-gaussian (> 0)')
     parser.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend under torch.distributed.run: nccl (= RCCL, '
                         'one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
     a = parser.parse_args()
@@ -114,6 +119,8 @@ if __name__ == '__main__':
         parser.error('--image-folder and --csv-folder go together')
     if a.batch_size < 1:
         parser.error('--batch-size must be >= 1')
+    if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
+        parser.error('--nms-sigma must be > 0')
     if a.max_detections is not None and a.max_detections < 1:
         parser.error('--max-detections must be >= 1')
     thresholds = metrics.COCO_IOU_THRESHOLDS if a.iou_thresholds is None else a.iou_thresholds
@@ -137,9 +144,10 @@ if __name__ == '__main__':
     else:
         examples = folder_examples(a.image_folder, a.csv_folder, a.image_format, world, rank)
     res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
-                                distributed=world > 1)
+                                distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma)
     if rank == 0:
         print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
+        print('NMS: {}'.format(a.nms + (' (sigma {:g})'.format(a.nms_sigma) if a.nms == 'soft-gaussian' else '')))
         print_table(res)
         if a.output_file:
             write_csv(res, a.output_file)

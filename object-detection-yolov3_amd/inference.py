@@ -19,7 +19,9 @@ def load_model(path):
     return YoloV3.from_file(path)
 
 
-def inference(image_folder, image_format, saved_model_filepath, output_folder, min_box_size, precision='fp32', batch_size=8):
+def inference(image_folder, image_format, saved_model_filepath, output_folder, min_box_size, precision='fp32', batch_size=8, nms='hard',
+              nms_sigma=0.5):
+    bbox_utils.check_nms_args(nms, nms_sigma)
     os.makedirs(output_folder, exist_ok=True)
     if image_format.startswith('.'):
         image_format = image_format[1:]
@@ -49,7 +51,7 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
         x = imagereader.zscore_normalize_device(x)                       # per-image statistics (inference.py:49)
         rows = yolo_model(x, training=False)                              # [B, Nb, 5+K]
         # clip to the image (the intent of inference.py:62-65, Q11), small-box filter (:72), class-wise NMS (:79)
-        dets = bbox_utils.detect(rows, min_box_size, clip_wh=(width, height))
+        dets = bbox_utils.detect(rows, min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma)   # --nms: extension
         for img_filepath, (boxes, scores, class_label, _) in zip(group, dets):
             file_name = os.path.split(img_filepath)[1]
             if boxes is None:                                             # the reference would crash here (Q11); write an empty csv
@@ -71,8 +73,13 @@ if __name__ == '__main__':
     parser.add_argument('--min-box-size', type=int, default=32, help='Smallest detection to consider. Default (32, 32).')
     parser.add_argument('--precision', choices=['fp32', 'bf16'], default='fp32', help='conv arithmetic (extension; the reference is fp32)')
     parser.add_argument('--batch-size', type=int, default=8, help='images per model call (extension; the reference runs one)')
+    parser.add_argument('--nms', choices=list(bbox_utils.NMS_METHODS), default='hard',
+                        help='NMS method (extension): hard (the reference\'s greedy NMS, default), diou, soft-linear or soft-gaussian')
+    parser.add_argument('--nms-sigma', dest='nms_sigma', type=float, default=0.5, help='sigma of --nms soft-gaussian (> 0)')
     a = parser.parse_args()
+    if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
+        parser.error('--nms-sigma must be > 0')
     print('Arguments:')
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
-    inference(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, a.min_box_size, a.precision, a.batch_size)
+    inference(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, a.min_box_size, a.precision, a.batch_size, a.nms, a.nms_sigma)

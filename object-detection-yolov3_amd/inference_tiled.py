@@ -184,10 +184,12 @@ def upload_bands(table, sizes, height):
     return out
 
 
-def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=None):
+def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5):
     """inference_tiled.py:185-310.  ``yolo_model(batch, training=False)`` maps CUDA float32 [B,C,h,w] (z-scored) to
     rows [B, Nb, 5+K] (CUDA tensor or ndarray).  batch_size None: BATCH_SIZE tiles per launch on the fp32 path,
-    plan_tile_batches() on the bf16 path."""
+    plan_tile_batches() on the bf16 path.  nms / nms_sigma: the per-tile NMS method (bbox_utils.NMS_METHODS) and its
+    Gaussian parameter; the merge of the tiles' detections does not depend on it."""
+    bbox_utils.check_nms_args(nms, nms_sigma)
     img_size = img.shape
     # the image goes to the GPU once, in its own dtype; cropping, reflect padding, astype(float32) and HWC -> CHW of
     # convert_image_to_tiles (inference_tiled.py:29-100,199-203) happen there, one launch per batch of tiles
@@ -257,7 +259,7 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
                 x = imagereader.zscore_normalize_device(x)               # per TILE statistics (inference_tiled.py:205, Q12)
                 rows = yolo_model(x, training=False, slot=bi % slots) if slots > 1 else yolo_model(x, training=False)
             rows = torch.as_tensor(rows, dtype=torch.float32).cuda().clone()   # the slot's output buffer is reused two batches later
-            queued.append((bbox_utils.detect_async(rows, min_roi_size), b0))
+            queued.append((bbox_utils.detect_async(rows, min_roi_size, method=nms, sigma=nms_sigma), b0))
     for item in queued:
         merge(*item)
     for s in streams:
@@ -268,7 +270,8 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
 
 
 def inference_image_folder(image_folder, image_format, saved_model_filepath, output_folder, tile_size, min_roi_size, precision='fp32',
-                           batch_size=None):
+                           batch_size=None, nms='hard', nms_sigma=0.5):
+    bbox_utils.check_nms_args(nms, nms_sigma)
     if not os.path.exists(saved_model_filepath):
         raise RuntimeError('Missing saved_model_filepath File')
     if image_format.startswith('.'):
@@ -293,7 +296,7 @@ def inference_image_folder(image_folder, image_format, saved_model_filepath, out
         img = imagereader.imread(img_filepath)
         if len(img.shape) == 2:
             img = np.expand_dims(img, -1)
-        predictions = inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size)
+        predictions = inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma)
         bbox_utils.write_boxes_from_ltrbpc(predictions, os.path.join(output_folder, file_name.replace(image_format, 'csv')))
 
 
@@ -308,5 +311,11 @@ if __name__ == '__main__':
     parser.add_argument('--min-box-size', type=int, default=32)
     parser.add_argument('--precision', choices=['fp32', 'bf16'], default='fp32', help='conv arithmetic (extension; the reference is fp32)')
     parser.add_argument('--batch-size', type=int, default=None, help='tiles per network launch (extension; default: %d on the fp32 path, planned per image on the bf16 path)' % BATCH_SIZE)
+    parser.add_argument('--nms', choices=list(bbox_utils.NMS_METHODS), default='hard',
+                        help='NMS method (extension): hard (the reference\'s greedy NMS, default), diou, soft-linear or soft-gaussian')
+    parser.add_argument('--nms-sigma', dest='nms_sigma', type=float, default=0.5, help='sigma of --nms soft-gaussian (> 0)')
     a = parser.parse_args()
-    inference_image_folder(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, [a.tile_height, a.tile_width], a.min_box_size, a.precision, a.batch_size)
+    if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
+        parser.error('--nms-sigma must be > 0')
+    inference_image_folder(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, [a.tile_height, a.tile_width], a.min_box_size, a.precision, a.batch_size,
+                           a.nms, a.nms_sigma)

@@ -69,6 +69,8 @@ def is_new_maximum(scores):
 
 
 MODEL_SELECTIONS = ('loss', 'map50', 'map50_95')
+# = yolo3.bbox_utils.NMS_METHODS, spelled out so that building the parser does not load the HIP library
+TEST_MAP_NMS_METHODS = ('hard', 'diou', 'soft-linear', 'soft-gaussian')
 
 
 def effective_test_map(test_map, model_selection):
@@ -78,12 +80,13 @@ def effective_test_map(test_map, model_selection):
     return bool(test_map) or model_selection != 'loss'
 
 
-def evaluate_test_map(yolo, strategy, database, batch_size, min_box_size, world, rank):
+def evaluate_test_map(yolo, strategy, database, batch_size, min_box_size, world, rank, nms='hard', nms_sigma=0.5):
     """One mAP pass over the test lmdb (COCO thresholds): this rank reads its keys[rank::world] share in this process and runs
     it through the live model's fp32 predict plan (the plan test_step uses), then the ranks' evaluators are merged.  With
     world > 1 the model evaluated is the one a checkpoint would save: the MEAN of the replicas' BN moving statistics
     (App. C4) is swapped in for the pass and every replica's own values are put back after.  A collective: every rank
-    calls it.  Returns (DetectionEvaluator.result() over the whole test set, images, seconds)."""
+    calls it.  nms / nms_sigma: the NMS method of the pass (bbox_utils.NMS_METHODS) and its Gaussian parameter.  Returns
+    (DetectionEvaluator.result() over the whole test set, images, seconds)."""
     from yolo3 import metrics
     t0 = time.time()
     own = None
@@ -93,7 +96,8 @@ def evaluate_test_map(yolo, strategy, database, batch_size, min_box_size, world,
         yolo.moving.copy_(mean)
     try:
         ev = metrics.DetectionEvaluator(yolo.number_classes)
-        metrics.evaluate_examples(yolo, metrics.database_examples(database, world, rank), ev, min_box_size, batch_size, precision='fp32')
+        metrics.evaluate_examples(yolo, metrics.database_examples(database, world, rank), ev, min_box_size, batch_size, precision='fp32',
+                                  nms=nms, nms_sigma=nms_sigma)
     finally:
         if own is not None:
             yolo.moving.copy_(own)
@@ -122,8 +126,11 @@ def effective_reader_count(requested, cpus, local_world):
 
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
-                test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0):
+                test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5):
     test_map = effective_test_map(test_map, model_selection)
+    if test_map:
+        from yolo3 import bbox_utils
+        bbox_utils.check_nms_args(test_map_nms, test_map_nms_sigma)
     ema_decay = float(ema_decay) if ema_decay else None
     os.makedirs(output_folder, exist_ok=True)
     anchors = [(64, 384), (384, 64)]
@@ -262,7 +269,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
 
             if test_map:
                 with averaged():
-                    res, map_images, map_secs = evaluate_test_map(yolo, strategy, test_database_filepath, batch_size, test_map_min_box_size, world, rank)
+                    res, map_images, map_secs = evaluate_test_map(yolo, strategy, test_database_filepath, batch_size, test_map_min_box_size, world, rank,
+                                                                     test_map_nms, test_map_nms_sigma)
                 print('Test Epoch: {}: mAP50 = {}, mAP50:95 = {} ({} images, mAP pass took {:.3f} s)'.format(
                     epoch, res['map50'], res['map50_95'], map_images, map_secs))
                 if model_selection != 'loss':
@@ -356,6 +364,10 @@ def build_parser():
                         help='(addition) 1: after every test epoch, one mAP pass over the test lmdb (COCO thresholds), printed and written to <output_dir>/test_map.csv')
     parser.add_argument('--test_map_min_box_size', dest='test_map_min_box_size', type=int, default=32,
                         help='(addition) smallest detection the mAP pass considers (as evaluate.py --min-box-size)')
+    parser.add_argument('--test_map_nms', dest='test_map_nms', choices=TEST_MAP_NMS_METHODS, default='hard',
+                        help='(addition) NMS method of the mAP pass (as evaluate.py --nms): hard (default), diou, soft-linear or soft-gaussian')
+    parser.add_argument('--test_map_nms_sigma', dest='test_map_nms_sigma', type=float, default=0.5,
+                        help='(addition) sigma of --test_map_nms soft-gaussian (> 0)')
     parser.add_argument('--model_selection', dest='model_selection', choices=MODEL_SELECTIONS, default='loss',
                         help='(addition) what picks the checkpoint and drives early stopping: the test loss (first minimum, as the reference) '
                              'or the test-set mAP50 / mAP50:95 (first maximum; implies --test_map 1)')
@@ -372,4 +384,5 @@ if __name__ == "__main__":
         print('{} = {}'.format(k, v))
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
-                a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay)
+                a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
+                a.test_map_nms_sigma)

@@ -12,13 +12,29 @@ import torch
 from ._hip import lib, check
 
 
+# opt-in NMS variants (y3_nms_per_class_ex); 'hard' is the reference's greedy NMS and the default everywhere
+NMS_METHODS = ('hard', 'diou', 'soft-linear', 'soft-gaussian')
+_NMS_CODES = {'hard': 0, 'diou': 1, 'soft-linear': 2, 'soft-gaussian': 3}     # Y3_NMS_* (yolo3hip.h)
+
+
+def check_nms_args(method, sigma=0.5, score_threshold=0.1):
+    """Host-side validation of an NMS method and its parameters (the library checks them again): ValueError on an
+    unknown method, soft-NMS with score_threshold <= 0 (nothing would ever drop), Gaussian soft-NMS with sigma <= 0."""
+    if method not in _NMS_CODES:
+        raise ValueError('nms method must be one of {}, got {!r}'.format(', '.join(NMS_METHODS), method))
+    if method.startswith('soft') and not float(score_threshold) > 0:
+        raise ValueError('{} needs score_threshold > 0, got {}'.format(method, score_threshold))
+    if method == 'soft-gaussian' and not float(sigma) > 0:
+        raise ValueError('soft-gaussian needs sigma > 0, got {}'.format(sigma))
+
+
 class _NmsBuffers:
     def __init__(self, n, nb, k, device):
         self.key = (n, nb, k, str(device))
         self.keep_idx = torch.empty(n, k, nb, dtype=torch.int32, device=device)
         self.keep_cnt = torch.zeros(n, k, dtype=torch.int32, device=device)
         self.keep_score = torch.empty(n, k, nb, dtype=torch.float32, device=device)
-        self.ws_bytes = int(lib.y3_nms_workspace_bytes(n, nb, k))
+        self.ws_bytes = int(lib.y3_nms_workspace_bytes(n, nb, k))          # >= every method's y3_nms_workspace_bytes_ex
         self.ws = torch.empty(self.ws_bytes // 4 + 4, dtype=torch.float32, device=device)
 
 
@@ -26,11 +42,15 @@ _cache = {}
 _copy_streams = {}
 
 
-def nms_device(rows, min_box_size=0.0, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, private_outputs=False):
+def nms_device(rows, min_box_size=0.0, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, private_outputs=False, method='hard',
+               sigma=0.5):
     """rows: CUDA float32 [N, Nb, 5+K].  Returns (keep_idx[N,K,Nb] int32,
     keep_cnt[N,K] int32, keep_score[N,K,Nb]) device tensors; entries beyond
     keep_cnt are undefined.  The outputs are per-shape cached buffers that the next call overwrites unless
-    private_outputs is set (the workspace is always shared: launches on one stream run in order)."""
+    private_outputs is set (the workspace is always shared: launches on one stream run in order).
+    method: one of NMS_METHODS ('hard': y3_nms_per_class; the others: y3_nms_per_class_ex, whose keep_score holds the
+    decayed scores of the soft methods); sigma: the Gaussian soft-NMS parameter."""
+    check_nms_args(method, sigma, score_threshold)
     assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3
     rows = rows.contiguous()
     n, nb, d = rows.shape
@@ -45,17 +65,23 @@ def nms_device(rows, min_box_size=0.0, iou_threshold=0.3, score_threshold=0.1, c
     else:
         keep_idx, keep_cnt, keep_score = buf.keep_idx, buf.keep_cnt, buf.keep_score
     cw, chh = (float(clip_wh[0]), float(clip_wh[1])) if clip_wh is not None else (-1.0, -1.0)
-    check(lib.y3_nms_per_class(rows.data_ptr(), n, nb, k, float(min_box_size), float(score_threshold), float(iou_threshold), cw, chh,
-                               keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(), nb, buf.ws.data_ptr(),
-                               buf.ws_bytes, st_obj.cuda_stream), 'y3_nms_per_class')
+    if method == 'hard':
+        check(lib.y3_nms_per_class(rows.data_ptr(), n, nb, k, float(min_box_size), float(score_threshold), float(iou_threshold), cw, chh,
+                                   keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(), nb, buf.ws.data_ptr(),
+                                   buf.ws_bytes, st_obj.cuda_stream), 'y3_nms_per_class')
+    else:
+        check(lib.y3_nms_per_class_ex(rows.data_ptr(), n, nb, k, _NMS_CODES[method], float(min_box_size), float(score_threshold),
+                                      float(iou_threshold), float(sigma), cw, chh, keep_idx.data_ptr(), keep_cnt.data_ptr(),
+                                      keep_score.data_ptr(), nb, buf.ws.data_ptr(), buf.ws_bytes, st_obj.cuda_stream), 'y3_nms_per_class_ex')
     return keep_idx, keep_cnt, keep_score
 
 
-def detect_async(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None):
+def detect_async(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5):
     """Enqueue clip -> small-box filter -> class-wise NMS for a batch and return a ``collect()`` callable; nothing
     synchronises until it is called, so the caller can queue the next batch's network first.  ``rows`` must stay
-    untouched until then (pass a clone of a buffer that the next forward overwrites)."""
-    keep_idx, keep_cnt, keep_score = nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh, private_outputs=True)
+    untouched until then (pass a clone of a buffer that the next forward overwrites).  method / sigma: see nms_device."""
+    keep_idx, keep_cnt, keep_score = nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh, private_outputs=True,
+                                                method=method, sigma=sigma)
     n, nb, d = rows.shape
     k = d - 5
     done = torch.cuda.Event()
@@ -98,10 +124,10 @@ def detect_async(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, cli
     return collect
 
 
-def detect(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None):
+def detect(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5):
     """inference.py:62-79 for a batch: returns, per image, (boxes[M,4], score[M],
-    label[M] int32, keep[M] row indices) as NumPy arrays, or (None,)*4."""
-    return detect_async(rows, min_box_size, iou_threshold, score_threshold, clip_wh)()
+    label[M] int32, keep[M] row indices) as NumPy arrays, or (None,)*4.  method / sigma: see nms_device."""
+    return detect_async(rows, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma)()
 
 
 def per_class_nms(boxes, objectness, class_probs, iou_threshold=0.3, score_threshold=0.1):

@@ -82,17 +82,21 @@ class DetectionEvaluator:
         self.num_images = 0
 
     # ---- input paths ----------------------------------------------------------------------------------------------
-    def add_batch(self, rows, gt_boxes_per_image, min_box_size, clip_wh=None, iou_threshold=0.3, score_threshold=0.1):
+    def add_batch(self, rows, gt_boxes_per_image, min_box_size, clip_wh=None, iou_threshold=0.3, score_threshold=0.1, nms='hard',
+                  nms_sigma=0.5):
         """rows: CUDA float32 [N, Nb, 5+K] (the network's decode rows); gt_boxes_per_image: N arrays [G,5] X,Y,W,H,C.
-        Runs the ``detect`` path's NMS (``bbox_utils.nms_device``, same clip / small-box filter / thresholds) and matches
-        its keep lists on the device; no detection leaves the GPU."""
+        Runs the ``detect`` path's NMS (``bbox_utils.nms_device``, same clip / small-box filter / thresholds; method
+        ``nms`` of bbox_utils.NMS_METHODS, Gaussian parameter ``nms_sigma``) and matches its keep lists on the device;
+        no detection leaves the GPU."""
+        bbox_utils.check_nms_args(nms, nms_sigma, score_threshold)
         assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3
         n, nb, d = rows.shape
         if d - 5 != self.num_classes:
             raise ValueError('rows carry {} classes, the evaluator {}'.format(d - 5, self.num_classes))
         gt = self._gt_batch(gt_boxes_per_image, n)
         rows = rows.contiguous()
-        keep_idx, keep_cnt, keep_score = bbox_utils.nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh)
+        keep_idx, keep_cnt, keep_score = bbox_utils.nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh, method=nms,
+                                                                sigma=nms_sigma)
         cw, chh = (float(clip_wh[0]), float(clip_wh[1])) if clip_wh is not None else (-1.0, -1.0)
         self._match(rows, n, nb, d, cw, chh, keep_idx, keep_cnt, keep_score, nb, gt)
 
@@ -413,13 +417,14 @@ def database_examples(path, num_shards=1, shard_index=0):
         env.close()
 
 
-def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, precision=None):
+def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, precision=None, nms='hard', nms_sigma=0.5):
     """Feeds (name, HWC image, [G,5] X,Y,W,H,C) examples through ``yolo`` (a YoloV3: per-image z-score -> predict ->
     clip -> small-box filter -> NMS, inference.py's path) into ``evaluator``, ``batch_size`` images per call, the short
-    tail as one smaller call.  precision: predict()'s ('fp32' / 'bf16'; default yolo.inference_precision).  Returns the
-    number of images added."""
+    tail as one smaller call.  precision: predict()'s ('fp32' / 'bf16'; default yolo.inference_precision).  nms /
+    nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its Gaussian parameter.  Returns the number of images added."""
     if batch_size < 1:
         raise ValueError('batch_size must be >= 1')
+    bbox_utils.check_nms_args(nms, nms_sigma)
     batch, count = [], 0
 
     def flush():
@@ -429,7 +434,7 @@ def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, preci
         height, width = imgs[0].shape[:2]
         x = torch.from_numpy(np.stack([np.ascontiguousarray(im.astype(np.float32).transpose((2, 0, 1))) for im in imgs])).to(yolo.device)
         rows = yolo.predict(imagereader.zscore_normalize_device(x), precision=precision)
-        evaluator.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height))
+        evaluator.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height), nms=nms, nms_sigma=nms_sigma)
         batch.clear()
 
     for ex in examples:
