@@ -316,6 +316,32 @@ int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float* anchors_h
                     float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream);
 size_t y3_loss_workspace_bytes(void);
 
+/* ---- opt-in IoU box-regression losses (not in the reference) -----------------------------------------
+ * y3_loss_fwd_bwd_ex: y3_loss_fwd_bwd with a choice of box term.  Y3_BOX_LOSS_MSE (box_weight must be 1) is exactly the
+ * launch of y3_loss_fwd_bwd: the reference's xy term (model.py:313-333, :351) and wh term (model.py:337-345, :352).  The
+ * other kinds depart from those lines only: objectness, class, ignore mask (Q7), the anchor-present flags, the 64-block partial
+ * reduction and the finalize step are the same code, so dfm[..., 4:] and loss4[2], loss4[3] keep their bits.  Per (cell,
+ * anchor) with label row g and gm = g[4], the predicted box as reorg_layer decodes it (Q6 included):
+ *   bx = (sigmoid(t0) + gx) sx, by = (sigmoid(t1) + gy) sy, bw = exp(t2) aw, bh = exp(t3) ah; target centre (g0, g1), size
+ *   (g2, g3); corners c -+ s/2.  inter = max(min(x1) - max(x0), 0) max(min(y1) - max(y0), 0), U = bw bh + g2 g3 - inter,
+ *   IoU = inter / U; enclosing box cw x ch, C = cw ch, c2 = cw^2 + ch^2, rho2 = (bx - g0)^2 + (by - g1)^2.
+ *   Y3_BOX_LOSS_GIOU (Rezatofighi et al. 2019): X = IoU - (C - U) / C.
+ *   Y3_BOX_LOSS_DIOU (Zheng et al. 2020):       X = IoU - rho2 / c2.
+ *   Y3_BOX_LOSS_CIOU (Zheng et al. 2020):       X = IoU - rho2 / c2 - alpha v, v = (4 / pi^2)(atan(g2 / g3) - atan(bw / bh))^2,
+ *                                               alpha = v / ((1 - IoU) + v + 1e-7), a constant of the backward pass.
+ * loss4[0] += sum(gm box_weight (1 - X)) / local batch, loss4[1] += 0, and dfm[..., 0:4] = gm box_weight d(1 - X)/dt /
+ * (local batch * global_batch); min, max and the clamp at 0 pass the gradient to the selected operand.  Where gm == 0 the
+ * term is skipped by a branch: dfm[..., 0:4] = +0 there whatever the logits are.  Finite for every logit in [-30, 30].
+ * box_loss outside 0..3, box_weight not finite or <= 0, or box_weight != 1 with Y3_BOX_LOSS_MSE: Y3_EINVAL + message,
+ * nothing launched.  workspace: y3_loss_workspace_bytes(), as for y3_loss_fwd_bwd. */
+#define Y3_BOX_LOSS_MSE  0   /* the reference's xy + wh terms: what y3_loss_fwd_bwd computes */
+#define Y3_BOX_LOSS_GIOU 1
+#define Y3_BOX_LOSS_DIOU 2
+#define Y3_BOX_LOSS_CIOU 3
+int y3_loss_fwd_bwd_ex(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors,
+                       int num_classes, int img_h, int img_w, float global_batch, int box_loss, float box_weight,
+                       float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream);
+
 /* ---- tf.keras.optimizers.Adam.apply_gradients (model.py:451,500) ----------
  * m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= lr_t*m/(sqrt(v)+eps), with
  * lr_t read from DEVICE memory (*lr_t_dev) so the launch is graph-replayable. */

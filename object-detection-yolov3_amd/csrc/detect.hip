@@ -2,6 +2,7 @@
 // analytic backward (model.py:230-354) and class-wise NMS (bbox_utils.py:200-281).
 // Compiled with -ffp-contract=off: the NMS arithmetic must round exactly like the
 // reference's NumPy float32 elementwise ops so the integer keep indices match.
+#include <float.h>
 #include <stdlib.h>
 
 #include "common.h"
@@ -102,6 +103,7 @@ struct LossArgs {
     float sx, sy;
     float aw[Y3_MAX_ANCHORS], ah[Y3_MAX_ANCHORS];
     float inv_b, gscale;  // 1/local batch, 1/(local batch * global batch)
+    float box_weight;     // factor of the box term of the IoU kinds (y3_loss_fwd_bwd_ex); the mse kernel does not read it
     int* present;         // [A] flags: anchor a has at least one GT cell in this batch
     float* partials;      // [blocks][4]
 };
@@ -116,6 +118,72 @@ __device__ __forceinline__ float sig_ce(float z, float x) {  // labels z, logits
     return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x)));
 }
 
+// The box term of the opt-in IoU losses (Y3_BOX_LOSS_GIOU / DIOU / CIOU) for one positive (cell, anchor): returns 1 - X and
+// writes d(1 - X)/d(bx, by, bw, bh) to gb[0..3].  Reverse mode by hand: every `a_q` is dX/dq.  min / max / the clamp at 0 hand the
+// gradient to the selected operand.  U, C, c2 reach 1e32 at a logit of 30, so none of them is squared: q / U^2 is (q / U) / U.
+template <int BOX>
+__device__ __forceinline__ float iou_box_loss(float bx, float by, float bw, float bh, const float* __restrict__ g, float* gb) {
+    const float g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
+    const float px0 = bx - bw / 2.0f, px1 = bx + bw / 2.0f, py0 = by - bh / 2.0f, py1 = by + bh / 2.0f;
+    const float gx0 = g0 - g2 / 2.0f, gx1 = g0 + g2 / 2.0f, gy0 = g1 - g3 / 2.0f, gy1 = g1 + g3 / 2.0f;
+    const float ixr = fminf(px1, gx1) - fmaxf(px0, gx0), iyr = fminf(py1, gy1) - fmaxf(py0, gy0);
+    const float ix = fmaxf(ixr, 0.f), iy = fmaxf(iyr, 0.f);
+    const float inter = ix * iy;
+    const float U = bw * bh + g2 * g3 - inter;
+    const float iou = inter / U;
+    const float cw = fmaxf(px1, gx1) - fminf(px0, gx0), ch = fmaxf(py1, gy1) - fminf(py0, gy0);
+    float X = iou;
+    float a_U = -(iou / U);             // through IoU = inter / U
+    float a_cw, a_ch;
+    float a_bx = 0.f, a_by = 0.f, a_bw = 0.f, a_bh = 0.f;
+    if (BOX == Y3_BOX_LOSS_GIOU) {
+        const float C = cw * ch;
+        X = iou - (C - U) / C;
+        a_U += 1.0f / C;
+        const float a_C = -((U / C) / C);
+        a_cw = a_C * ch;
+        a_ch = a_C * cw;
+    } else {
+        const float c2 = cw * cw + ch * ch;
+        const float dx = bx - g0, dy = by - g1;
+        const float rho2 = dx * dx + dy * dy;
+        X = iou - rho2 / c2;
+        const float a_c2 = (rho2 / c2) / c2;
+        a_cw = a_c2 * (2.0f * cw);
+        a_ch = a_c2 * (2.0f * ch);
+        a_bx = -(2.0f * dx) / c2;
+        a_by = -(2.0f * dy) / c2;
+        if (BOX == Y3_BOX_LOSS_CIOU) {
+            const float k = 0.40528473456935109f;  // 4 / pi^2
+            const float da = atanf(g2 / g3) - atanf(bw / bh);
+            const float v = k * (da * da);
+            const float alpha = v / ((1.0f - iou) + v + 1e-7f);  // a constant of the backward pass
+            X = X - alpha * v;
+            // dv/d atan(bw/bh) = -2 k da ;  d atan(bw/bh) / d(bw, bh) = (bh, -bw) / (bw^2 + bh^2)
+            const float a_at = alpha * (2.0f * k * da);
+            const float q = bw * bw + bh * bh;
+            a_bw = a_at * (bh / q);
+            a_bh = -(a_at * (bw / q));
+        }
+    }
+    const float a_inter = 1.0f / U - a_U;  // U = bw bh + g2 g3 - inter
+    a_bw += a_U * bh;
+    a_bh += a_U * bw;
+    const float a_ixr = ixr >= 0.f ? a_inter * iy : 0.f, a_iyr = iyr >= 0.f ? a_inter * ix : 0.f;
+    // corners: the intersection takes the inner edge of each pair, the enclosing box the outer one
+    const float a_px1 = px1 < gx1 ? a_ixr : (px1 > gx1 ? a_cw : 0.5f * (a_ixr + a_cw));
+    const float a_px0 = px0 > gx0 ? -a_ixr : (px0 < gx0 ? -a_cw : -0.5f * (a_ixr + a_cw));
+    const float a_py1 = py1 < gy1 ? a_iyr : (py1 > gy1 ? a_ch : 0.5f * (a_iyr + a_ch));
+    const float a_py0 = py0 > gy0 ? -a_iyr : (py0 < gy0 ? -a_ch : -0.5f * (a_iyr + a_ch));
+    gb[0] = -(a_bx + (a_px0 + a_px1));
+    gb[1] = -(a_by + (a_py0 + a_py1));
+    gb[2] = -(a_bw + (a_px1 - a_px0) / 2.0f);
+    gb[3] = -(a_bh + (a_py1 - a_py0) / 2.0f);
+    return 1.0f - X;
+}
+
+// BOX == Y3_BOX_LOSS_MSE is the reference's loss; the other kinds replace its xy and wh terms by iou_box_loss and leave the rest alone
+template <int BOX>
 __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
     __shared__ float sm[4][256];
     const int D = 5 + p.K;
@@ -161,7 +229,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
             d[5 + k] = gm * (sigmoidf_(t[5 + k]) - g[5 + k]) * p.gscale;
         }
         // xy: squared error in logit space of the clipped in-cell position
-        {
+        if (BOX == Y3_BOX_LOSS_MSE) {
             const float txr = g[0] / p.sx - offx, tyr = g[1] / p.sy - offy;
             const float pxr = bx / p.sx - offx, pyr = by / p.sy - offy;
             const float tx = fminf(fmaxf(txr, 0.01f), 0.99f), ty = fminf(fmaxf(tyr, 0.01f), 0.99f);
@@ -177,7 +245,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
             d[1] = gm * (-2.f * ey) * gy_ * p.gscale;
         }
         // wh: squared error of log(size / anchor)
-        {
+        if (BOX == Y3_BOX_LOSS_MSE) {
             float tw = g[2] / aw, th = g[3] / ah;
             float pw = bw / aw, ph = bh / ah;
             const bool pw_nz = pw != 0.f, ph_nz = ph != 0.f;
@@ -194,6 +262,25 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
             const float gh_ = (ph_nz && ph >= 1e-9f && ph <= 1e9f) ? 1.f : 0.f;
             d[2] = gm * (-2.f * ew_) * gw_ * p.gscale;
             d[3] = gm * (-2.f * eh_) * gh_ * p.gscale;
+        }
+        // IoU-family box term in place of xy + wh, accumulated in the xy slot.  A branch, not a product with gm: a cell without an
+        // object writes +0 whatever its logits are (expf may have overflowed there).  Positives are tens per batch, so the few lanes
+        // that take the branch cost one divergent pass per wave that holds one.
+        if (BOX != Y3_BOX_LOSS_MSE) {
+            float gb[4] = {0.f, 0.f, 0.f, 0.f};
+            if (gm != 0.f) {
+                const float w = gm * p.box_weight;
+                l_xy += w * iou_box_loss<BOX>(bx, by, bw, bh, g, gb);
+                // d(bx)/dt0 = sx * sigmoid'(t0) ;  d(bw)/dt2 = bw
+                gb[0] = w * (gb[0] * (p.sx * (sgx * (1.f - sgx)))) * p.gscale;
+                gb[1] = w * (gb[1] * (p.sy * (sgy * (1.f - sgy)))) * p.gscale;
+                gb[2] = w * (gb[2] * bw) * p.gscale;
+                gb[3] = w * (gb[3] * bh) * p.gscale;
+            }
+            d[0] = gb[0];
+            d[1] = gb[1];
+            d[2] = gb[2];
+            d[3] = gb[3];
         }
     }
     sm[0][threadIdx.x] = l_xy;
@@ -224,8 +311,13 @@ __global__ void loss_finalize_kernel(const float* partials, int nblocks, float* 
 #define Y3_LOSS_BLOCKS 64
 extern "C" size_t y3_loss_workspace_bytes(void) { return (Y3_MAX_ANCHORS + Y3_LOSS_BLOCKS * 4) * sizeof(float); }
 
-extern "C" int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
-                               int img_w, float global_batch, float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
+static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h, int img_w,
+                       float global_batch, int box_loss, float box_weight, float* loss4, const y3_tensor* dfm, void* workspace,
+                       y3_stream_t stream) {
+    Y3_CHECK_ARG(box_loss >= Y3_BOX_LOSS_MSE && box_loss <= Y3_BOX_LOSS_CIOU, "loss_fwd_bwd: unknown box_loss %d", box_loss);
+    Y3_CHECK_ARG(box_weight > 0.f && box_weight <= FLT_MAX, "loss_fwd_bwd: box_weight must be finite and > 0 (got %g)", (double)box_weight);
+    Y3_CHECK_ARG(box_loss != Y3_BOX_LOSS_MSE || box_weight == 1.f, "loss_fwd_bwd: box_weight %g needs an IoU box_loss (mse takes 1)",
+                 (double)box_weight);
     Y3_CHECK_ARG(fm && fm->ptr && dfm && dfm->ptr && gt && anchors_host && loss4 && workspace, "loss_fwd_bwd: null pointer");
     Y3_CHECK_ARG(num_anchors >= 1 && num_anchors <= Y3_MAX_ANCHORS && num_classes >= 1, "loss_fwd_bwd: anchors/classes");
     const int D = num_anchors * (5 + num_classes);
@@ -250,6 +342,7 @@ extern "C" int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float
     }
     p.inv_b = 1.f / (float)fm->n;
     p.gscale = 1.f / ((float)fm->n * global_batch);
+    p.box_weight = box_weight;
     p.present = (int*)workspace;
     p.partials = (float*)workspace + Y3_MAX_ANCHORS;
     // (a kernel, not hipMemsetAsync: as a memset NODE of a captured graph the clear was not reliably ordered against the loss kernels of
@@ -263,11 +356,31 @@ extern "C" int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float
     Y3_CHECK_LAUNCH("loss_present");
     int blocks = (int)((total + 255) / 256);
     if (blocks > Y3_LOSS_BLOCKS) blocks = Y3_LOSS_BLOCKS;
-    hipLaunchKernelGGL(loss_kernel, dim3(blocks), dim3(256), 0, st, p);
+    if (box_loss == Y3_BOX_LOSS_MSE)
+        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_MSE>, dim3(blocks), dim3(256), 0, st, p);
+    else if (box_loss == Y3_BOX_LOSS_GIOU)
+        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_GIOU>, dim3(blocks), dim3(256), 0, st, p);
+    else if (box_loss == Y3_BOX_LOSS_DIOU)
+        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_DIOU>, dim3(blocks), dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_CIOU>, dim3(blocks), dim3(256), 0, st, p);
     Y3_CHECK_LAUNCH("loss");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)p.partials, blocks, loss4);
     Y3_CHECK_LAUNCH("loss_finalize");
     return Y3_OK;
+}
+
+extern "C" int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
+                               int img_w, float global_batch, float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, Y3_BOX_LOSS_MSE, 1.f, loss4, dfm, workspace,
+                       stream);
+}
+
+extern "C" int y3_loss_fwd_bwd_ex(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
+                                  int img_w, float global_batch, int box_loss, float box_weight, float* loss4, const y3_tensor* dfm,
+                                  void* workspace, y3_stream_t stream) {
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, loss4, dfm, workspace,
+                       stream);
 }
 
 // ---------------------------------------------------------------------------

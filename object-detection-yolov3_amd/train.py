@@ -12,7 +12,9 @@ early stopping with CONVERGENCE_TOLERANCE 1e-4 (:185-197), final export of the b
 Added (opt-in, off by default): --test_map 1 runs a test-set mAP pass after every test epoch (<out>/test_map.csv), and
 --model_selection map50 / map50_95 checkpoints and stops early on that mAP instead of the test loss, and
 --ema_decay D keeps an exponential moving average of the weights whose copy the test loss, the mAP pass and the checkpoint
-(hence the export) use.
+(hence the export) use, and --box_loss giou / diou / ciou (with --box_loss_weight W) trains and tests with an
+IoU-family box-regression loss in place of the reference's xy + wh terms.  The scalar CSVs keep their columns:
+with an IoU loss `loss_xy` carries the box term and `loss_wh` is 0.  The weight files do not record the choice.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -71,6 +73,8 @@ def is_new_maximum(scores):
 MODEL_SELECTIONS = ('loss', 'map50', 'map50_95')
 # = yolo3.bbox_utils.NMS_METHODS, spelled out so that building the parser does not load the HIP library
 TEST_MAP_NMS_METHODS = ('hard', 'diou', 'soft-linear', 'soft-gaussian')
+# yolo3.model.BOX_LOSSES, restated so that --help needs no device library
+BOX_LOSSES = ('mse', 'giou', 'diou', 'ciou')
 
 
 def effective_test_map(test_map, model_selection):
@@ -126,8 +130,11 @@ def effective_reader_count(requested, cpus, local_world):
 
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
-                test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5):
+                test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
+                box_loss='mse', box_loss_weight=1.0):
     test_map = effective_test_map(test_map, model_selection)
+    from yolo3.model import check_box_loss_args
+    check_box_loss_args(box_loss, box_loss_weight)
     if test_map:
         from yolo3 import bbox_utils
         bbox_utils.check_nms_args(test_map_nms, test_map_nms_sigma)
@@ -191,7 +198,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
 
         print('Creating model')
         number_classes = train_reader.get_number_classes()
-        yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay)
+        yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
+                            box_loss=box_loss, box_loss_weight=box_loss_weight)
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
@@ -334,7 +342,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     if training_checkpoint_filepath is not None and rank == 0:
         print('Converting checkpoint into Saved_Model')
         from yolo3 import model
-        best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate)
+        best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate,
+                            box_loss=box_loss, box_loss_weight=box_loss_weight)
         best.load_weights(training_checkpoint_filepath)
         os.makedirs(os.path.join(output_folder, 'saved_model'), exist_ok=True)
         best.save_weights(os.path.join(output_folder, 'saved_model', 'yolov3.npz'))
@@ -374,6 +383,12 @@ def build_parser():
     parser.add_argument('--ema_decay', dest='ema_decay', type=float, default=0.0,
                         help='(addition) 0 (default): off; in (0, 1): keep an exponential moving average of the weights (decay ramped up '
                              'over the first few thousand steps) and use it for the test loss, the mAP pass, the checkpoint and the export')
+    parser.add_argument('--box_loss', dest='box_loss', choices=BOX_LOSSES, default='mse',
+                        help='(addition) box-regression term of the training and test loss: mse (default) = the reference\'s xy + wh terms; '
+                             'giou, diou or ciou = 1 - that IoU measure per labelled cell.  With an IoU loss the loss_xy column of the scalar '
+                             'CSVs carries the box term and loss_wh is 0')
+    parser.add_argument('--box_loss_weight', dest='box_loss_weight', type=float, default=1.0,
+                        help='(addition) factor of the box term of --box_loss giou / diou / ciou (finite, > 0; mse takes 1)')
     return parser
 
 
@@ -385,4 +400,4 @@ if __name__ == "__main__":
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
-                a.test_map_nms_sigma)
+                a.test_map_nms_sigma, a.box_loss, a.box_loss_weight)

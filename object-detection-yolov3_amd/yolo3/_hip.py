@@ -96,6 +96,7 @@ SIGNATURES = {
     'y3_colsum': (i32, [TP, fp, vp]),
     'y3_decode_fwd': (i32, [TP, i32, C.POINTER(C.c_float), i32, i32, i32, i32, fp, vp]),
     'y3_loss_fwd_bwd': (i32, [TP, fp, C.POINTER(C.c_float), i32, i32, i32, i32, f32, fp, TP, vp, vp]),
+    'y3_loss_fwd_bwd_ex': (i32, [TP, fp, C.POINTER(C.c_float), i32, i32, i32, i32, f32, i32, f32, fp, TP, vp, vp]),
     'y3_loss_workspace_bytes': (sz, []),
     'y3_adam_step': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, vp]),
     'y3_adam_step_ema': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, fp, fp, sz, fp, vp]),

@@ -37,6 +37,25 @@ def ema_one_minus_decay(ema_decay, ema_warmup, t):
     return np.float32(1.0 - d)
 
 
+BOX_LOSSES = ('mse', 'giou', 'diou', 'ciou')     # index = Y3_BOX_LOSS_* of y3_loss_fwd_bwd_ex
+
+
+def check_box_loss_args(box_loss, box_loss_weight=1.0):
+    """Host-side validation of a box-regression loss and its weight (the library checks them again): ValueError on an unknown
+    kind, a weight that is not a finite number > 0, or a weight other than 1 with 'mse' (the reference's loss has no such factor)."""
+    if box_loss not in BOX_LOSSES:
+        raise ValueError('box_loss must be one of {}, got {!r}'.format(', '.join(BOX_LOSSES), box_loss))
+    try:
+        w = float(box_loss_weight)
+    except (TypeError, ValueError):
+        raise ValueError('box_loss_weight must be a number, got {!r}'.format(box_loss_weight))
+    if not (w > 0.0 and math.isfinite(w)):
+        raise ValueError('box_loss_weight must be finite and > 0, got {!r}'.format(box_loss_weight))
+    if box_loss == 'mse' and w != 1.0:
+        raise ValueError("box_loss_weight {!r} needs an IoU box_loss (giou, diou, ciou): 'mse' is the reference's loss, unweighted"
+                         .format(box_loss_weight))
+
+
 def _round_up(v, a):
     return (v + a - 1) // a * a
 
@@ -406,8 +425,14 @@ class _Plan:
         self.loss_calls = []
         for si, (f, g) in enumerate(zip(self.fms, self.gt)):
             f.grad = self._new(N, f.h, f.w, D, Dld, zero=True)
-            self.loss_calls.append((lib.y3_loss_fwd_bwd, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
-                                                          self.loss4.data_ptr(), f.grad.v, self.loss_ws.data_ptr() + 4 * si * ws_floats)))
+            ws = self.loss_ws.data_ptr() + 4 * si * ws_floats
+            if mdl.box_loss == 'mse':    # the reference's loss: the call list of a model built without box-loss arguments
+                self.loss_calls.append((lib.y3_loss_fwd_bwd, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                                                              self.loss4.data_ptr(), f.grad.v, ws)))
+            else:                        # IoU box term in loss4[0], loss4[1] stays 0
+                self.loss_calls.append((lib.y3_loss_fwd_bwd_ex, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                                                                 BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
+                                                                 self.loss4.data_ptr(), f.grad.v, ws)))
             f.gw = True
         if tr:
             self._build_backward()
@@ -680,7 +705,12 @@ class YoloV3:
     WEIGHT_DECAY = 5e-4      # declared by the reference but never applied (Q9)
 
     def __init__(self, global_batch_size, img_size, number_classes, anchors=None, learning_rate=1e-4, device=None, seed=None,
-                 use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000):
+                 use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
+                 box_loss='mse', box_loss_weight=1.0):
+        # box-regression term of the loss: 'mse' = the reference's xy + wh terms; checked before the device is needed
+        check_box_loss_args(box_loss, box_loss_weight)
+        self.box_loss = box_loss
+        self.box_loss_weight = float(box_loss_weight)
         # exponential moving average of the weights: None / 0 = off; checked before the device is needed
         if ema_decay is not None and ema_decay != 0 and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError('ema_decay must be None (off) or in (0, 1), got %r' % (ema_decay,))
