@@ -27,7 +27,12 @@ def _two_steps(yolo, images, gts, tag):
     _check(tf.check_step(cap, forward_only=True, tag=tag + ' step 2'))
 
 
-@pytest.mark.parametrize('img,n,arith', [(96, 4, 'f32'), (96, 4, 'x3'), (96, 4, 'x3-all'), (416, 8, 'f32'), (416, 8, 'x3')])
+# (320, 8): of the (image side, batch) pairs of the plan-form envelope (tests/plan_forms.py) whose oracle costs no more than (416, 8)'s,
+# the one whose step runs the most forward / data-gradient plan forms that no other shape list of the suite reaches but
+# test_gpu_plan_forms.py (plan_forms.step_classes; test_cpu_plan_forms.py prints the table: 9 at (320, 8), 6 at (320, 4) and (512, 4),
+# 3 at (416, 2) / (416, 4)).  It is also the second training geometry of the stride-2 merged data gradient, the BatchNorm-backward
+# plan and the kernel gradient, which have no plan query to enumerate their forms with.
+@pytest.mark.parametrize('img,n,arith', [(96, 4, 'f32'), (96, 4, 'x3'), (96, 4, 'x3-all'), (416, 8, 'f32'), (416, 8, 'x3'), (320, 8, 'f32'), (320, 8, 'x3')])
 def test_train_step_layers_teacher_forced(img, n, arith):
     """(416, 8) is the benchmarked step; 'x3-all' also puts the x3 kernels on the 1x1 layers and the 64-channel stride-2 data gradient."""
     from test_gpu_model import _setup
@@ -63,7 +68,7 @@ def test_train_step_layers_teacher_forced_nonsquare_grayscale_three_anchors():
 
 
 @pytest.mark.parametrize('arith', ['f32', 'x3'])
-@pytest.mark.parametrize('img,n', [(416, 8), (608, 2)])
+@pytest.mark.parametrize('img,n', [(416, 8), (608, 2), (512, 4)])      # (512, 4): more otherwise-unreached forward plan forms than (608, 4) (2 against 1)
 def test_inference_layers_teacher_forced(img, n, arith):
     """predict() on the fp32 plan: folded BatchNorm, the fused epilogue with the residual, the x3 forward; randomised BatchNorm."""
     from test_gpu_model import _setup
