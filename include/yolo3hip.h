@@ -20,6 +20,7 @@
 #ifndef YOLO3HIP_H
 #define YOLO3HIP_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -361,6 +362,40 @@ int y3_adam_step_ema(float* param, const float* grad, float* m, float* v, size_t
                      const float* lr_t_dev, float beta1, float beta2, float eps,
                      float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
                      const float* omd_dev, y3_stream_t stream);
+
+/* ---- gradient accumulation and global-norm gradient clipping (DESIGN 3.10;
+ * Keras Adam(global_clipnorm=...) and the accumulation every YOLO trainer has;
+ * no counterpart in the reference).  One optimiser step = k micro-steps:
+ *   y3_grad_accumulate   acc = *first_dev ? grad : acc + grad  (plain fp32), and
+ *                        the per-block fp64 sums of squares of the result
+ *   y3_grad_sumsq        the same partial sums of grad alone (k = 1)
+ *   y3_grad_clip_scale   S = the partials added in index order by one workgroup
+ *                        (no atomics: the same bits on every run);
+ *                        *norm_dev  = (float)(norm = sqrt(S) / k)
+ *                        *scale_dev = (float)((1/k) * (clip / max(norm, clip))),
+ *                        (float)(1/k) with clip_norm == Y3_GRAD_CLIP_OFF; fp64
+ *   y3_adam_step_scaled / y3_adam_step_ema_scaled
+ *                        y3_adam_step / y3_adam_step_ema on grad[i] * *scale_dev
+ *                        (one fp32 multiply; the same bits when the scale is 1)
+ * first_dev (int32), norm_dev, scale_dev are DEVICE memory, so a replayed graph
+ * picks up each step's values.  workspace: y3_grad_norm_workspace_bytes(count),
+ * 8-byte aligned, written whole by every accumulate / sumsq launch (no zeroing)
+ * and read by the y3_grad_clip_scale that follows with the same count.  Arenas
+ * 16-byte aligned; counts need not be multiples of 4. */
+#define Y3_GRAD_CLIP_OFF ((double)INFINITY)
+size_t y3_grad_norm_workspace_bytes(size_t count);
+int y3_grad_accumulate(float* acc, const float* grad, size_t count, const int* first_dev, void* workspace,
+                       y3_stream_t stream);
+int y3_grad_sumsq(const float* grad, size_t count, void* workspace, y3_stream_t stream);
+int y3_grad_clip_scale(const void* workspace, size_t count, int accumulate_steps, double clip_norm, float* norm_dev,
+                       float* scale_dev, y3_stream_t stream);
+int y3_adam_step_scaled(float* param, const float* grad, float* m, float* v, size_t count,
+                        const float* lr_t_dev, float beta1, float beta2, float eps, const float* scale_dev,
+                        y3_stream_t stream);
+int y3_adam_step_ema_scaled(float* param, const float* grad, float* m, float* v, size_t count,
+                            const float* lr_t_dev, float beta1, float beta2, float eps,
+                            float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
+                            const float* omd_dev, const float* scale_dev, y3_stream_t stream);
 
 /* ---- class-wise NMS (bbox_utils.py:200-281; inference.py:72-79) ------------
  * rows [N,Nb,5+K].  A row is a candidate of class c if w > min_box and

@@ -15,6 +15,10 @@ Added (opt-in, off by default): --test_map 1 runs a test-set mAP pass after ever
 (hence the export) use, and --box_loss giou / diou / ciou (with --box_loss_weight W) trains and tests with an
 IoU-family box-regression loss in place of the reference's xy + wh terms.  The scalar CSVs keep their columns:
 with an IoU loss `loss_xy` carries the box term and `loss_wh` is 0.  The weight files do not record the choice.
+--accumulate_steps N sums the gradients of N consecutive batches into one optimiser step (effective batch = batch_size x
+replicas x N; a "step" of the loop, of --test_every_n_steps and of train.csv stays one batch) and --grad_clip_norm X bounds the
+global L2 norm of the (averaged) gradient at X; with either, <scalars>/grad_norm.csv gets one row per optimiser
+step: the train.csv step that completed it, the norm before clipping and the factor applied to the summed gradient.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -131,10 +135,11 @@ def effective_reader_count(requested, cpus, local_world):
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
-                box_loss='mse', box_loss_weight=1.0):
+                box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None):
     test_map = effective_test_map(test_map, model_selection)
-    from yolo3.model import check_box_loss_args
+    from yolo3.model import check_box_loss_args, check_grad_args
     check_box_loss_args(box_loss, box_loss_weight)
+    check_grad_args(accumulate_steps, grad_clip_norm)
     if test_map:
         from yolo3 import bbox_utils
         bbox_utils.check_nms_args(test_map_nms, test_map_nms_sigma)
@@ -199,7 +204,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Creating model')
         number_classes = train_reader.get_number_classes()
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
-                            box_loss=box_loss, box_loss_weight=box_loss_weight)
+                            box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
+                            grad_clip_norm=grad_clip_norm)
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
@@ -208,6 +214,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         if ema_decay is not None:
             print('Using an exponential moving average of the weights (decay {}, warm-up {:g} steps) for the test loss, the mAP pass '
                   'and the checkpoint'.format(ema_decay, yolo.ema_warmup))
+
+        log_grad_norm = accumulate_steps > 1 or grad_clip_norm is not None
+        if log_grad_norm:
+            print('Effective batch size {} = batch_size {} x {} replicas x {} accumulated steps; gradient norm {}'.format(
+                batch_size * world * accumulate_steps, batch_size, world, accumulate_steps,
+                'clipped at {}'.format(grad_clip_norm) if grad_clip_norm is not None else 'not clipped'))
 
         def averaged():
             """The model the loop judges and keeps: the EMA copy when there is one (each replica's own EMA moving statistics,
@@ -230,6 +242,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             for split in ('train', 'test'):
                 with open(os.path.join(log_dir, split + '.csv'), 'w') as fh:
                     fh.write('step,' + ','.join(names) + '\n')
+            if log_grad_norm:
+                with open(os.path.join(log_dir, 'grad_norm.csv'), 'w') as fh:
+                    fh.write('step,grad_norm,scale\n')
 
         def log_scalars(split, step, metrics):
             if rank == 0:
@@ -257,6 +272,10 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 abort_on_nan(loss_value, 'Training Loss went to NaN, try a lower learning rate')
                 print('Train Epoch {}: Batch {}/{}: Loss {}'.format(epoch, step, train_epoch_size, train_metrics[0].result()))
                 log_scalars('train', int(epoch * train_epoch_size + step), train_metrics)
+                if log_grad_norm and rank == 0 and yolo.micro_step == 0:      # this batch completed an optimiser step
+                    with open(os.path.join(log_dir, 'grad_norm.csv'), 'a') as fh:
+                        fh.write('{},{!r},{!r}\n'.format(int(epoch * train_epoch_size + step), float(yolo.last_grad_norm),
+                                                        float(yolo.grad_scale_dev)))
                 for m in train_metrics:
                     m.reset_states()
 
@@ -353,6 +372,26 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         dist.destroy_process_group()
 
 
+def _accumulate_steps_arg(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    if k < 1:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    return k
+
+
+def _grad_clip_norm_arg(text):
+    try:
+        c = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a finite number > 0, got {!r}'.format(text))
+    if not (c > 0.0 and c != float('inf')):
+        raise argparse.ArgumentTypeError('a finite number > 0, got {!r}'.format(text))
+    return c
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog='train_yolo', description='Script which trains a yolo_v3 model')
     parser.add_argument('--batch_size', dest='batch_size', type=int, help='training batch size', default=8)
@@ -389,6 +428,12 @@ def build_parser():
                              'CSVs carries the box term and loss_wh is 0')
     parser.add_argument('--box_loss_weight', dest='box_loss_weight', type=float, default=1.0,
                         help='(addition) factor of the box term of --box_loss giou / diou / ciou (finite, > 0; mse takes 1)')
+    parser.add_argument('--accumulate_steps', dest='accumulate_steps', type=_accumulate_steps_arg, default=1,
+                        help='(addition) 1 (default): off; N > 1: sum the gradients of N consecutive batches into one optimiser step '
+                             '(effective batch = batch_size x replicas x N at the activation memory of one batch)')
+    parser.add_argument('--grad_clip_norm', dest='grad_clip_norm', type=_grad_clip_norm_arg, default=None,
+                        help='(addition) off by default; X > 0: scale the gradient of an optimiser step so that its global L2 norm is at '
+                             'most X (as Keras Adam(global_clipnorm=X))')
     return parser
 
 
@@ -400,4 +445,4 @@ if __name__ == "__main__":
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
-                a.test_map_nms_sigma, a.box_loss, a.box_loss_weight)
+                a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm)

@@ -100,6 +100,12 @@ SIGNATURES = {
     'y3_loss_workspace_bytes': (sz, []),
     'y3_adam_step': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, vp]),
     'y3_adam_step_ema': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, fp, fp, sz, fp, vp]),
+    'y3_grad_norm_workspace_bytes': (sz, [sz]),
+    'y3_grad_accumulate': (i32, [fp, fp, sz, ip, vp, vp]),
+    'y3_grad_sumsq': (i32, [fp, sz, vp, vp]),
+    'y3_grad_clip_scale': (i32, [vp, sz, i32, C.c_double, fp, fp, vp]),
+    'y3_adam_step_scaled': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, vp]),
+    'y3_adam_step_ema_scaled': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, fp, fp, sz, fp, fp, vp]),
     'y3_nms_per_class': (i32, [fp, i32, i32, i32, f32, f32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
     'y3_nms_workspace_bytes': (sz, [i32, i32, i32]),
     'y3_nms_single_class': (i32, [fp, i32, f32, ip, ip, fp, vp, sz, vp]),

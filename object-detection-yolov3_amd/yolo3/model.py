@@ -56,6 +56,32 @@ def check_box_loss_args(box_loss, box_loss_weight=1.0):
                          .format(box_loss_weight))
 
 
+def check_grad_args(accumulate_steps=1, grad_clip_norm=None):
+    """Host-side validation of the gradient accumulation count and the global-norm clip (the library checks them
+    again): ValueError unless accumulate_steps is an integer >= 1 and grad_clip_norm is None (off) or a finite number > 0."""
+    k = accumulate_steps
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError('accumulate_steps must be an integer >= 1, got {!r}'.format(accumulate_steps))
+    if grad_clip_norm is None:
+        return
+    try:
+        c = float(grad_clip_norm)
+    except (TypeError, ValueError):
+        raise ValueError('grad_clip_norm must be None (off) or a number, got {!r}'.format(grad_clip_norm))
+    if isinstance(grad_clip_norm, bool) or not (c > 0.0 and math.isfinite(c)):
+        raise ValueError('grad_clip_norm must be None (off) or finite and > 0, got {!r}'.format(grad_clip_norm))
+
+
+def clip_scale(norm, clip, k):
+    """The factor the scaled Adam kernel multiplies the accumulated gradient with (y3_grad_clip_scale, restated on the host for
+    tests and logs): (1/k) * (clip / max(norm, clip)) for the pre-clip global norm `norm` of the averaged gradient, 1/k with
+    clip None.  fp64, rounded once to fp32."""
+    s = 1.0 / float(k)
+    if clip is not None:
+        s = s * (float(clip) / max(float(norm), float(clip)))
+    return np.float32(s)
+
+
 def _round_up(v, a):
     return (v + a - 1) // a * a
 
@@ -207,6 +233,7 @@ class _Plan:
         self.keep = []     # ctypes objects / tensors that must outlive the lists
         self.tensors = []
         self.graph = None
+        self.graph_micro = None      # gradient accumulation: the captured micro-step that ends in the accumulator (YoloV3._capture)
         self.infer_graph = None
         self.infer_graph_tiles = None     # forward (without the input transpose) + decode, for predict_tiles
         self.zs_ws = None
@@ -706,7 +733,12 @@ class YoloV3:
 
     def __init__(self, global_batch_size, img_size, number_classes, anchors=None, learning_rate=1e-4, device=None, seed=None,
                  use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
-                 box_loss='mse', box_loss_weight=1.0):
+                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None):
+        # gradient accumulation and global-norm clipping: 1 / None = off; checked before the device is needed
+        check_grad_args(accumulate_steps, grad_clip_norm)
+        self.accumulate_steps = int(accumulate_steps)
+        self.grad_clip_norm = float(grad_clip_norm) if grad_clip_norm is not None else None
+        self.micro_step = 0                       # micro-steps of the pending optimiser step already taken: 0 .. accumulate_steps - 1
         # box-regression term of the loss: 'mse' = the reference's xy + wh terms; checked before the device is needed
         check_box_loss_args(box_loss, box_loss_weight)
         self.box_loss = box_loss
@@ -762,6 +794,17 @@ class YoloV3:
             self.ema_moving = z(2 * self.moving_stride)
             self.ema_omd_dev = z(1)
             self._ema_stash = (z(self.arena_floats), z(2 * self.moving_stride))
+        # accumulator (only with accumulate_steps > 1), the fp64 per-block partial sums of squares, and the scalars the kernels
+        # hand each other in device memory: `first` of the accumulate pass, the pre-clip norm, the scale of the Adam pass
+        self.grad_acc = self.last_grad_norm = self.grad_scale_dev = self._grad_ws = self._acc_first_dev = self._grad_scalars = None
+        if self.accumulate_steps > 1 or self.grad_clip_norm is not None:
+            if self.accumulate_steps > 1:
+                self.grad_acc = z(self.arena_floats)
+                self._acc_first_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._grad_ws = torch.zeros(int(lib.y3_grad_norm_workspace_bytes(self.arena_floats)) // 8, dtype=torch.float64, device=dev)
+            self._grad_scalars = z(2)
+            self.last_grad_norm = self._grad_scalars[0]      # 0-d views: the values of the last optimiser step, read when used
+            self.grad_scale_dev = self._grad_scalars[1]
         self.use_graph = bool(use_graph)
         if inference_precision not in ('fp32', 'bf16'):
             raise ValueError("inference_precision must be 'fp32' or 'bf16'")
@@ -869,7 +912,9 @@ class YoloV3:
     # ---- exponential moving average of the weights ---------------------------
     def reset_ema(self):
         """Restart the average from the current weights and moving statistics (no-op when the EMA is off).  set_weights does
-        it; a data-parallel trainer calls it again after broadcasting rank 0's weights."""
+        it; a data-parallel trainer calls it again after broadcasting rank 0's weights.  Either way a half-accumulated optimiser
+        step is dropped (micro_step back to 0: its gradients belong to other weights)."""
+        self.micro_step = 0
         if self.ema_decay is None:
             return
         if self._ema_swapped:
@@ -1157,8 +1202,35 @@ class YoloV3:
             self.dist.begin_step()
         plan.run_backward(st, hook)
 
+    def _grad_passes(self, st, last):
+        """After the backward pass of a micro-step (kernel gradients joined into `st` by run_backward, all-reduce by finish_step):
+        fold grads into the accumulator, and on the last micro-step leave the norm and the Adam scale in device memory."""
+        n = self.arena_floats
+        if self.grad_acc is not None:
+            check(lib.y3_grad_accumulate(self.grad_acc.data_ptr(), self.grads.data_ptr(), n, self._acc_first_dev.data_ptr(),
+                                         self._grad_ws.data_ptr(), st), 'y3_grad_accumulate')
+        elif last:
+            check(lib.y3_grad_sumsq(self.grads.data_ptr(), n, self._grad_ws.data_ptr(), st), 'y3_grad_sumsq')
+        if last:
+            clip = self.grad_clip_norm if self.grad_clip_norm is not None else math.inf        # Y3_GRAD_CLIP_OFF
+            check(lib.y3_grad_clip_scale(self._grad_ws.data_ptr(), n, self.accumulate_steps, clip, self.last_grad_norm.data_ptr(),
+                                         self.grad_scale_dev.data_ptr(), st), 'y3_grad_clip_scale')
+
     def _adam(self, st):
-        if self.ema_decay is None:
+        if self._grad_ws is not None:
+            # accumulation / clipping on: the same update on (accumulated gradient) * scale (DESIGN §3.10)
+            g = self.grad_acc if self.grad_acc is not None else self.grads
+            if self.ema_decay is None:
+                check(lib.y3_adam_step_scaled(self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                              self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps,
+                                              self.grad_scale_dev.data_ptr(), st), 'y3_adam_step_scaled')
+            else:
+                check(lib.y3_adam_step_ema_scaled(self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
+                                                  self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps,
+                                                  self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr(),
+                                                  self.moving.numel(), self.ema_omd_dev.data_ptr(), self.grad_scale_dev.data_ptr(), st),
+                      'y3_adam_step_ema_scaled')
+        elif self.ema_decay is None:
             check(lib.y3_adam_step(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
                                    self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps, st), 'y3_adam_step')
         else:
@@ -1172,7 +1244,9 @@ class YoloV3:
     def train_step(self, inputs):
         """model.py:481-508 for this replica.  inputs = (images, (gt1, gt2, gt3),
         loss_metric, loss_xy_metric, loss_wh_metric, loss_obj_metric, loss_class_metric);
-        metrics may be None.  Returns the loss value as a 0-d device tensor."""
+        metrics may be None.  Returns the loss value as a 0-d device tensor.
+        With accumulate_steps = k > 1 this is one MICRO-step: forward, loss, backward (and all-reduce) as ever, grads folded into
+        the accumulator; only the k-th call in a row advances `iterations` and updates weights, moments and EMA."""
         images, gt_data = inputs[0], inputs[1]
         metrics = list(inputs[2:]) + [None] * 5
         n = int(images.shape[0])
@@ -1180,21 +1254,30 @@ class YoloV3:
             raise RuntimeError('train_step inside ema_weights(): the live weights are parked')
         plan = self._plan(n, True)
         self._load_inputs(plan, images, gt_data)
-        self.iterations += 1
-        self._bf16_stale = True
-        self.lr_t_dev.fill_(self._lr_t())
-        if self.ema_decay is not None:
-            self.ema_omd_dev.fill_(float(self._ema_omd()))
+        last = self.micro_step == self.accumulate_steps - 1          # always, without accumulation
+        if last:
+            self.iterations += 1
+            self._bf16_stale = True
+            self.lr_t_dev.fill_(self._lr_t())
+            if self.ema_decay is not None:
+                self.ema_omd_dev.fill_(float(self._ema_omd()))
+        if self.grad_acc is not None:
+            self._acc_first_dev.fill_(1 if self.micro_step == 0 else 0)
         st = self._stream()
         if self.use_graph and self.dist is None:
-            if plan.graph is None:
-                self._capture(plan)
-            plan.graph.replay()
+            which = 'graph' if last else 'graph_micro'
+            if getattr(plan, which) is None:
+                self._capture(plan, last)
+            getattr(plan, which).replay()
         else:
             self._fwd_bwd(plan, st)
             if self.dist is not None:
                 self.dist.finish_step()
-            self._adam(st)
+            if self._grad_ws is not None:
+                self._grad_passes(st, last)
+            if last:
+                self._adam(st)
+        self.micro_step = 0 if last else self.micro_step + 1
         parts = plan.loss4.clone()
         loss_value = parts.sum() / float(self.global_batch_size)
         for mtr, val in zip(metrics[:5], [loss_value, parts[0], parts[1], parts[2], parts[3]]):
@@ -1202,11 +1285,15 @@ class YoloV3:
                 mtr.update_state(val)
         return loss_value
 
-    def _capture(self, plan):
+    def _capture(self, plan, last=True):
         """Capture forward + loss + backward + Adam of one step into a HIP graph.
         A warm-up pass (no Adam) runs first so lazy initialisation happens
         outside the capture; it only touches scratch state plus the BN moving
-        statistics, which are restored before capturing."""
+        statistics, which are restored before capturing.
+        With gradient accumulation there are two graphs per plan: last=False is a
+        micro-step that only folds its gradients into the accumulator (`first`
+        comes from device memory, so one graph serves micro-steps 1 .. k-1),
+        last=True adds the norm, the scale and the scaled Adam step."""
         moving = self.moving.clone()
         st = self._stream()
         plan.run_forward(st)
@@ -1220,8 +1307,11 @@ class YoloV3:
             plan.run_forward(st)
             plan.run_loss(st)
             plan.run_backward(st)
-            self._adam(st)
-        plan.graph = g
+            if self._grad_ws is not None:
+                self._grad_passes(st, last)
+            if last:
+                self._adam(st)
+        setattr(plan, 'graph' if last else 'graph_micro', g)
 
     def dist_train_step(self, dist_strategy, inputs):
         """model.py:510-515: per-replica step + SUM of the per-replica losses."""
