@@ -270,7 +270,7 @@ int y3_conv2d_fwd_bf16(const y3_tensor* src, const void* wt_t_bf16, const float*
                        const float* scale, const float* shift, const y3_tensor* resid, y3_stream_t stream);
 /* The same with a caller-owned workspace (y3_conv2d_fwd_bf16_workspace(m = N*OH*OW, cin, ksize, cout) bytes; zero it once, the
  * first 256 KiB are per-tile tickets (the same header as the fp32 entries, so one zeroed workspace can serve both) that every launch leaves at zero; one stream per workspace): the small-M layers
- * (<= 1 024 tiles of 64 x 64 and >= 32 K steps: the 13x13 / 26x26 / 19x19 grids at batch 8) are then split along K into up to 8
+ * (<= 512 tiles of 64 x 64 and >= 32 K steps: the 13x13 / 26x26 / 19x19 grids at batch 8) are then split along K into up to 8
  * slices whose fp32 partial sums the last-arriving slice adds in slice order inside the kernel (bit-reproducible).  Without a
  * workspace (or with y3_conv2d_fwd_bf16) every tile walks its whole K. */
 size_t y3_conv2d_fwd_bf16_workspace(int m, int cin, int ksize, int cout);
@@ -278,6 +278,26 @@ int y3_conv2d_fwd_bf16_ws(const y3_tensor* src, const void* wt_t_bf16, const flo
                           const y3_tensor* dst, int dst_is_f32, unsigned flags, float alpha,
                           const float* scale, const float* shift, const y3_tensor* resid,
                           void* workspace, size_t workspace_bytes, y3_stream_t stream);
+/* Which kernel y3_conv2d_fwd_bf16_ws would run for exactly these arguments (without the stream), on which tile and grid: a dry
+ * run of the entry point's own decision code, host only -- nothing is launched and no pointer is dereferenced (of src / dst /
+ * resid -> ptr, the weights, the bias and the workspace only alignment and null-ness are read; scale / shift: null-ness).
+ * Returns the workspace bytes the launch would use (0: no split-K) and fills out12 with
+ *   {route, bm, bn, bk, grid, threads, splits, chunk, vec_ok, patch stride, patch residual, nk}
+ * route: one of Y3_BF16_ROUTE_*; bm x bn the output tile (patch kernels: the 32 x 8 / 4 / 2 output pixels of one row group by
+ * Cout), bk the K step; grid workgroups of `threads`; every tile cut into `splits` K slices of `chunk` steps, the last one
+ * nk - (splits - 1) * chunk long (nk = K / bk steps in all; splits == 1: whole); vec_ok: 16-byte epilogue accesses (aligned
+ * dst / resid rows), 0: element by element; patch stride / residual: the template instantiation of a patch kernel (stride 1 / 2;
+ * residual 0 / 1, always 0 for the 64 -> 128 kernel, which tests it at run time), 0 / 0 elsewhere.  A launch the entry point
+ * would refuse gives route 0 and returns 0; y3_last_error() has the reason.  y3_conv2d_fwd_bf16 is the same launch with a null
+ * workspace. */
+#define Y3_BF16_ROUTE_PP 1    /* the 256 x 256 ping-pong kernel */
+#define Y3_BF16_ROUTE_C32 2   /* the 32 -> 64 3x3 patch kernel */
+#define Y3_BF16_ROUTE_C64 3   /* the 64 -> 128 3x3 patch kernel */
+#define Y3_BF16_ROUTE_RING 4  /* the LDS-DMA ring kernel (tiles 128x32, 128x64, 256x128, 128x128, 64x64; split-K on 64x64) */
+size_t y3_conv2d_fwd_bf16_plan(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride,
+                               const y3_tensor* dst, int dst_is_f32, unsigned flags, float alpha,
+                               const float* scale, const float* shift, const y3_tensor* resid,
+                               void* workspace, size_t workspace_bytes, int* out12);
 /* The first (RGB) conv_layer straight to bf16: src fp32 NHWC with Cin padded to 4, wt the fp32 Keras kernel
  * [3][3][4][32], 3x3 stride 1 SAME, dst bf16 with 32 channels; same epilogue order as above.  fp32-accurate: input and
  * weights are split into three bf16 pieces each and multiplied on the matrix pipe (fp32 accumulation), one rounding on the

@@ -1376,8 +1376,26 @@ static int check_bf16_tensor(const y3_tensor* t, const char* name) {
     return 0;
 }
 
+// Dry run of conv2d_fwd_bf16_impl (y3_conv2d_fwd_bf16_plan): where `dry` is given, the decision is written to dry->out in place of
+// every launch -- {route, bm, bn, bk, grid, threads, splits, chunk, vec_ok, patch stride, patch residual, K steps of bk} -- and
+// nothing is launched or dereferenced.
+struct Bf16Dry {
+    int* out;
+    size_t ws;      // workspace bytes the launch would use
+};
+static void bf16_dry_report(Bf16Dry* dry, const Bf16Args& p, int route, int bm, int bn, int bk, long long grid, int threads, int splits, int chunk,
+                            int patch_stride, int patch_resid, size_t ws) {
+    const int v[12] = {route, bm, bn, bk, (int)grid, threads, splits, chunk, p.vec_ok, patch_stride, patch_resid, p.K / bk};
+    for (int i = 0; i < 12; ++i) dry->out[i] = v[i];
+    dry->ws = ws;
+}
+
 template <int BM, int BN, int WM, int WN, int BK = 32>
-static void launch_bf16(const Bf16Args& args, int grid, hipStream_t st) {
+static void launch_bf16(const Bf16Args& args, int grid, hipStream_t st, Bf16Dry* dry) {
+    if (dry) {
+        bf16_dry_report(dry, args, Y3_BF16_ROUTE_RING, BM, BN, BK, grid, 64 * WM * WN, 1, args.K / BK, 0, 0, 0);
+        return;
+    }
     Bf16Args p = args;
     p.ohw = p.OH * p.OW;
     p.dv_nbn = y3_make_div(p.nbn);
@@ -1421,7 +1439,7 @@ extern "C" size_t y3_conv2d_fwd_bf16_workspace(int m, int cin, int ksize, int co
 
 static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
                                 int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                void* workspace, size_t workspace_bytes, y3_stream_t stream);
+                                void* workspace, size_t workspace_bytes, y3_stream_t stream, Bf16Dry* dry = nullptr);
 
 extern "C" int y3_conv2d_fwd_bf16(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
                                   int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
@@ -1433,10 +1451,23 @@ extern "C" int y3_conv2d_fwd_bf16_ws(const y3_tensor* src, const void* wt_t_bf16
                                      void* workspace, size_t workspace_bytes, y3_stream_t stream) {
     return conv2d_fwd_bf16_impl(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, workspace, workspace_bytes, stream);
 }
+// the decision of the launch above, by running its own code dry (host only; a refused launch: route 0, y3_last_error() says why)
+extern "C" size_t y3_conv2d_fwd_bf16_plan(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
+                                          int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
+                                          void* workspace, size_t workspace_bytes, int* out12) {
+    if (!out12) return 0;
+    for (int i = 0; i < 12; ++i) out12[i] = 0;
+    Bf16Dry dry = {out12, 0};
+    if (conv2d_fwd_bf16_impl(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, workspace, workspace_bytes, nullptr, &dry) != Y3_OK) {
+        out12[0] = 0;
+        return 0;
+    }
+    return dry.ws;
+}
 
 static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
                                 int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+                                void* workspace, size_t workspace_bytes, y3_stream_t stream, Bf16Dry* dry) {
     if (int e = check_bf16_tensor(src, "conv2d_fwd_bf16 src")) return e;
     if (int e = check_bf16_tensor(dst, "conv2d_fwd_bf16 dst")) return e;
     Y3_CHECK_ARG(wt_t_bf16, "conv2d_fwd_bf16: null weights");
@@ -1534,6 +1565,10 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
         p.dv_nbn = y3_make_div(p.nbn);
         p.dv_ohw = y3_make_div(p.ohw);
         p.dv_ow = y3_make_div(p.OW);
+        if (dry) {
+            bf16_dry_report(dry, p, Y3_BF16_ROUTE_PP, 256, 256, 64, tpp, 512, 1, p.K / 64, 0, 0, 0);
+            return Y3_OK;
+        }
         hipLaunchKernelGGL(conv_bf16_pp_kernel, dim3((unsigned)tpp), dim3(512), 0, st, p);
         Y3_CHECK_LAUNCH("conv_bf16_pp");
         return Y3_OK;
@@ -1572,6 +1607,10 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
         q.flags = flags;
         q.alpha = alpha;
         const unsigned grid = (unsigned)(groups < 512 ? groups : 512);       // two workgroups per CU, each a contiguous run of groups
+        if (dry) {      // (bm: the 32 x 8 / 32 x 4 output pixels of one row group)
+            bf16_dry_report(dry, p, Y3_BF16_ROUTE_C32, stride == 1 ? 256 : 128, 64, 32, grid, 256, 1, p.K / 32, stride, q.resid ? 1 : 0, 0);
+            return Y3_OK;
+        }
         if (stride == 1 && q.resid)
             hipLaunchKernelGGL((conv_bf16_c32_kernel<1, true>), dim3(grid), dim3(256), 0, st, q);
         else if (stride == 1)
@@ -1614,6 +1653,10 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
         q.flags = flags;
         q.alpha = alpha;
         const unsigned grid = (unsigned)(groups < 256 ? groups : 256);       // one workgroup of 8 waves per CU
+        if (dry) {      // (bm: the 32 x 4 / 32 x 2 output pixels of one row group; the residual is a run-time branch of this kernel)
+            bf16_dry_report(dry, p, Y3_BF16_ROUTE_C64, stride == 1 ? 128 : 64, 128, 64, grid, 512, 1, p.K / 64, stride, 0, 0);
+            return Y3_OK;
+        }
         if (stride == 1)
             hipLaunchKernelGGL(conv_bf16_c64_kernel<1>, dim3(grid), dim3(512), 0, st, q);
         else
@@ -1623,21 +1666,21 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
     }
     if (p.Nout <= 32) {
         p.nbn = 1;
-        launch_bf16<128, 32, 4, 1>(p, y3_cdiv(p.M, 128), st);
+        launch_bf16<128, 32, 4, 1>(p, y3_cdiv(p.M, 128), st, dry);
     } else if (p.Nout <= 64) {
         p.nbn = 1;
-        launch_bf16<128, 64, 4, 1>(p, y3_cdiv(p.M, 128), st);
+        launch_bf16<128, 64, 4, 1>(p, y3_cdiv(p.M, 128), st, dry);
     } else if (k64 && t256 >= 150 && t256 <= 300) {
         p.nbn = y3_cdiv(p.Nout, 128);
         // (staged epilogue without a residual too, as for the 128 x 128 launches below: same box 8 x 608^2 2.552 -> 2.530 ms, 8 x 416^2
         // 1.729 -> 1.722, 25 / 45 tiles unchanged)
-        launch_bf16<256, 128, 4, 2, 64>(p, y3_cdiv(p.M, 256) * p.nbn, st);
+        launch_bf16<256, 128, 4, 2, 64>(p, y3_cdiv(p.M, 256) * p.nbn, st, dry);
     } else if (t128 >= 512) {
         p.nbn = y3_cdiv(p.Nout, 128);
         // with or without a residual through the staged epilogue (16-byte stores over whole tile rows).  Round 2 preferred a direct
         // one (2-byte stores from registers, 3 waves per SIMD) where there is nothing to load; re-measured at the batches the tiled path
         // plans (45 x 608^2, same box): the ten 256 -> 128 1x1 launches of the 76^2 stage 60 -> 55 us, 512 -> 128 88 -> 76
-        launch_bf16<128, 128, 2, 2>(p, y3_cdiv(p.M, 128) * p.nbn, st);
+        launch_bf16<128, 128, 2, 2>(p, y3_cdiv(p.M, 128) * p.nbn, st, dry);
     } else {
         p.nbn = y3_cdiv(p.Nout, 64);
         const int tiles = y3_cdiv(p.M, 64) * p.nbn;
@@ -1652,11 +1695,16 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
             p.dv_nbn = y3_make_div(p.nbn);
             p.dv_ohw = y3_make_div(p.ohw);
             p.dv_ow = y3_make_div(p.OW);
+            if (dry) {
+                bf16_dry_report(dry, p, Y3_BF16_ROUTE_RING, 64, 64, 32, (long long)tiles * sk.splits, 256, sk.splits, sk.chunk, 0, 0, sk.ws_bytes);
+                return Y3_OK;
+            }
             hipLaunchKernelGGL((conv_bf16_kernel<64, 64, 2, 2, 32, true>), dim3(tiles * sk.splits), dim3(256), 0, st, p);
         } else {
-            launch_bf16<64, 64, 2, 2>(p, tiles, st);
+            launch_bf16<64, 64, 2, 2>(p, tiles, st, dry);
         }
     }
+    if (dry) return Y3_OK;
     Y3_CHECK_LAUNCH("conv_bf16");
     return Y3_OK;
 }

@@ -84,6 +84,7 @@ SIGNATURES = {
     'y3_conv2d_fwd_bf16': (i32, [TP, vp, fp, i32, i32, TP, i32, u32, f32, fp, fp, TP, vp]),
     'y3_conv2d_fwd_bf16_ws': (i32, [TP, vp, fp, i32, i32, TP, i32, u32, f32, fp, fp, TP, vp, sz, vp]),
     'y3_conv2d_fwd_bf16_workspace': (sz, [i32, i32, i32, i32]),
+    'y3_conv2d_fwd_bf16_plan': (sz, [TP, vp, fp, i32, i32, TP, i32, u32, f32, fp, fp, TP, vp, sz, ip]),
     'y3_f32_to_bf16': (i32, [fp, vp, sz, vp]),
     'y3_conv2d_first_bf16': (i32, [TP, fp, fp, TP, u32, f32, fp, fp, vp]),
     'y3_tile_gather': (i32, [vp, i32, i32, i32, i32, ip, i32, i32, i32, fp, vp]),
@@ -140,6 +141,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 EPI_LRELU = 1
 EPI_ACCUM = 2
+BF16_ROUTE_PP, BF16_ROUTE_C32, BF16_ROUTE_C64, BF16_ROUTE_RING = 1, 2, 3, 4   # Y3_BF16_ROUTE_*: out12[0] of y3_conv2d_fwd_bf16_plan
 BF16_NO_PATCH = 8   # Y3_BF16_NO_PATCH: keep a y3_conv2d_fwd_bf16 launch off the patch kernels (small batches, yolo3hip.h)
 CONV_X3 = 4      # Y3_CONV_X3: fp32 arithmetic as three bf16 pieces per operand (conv_x3.hip); the weight operand changes layout
 

@@ -164,29 +164,64 @@ def test_bf16_inference_matches_bf16_oracle(img, n):
     assert torch.equal(yolo2.predict(images.cuda()).cpu(), torch.from_numpy(out16))    # constructor default, deterministic
 
 
-@pytest.mark.parametrize('img,n', [(96, 2), (608, 2)])
+def _bf16_conv_routes(plan):
+    """[(route, flags)] of the bf16 conv launches the plan emits, in emission order: each call's own arguments through
+    y3_conv2d_fwd_bf16_plan (a dry run of the entry point: nothing is launched)"""
+    import ctypes as C
+    from yolo3 import _hip
+    out = []
+    for fn, args in plan.fwd:
+        if fn is _hip.lib.y3_conv2d_fwd_bf16_ws:
+            o = (C.c_int * 12)()
+            _hip.lib.y3_conv2d_fwd_bf16_plan(*(tuple(args) + (o,)))
+            assert o[0] != 0, _hip.lib.y3_last_error()
+            out.append((o[0], args[7]))
+    return out
+
+
+@pytest.mark.parametrize('img,n', [(96, 2), (608, 2), (608, 10), (608, 45)])
 def test_bf16_layers_teacher_forced(img, n):
-    """(608 = the tile size of BASELINE.json configs[4]: the real model on a batch of full-size tiles.)
+    """(608 = the tile size of BASELINE.json configs[4]: the real model on a batch of full-size tiles; 10 and 45 are the batches
+    the tiled path plans for a 4096^2 image, where the early layers run the patch kernels, the 76^2 stage the 128 x 128 tile and
+    most of the rest the ping-pong kernel: at batch 2 the ring kernel runs almost everywhere.)
     Every layer of the bf16 plan on its own: the oracle (fp64 arithmetic, bf16 rounding points) recomputes layer i
     from the GPU's OWN bf16 inputs (teacher forcing), so nothing compounds.  Bound per element against the oracle's
     value BEFORE rounding: half a bf16 ulp (round to nearest; a tie or near-tie may legitimately fall either way, which
     is why the comparison is not against the oracle's rounded value) plus 3e-5 of the layer's scale for fp32
-    accumulation order / the folded BatchNorm affine."""
+    accumulation order / the folded BatchNorm affine.
+    Batches above three: the oracle recomputes the first, the middle and the last image only (every layer is independent per
+    image; the 72 layer outputs of 45 tiles in fp64 do not fit the host comfortably), sliced on the device before the copy.
+    Which kernel every conv launch takes is asked of the library (y3_conv2d_fwd_bf16_plan) and compared with what
+    tests/bf16_routes.py predicts for this batch: that ties the helper's restatement of the network and of the 300 MB rule
+    (BF16_PATCH_MIN_BYTES) to the model."""
+    import bf16_routes as br
+    from yolo3 import _hip
     om, params, yolo, images, _ = _setup(img, n, 11, True)
     yolo.predict(images.cuda(), precision='bf16')
     plan = yolo._plan(n, False, True)
     torch.cuda.synchronize()
-    nchw = lambda t: t.torch_view().float().permute(0, 3, 1, 2).cpu()
+    routes = _bf16_conv_routes(plan)
+    assert routes == br.predicted_routes(img, n, len(ANCHORS) * (5 + K)), 'tests/bf16_routes.py predicts other kernels or flags than the model launches'
+    reached = set(r for r, _ in routes)
+    if (img, n) == (608, 45):
+        tiles = set(tuple(mb.plan()[0][:3]) for mb in br.launches(img, n, len(ANCHORS) * (5 + K)))
+        assert reached == {_hip.BF16_ROUTE_PP, _hip.BF16_ROUTE_C32, _hip.BF16_ROUTE_C64, _hip.BF16_ROUTE_RING} and (_hip.BF16_ROUTE_RING, 128, 128) in tiles
+    if n == 2:      # the 300 MB rule: no layer of a batch of two streams from HBM
+        assert not reached & {_hip.BF16_ROUTE_C32, _hip.BF16_ROUTE_C64}
+        assert all(f == _hip.EPI_LRELU | _hip.BF16_NO_PATCH for _, f in routes if f)
+    keep = list(range(n)) if n <= 3 else [0, n // 2, n - 1]
+    idx = torch.tensor(keep, device='cuda')
+    nchw = lambda t: t.torch_view().index_select(0, idx).float().permute(0, 3, 1, 2).cpu()
     layers = [nchw(t) for t in plan.layer_out]
     ups = [nchw(op[2]) for op in plan.ops if op[0] == 'upsample']
-    fms_gpu = [f.cpu() for f in yolo.feature_maps(images.cuda(), precision='bf16')]
+    fms_gpu = [f.index_select(0, idx).cpu() for f in yolo.feature_maps(images.cuda(), precision='bf16')]
     assert len(layers) == 72 and len(ups) == 2
     net = om.Net(params, 3, len(ANCHORS), K, dtype=torch.float64)
     net.bf16 = True
     net.trace_exact, net.up_trace = [], []
     net.force = {'layers': layers, 'up': ups}
     with torch.no_grad():
-        fms = net.feature_maps(images.double(), training=False)
+        fms = net.feature_maps(images[keep].double(), training=False)
 
     def ok(got, ref, what):
         got, ref = got.double(), ref.double()
