@@ -986,6 +986,28 @@ struct ConvPlan {
 };
 // The K loop of conv_fast_body runs its steps in pairs (an odd count is padded with a dead step): slices get an even step count.
 static inline int even_steps(int chunk) { return chunk + (chunk & 1); }
+// No tile is cut: every tile is one slice of `chunk` K steps, and the launch needs no slabs.  Where the planners start, and what
+// a plan falls back to when its slabs have no room.
+static void whole_tiles(ConvPlan& pl, int chunk) {
+    pl.f = pl.tiles;
+    pl.s0 = pl.s1 = 1;
+    pl.chunk0 = pl.chunk1 = chunk;
+    pl.ws_bytes = 0;
+}
+// The end of both planners: the workspace a split plan needs (ticket header + one slab per slice of a cut tile).  Slab offsets
+// are 32-bit buffer offsets: a plan whose slabs would not fit them falls back to whole tiles of `whole_chunk` steps.
+static void size_slabs(ConvPlan& pl, int whole_chunk) {
+    const long long split_items = pl.s0 > 1 ? (long long)pl.f * pl.s0 + (long long)(pl.tiles - pl.f) * pl.s1 : (pl.s1 > 1 ? (long long)(pl.tiles - pl.f) * pl.s1 : 0);
+    const long long slab_bytes = split_items * pl.t.bm * pl.t.bn * 4;
+    if (slab_bytes >= 0x7ff00000LL)
+        whole_tiles(pl, whole_chunk);
+    else
+        pl.ws_bytes = split_items > 0 ? (size_t)Y3_WS_HEADER + (size_t)slab_bytes : 0;
+}
+// The caller's workspace cannot hold the `need` bytes of a split plan (the launch then runs whole_tiles)
+static bool no_room(size_t need, const void* workspace, size_t workspace_bytes) {
+    return need > 0 && (workspace == nullptr || workspace_bytes < need);
+}
 // The x3 kernels (conv_x3.hip): 128 x 128 tiles (128 x 64 for <= 64 output columns), two to three workgroups per CU.  Every
 // launch of the layers they are used for is cut along K into slices of >= 12 K steps so that ~700 workgroups share the work
 // evenly -- 2.7 per CU, dealt out as slots free up -- e.g. 338 tiles x 2, 172 x 4, 88 x 8 slices of 36 steps for the 3x3 layers
@@ -998,9 +1020,8 @@ static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
     pl.t = {128, Nout <= 64 ? 64 : 128, 16};
     const int tiles = y3_cdiv(M, pl.t.bm) * y3_cdiv(Nout, pl.t.bn);
     const int nk = K / 16;
-    pl.tiles = pl.f = tiles;
-    pl.s0 = pl.s1 = 1;
-    pl.chunk0 = pl.chunk1 = even_steps(nk);
+    pl.tiles = tiles;
+    whole_tiles(pl, even_steps(nk));
     constexpr int min_steps = 12;
     // slices are whole units of K steps: 3x3 launches in units of 18 (two 16-channel chunks of nine taps: the patch kernel's loop
     // body, conv_x3.hip), the others in pairs of steps
@@ -1072,29 +1093,18 @@ static ConvPlan plan_conv_x3(int M, int Nout, int K, int ntaps) {
         }
     }
     pl.stats_tiles = y3_cdiv(M, pl.t.bm);
-    const long long split_items = pl.s0 > 1 ? (long long)pl.f * pl.s0 + (long long)(tiles - pl.f) * pl.s1 : (pl.s1 > 1 ? (long long)(tiles - pl.f) * pl.s1 : 0);
-    const long long slab_bytes = split_items * pl.t.bm * pl.t.bn * 4;
-    if (slab_bytes >= 0x7ff00000LL) {
-        pl.f = tiles;
-        pl.s0 = pl.s1 = 1;
-        pl.chunk0 = pl.chunk1 = even_steps(nk);
-        pl.ws_bytes = 0;
-    } else {
-        pl.ws_bytes = split_items > 0 ? (size_t)Y3_WS_HEADER + (size_t)slab_bytes : 0;
-    }
+    size_slabs(pl, even_steps(nk));
     return pl;
 }
 // fast_ok: the launch qualifies for conv_igemm_fast_kernel (the only kernel with split-K)
-static ConvPlan plan_conv(int M, int Nout, int K, bool fast_ok, bool x3 = false, int ntaps = 1) {
-    if (x3) return plan_conv_x3(M, Nout, K, ntaps);
+static ConvPlan plan_conv(int M, int Nout, int K, bool fast_ok) {
     ConvPlan pl;
     pl.t = pick_tile(M, Nout);
     const int tiles = y3_cdiv(M, pl.t.bm) * y3_cdiv(Nout, pl.t.bn);
     const int nk = K / pl.t.bk;                                   // K steps (fast path: K % bk == 0)
+    const int whole = nk > 0 ? nk : 1;
     pl.tiles = tiles;
-    pl.f = tiles;
-    pl.s0 = pl.s1 = 1;
-    pl.chunk0 = pl.chunk1 = nk > 0 ? nk : 1;
+    whole_tiles(pl, whole);
     constexpr int want = 2000;    // workgroups to aim for (swept with tools/fwd_time.py: 1000 / 1400 / 2000 / 2800)
     constexpr int min_k = 256;    // shortest K slice worth a launch
     constexpr int cus = 256;
@@ -1133,16 +1143,7 @@ static ConvPlan plan_conv(int M, int Nout, int K, bool fast_ok, bool x3 = false,
         }
     }
     pl.stats_tiles = y3_cdiv(M, pl.t.bm);
-    const long long split_items = pl.s0 > 1 ? (long long)pl.f * pl.s0 + (long long)(tiles - pl.f) * pl.s1 : (pl.s1 > 1 ? (long long)(tiles - pl.f) * pl.s1 : 0);
-    const long long slab_bytes = split_items * pl.t.bm * pl.t.bn * 4;
-    if (slab_bytes >= 0x7ff00000LL) {   // slab offsets are 32-bit buffer offsets: fall back to whole tiles
-        pl.f = tiles;
-        pl.s0 = pl.s1 = 1;
-        pl.chunk0 = pl.chunk1 = nk > 0 ? nk : 1;
-        pl.ws_bytes = 0;
-    } else {
-        pl.ws_bytes = split_items > 0 ? (size_t)Y3_WS_HEADER + (size_t)slab_bytes : 0;
-    }
+    size_slabs(pl, whole);
     return pl;
 }
 // Debug switch of the product library (documented in yolo3hip.h): with Y3_CHECK_TICKETS=1 every launch that uses the ticket
@@ -1169,19 +1170,30 @@ static int check_tickets(const char* what, const void* workspace, hipStream_t st
 static bool fast_shape_ok(int C, int Nout, int K, int ntaps) {
     return !getenv("Y3_NO_FAST") && C % 16 == 0 && K % 16 == 0 && (ntaps == 1 || y3_is_pow2(C));
 }
+// One gather-GEMM launch (the forward, a stride-1 data gradient, one parity class of a stride-2 one) described from its shape
+// alone: M rows, ntaps * C contracted, Nout columns.  The queries read this description, launch_igemm issues it.
+struct GemmDesc {
+    bool x3;        // Y3_CONV_X3 was asked for and the x3 kernels take the shape
+    bool fast;      // x3, or conv_igemm_fast_kernel; false: the generic kernel, whole tiles
+    ConvPlan pl;
+};
+static GemmDesc describe_gemm(int M, int C, int ntaps, int Nout, unsigned flags) {
+    GemmDesc d;
+    const int K = ntaps * C;
+    d.x3 = (flags & Y3_CONV_X3) && x3_shape_ok(C, Nout, K, ntaps);
+    d.fast = d.x3 || fast_shape_ok(C, Nout, K, ntaps);
+    d.pl = d.x3 ? plan_conv_x3(M, Nout, K, ntaps) : plan_conv(M, Nout, K, d.fast);
+    return d;
+}
 
 extern "C" int y3_conv2d_x3_ok(int m, int c, int ntaps, int nout) {
     return (m > 0 && (ntaps == 1 || ntaps == 9 || ntaps == 2 || ntaps == 4) && x3_shape_ok(c, nout, ntaps * c, ntaps)) ? 1 : 0;
 }
 extern "C" int y3_conv2d_stats_tiles_x(int m, int cin, int ksize, int cout, unsigned flags) {
-    const int taps = ksize * ksize;
-    const bool x3 = (flags & Y3_CONV_X3) && x3_shape_ok(cin, cout, taps * cin, taps);
-    return plan_conv(m, cout, taps * cin, fast_shape_ok(cin, cout, taps * cin, taps), x3, taps).stats_tiles;
+    return describe_gemm(m, cin, ksize * ksize, cout, flags).pl.stats_tiles;
 }
 extern "C" size_t y3_conv2d_fwd_workspace_x(int m, int cin, int ksize, int cout, unsigned flags) {
-    const int taps = ksize * ksize;
-    const bool x3 = (flags & Y3_CONV_X3) && x3_shape_ok(cin, cout, taps * cin, taps);
-    return plan_conv(m, cout, taps * cin, fast_shape_ok(cin, cout, taps * cin, taps), x3, taps).ws_bytes;
+    return describe_gemm(m, cin, ksize * ksize, cout, flags).pl.ws_bytes;
 }
 extern "C" int y3_conv2d_stats_tiles(int m, int cin, int ksize, int cout) { return y3_conv2d_stats_tiles_x(m, cin, ksize, cout, 0u); }
 extern "C" size_t y3_conv2d_fwd_workspace(int m, int cin, int ksize, int cout) { return y3_conv2d_fwd_workspace_x(m, cin, ksize, cout, 0u); }
@@ -1189,70 +1201,128 @@ extern "C" size_t y3_conv2d_fwd_workspace(int m, int cin, int ksize, int cout) {
 // Diagnostics (include/yolo3hip.h): the plan behind y3_conv2d_fwd / stride-1 y3_conv2d_dgrad for an M x cout x (ksize^2 cin) GEMM
 extern "C" size_t y3_conv2d_plan(int m, int cin, int ksize, int cout, int* out13) { return y3_conv2d_plan_x(m, cin, ksize, cout, 0u, out13); }
 extern "C" size_t y3_conv2d_plan_x(int m, int cin, int ksize, int cout, unsigned flags, int* out13) {
-    const int taps = ksize * ksize, K = taps * cin;
-    const bool x3 = (flags & Y3_CONV_X3) && x3_shape_ok(cin, cout, K, taps);
-    const bool fast = x3 || fast_shape_ok(cin, cout, K, taps);
-    const ConvPlan pl = plan_conv(m, cout, K, fast, x3, taps);
+    const GemmDesc d = describe_gemm(m, cin, ksize * ksize, cout, flags);
+    const ConvPlan& pl = d.pl;
     if (out13) {
         const int v[13] = {pl.t.bm, pl.t.bn, pl.t.bk, pl.tiles, pl.f, pl.s0, pl.s1, pl.chunk0, pl.chunk1,
-                           pl.f * pl.s0 + (pl.tiles - pl.f) * pl.s1, pl.stats_tiles, (fast ? 1 : 0) | (pl.short_last ? 2 : 0), K / pl.t.bk};
+                           pl.f * pl.s0 + (pl.tiles - pl.f) * pl.s1, pl.stats_tiles, (d.fast ? 1 : 0) | (pl.short_last ? 2 : 0), ksize * ksize * cin / pl.t.bk};
         for (int i = 0; i < 13; ++i) out13[i] = v[i];
     }
     return pl.ws_bytes;
 }
 
-template <int BM, int BN, int WM, int WN, int BK>
-static void launch_cfg(const ConvArgs& p, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WM, WN, BK>), dim3(grid), dim3(64 * WM * WN), 0, st, p);
-}
-template <int BM, int BN, int WM, int WN, int BK>
-static void launch_fast(const FastArgs& p, bool dense, int grid, hipStream_t st) {
+// Tile -> kernel instantiation: one dispatch per kernel family; false if the family has no kernel for the tile.
+template <int BM, int BN, int WM, int WN>
+static void launch_fast_cfg(const FastArgs& p, bool dense, int grid, hipStream_t st) {
     const dim3 g(grid), b(64 * WM * WN);
     if (p.bn_a)      // launch_igemm has checked: dense destination
-        hipLaunchKernelGGL((conv_igemm_fast_kernel<BM, BN, WM, WN, BK, true, true>), g, b, 0, st, p);
+        hipLaunchKernelGGL((conv_igemm_fast_kernel<BM, BN, WM, WN, 16, true, true>), g, b, 0, st, p);
     else if (dense)
-        hipLaunchKernelGGL((conv_igemm_fast_kernel<BM, BN, WM, WN, BK, true>), g, b, 0, st, p);
+        hipLaunchKernelGGL((conv_igemm_fast_kernel<BM, BN, WM, WN, 16, true>), g, b, 0, st, p);
     else
-        hipLaunchKernelGGL((conv_igemm_fast_kernel<BM, BN, WM, WN, BK, false>), g, b, 0, st, p);
+        hipLaunchKernelGGL((conv_igemm_fast_kernel<BM, BN, WM, WN, 16, false>), g, b, 0, st, p);
+}
+static bool launch_fast(const TileCfg& t, const FastArgs& p, bool dense, int grid, hipStream_t st) {
+    switch (t.bm * 1000 + t.bn) {
+        case 128 * 1000 + 128: launch_fast_cfg<128, 128, 2, 2>(p, dense, grid, st); return true;
+        case 128 * 1000 + 64: launch_fast_cfg<128, 64, 4, 1>(p, dense, grid, st); return true;
+        case 128 * 1000 + 32: launch_fast_cfg<128, 32, 4, 1>(p, dense, grid, st); return true;
+        case 64 * 1000 + 64: launch_fast_cfg<64, 64, 2, 2>(p, dense, grid, st); return true;
+        case 64 * 1000 + 128: launch_fast_cfg<64, 128, 2, 2>(p, dense, grid, st); return true;
+    }
+    return false;
+}
+static bool launch_generic(const TileCfg& t, const ConvArgs& p, int grid, hipStream_t st) {
+    const dim3 g(grid), b(256);
+    switch (t.bm * 1000 + t.bn) {
+        case 128 * 1000 + 128: hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 2, 16>), g, b, 0, st, p); return true;
+        case 128 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_kernel<128, 64, 4, 1, 16>), g, b, 0, st, p); return true;
+        case 128 * 1000 + 32: hipLaunchKernelGGL((conv_igemm_kernel<128, 32, 4, 1, 16>), g, b, 0, st, p); return true;
+        case 64 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_kernel<64, 64, 2, 2, 16>), g, b, 0, st, p); return true;
+        case 64 * 1000 + 128: hipLaunchKernelGGL((conv_igemm_kernel<64, 128, 2, 2, 16>), g, b, 0, st, p); return true;
+    }
+    return false;
+}
+// (no 128 x 128: that instantiation of the merged kernel spills -- four argument sets live)
+template <bool BNS>
+static bool launch_fast_multi(const TileCfg& t, const FastArgs4& m, int grid, hipStream_t st) {
+    const dim3 g(grid), b(256);
+    switch (t.bm * 1000 + t.bn) {
+        case 128 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<128, 64, 4, 1, 16, BNS>), g, b, 0, st, m); return true;
+        case 128 * 1000 + 32: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<128, 32, 4, 1, 16, BNS>), g, b, 0, st, m); return true;
+        case 64 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<64, 64, 2, 2, 16, BNS>), g, b, 0, st, m); return true;
+        case 64 * 1000 + 128: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<64, 128, 2, 2, 16, BNS>), g, b, 0, st, m); return true;
+    }
+    return false;
 }
 
-// Build the fast kernel's arguments; false if the launch does not qualify.
-static bool make_fast(const ConvArgs& a, int ntaps, int bk, FastArgs* f) {
+// What the fast kernels' arguments need from the geometry of a launch: the tap list as the kernels address it and the extents
+// of the buffer descriptors.
+struct FastGeom {
+    int min_off;                   // most negative tap offset (floats): the source pointer is biased by it
+    int dh[9], dw[9], off[9], wrow[9];
+    int nx;                        // the tap list as a (rows x nx) grid
+    unsigned src_bytes, wt_bytes, dst_bytes, resid_bytes;
+};
+// Geometry only (no data pointer is read); false if the launch does not qualify for the fast kernels: 2 GiB buffer limits, tap grid.
+static bool fast_geom(const ConvArgs& a, int ntaps, int bk, FastGeom* g) {
     // Nout need not be a multiple of 4 (the detection heads): a weight-row load that runs past column Nout - 1 picks up the
     // head of the next row (zeros past the end of the buffer) into accumulator columns >= Nout, which the epilogue never stores
     if (a.C % bk != 0 || a.K % bk != 0) return false;
     if (ntaps > 1 && !y3_is_pow2(a.C)) return false;
-    const long long src_elems = (long long)(a.M > 0 ? 1 : 0) * 0;  // (unused)
-    (void)src_elems;
-    FastArgs p = {};
     // bias the base pointer by the most negative tap offset so that scalar offsets stay non-negative
-    int min_off = 0;
-    int dh[9], dw[9];
+    g->min_off = 0;
     for (int t = 0; t < ntaps; ++t) {
         const int code = (int)((a.tap_dhdw >> (4 * t)) & 15ull);
-        dh[t] = (code & 3) - 1;
-        dw[t] = (code >> 2) - 1;
-        const int off = (dh[t] * a.W + dw[t]) * a.src_ld;
-        if (off < min_off) min_off = off;
+        g->dh[t] = (code & 3) - 1;
+        g->dw[t] = (code >> 2) - 1;
+        const int off = (g->dh[t] * a.W + g->dw[t]) * a.src_ld;
+        if (off < g->min_off) g->min_off = off;
     }
-    const long long total = (long long)a.src_n * a.H * a.W * a.src_ld - min_off;
+    const long long total = (long long)a.src_n * a.H * a.W * a.src_ld - g->min_off;
     const long long wtotal = (long long)(a.wt_rows) * a.Nout;
-    if (total * 4 >= 0x7fffffffLL || wtotal * 4 >= 0x7fffffffLL) return false;
-    p.src = a.src ? a.src + min_off : nullptr;      // (null in the dry runs of the *_tiles queries)
-    p.src_bytes = (unsigned)(total * 4);
+    // x3: three bf16 piece planes of the K-contiguous copy (y3_x3_split_weights): 6 bytes per element, same 2 GiB limit
+    if (total * 4 >= 0x7fffffffLL || wtotal * (a.x3 ? 6 : 4) >= 0x7fffffffLL) return false;
+    g->src_bytes = (unsigned)(total * 4);
+    g->wt_bytes = (unsigned)(wtotal * (a.x3 ? 6 : 4));
+    for (int t = 0; t < ntaps; ++t) {
+        g->off[t] = ((g->dh[t] * a.W + g->dw[t]) * a.src_ld - g->min_off) * 4;
+        g->wrow[t] = (int)((a.tap_wsel >> (4 * t)) & 15ull) * a.C;
+    }
+    // the tap list as a (rows x nx) grid: nx = length of the first run of equal dh
+    int nx = 1;
+    while (nx < ntaps && g->dh[nx] == g->dh[0]) ++nx;
+    if (ntaps % nx != 0 || nx > 3) return false;
+    g->nx = nx;
+    const int offx = nx > 1 ? g->off[1] - g->off[0] : 0, wx = nx > 1 ? g->wrow[1] - g->wrow[0] : 0;
+    const int offy = ntaps > nx ? g->off[nx] - g->off[0] : 0, wy = ntaps > nx ? g->wrow[nx] - g->wrow[0] : 0;
+    for (int t = 0; t < ntaps; ++t)
+        if (g->off[t] != g->off[0] + (t / nx) * offy + (t % nx) * offx || g->wrow[t] != g->wrow[0] + (t / nx) * wy + (t % nx) * wx)
+            return false;   // not a grid: the generic kernel takes it
+    const long long dpix = a.dense_dst ? (long long)a.M : (long long)a.src_n * a.DH * a.DW;
+    const long long db = dpix * a.dst_ld * 4, rb = dpix * (long long)a.resid_ld * 4;
+    if (db >= 0x7fffffffLL || rb >= 0x7fffffffLL) return false;
+    g->dst_bytes = (unsigned)db;
+    g->resid_bytes = (unsigned)rb;
+    return true;
+}
+
+// Build the fast kernel's arguments; false if the launch does not qualify.
+static bool make_fast(const ConvArgs& a, int ntaps, int bk, FastArgs* f) {
+    FastGeom g;
+    if (!fast_geom(a, ntaps, bk, &g)) return false;
+    FastArgs p = {};
+    p.src = a.src + g.min_off;
+    p.src_bytes = g.src_bytes;
     p.wt = a.wt;
     p.Cper = a.C;
-    p.wt_bytes = (unsigned)(wtotal * 4);
-    if (a.x3) {      // three bf16 piece planes of the K-contiguous copy (y3_x3_split_weights): 6 bytes per element, same 2 GiB limit
-        if (wtotal * 6 >= 0x7fffffffLL) return false;
-        p.wt_bytes = (unsigned)(wtotal * 6);
-        p.x3_mode = 1;      // non-temporal activation loads
-    }
+    p.wt_bytes = g.wt_bytes;
+    if (a.x3) p.x3_mode = 1;      // non-temporal activation loads
     for (int t = 0; t < ntaps; ++t) {
-        p.tap_dh[t] = dh[t];
-        p.tap_dw[t] = dw[t];
-        p.tap_off[t] = ((dh[t] * a.W + dw[t]) * a.src_ld - min_off) * 4;
-        p.tap_wrow[t] = (int)((a.tap_wsel >> (4 * t)) & 15ull) * a.C;
+        p.tap_dh[t] = g.dh[t];
+        p.tap_dw[t] = g.dw[t];
+        p.tap_off[t] = g.off[t];
+        p.tap_wrow[t] = g.wrow[t];
     }
     p.ntaps = ntaps;
     p.korder = ntaps > 1 ? (a.C % 32 != 0 ? 1 : 2) : 0;
@@ -1260,32 +1330,17 @@ static bool make_fast(const ConvArgs& a, int ntaps, int bk, FastArgs* f) {
     p.ohw = a.OH * a.OW;
     p.dv_ohw = y3_make_div(p.ohw);
     p.dv_ow = y3_make_div(a.OW);
-    {
-        // the tap list as a (rows x nx) grid: nx = length of the first run of equal dh
-        int nx = 1;
-        while (nx < ntaps && dh[nx] == dh[0]) ++nx;
-        if (ntaps % nx != 0) return false;
-        p.tg_nx = nx;
-        p.tg_mul = nx == 1 ? 32 : (nx == 2 ? 16 : 11);
-        p.tg_off0 = p.tap_off[0];
-        p.tg_w0 = p.tap_wrow[0];
-        p.tg_offx = nx > 1 ? p.tap_off[1] - p.tap_off[0] : 0;
-        p.tg_wx = nx > 1 ? p.tap_wrow[1] - p.tap_wrow[0] : 0;
-        p.tg_offy = ntaps > nx ? p.tap_off[nx] - p.tap_off[0] : 0;
-        p.tg_wy = ntaps > nx ? p.tap_wrow[nx] - p.tap_wrow[0] : 0;
-        if (nx > 3) return false;
-        for (int t = 0; t < ntaps; ++t)
-            if (p.tap_off[t] != p.tg_off0 + (t / nx) * p.tg_offy + (t % nx) * p.tg_offx ||
-                p.tap_wrow[t] != p.tg_w0 + (t / nx) * p.tg_wy + (t % nx) * p.tg_wx)
-                return false;   // not a grid: the generic kernel takes it
-    }
-    {
-        const long long dpix = a.dense_dst ? (long long)a.M : (long long)a.src_n * a.DH * a.DW;
-        const long long db = dpix * a.dst_ld * 4, rb = dpix * (long long)a.resid_ld * 4;
-        if (db >= 0x7fffffffLL || rb >= 0x7fffffffLL) return false;
-        p.dst_bytes = (unsigned)db;
-        p.resid_bytes = (unsigned)rb;
-    }
+    const int nx = g.nx;
+    p.tg_nx = nx;
+    p.tg_mul = nx == 1 ? 32 : (nx == 2 ? 16 : 11);
+    p.tg_off0 = p.tap_off[0];
+    p.tg_w0 = p.tap_wrow[0];
+    p.tg_offx = nx > 1 ? p.tap_off[1] - p.tap_off[0] : 0;
+    p.tg_wx = nx > 1 ? p.tap_wrow[1] - p.tap_wrow[0] : 0;
+    p.tg_offy = ntaps > nx ? p.tap_off[nx] - p.tap_off[0] : 0;
+    p.tg_wy = ntaps > nx ? p.tap_wrow[nx] - p.tap_wrow[0] : 0;
+    p.dst_bytes = g.dst_bytes;
+    p.resid_bytes = g.resid_bytes;
     p.dst = a.dst;
     p.bias = a.bias;
     p.scale = a.scale;
@@ -1322,48 +1377,46 @@ static bool make_fast(const ConvArgs& a, int ntaps, int bk, FastArgs* f) {
     *f = p;
     return true;
 }
+// The split-K bookkeeping of a plan as the kernels read it (FastArgs::sk_*; sk_slab0 is the caller's)
+static void set_split(FastArgs& f, const ConvPlan& pl) {
+    f.dv_s0 = y3_make_div(pl.s0);
+    f.dv_s1 = y3_make_div(pl.s1);
+    f.sk_f = pl.f;
+    f.sk_s0 = pl.s0;
+    f.sk_s1 = pl.s1;
+    f.sk_n0 = pl.f * pl.s0;
+    f.sk_chunk0 = pl.chunk0;
+    f.sk_chunk1 = pl.chunk1;
+}
 
-static int launch_igemm(const ConvArgs& a, void* workspace, size_t workspace_bytes, hipStream_t st) {
+static GemmDesc describe_gemm(const ConvArgs& a) { return describe_gemm(a.M, a.C, a.K / a.C, a.Nout, a.x3 ? Y3_CONV_X3 : 0u); }
+
+// Issue one described launch: d = describe_gemm(a).
+static int launch_igemm(const ConvArgs& a, const GemmDesc& d, void* workspace, size_t workspace_bytes, hipStream_t st) {
     ConvArgs p = a;
     const int ntaps = p.K / p.C;
-    const bool x3 = p.x3 != 0;
-    if (x3 && !x3_shape_ok(p.C, p.Nout, p.K, ntaps)) {
+    if (p.x3 && !d.x3) {
         y3_set_error("conv: Y3_CONV_X3 does not take this shape (C %d, Nout %d, K %d): ask y3_conv2d_x3_ok() first", p.C, p.Nout, p.K);
         return Y3_EINVAL;
     }
-    const bool fast_ok = x3 || fast_shape_ok(p.C, p.Nout, p.K, ntaps);
-    ConvPlan pl = plan_conv(p.M, p.Nout, p.K, fast_ok, x3, ntaps);
-    if (pl.ws_bytes > 0 && (workspace == nullptr || workspace_bytes < pl.ws_bytes)) {  // no room for slabs: whole tiles
-        pl.f = pl.tiles;
-        pl.s0 = pl.s1 = 1;
-        pl.chunk0 = pl.chunk1 = even_steps(p.K / pl.t.bk);
-        pl.ws_bytes = 0;
-    }
+    ConvPlan pl = d.pl;
+    if (no_room(pl.ws_bytes, workspace, workspace_bytes)) whole_tiles(pl, even_steps(p.K / pl.t.bk));
     const TileCfg t = pl.t;
     p.nbn = y3_cdiv(p.Nout, t.bn);
-    const int tiles = y3_cdiv(p.M, t.bm) * p.nbn;
-    const int key = t.bm * 10000 + t.bn * 10 + (t.bk == 32 ? 1 : 0);
     FastArgs f;
-    if (fast_ok && make_fast(p, ntaps, t.bk, &f)) {
+    if (d.fast && make_fast(p, ntaps, t.bk, &f)) {
         f.nbn = p.nbn;
         f.nbm = y3_cdiv(p.M, t.bm);
         f.col_major = ((long long)p.K * p.Nout * 4 > 2048LL * 1024) ? 1 : 0;     // kernel matrix larger than 2 MiB: column-major tile ids
         f.nb_fast = f.col_major ? f.nbm : f.nbn;
         f.dv_nb = y3_make_div(f.nb_fast);
-        f.dv_s0 = y3_make_div(pl.s0);
-        f.dv_s1 = y3_make_div(pl.s1);
-        f.sk_f = pl.f;
-        f.sk_s0 = pl.s0;
-        f.sk_s1 = pl.s1;
-        f.sk_n0 = pl.f * pl.s0;
-        f.sk_chunk0 = pl.chunk0;
-        f.sk_chunk1 = pl.chunk1;
+        set_split(f, pl);
         f.sk_slab0 = pl.s0 > 1 ? 0 : f.sk_n0;
         f.tickets = pl.ws_bytes ? (int*)workspace : nullptr;
         if (f.tickets)
             if (int e = check_tickets("conv2d", workspace, st)) return e;
         f.slab = pl.ws_bytes ? (float*)((char*)workspace + Y3_WS_HEADER) : nullptr;
-        const int grid = f.sk_n0 + (tiles - pl.f) * pl.s1;
+        const int grid = f.sk_n0 + (pl.tiles - pl.f) * pl.s1;
         const bool dense = p.dense_dst != 0;
         if (t.bk != 16) {
             y3_set_error("conv: the fast kernel is built for K steps of 16 (tile %dx%dx%d)", t.bm, t.bn, t.bk);
@@ -1373,8 +1426,8 @@ static int launch_igemm(const ConvArgs& a, void* workspace, size_t workspace_byt
             y3_set_error("conv: BatchNorm-backward statistics need the dense fast kernel with K steps of 16");
             return Y3_EINVAL;
         }
-        if (x3) {
-            if (pl.short_last && pl.f == tiles) f.x3_mode |= 8;
+        if (d.x3) {
+            if (pl.short_last && pl.f == pl.tiles) f.x3_mode |= 8;
             if (!y3_x3_launch(f, t.bm, t.bn, dense, grid, st)) {
                 y3_set_error("conv: no x3 kernel for tile %dx%d", t.bm, t.bn);
                 return Y3_EINVAL;
@@ -1382,32 +1435,20 @@ static int launch_igemm(const ConvArgs& a, void* workspace, size_t workspace_byt
             Y3_CHECK_LAUNCH("conv_x3");
             return Y3_OK;
         }
-        switch (key) {
-            case 128 * 10000 + 128 * 10 + 0: launch_fast<128, 128, 2, 2, 16>(f, dense, grid, st); break;
-            case 128 * 10000 + 64 * 10 + 0: launch_fast<128, 64, 4, 1, 16>(f, dense, grid, st); break;
-            case 128 * 10000 + 32 * 10 + 0: launch_fast<128, 32, 4, 1, 16>(f, dense, grid, st); break;
-            case 64 * 10000 + 64 * 10 + 0: launch_fast<64, 64, 2, 2, 16>(f, dense, grid, st); break;
-            case 64 * 10000 + 128 * 10 + 0: launch_fast<64, 128, 2, 2, 16>(f, dense, grid, st); break;
-            default: y3_set_error("conv: no fast kernel for tile %dx%dx%d", t.bm, t.bn, t.bk); return Y3_EINVAL;
+        if (!launch_fast(t, f, dense, grid, st)) {
+            y3_set_error("conv: no fast kernel for tile %dx%dx%d", t.bm, t.bn, t.bk);
+            return Y3_EINVAL;
         }
         Y3_CHECK_LAUNCH("conv_igemm_fast");
         return Y3_OK;
     }
-    if (p.bn_a || x3) {
-        y3_set_error("conv: %s not available on the generic kernel (shape %d x %d x %d)", x3 ? "Y3_CONV_X3 is" : "BatchNorm-backward statistics are", p.M, p.Nout, p.K);
+    if (p.bn_a || d.x3) {
+        y3_set_error("conv: %s not available on the generic kernel (shape %d x %d x %d)", d.x3 ? "Y3_CONV_X3 is" : "BatchNorm-backward statistics are", p.M, p.Nout, p.K);
         return Y3_EINVAL;
     }
-    const int grid = tiles;
-    switch (key) {
-        case 128 * 10000 + 128 * 10 + 0: launch_cfg<128, 128, 2, 2, 16>(p, grid, st); break;
-        case 128 * 10000 + 64 * 10 + 0: launch_cfg<128, 64, 4, 1, 16>(p, grid, st); break;
-        case 128 * 10000 + 32 * 10 + 0: launch_cfg<128, 32, 4, 1, 16>(p, grid, st); break;
-        case 64 * 10000 + 64 * 10 + 0: launch_cfg<64, 64, 2, 2, 16>(p, grid, st); break;
-        case 64 * 10000 + 128 * 10 + 0: launch_cfg<64, 128, 2, 2, 16>(p, grid, st); break;
-        default:   // shapes only the fast kernel is instantiated for (forced tiles): the generic 64x64
-            p.nbn = y3_cdiv(p.Nout, 64);
-            launch_cfg<64, 64, 2, 2, 16>(p, y3_cdiv(p.M, 64) * p.nbn, st);
-            break;
+    if (!launch_generic(t, p, pl.tiles, st)) {
+        y3_set_error("conv: no kernel for tile %dx%dx%d", t.bm, t.bn, t.bk);
+        return Y3_EINVAL;
     }
     Y3_CHECK_LAUNCH("conv_igemm");
     return Y3_OK;
@@ -1483,12 +1524,144 @@ extern "C" int y3_conv2d_fwd(const y3_tensor* src, const float* wt, const float*
     p.alpha = alpha;
     p.src_n = src->n;
     p.wt_rows = taps * src->c;
-    return launch_igemm(p, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_igemm(p, describe_gemm(p), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-static int conv2d_dgrad_impl(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags,
-                             const y3_tensor* bn_a, float* bn_partials, void* workspace, size_t workspace_bytes, y3_stream_t stream,
-                             int* dry_rows = nullptr, size_t* dry_ws = nullptr);
+// ---- data gradient -----------------------------------------------------------
+// The merged launch of the parity classes of a stride-2 data gradient (conv_igemm_fast_multi_kernel, conv_x3_multi_kernel): one
+// plan per class, each with ONE slice count for all its tiles (f32: whole tiles, no workspace)
+struct MultiPlan {
+    ConvPlan c[4];      // c[].ws_bytes is not used: the classes share one workspace
+    int rows;           // row tiles over all classes: rows of the partial statistics
+    size_t ws;          // ticket header + the slabs of all cut classes
+};
+// f32: whole tiles of one size for all classes
+static bool plan_dgrad_multi_f32(const ConvArgs* cls, int ncls, MultiPlan* pl) {
+    int mmax = 0;
+    for (int c = 0; c < ncls; ++c) mmax = cls[c].M > mmax ? cls[c].M : mmax;
+    TileCfg t = pick_tile(mmax * ncls, cls[0].Nout);   // the classes share one grid: size the tile for their sum
+    if (t.bm == 128 && t.bn == 128) t.bm = 64;          // launch_fast_multi has no 128 x 128
+    pl->rows = 0;
+    pl->ws = 0;
+    for (int c = 0; c < ncls; ++c) {
+        if (!fast_shape_ok(cls[c].C, cls[c].Nout, cls[c].K, cls[c].K / cls[c].C)) return false;
+        ConvPlan& q = pl->c[c];
+        q.t = t;
+        q.stats_tiles = y3_cdiv(cls[c].M, t.bm);
+        q.tiles = q.stats_tiles * y3_cdiv(cls[c].Nout, t.bn);
+        whole_tiles(q, cls[c].K / t.bk);
+        pl->rows += q.stats_tiles;
+    }
+    return true;
+}
+// x3 (conv_x3_multi_kernel).  The classes carry 1 / 2 / 2 / 4 taps, i.e. K steps in the ratio 1 : 2 : 2 : 4, and the x3 loop wants
+// the launch to fill the 512 workgroup slots once: every class is cut along K into slices of about the same length L -- the
+// smallest L for which the launch still fits the slots.
+static bool plan_dgrad_multi_x3(const ConvArgs* cls, int ncls, MultiPlan* pl) {
+    const int Nout = cls[0].Nout;
+    if (Nout < 64) return false;
+    const TileCfg t = {128, Nout >= 128 ? 128 : 64, 16};
+    int steps[4], tsum = 0, smax = 0;
+    long long total = 0;
+    pl->rows = 0;
+    for (int c = 0; c < ncls; ++c) {
+        if (cls[c].Nout != Nout || !x3_shape_ok(cls[c].C, Nout, cls[c].K, cls[c].K / cls[c].C)) return false;
+        ConvPlan& q = pl->c[c];
+        q.t = t;
+        q.stats_tiles = y3_cdiv(cls[c].M, t.bm);
+        q.tiles = q.stats_tiles * y3_cdiv(Nout, t.bn);
+        steps[c] = cls[c].K / 16;
+        whole_tiles(q, even_steps(steps[c]));
+        pl->rows += q.stats_tiles;
+        tsum += q.tiles;
+        total += (long long)q.tiles * steps[c];
+        smax = steps[c] > smax ? steps[c] : smax;
+    }
+    if (tsum < x3_slots && tsum <= Y3_MAX_TICKETS) {
+        int L = even_steps(y3_cdiv(total, x3_slots));
+        if (L < 12) L = 12;
+        for (; L < smax; L += 2) {
+            long long g = 0;
+            for (int c = 0; c < ncls; ++c) g += (long long)pl->c[c].tiles * y3_cdiv(steps[c], L);
+            if (g <= x3_slots) break;
+        }
+        for (int c = 0; c < ncls; ++c) {
+            const int sc = y3_cdiv(steps[c], L);
+            if (sc > 1) {
+                ConvPlan& q = pl->c[c];
+                q.chunk0 = q.chunk1 = even_steps(y3_cdiv(steps[c], sc));
+                q.s0 = q.s1 = y3_cdiv(steps[c], q.chunk0);
+            }
+        }
+    }
+    size_t slab = 0;
+    for (int c = 0; c < ncls; ++c)
+        if (pl->c[c].s0 > 1) slab += (size_t)pl->c[c].tiles * pl->c[c].s0 * t.bm * t.bn * 4;
+    pl->ws = slab ? (size_t)Y3_WS_HEADER + slab : 0;
+    return true;
+}
+// false if the classes do not qualify for one merged launch (they are then launched one by one)
+static bool plan_dgrad_multi(const ConvArgs* cls, int ncls, MultiPlan* pl) {
+    if (ncls < 2 || ncls > 4) return false;
+    if (!(cls[0].x3 ? plan_dgrad_multi_x3(cls, ncls, pl) : plan_dgrad_multi_f32(cls, ncls, pl))) return false;
+    FastGeom g;
+    for (int c = 0; c < ncls; ++c)
+        if (!fast_geom(cls[c], cls[c].K / cls[c].C, 16, &g)) return false;
+    return true;
+}
+// Issue the merged launch plan_dgrad_multi accepted
+static int launch_dgrad_multi(const ConvArgs* cls, int ncls, MultiPlan pl, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (no_room(pl.ws, workspace, workspace_bytes)) {
+        for (int c = 0; c < ncls; ++c) whole_tiles(pl.c[c], even_steps(cls[c].K / 16));
+        pl.ws = 0;
+    }
+    const TileCfg t = pl.c[0].t;
+    FastArgs4 m = {};
+    int first = 0, rows = 0, tick = 0;
+    size_t slab_floats = 0;
+    for (int c = 0; c < ncls; ++c) {
+        const ConvPlan& q = pl.c[c];
+        FastArgs& a = m.a[c];
+        if (!make_fast(cls[c], cls[c].K / cls[c].C, 16, &a)) {
+            y3_set_error("conv2d_dgrad: parity class %d of the merged launch does not qualify for the fast kernels", c);
+            return Y3_EINVAL;
+        }
+        a.nbn = y3_cdiv(cls[c].Nout, t.bn);
+        a.nbm = q.stats_tiles;
+        a.col_major = 0;
+        a.nb_fast = a.nbn;
+        a.dv_nb = y3_make_div(a.nbn);
+        set_split(a, q);
+        a.sk_slab0 = 0;
+        const bool split = q.s0 > 1;
+        a.tickets = split ? (int*)workspace + tick : nullptr;
+        a.slab = split ? (float*)((char*)workspace + Y3_WS_HEADER) + slab_floats : nullptr;
+        if (split) {
+            tick += q.tiles;
+            slab_floats += (size_t)q.tiles * q.s0 * t.bm * t.bn;
+        }
+        a.bn_row0 = rows;
+        rows += a.nbm;
+        m.first[c] = first;
+        first += q.tiles * q.s0;
+    }
+    for (int c = ncls; c <= 4; ++c) m.first[c] = first;
+    const bool bns = cls[0].bn_a != nullptr;
+    if (cls[0].x3) {
+        if (pl.ws > 0)
+            if (int e = check_tickets("conv2d_dgrad (stride 2, x3)", workspace, st)) return e;
+        if (!y3_x3_multi_launch(m, t.bn, bns, first, st)) {
+            y3_set_error("conv2d_dgrad: no merged x3 kernel for tile %dx%d", t.bm, t.bn);
+            return Y3_EINVAL;
+        }
+    } else if (!(bns ? launch_fast_multi<true>(t, m, first, st) : launch_fast_multi<false>(t, m, first, st))) {
+        y3_set_error("conv2d_dgrad: no merged kernel for tile %dx%d", t.bm, t.bn);
+        return Y3_EINVAL;
+    }
+    Y3_CHECK_LAUNCH("conv_igemm_fast_multi");
+    return Y3_OK;
+}
+
 // shapes the x3 data gradient takes: stride 1 as the forward; stride 2 (3x3, the merged launch of the parity classes): >= 64 input
 // channels of the layer (output columns of the GEMM), its output channels a power of two
 static bool dgrad_x3(unsigned flags, const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc) {
@@ -1500,260 +1673,32 @@ extern "C" int y3_conv2d_dgrad_x3_ok(const y3_tensor* ddst, int ksize, int strid
     return dgrad_x3(Y3_CONV_X3, ddst, ksize, stride, dsrc) ? 1 : 0;
 }
 
-extern "C" size_t y3_conv2d_dgrad_workspace(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc) {
-    return y3_conv2d_dgrad_workspace_x(ddst, ksize, stride, dsrc, 0u);
-}
-extern "C" size_t y3_conv2d_dgrad_workspace_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags) {
-    const int taps = ksize * ksize;
-    if (stride == 1) {
-        const int K = taps * ddst->c;
-        const bool x3 = (flags & Y3_CONV_X3) && x3_shape_ok(ddst->c, dsrc->c, K, taps);
-        return plan_conv(dsrc->n * dsrc->h * dsrc->w, dsrc->c, K, fast_shape_ok(ddst->c, dsrc->c, K, taps), x3, taps).ws_bytes;
-    }
-    if (dgrad_x3(flags, ddst, ksize, stride, dsrc)) {      // the merged x3 launch: slabs of all classes behind one ticket header
-        int rows = 0;
-        size_t ws = 0;
-        if (conv2d_dgrad_impl(ddst, nullptr, ksize, 2, dsrc, Y3_CONV_X3, nullptr, nullptr, nullptr, 0, nullptr, &rows, &ws) == Y3_OK && rows > 0) return ws;
-    }
-    size_t best = 0;
-    for (int nt = 1; nt <= 4; nt *= 2) {  // parity classes carry 1, 2, 2 and 4 taps of a 3x3 kernel
-        const int K = nt * ddst->c;
-        const int M = dsrc->n * ((dsrc->h + 1) / 2) * ((dsrc->w + 1) / 2);
-        const size_t b = plan_conv(M, dsrc->c, K, fast_shape_ok(ddst->c, dsrc->c, K, nt)).ws_bytes;
-        if (b > best) best = b;
-    }
-    return best;
-}
-
-// The merged stride-2 data gradient on the x3 kernels (conv_x3_multi_kernel).  The classes carry 1 / 2 / 2 / 4 taps, i.e. K steps
-// in the ratio 1 : 2 : 2 : 4, and the x3 loop wants the launch to fill the 512 workgroup slots once: every class is cut along K
-// into slices of about the same length L -- the smallest L for which the launch still fits the slots.
-struct MultiX3Plan {
-    int bn, tiles[4], s[4], chunk[4], grid, rows;
-    size_t ws;
+// A data gradient described from the geometry of its tensors alone (no data pointer is read or needed).  The queries read the
+// description; y3_conv2d_dgrad / y3_conv2d_dgrad_bn build it once, fill in the pointers and issue it (issue_dgrad).
+enum DgradHow {
+    DGRAD_SINGLE,        // stride 1: one launch_igemm
+    DGRAD_MERGED_F32,    // stride 2: the parity classes in one launch of conv_igemm_fast_multi_kernel
+    DGRAD_MERGED_X3,     // ... of conv_x3_multi_kernel
+    DGRAD_BY_CLASS       // stride 2 off the fast path: one launch_igemm per parity class
 };
-static bool plan_dgrad_multi_x3(const ConvArgs* cls, int ncls, MultiX3Plan* pl) {
-    if (ncls < 2 || ncls > 4) return false;
-    const int Nout = cls[0].Nout;
-    if (Nout < 64) return false;
-    pl->bn = Nout >= 128 ? 128 : 64;
-    int steps[4], tsum = 0, smax = 0;
-    long long total = 0;
-    pl->rows = 0;
-    for (int c = 0; c < ncls; ++c) {
-        const int ntaps = cls[c].K / cls[c].C;
-        if (cls[c].Nout != Nout || !x3_shape_ok(cls[c].C, Nout, cls[c].K, ntaps)) return false;
-        pl->tiles[c] = y3_cdiv(cls[c].M, 128) * y3_cdiv(Nout, pl->bn);
-        pl->rows += y3_cdiv(cls[c].M, 128);
-        steps[c] = cls[c].K / 16;
-        pl->s[c] = 1;
-        pl->chunk[c] = even_steps(steps[c]);
-        tsum += pl->tiles[c];
-        total += (long long)pl->tiles[c] * steps[c];
-        smax = steps[c] > smax ? steps[c] : smax;
-    }
-    if (tsum < x3_slots && tsum <= Y3_MAX_TICKETS) {
-        int L = even_steps(y3_cdiv(total, x3_slots));
-        if (L < 12) L = 12;
-        for (; L < smax; L += 2) {
-            long long g = 0;
-            for (int c = 0; c < ncls; ++c) g += (long long)pl->tiles[c] * y3_cdiv(steps[c], L);
-            if (g <= x3_slots) break;
-        }
-        for (int c = 0; c < ncls; ++c) {
-            const int sc = y3_cdiv(steps[c], L);
-            if (sc > 1) {
-                pl->chunk[c] = even_steps(y3_cdiv(steps[c], sc));
-                pl->s[c] = y3_cdiv(steps[c], pl->chunk[c]);
-            }
-        }
-    }
-    pl->grid = 0;
-    size_t slab = 0;
-    for (int c = 0; c < ncls; ++c) {
-        pl->grid += pl->tiles[c] * pl->s[c];
-        if (pl->s[c] > 1) slab += (size_t)pl->tiles[c] * pl->s[c] * 128 * pl->bn * 4;
-    }
-    pl->ws = slab ? (size_t)Y3_WS_HEADER + slab : 0;
-    return true;
-}
-static bool launch_dgrad_multi_x3(const ConvArgs* cls, int ncls, hipStream_t st, int* dry, size_t* dry_ws, void* workspace, size_t workspace_bytes) {
-    MultiX3Plan pl;
-    if (!plan_dgrad_multi_x3(cls, ncls, &pl)) return false;
-    if (!dry && pl.ws > 0 && (workspace == nullptr || workspace_bytes < pl.ws)) {      // no room for slabs: whole tiles
-        for (int c = 0; c < ncls; ++c) {
-            pl.s[c] = 1;
-            pl.chunk[c] = even_steps(cls[c].K / 16);
-        }
-        pl.ws = 0;
-    }
-    FastArgs4 m = {};
-    int first = 0, rows = 0, tick = 0;
-    size_t slab_floats = 0;
-    for (int c = 0; c < ncls; ++c) {
-        const int ntaps = cls[c].K / cls[c].C;
-        if (!make_fast(cls[c], ntaps, 16, &m.a[c])) return false;
-        FastArgs& a = m.a[c];
-        a.nbn = y3_cdiv(cls[c].Nout, pl.bn);
-        a.nbm = y3_cdiv(cls[c].M, 128);
-        a.col_major = 0;
-        a.nb_fast = a.nbn;
-        a.dv_nb = y3_make_div(a.nbn);
-        a.dv_s0 = a.dv_s1 = y3_make_div(pl.s[c]);
-        a.sk_f = pl.tiles[c];
-        a.sk_s0 = a.sk_s1 = pl.s[c];
-        a.sk_n0 = pl.tiles[c] * pl.s[c];
-        a.sk_chunk0 = a.sk_chunk1 = pl.chunk[c];
-        a.sk_slab0 = 0;
-        const bool split = pl.s[c] > 1 && pl.ws > 0;
-        const bool have = split && workspace != nullptr;      // (dry runs plan without a workspace)
-        a.tickets = have ? (int*)workspace + tick : nullptr;
-        a.slab = have ? (float*)((char*)workspace + Y3_WS_HEADER) + slab_floats : nullptr;
-        if (split) {
-            tick += pl.tiles[c];
-            slab_floats += (size_t)pl.tiles[c] * pl.s[c] * 128 * pl.bn;
-        }
-        a.bn_row0 = rows;
-        rows += a.nbm;
-        m.first[c] = first;
-        first += pl.tiles[c] * pl.s[c];
-    }
-    for (int c = ncls; c <= 4; ++c) m.first[c] = first;
-    if (dry) {
-        *dry = rows;
-        if (dry_ws) *dry_ws = pl.ws;
-        return true;
-    }
-    if (pl.ws > 0)
-        if (check_tickets("conv2d_dgrad (stride 2, x3)", workspace, st) != Y3_OK) return false;
-    return y3_x3_multi_launch(m, pl.bn, cls[0].bn_a != nullptr, first, st);
-}
-
-// One launch for all parity classes of a stride-2 data gradient; false if the shapes do not qualify (the caller then
-// launches the classes one by one).
-// dry != nullptr: nothing is launched, *dry receives the number of partial-statistics rows (row tiles over all classes)
-static bool launch_dgrad_multi(const ConvArgs* cls, int ncls, hipStream_t st, int* dry = nullptr, size_t* dry_ws = nullptr, void* workspace = nullptr,
-                              size_t workspace_bytes = 0) {
-    if (ncls < 2 || ncls > 4) return false;
-    if (cls[0].x3) return launch_dgrad_multi_x3(cls, ncls, st, dry, dry_ws, workspace, workspace_bytes);
-    if (dry_ws) *dry_ws = 0;
-    FastArgs4 m = {};
-    int mmax = 0;
-    for (int c = 0; c < ncls; ++c) mmax = cls[c].M > mmax ? cls[c].M : mmax;
-    const int ntaps_max = cls[0].K / cls[0].C;
-    if (!fast_shape_ok(cls[0].C, cls[0].Nout, cls[0].K, ntaps_max)) return false;
-    TileCfg t = pick_tile(mmax * ncls, cls[0].Nout);   // the classes share one grid: size the tile for their sum
-    if (t.bm == 128 && t.bn == 128) t.bm = 64;   // the 128x128 instantiation of the merged kernel spills (four argument sets live)
-    if (t.bk != 16) return false;
-    int first = 0, rows = 0;
-    for (int c = 0; c < ncls; ++c) {
-        const int ntaps = cls[c].K / cls[c].C;
-        if (!fast_shape_ok(cls[c].C, cls[c].Nout, cls[c].K, ntaps) || !make_fast(cls[c], ntaps, t.bk, &m.a[c])) return false;
-        m.a[c].nbn = y3_cdiv(cls[c].Nout, t.bn);
-        m.a[c].nbm = y3_cdiv(cls[c].M, t.bm);
-        m.a[c].col_major = 0;
-        m.a[c].nb_fast = m.a[c].nbn;
-        m.a[c].dv_nb = y3_make_div(m.a[c].nbn);
-        m.a[c].dv_s0 = m.a[c].dv_s1 = y3_make_div(1);
-        m.a[c].sk_f = m.a[c].sk_n0 = y3_cdiv(cls[c].M, t.bm) * m.a[c].nbn;   // whole tiles only
-        m.a[c].sk_s0 = m.a[c].sk_s1 = 1;
-        m.a[c].sk_chunk0 = m.a[c].sk_chunk1 = cls[c].K / t.bk;
-        m.a[c].sk_slab0 = 0;
-        m.a[c].slab = nullptr;
-        m.a[c].tickets = nullptr;
-        m.a[c].bn_row0 = rows;
-        rows += m.a[c].nbm;
-        m.first[c] = first;
-        first += y3_cdiv(cls[c].M, t.bm) * m.a[c].nbn;
-    }
-    for (int c = ncls; c <= 4; ++c) m.first[c] = first;
-    const int key = t.bm * 1000 + t.bn;
-    if (dry) {
-        *dry = rows;
-        return key == 128 * 1000 + 64 || key == 128 * 1000 + 32 || key == 64 * 1000 + 64 || key == 64 * 1000 + 128;
-    }
-    if (cls[0].bn_a) {
-        switch (key) {
-            case 128 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<128, 64, 4, 1, 16, true>), dim3(first), dim3(256), 0, st, m); break;
-            case 128 * 1000 + 32: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<128, 32, 4, 1, 16, true>), dim3(first), dim3(256), 0, st, m); break;
-            case 64 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<64, 64, 2, 2, 16, true>), dim3(first), dim3(256), 0, st, m); break;
-            case 64 * 1000 + 128: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<64, 128, 2, 2, 16, true>), dim3(first), dim3(256), 0, st, m); break;
-            default: return false;
-        }
-        return true;
-    }
-    switch (key) {
-        case 128 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<128, 64, 4, 1, 16>), dim3(first), dim3(256), 0, st, m); break;
-        case 128 * 1000 + 32: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<128, 32, 4, 1, 16>), dim3(first), dim3(256), 0, st, m); break;
-        case 64 * 1000 + 64: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<64, 64, 2, 2, 16>), dim3(first), dim3(256), 0, st, m); break;
-        case 64 * 1000 + 128: hipLaunchKernelGGL((conv_igemm_fast_multi_kernel<64, 128, 2, 2, 16>), dim3(first), dim3(256), 0, st, m); break;
-        default: return false;
-    }
-    return true;
-}
-
-extern "C" int y3_conv2d_dgrad(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags,
-                               void* workspace, size_t workspace_bytes, y3_stream_t stream) {
-    return conv2d_dgrad_impl(ddst, wt_t, ksize, stride, dsrc, flags, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-
-// Row tiles of the partial statistics y3_conv2d_dgrad_bn writes for this shape, 0 if the shape does not qualify (stride 2,
-// channel counts off the fast path): the caller then runs y3_bn_bwd_stats on the finished gradient instead.
-extern "C" int y3_conv2d_dgrad_bn_tiles(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc) {
-    return y3_conv2d_dgrad_bn_tiles_x(ddst, ksize, stride, dsrc, 0u);
-}
-extern "C" int y3_conv2d_dgrad_bn_tiles_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags) {
-    if (!ddst || !dsrc || (ksize != 1 && ksize != 3)) return 0;
-    if (stride == 2) {      // the merged launch of the four parity classes: rows of all classes, or 0 if it would not be taken
-        if (ksize != 3 || ddst->h != (dsrc->h + 1) / 2 || ddst->w != (dsrc->w + 1) / 2 || ddst->n != dsrc->n) return 0;
-        int rows = 0;
-        const unsigned x3f = dgrad_x3(flags, ddst, ksize, stride, dsrc) ? Y3_CONV_X3 : 0u;
-        if (conv2d_dgrad_impl(ddst, nullptr, ksize, 2, dsrc, x3f, nullptr, nullptr, nullptr, 0, nullptr, &rows) != Y3_OK) return 0;
-        return rows;
-    }
-    if (stride != 1) return 0;
-    if (ddst->h != dsrc->h || ddst->w != dsrc->w || ddst->n != dsrc->n) return 0;
-    const int taps = ksize * ksize, K = taps * ddst->c, M = dsrc->n * dsrc->h * dsrc->w;
-    const bool x3 = dgrad_x3(flags, ddst, ksize, stride, dsrc);
-    if (!x3 && !fast_shape_ok(ddst->c, dsrc->c, K, taps)) return 0;
-    const ConvPlan pl = plan_conv(M, dsrc->c, K, true, x3, taps);
-    if (pl.t.bk != 16) return 0;
-    // the launch itself must be accepted too (2 GiB buffer limits, tap grid): dry run of the argument builder
-    int ok = 0;
-    if (conv2d_dgrad_impl(ddst, nullptr, ksize, 1, dsrc, x3 ? Y3_CONV_X3 : 0u, nullptr, nullptr, nullptr, 0, nullptr, &ok) != Y3_OK || !ok) return 0;
-    return y3_cdiv(M, pl.t.bm);
-}
-
-extern "C" int y3_conv2d_dgrad_bn(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags,
-                                  const y3_tensor* bn_a, float* bn_partials, void* workspace, size_t workspace_bytes, y3_stream_t stream) {
-    if (int e = check_tensor(bn_a, "conv2d_dgrad_bn bn_a")) return e;
-    Y3_CHECK_ARG(bn_partials, "conv2d_dgrad_bn: null partials");
-    Y3_CHECK_ARG(dsrc && bn_a->n == dsrc->n && bn_a->h == dsrc->h && bn_a->w == dsrc->w && bn_a->c == dsrc->c, "conv2d_dgrad_bn: bn_a must have dsrc's geometry");
-    Y3_CHECK_ARG((long long)bn_a->n * bn_a->h * bn_a->w * bn_a->ld * 4 < 0x7fffffffLL, "conv2d_dgrad_bn: bn_a of 2 GiB or more");
-    Y3_CHECK_ARG(y3_conv2d_dgrad_bn_tiles_x(ddst, ksize, stride, dsrc, flags) > 0, "conv2d_dgrad_bn: shape does not qualify (y3_conv2d_dgrad_bn_tiles() == 0)");
-    return conv2d_dgrad_impl(ddst, wt_t, ksize, stride, dsrc, flags, bn_a, bn_partials, workspace, workspace_bytes, stream);
-}
-
-static int conv2d_dgrad_impl(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags,
-                             const y3_tensor* bn_a, float* bn_partials, void* workspace, size_t workspace_bytes, y3_stream_t stream,
-                             int* dry_rows, size_t* dry_ws) {
-    if (!dry_rows) {      // dry run (y3_conv2d_dgrad_bn_tiles, stride 2): geometry only, pointers may be null
-        if (int e = check_tensor(ddst, "conv2d_dgrad ddst")) return e;
-        if (int e = check_tensor(dsrc, "conv2d_dgrad dsrc")) return e;
-        Y3_CHECK_ARG(wt_t, "conv2d_dgrad: null weights");
-    }
+struct DgradDesc {
+    ConvArgs cls[4];     // one per launch or parity class, longest K first; src / wt / dst / bn_* stay null until issue_dgrad
+    int ncls;
+    DgradHow how;
+    GemmDesc g[4];       // DGRAD_SINGLE (g[0]), DGRAD_BY_CLASS: the plan of each launch
+    MultiPlan multi;     // DGRAD_MERGED_*
+    int rows;            // rows of partial statistics y3_conv2d_dgrad_bn writes (row tiles over all classes); 0: it does not take the shape
+    size_t ws_bytes;     // workspace the launches use at most
+};
+// Y3_CONV_X3 in `flags` counts where dgrad_x3 takes the shape (the entry points refuse the others before they come here).
+static int describe_dgrad(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags, DgradDesc* d) {
     Y3_CHECK_ARG(ksize == 1 || ksize == 3, "conv2d_dgrad: ksize %d unsupported", ksize);
     Y3_CHECK_ARG(stride == 1 || stride == 2, "conv2d_dgrad: stride %d unsupported", stride);
     const int OH = (dsrc->h + stride - 1) / stride, OW = (dsrc->w + stride - 1) / stride;
     Y3_CHECK_ARG(ddst->n == dsrc->n && ddst->h == OH && ddst->w == OW, "conv2d_dgrad: geometry mismatch");
-    Y3_CHECK_ARG((flags & ~(Y3_EPI_ACCUM | Y3_CONV_X3)) == 0, "conv2d_dgrad: only Y3_EPI_ACCUM and Y3_CONV_X3 allowed");
-    Y3_CHECK_ARG(!(flags & Y3_CONV_X3) || dgrad_x3(flags, ddst, ksize, stride, dsrc), "conv2d_dgrad: Y3_CONV_X3 does not take this shape (ask y3_conv2d_dgrad_x3_ok())");
     const int pbh = y3_same_pad_before(dsrc->h, ksize, stride), pbw = y3_same_pad_before(dsrc->w, ksize, stride);
     // the contraction runs over (tap, cout): channels of ddst
     ConvArgs base = {};
-    base.src = ddst->ptr;
-    base.wt = wt_t;
-    base.dst = dsrc->ptr;
     base.H = ddst->h;
     base.W = ddst->w;
     base.C = ddst->c;
@@ -1761,14 +1706,19 @@ static int conv2d_dgrad_impl(const y3_tensor* ddst, const float* wt_t, int ksize
     base.dst_ld = dsrc->ld;
     base.Nout = dsrc->c;
     base.flags = flags & ~Y3_CONV_X3;
-    base.x3 = (flags & Y3_CONV_X3) ? 1 : 0;
+    base.x3 = dgrad_x3(flags, ddst, ksize, stride, dsrc) ? 1 : 0;
     base.DH = dsrc->h;
     base.DW = dsrc->w;
     base.sh = base.sw = 1;
     base.src_n = ddst->n;
     base.wt_rows = ksize * ksize * ddst->c;
+    d->ncls = 0;
+    d->rows = 0;
+    d->ws_bytes = 0;
     if (stride == 1) {
-        ConvArgs p = base;
+        ConvArgs& p = d->cls[0];
+        p = base;
+        d->ncls = 1;
         const int taps = ksize * ksize;
         if (int e = set_channels(ddst->c, taps, &p.logC, &p.cmask)) return e;
         for (int kh = 0; kh < ksize; ++kh)
@@ -1784,22 +1734,17 @@ static int conv2d_dgrad_impl(const y3_tensor* ddst, const float* wt_t, int ksize
         p.dense_dst = 1;
         p.K = taps * ddst->c;
         p.M = dsrc->n * p.OH * p.OW;
-        if (dry_rows) {      // would launch_igemm take the fast kernel for this shape?  (pointers are not dereferenced)
-            FastArgs f;
-            *dry_rows = ((p.x3 || fast_shape_ok(p.C, p.Nout, p.K, taps)) && make_fast(p, taps, 16, &f)) ? 1 : 0;
-            return Y3_OK;
-        }
-        if (bn_a) {
-            p.bn_a = bn_a->ptr;
-            p.bn_a_ld = bn_a->ld;
-            p.bn_part = bn_partials;
-        }
-        return launch_igemm(p, workspace, workspace_bytes, (hipStream_t)stream);
+        d->how = DGRAD_SINGLE;
+        d->g[0] = describe_gemm(p);
+        d->ws_bytes = d->g[0].pl.ws_bytes;
+        // the statistics live in the dense fast kernels: the launch itself must take them too (2 GiB buffer limits, tap grid)
+        FastGeom fg;
+        if (d->g[0].fast && d->g[0].pl.t.bk == 16 && fast_geom(p, taps, 16, &fg)) d->rows = d->g[0].pl.stats_tiles;
+        return Y3_OK;
     }
     // stride 2: forward out o reads in[2o + k - pad]; input pixel i = 2q + par receives from the taps with
-    // (par + pad - k) even, at o = q + (par + pad - k)/2.  One launch per (row parity, col parity).
-    ConvArgs cls[4];
-    int ncls = 0;
+    // (par + pad - k) even, at o = q + (par + pad - k)/2.  One class per (row parity, col parity).
+    ConvArgs* cls = d->cls;
     for (int ph = 0; ph < 2; ++ph)
         for (int pw = 0; pw < 2; ++pw) {
             ConvArgs p = base;
@@ -1823,49 +1768,112 @@ static int conv2d_dgrad_impl(const y3_tensor* ddst, const float* wt_t, int ksize
             p.dow = pw;
             p.dense_dst = 0;
             p.M = dsrc->n * p.OH * p.OW;
-            if (nt == 0) {
-                // no tap reaches this parity class (1x1 stride 2): gradient is zero there
-                Y3_CHECK_ARG(false, "conv2d_dgrad: 1x1 stride-2 not supported");
-            }
-            if (int e = set_channels(ddst->c, nt == 1 ? 1 : 9, &p.logC, &p.cmask)) return e;
-            if (nt == 1) {  // single tap: plain k = c (no power-of-two requirement)
-                p.logC = 31;
-                p.cmask = 0x7fffffff;
-            }
+            // no tap reaches this parity class (1x1 stride 2): gradient is zero there
+            Y3_CHECK_ARG(nt > 0, "conv2d_dgrad: 1x1 stride-2 not supported");
+            if (int e = set_channels(ddst->c, nt == 1 ? 1 : 9, &p.logC, &p.cmask)) return e;   // single tap: plain k = c (no power-of-two requirement)
             p.K = nt * ddst->c;
-            if (bn_a) {
-                p.bn_a = bn_a->ptr;
-                p.bn_a_ld = bn_a->ld;
-                p.bn_part = bn_partials;
-            }
-            cls[ncls++] = p;
+            cls[d->ncls++] = p;
         }
     // longest contraction first, so that the 4-tap workgroups of a merged launch start before the 1-tap ones
-    for (int i = 1; i < ncls; ++i)
+    for (int i = 1; i < d->ncls; ++i)
         for (int j = i; j > 0 && cls[j].K > cls[j - 1].K; --j) {
             const ConvArgs tmp = cls[j];
             cls[j] = cls[j - 1];
             cls[j - 1] = tmp;
         }
-    if (dry_rows) {
-        *dry_rows = 0;
-        int rows = 0;
-        if (launch_dgrad_multi(cls, ncls, (hipStream_t)stream, &rows, dry_ws)) *dry_rows = rows;
+    if (plan_dgrad_multi(cls, d->ncls, &d->multi)) {
+        d->how = base.x3 ? DGRAD_MERGED_X3 : DGRAD_MERGED_F32;
+        d->rows = d->multi.rows;
+        d->ws_bytes = d->multi.ws;
         return Y3_OK;
     }
-    if (launch_dgrad_multi(cls, ncls, (hipStream_t)stream, nullptr, nullptr, workspace, workspace_bytes)) {
-        Y3_CHECK_LAUNCH("conv_igemm_fast_multi");
-        return Y3_OK;
+    d->how = DGRAD_BY_CLASS;
+    for (int c = 0; c < d->ncls; ++c) {
+        d->g[c] = describe_gemm(cls[c]);
+        if (d->g[c].pl.ws_bytes > d->ws_bytes) d->ws_bytes = d->g[c].pl.ws_bytes;
     }
-    Y3_CHECK_ARG(!bn_a, "conv2d_dgrad_bn: the merged stride-2 launch is not available for this shape");
-    for (int c = 0; c < ncls; ++c)
-        if (int e = launch_igemm(cls[c], workspace, workspace_bytes, (hipStream_t)stream)) return e;
     return Y3_OK;
+}
+// Fill the pointers into a description and launch it
+static int issue_dgrad(DgradDesc& d, const y3_tensor* ddst, const float* wt_t, const y3_tensor* dsrc, const y3_tensor* bn_a, float* bn_partials,
+                       void* workspace, size_t workspace_bytes, hipStream_t st) {
+    for (int c = 0; c < d.ncls; ++c) {
+        ConvArgs& p = d.cls[c];
+        p.src = ddst->ptr;
+        p.wt = wt_t;
+        p.dst = dsrc->ptr;
+        if (bn_a) {
+            p.bn_a = bn_a->ptr;
+            p.bn_a_ld = bn_a->ld;
+            p.bn_part = bn_partials;
+        }
+    }
+    if (d.how == DGRAD_MERGED_F32 || d.how == DGRAD_MERGED_X3) return launch_dgrad_multi(d.cls, d.ncls, d.multi, workspace, workspace_bytes, st);
+    for (int c = 0; c < d.ncls; ++c)      // DGRAD_SINGLE: one launch; DGRAD_BY_CLASS: one per class
+        if (int e = launch_igemm(d.cls[c], d.g[c], workspace, workspace_bytes, st)) return e;
+    return Y3_OK;
+}
+
+extern "C" size_t y3_conv2d_dgrad_workspace(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc) {
+    return y3_conv2d_dgrad_workspace_x(ddst, ksize, stride, dsrc, 0u);
+}
+extern "C" size_t y3_conv2d_dgrad_workspace_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags) {
+    if (stride == 1) return describe_gemm(dsrc->n * dsrc->h * dsrc->w, ddst->c, ksize * ksize, dsrc->c, flags).pl.ws_bytes;
+    DgradDesc d;
+    if (describe_dgrad(ddst, ksize, stride, dsrc, flags, &d) == Y3_OK && d.how == DGRAD_MERGED_X3) return d.ws_bytes;   // slabs of all classes behind one ticket header
+    // Every other stride-2 launch: a deliberately loose bound, kept as it has always been answered -- every parity class (1, 2, 2
+    // and 4 taps of a 3x3 kernel) planned as an f32 launch of its own with the M of the largest class, although the merged f32
+    // launch needs no workspace at all (d.ws_bytes is the exact figure).
+    size_t best = 0;
+    for (int nt = 1; nt <= 4; nt *= 2) {
+        const size_t b = describe_gemm(dsrc->n * ((dsrc->h + 1) / 2) * ((dsrc->w + 1) / 2), ddst->c, nt, dsrc->c, 0u).pl.ws_bytes;
+        if (b > best) best = b;
+    }
+    return best;
+}
+
+// Row tiles of the partial statistics y3_conv2d_dgrad_bn writes for this shape, 0 if the shape does not qualify (channel counts
+// off the fast path; stride 2: no merged launch): the caller then runs y3_bn_bwd_stats on the finished gradient instead.
+extern "C" int y3_conv2d_dgrad_bn_tiles(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc) {
+    return y3_conv2d_dgrad_bn_tiles_x(ddst, ksize, stride, dsrc, 0u);
+}
+extern "C" int y3_conv2d_dgrad_bn_tiles_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags) {
+    DgradDesc d;
+    return ddst && dsrc && describe_dgrad(ddst, ksize, stride, dsrc, flags, &d) == Y3_OK ? d.rows : 0;
+}
+
+// What both entry points check of their arguments before the launch is described
+static int check_dgrad_args(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags) {
+    if (int e = check_tensor(ddst, "conv2d_dgrad ddst")) return e;
+    if (int e = check_tensor(dsrc, "conv2d_dgrad dsrc")) return e;
+    Y3_CHECK_ARG(wt_t, "conv2d_dgrad: null weights");
+    Y3_CHECK_ARG((flags & ~(Y3_EPI_ACCUM | Y3_CONV_X3)) == 0, "conv2d_dgrad: only Y3_EPI_ACCUM and Y3_CONV_X3 allowed");
+    Y3_CHECK_ARG(!(flags & Y3_CONV_X3) || dgrad_x3(flags, ddst, ksize, stride, dsrc), "conv2d_dgrad: Y3_CONV_X3 does not take this shape (ask y3_conv2d_dgrad_x3_ok())");
+    return Y3_OK;
+}
+extern "C" int y3_conv2d_dgrad(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags,
+                               void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    if (int e = check_dgrad_args(ddst, wt_t, ksize, stride, dsrc, flags)) return e;
+    DgradDesc d;
+    if (int e = describe_dgrad(ddst, ksize, stride, dsrc, flags, &d)) return e;
+    return issue_dgrad(d, ddst, wt_t, dsrc, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+extern "C" int y3_conv2d_dgrad_bn(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags,
+                                  const y3_tensor* bn_a, float* bn_partials, void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    if (int e = check_tensor(bn_a, "conv2d_dgrad_bn bn_a")) return e;
+    Y3_CHECK_ARG(bn_partials, "conv2d_dgrad_bn: null partials");
+    Y3_CHECK_ARG(dsrc && bn_a->n == dsrc->n && bn_a->h == dsrc->h && bn_a->w == dsrc->w && bn_a->c == dsrc->c, "conv2d_dgrad_bn: bn_a must have dsrc's geometry");
+    Y3_CHECK_ARG((long long)bn_a->n * bn_a->h * bn_a->w * bn_a->ld * 4 < 0x7fffffffLL, "conv2d_dgrad_bn: bn_a of 2 GiB or more");
+    DgradDesc d;
+    Y3_CHECK_ARG(ddst && describe_dgrad(ddst, ksize, stride, dsrc, flags, &d) == Y3_OK && d.rows > 0, "conv2d_dgrad_bn: shape does not qualify (y3_conv2d_dgrad_bn_tiles() == 0)");
+    if (int e = check_dgrad_args(ddst, wt_t, ksize, stride, dsrc, flags)) return e;
+    return issue_dgrad(d, ddst, wt_t, dsrc, bn_a, bn_partials, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- wgrad ---------------------------------------------------------------
 struct WgradPlan {
     int bkr, bn, splits, chunk, tiles;
+    bool x3;      // Y3_CONV_X3 was asked for and conv_wgrad_x3_kernel takes the shape
 };
 static WgradPlan plan_wgrad(int K, int Nout, int M, int taps) {
     WgradPlan w;
@@ -1925,6 +1933,13 @@ static WgradPlan plan_wgrad_x3(int K, int Nout, int M) {
     w.chunk = chunk;
     return w;
 }
+// The plan of a kernel gradient from its shape alone: the queries read it, y3_conv2d_wgrad_x issues it
+static WgradPlan describe_wgrad(int M, int cin, int taps, int Nout, unsigned flags) {
+    const bool x3 = (flags & Y3_CONV_X3) && wgrad_x3_shape_ok(taps * cin, Nout, taps, cin);
+    WgradPlan w = x3 ? plan_wgrad_x3(taps * cin, Nout, M) : plan_wgrad(taps * cin, Nout, M, taps);
+    w.x3 = x3;
+    return w;
+}
 
 // splits <= Y3_WG_FANIN: the reduction runs inside the kernel (one level: tickets + fragment-order slabs behind the header);
 // more splits: natural-layout slabs [split][K][Nout] + slab_reduce_kernel (measured: a multi-level in-kernel tree costs more
@@ -1941,15 +1956,13 @@ static size_t wgrad_ws_bytes(const WgradPlan& w, int K, int Nout) {
 // Diagnostics (include/yolo3hip.h): the plan behind y3_conv2d_wgrad
 extern "C" size_t y3_conv2d_wgrad_plan(int m, int cin, int ksize, int cout, int* out8) { return y3_conv2d_wgrad_plan_x(m, cin, ksize, cout, 0u, out8); }
 extern "C" size_t y3_conv2d_wgrad_plan_x(int m, int cin, int ksize, int cout, unsigned flags, int* out8) {
-    const int taps = ksize * ksize, K = taps * cin;
-    const bool x3 = (flags & Y3_CONV_X3) && wgrad_x3_shape_ok(K, cout, taps, cin);
-    const WgradPlan w = x3 ? plan_wgrad_x3(K, cout, m) : plan_wgrad(K, cout, m, taps);
+    const WgradPlan w = describe_wgrad(m, cin, ksize * ksize, cout, flags);
     if (out8) {
         const int v[8] = {w.bkr, w.bn, w.splits, w.chunk, w.tiles, wgrad_in_kernel(w) ? 1 : 0,
                           (w.splits >= 32 ? y3_cdiv(w.splits, 8) * 8 : w.splits) * w.tiles, Y3_WG_TABLE};
         for (int i = 0; i < 8; ++i) out8[i] = v[i];
     }
-    return wgrad_ws_bytes(w, K, cout);
+    return wgrad_ws_bytes(w, ksize * ksize * cin, cout);
 }
 
 extern "C" int y3_conv2d_wgrad_x3_ok(int m, int cin, int ksize, int cout) {
@@ -1957,11 +1970,8 @@ extern "C" int y3_conv2d_wgrad_x3_ok(int m, int cin, int ksize, int cout) {
 }
 extern "C" size_t y3_conv2d_wgrad_workspace_x(const y3_tensor* src, const y3_tensor* ddst, int ksize, int stride, unsigned flags) {
     (void)stride;
-    const int K = ksize * ksize * src->c;
-    const int M = ddst->n * ddst->h * ddst->w;
-    const bool x3 = (flags & Y3_CONV_X3) && wgrad_x3_shape_ok(K, ddst->c, ksize * ksize, src->c);
-    const WgradPlan w = x3 ? plan_wgrad_x3(K, ddst->c, M) : plan_wgrad(K, ddst->c, M, ksize * ksize);
-    return wgrad_ws_bytes(w, K, ddst->c);
+    const WgradPlan w = describe_wgrad(ddst->n * ddst->h * ddst->w, src->c, ksize * ksize, ddst->c, flags);
+    return wgrad_ws_bytes(w, ksize * ksize * src->c, ddst->c);
 }
 extern "C" size_t y3_conv2d_wgrad_workspace(const y3_tensor* src, const y3_tensor* ddst, int ksize, int stride) {
     return y3_conv2d_wgrad_workspace_x(src, ddst, ksize, stride, 0u);
@@ -2011,9 +2021,8 @@ extern "C" int y3_conv2d_wgrad_x(const y3_tensor* src, const y3_tensor* ddst, in
         p.dd_bytes = (unsigned)db;
     }
     Y3_CHECK_ARG((flags & ~Y3_CONV_X3) == 0, "conv2d_wgrad: only Y3_CONV_X3 allowed in flags");
-    const bool x3 = (flags & Y3_CONV_X3) != 0;
-    Y3_CHECK_ARG(!x3 || wgrad_x3_shape_ok(p.K, p.Nout, taps, src->c), "conv2d_wgrad: Y3_CONV_X3 does not take this shape (ask y3_conv2d_wgrad_x3_ok())");
-    const WgradPlan w = x3 ? plan_wgrad_x3(p.K, p.Nout, p.M) : plan_wgrad(p.K, p.Nout, p.M, taps);
+    const WgradPlan w = describe_wgrad(p.M, src->c, taps, p.Nout, flags);
+    Y3_CHECK_ARG(!(flags & Y3_CONV_X3) || w.x3, "conv2d_wgrad: Y3_CONV_X3 does not take this shape (ask y3_conv2d_wgrad_x3_ok())");
     p.chunk = w.chunk;
     p.nbn = y3_cdiv(p.Nout, w.bn);
     p.ohw = OH * OW;
@@ -2042,7 +2051,7 @@ extern "C" int y3_conv2d_wgrad_x(const y3_tensor* src, const y3_tensor* ddst, in
     // per CU (the occupancy their register budget aims at): step 18.21 -> 18.03 ms (A/B, two rounds; padding
     // the 32 KB 64x64 variant as well: no further change).
     constexpr int pad40 = 8192;
-    if (x3) {
+    if (w.x3) {
         if (!y3_wgrad_x3_launch(p, w.bkr, w.bn, grid.x, st)) {
             y3_set_error("conv2d_wgrad: no x3 kernel for tile %dx%d", w.bkr, w.bn);
             return Y3_EINVAL;
