@@ -155,6 +155,19 @@ int y3_conv2d_dgrad_bn(const y3_tensor* ddst, const float* wt_t, int ksize, int 
                        void* workspace, size_t workspace_bytes, y3_stream_t stream);
 int y3_conv2d_dgrad_bn_tiles(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc);
 int y3_conv2d_dgrad_bn_tiles_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags);
+/* Diagnostics (host only, no launch; the tensors' geometry is read, their data pointers are not): how y3_conv2d_dgrad /
+ * y3_conv2d_dgrad_bn send this data gradient out.  out51 = {how, classes, rows, then 12 numbers per class}:
+ *   how      0 one launch (stride 1), 1 the parity classes merged into one f32 launch, 2 merged into one x3 launch, 3 one launch per
+ *            parity class (stride 2 off the fast path); -1 (and 0 returned) if the geometry is refused;
+ *   classes  1 (stride 1), else the parity classes that have pixels (up to 4);
+ *   rows     rows of partial statistics y3_conv2d_dgrad_bn writes (= y3_conv2d_dgrad_bn_tiles_x);
+ *   per class, longest contraction first as the launch orders them, at out51[3 + 12 * c]:
+ *            {taps, m, bm, bn, tiles, f, s0, s1, chunk0, chunk1, nk, fast}: `taps` kernel taps reach the class, m its pixels, tiles of
+ *            bm x bn; tiles [0, f) are cut into s0 K slices of chunk0 K steps, tiles [f, tiles) into s1 of chunk1, nk K steps in all
+ *            (a merged launch gives one slice count to all tiles of a class: f = tiles, s1 = s0); fast as in y3_conv2d_plan_x.
+ * Stride 1: class 0 carries what y3_conv2d_plan_x(m, Cout, ksize, Cin) answers.  Returns the workspace bytes the launches use at most
+ * -- exact: a merged f32 launch needs none, where y3_conv2d_dgrad_workspace_x keeps answering a loose bound. */
+size_t y3_conv2d_dgrad_plan_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags, int* out51);
 
 /*
  * Gradient w.r.t. the kernel:  dw[tap][ci][co] = sum_pixels src*ddst.

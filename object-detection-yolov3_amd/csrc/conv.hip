@@ -1842,6 +1842,30 @@ extern "C" int y3_conv2d_dgrad_bn_tiles_x(const y3_tensor* ddst, int ksize, int 
     return ddst && dsrc && describe_dgrad(ddst, ksize, stride, dsrc, flags, &d) == Y3_OK ? d.rows : 0;
 }
 
+// Diagnostics (include/yolo3hip.h): how y3_conv2d_dgrad / y3_conv2d_dgrad_bn send this data gradient out, class by class
+extern "C" size_t y3_conv2d_dgrad_plan_x(const y3_tensor* ddst, int ksize, int stride, const y3_tensor* dsrc, unsigned flags, int* out51) {
+    DgradDesc d;
+    if (!ddst || !dsrc || describe_dgrad(ddst, ksize, stride, dsrc, flags, &d) != Y3_OK) {
+        if (out51) out51[0] = -1;
+        return 0;
+    }
+    if (out51) {
+        for (int i = 0; i < 51; ++i) out51[i] = 0;
+        out51[0] = (int)d.how;
+        out51[1] = d.ncls;
+        out51[2] = d.rows;
+        const bool merged = d.how == DGRAD_MERGED_F32 || d.how == DGRAD_MERGED_X3;
+        for (int c = 0; c < d.ncls; ++c) {
+            const ConvPlan& pl = merged ? d.multi.c[c] : d.g[c].pl;
+            const int fast = merged ? 1 : ((d.g[c].fast ? 1 : 0) | (pl.short_last ? 2 : 0));
+            const int v[12] = {d.cls[c].K / d.cls[c].C, d.cls[c].M, pl.t.bm, pl.t.bn, pl.tiles, pl.f, pl.s0, pl.s1, pl.chunk0, pl.chunk1,
+                               d.cls[c].K / pl.t.bk, fast};
+            for (int i = 0; i < 12; ++i) out51[3 + 12 * c + i] = v[i];
+        }
+    }
+    return d.ws_bytes;
+}
+
 // What both entry points check of their arguments before the launch is described
 static int check_dgrad_args(const y3_tensor* ddst, const float* wt_t, int ksize, int stride, const y3_tensor* dsrc, unsigned flags) {
     if (int e = check_tensor(ddst, "conv2d_dgrad ddst")) return e;

@@ -121,6 +121,7 @@ SIGNATURES = {
     'y3_conv2d_wgrad_plan': (sz, [i32, i32, i32, i32, C.POINTER(C.c_int)]),
     'y3_conv2d_plan_x': (sz, [i32, i32, i32, i32, u32, C.POINTER(C.c_int)]),
     'y3_conv2d_wgrad_plan_x': (sz, [i32, i32, i32, i32, u32, C.POINTER(C.c_int)]),
+    'y3_conv2d_dgrad_plan_x': (sz, [TP, i32, i32, TP, u32, C.POINTER(C.c_int)]),
     'y3_comm_info': (i32, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'y3_comm_destroy': (i32, [vp]),
     'y3_zscore': (i32, [fp, fp, i32, sz, vp, vp]),
