@@ -291,9 +291,10 @@ int y3_conv2d_fwd_bf16_ws(const y3_tensor* src, const void* wt_t_bf16, const flo
                           const y3_tensor* dst, int dst_is_f32, unsigned flags, float alpha,
                           const float* scale, const float* shift, const y3_tensor* resid,
                           void* workspace, size_t workspace_bytes, y3_stream_t stream);
-/* Which kernel y3_conv2d_fwd_bf16_ws would run for exactly these arguments (without the stream), on which tile and grid: a dry
- * run of the entry point's own decision code, host only -- nothing is launched and no pointer is dereferenced (of src / dst /
- * resid -> ptr, the weights, the bias and the workspace only alignment and null-ness are read; scale / shift: null-ness).
+/* Which kernel y3_conv2d_fwd_bf16_ws would run for exactly these arguments (without the stream), on which tile and grid: the
+ * entry point's own description of the launch (the fields it dispatches on), host only -- nothing is launched and no pointer
+ * is dereferenced (of src / dst / resid -> ptr, the weights, the bias and the workspace only alignment and null-ness are read;
+ * scale / shift: null-ness).
  * Returns the workspace bytes the launch would use (0: no split-K) and fills out12 with
  *   {route, bm, bn, bk, grid, threads, splits, chunk, vec_ok, patch stride, patch residual, nk}
  * route: one of Y3_BF16_ROUTE_*; bm x bn the output tile (patch kernels: the 32 x 8 / 4 / 2 output pixels of one row group by

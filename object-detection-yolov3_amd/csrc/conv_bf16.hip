@@ -1376,34 +1376,6 @@ static int check_bf16_tensor(const y3_tensor* t, const char* name) {
     return 0;
 }
 
-// Dry run of conv2d_fwd_bf16_impl (y3_conv2d_fwd_bf16_plan): where `dry` is given, the decision is written to dry->out in place of
-// every launch -- {route, bm, bn, bk, grid, threads, splits, chunk, vec_ok, patch stride, patch residual, K steps of bk} -- and
-// nothing is launched or dereferenced.
-struct Bf16Dry {
-    int* out;
-    size_t ws;      // workspace bytes the launch would use
-};
-static void bf16_dry_report(Bf16Dry* dry, const Bf16Args& p, int route, int bm, int bn, int bk, long long grid, int threads, int splits, int chunk,
-                            int patch_stride, int patch_resid, size_t ws) {
-    const int v[12] = {route, bm, bn, bk, (int)grid, threads, splits, chunk, p.vec_ok, patch_stride, patch_resid, p.K / bk};
-    for (int i = 0; i < 12; ++i) dry->out[i] = v[i];
-    dry->ws = ws;
-}
-
-template <int BM, int BN, int WM, int WN, int BK = 32>
-static void launch_bf16(const Bf16Args& args, int grid, hipStream_t st, Bf16Dry* dry) {
-    if (dry) {
-        bf16_dry_report(dry, args, Y3_BF16_ROUTE_RING, BM, BN, BK, grid, 64 * WM * WN, 1, args.K / BK, 0, 0, 0);
-        return;
-    }
-    Bf16Args p = args;
-    p.ohw = p.OH * p.OW;
-    p.dv_nbn = y3_make_div(p.nbn);
-    p.dv_ohw = y3_make_div(p.ohw);
-    p.dv_ow = y3_make_div(p.OW);
-    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, BK>), dim3(grid), dim3(64 * WM * WN), 0, st, p);
-}
-
 // Split-K plan of the 64 x 64-tile path (the small-M layers: 13x13 / 26x26 grids at batch 8, 19x19 at 8 x 608^2): without it a
 // workgroup walks the whole K = 9 Cin (144 steps of 32 at Cin = 512) on its own while most of the chip's wave slots idle.
 #define Y3_BF16_SK_HEADER (256 * 1024)     // tickets: the same 256 KiB header as the fp32 entries (yolo3hip.h workspace contract), so a shared workspace has ONE layout
@@ -1437,37 +1409,84 @@ extern "C" size_t y3_conv2d_fwd_bf16_workspace(int m, int cin, int ksize, int co
     return plan_bf16_split(m, cout, ksize * ksize * cin).ws_bytes;      // (only consulted when the 64 x 64-tile path is taken)
 }
 
-static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
-                                int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                void* workspace, size_t workspace_bytes, y3_stream_t stream, Bf16Dry* dry = nullptr);
+// One bf16 conv launch, described once: describe_bf16 checks the entry point's arguments, decides the route and fills the kernel's
+// arguments, issue_bf16 launches exactly that, y3_conv2d_fwd_bf16_plan reports it.
+struct Bf16Desc {
+    int route;                        // Y3_BF16_ROUTE_*
+    int bm, bn, bk;                   // output tile (patch kernels: the output pixels of one row group by Cout) and K step
+    unsigned grid;                    // workgroups
+    int threads;
+    int splits, chunk;                // K slices per tile and K steps per slice (splits == 1: chunk = K / bk, whole)
+    int patch_stride, patch_resid;    // the template instantiation of a patch kernel, 0 / 0 elsewhere
+    size_t ws;                        // workspace bytes the launch uses
+    Bf16Args a;                       // ring / ping-pong routes (C, K, vec_ok ...: every route)
+    PatchArgs q;                      // patch routes
+};
 
-extern "C" int y3_conv2d_fwd_bf16(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
-                                  int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                  y3_stream_t stream) {
-    return conv2d_fwd_bf16_impl(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, nullptr, 0, stream);
-}
-extern "C" int y3_conv2d_fwd_bf16_ws(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
-                                     int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                     void* workspace, size_t workspace_bytes, y3_stream_t stream) {
-    return conv2d_fwd_bf16_impl(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, workspace, workspace_bytes, stream);
-}
-// the decision of the launch above, by running its own code dry (host only; a refused launch: route 0, y3_last_error() says why)
-extern "C" size_t y3_conv2d_fwd_bf16_plan(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
-                                          int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                          void* workspace, size_t workspace_bytes, int* out12) {
-    if (!out12) return 0;
-    for (int i = 0; i < 12; ++i) out12[i] = 0;
-    Bf16Dry dry = {out12, 0};
-    if (conv2d_fwd_bf16_impl(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, workspace, workspace_bytes, nullptr, &dry) != Y3_OK) {
-        out12[0] = 0;
-        return 0;
-    }
-    return dry.ws;
+// a ring / ping-pong launch of whole-K bm x bn tiles
+static void set_tile(Bf16Desc* d, int route, int bm, int bn, int bk, int threads) {
+    d->route = route;
+    d->bm = bm;
+    d->bn = bn;
+    d->bk = bk;
+    d->threads = threads;
+    d->a.nbn = y3_cdiv(d->a.Nout, bn);
+    d->grid = y3_cdiv(d->a.M, bm) * d->a.nbn;
+    d->splits = 1;
+    d->chunk = d->a.K / bk;
 }
 
-static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
-                                int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
-                                void* workspace, size_t workspace_bytes, y3_stream_t stream, Bf16Dry* dry) {
+// a patch launch (d->a is filled): row groups of 32 x `rows` output pixels, a persistent grid of at most `cap` workgroups, each a
+// contiguous run of groups
+static int set_patch(Bf16Desc* d, int route, const y3_tensor* src, int rows, int cap, int threads) {
+    const Bf16Args& p = d->a;
+    PatchArgs& q = d->q;
+    q.src = (const u16*)src->ptr;
+    q.wt = p.wt;
+    q.dst = (u16*)p.dst;
+    q.bias = p.bias;
+    q.scale = p.scale;
+    q.shift = p.shift;
+    q.resid = p.resid;
+    q.src_bytes = (unsigned)((long long)src->n * src->h * src->w * src->ld * 2);
+    q.dst_bytes = p.dst_bytes;
+    q.resid_bytes = p.resid_bytes;      // (0 without a residual)
+    q.H = p.H;
+    q.W = p.W;
+    q.OH = p.OH;
+    q.OW = p.OW;
+    q.src_ld = p.src_ld;
+    q.dst_ld = p.dst_ld;
+    q.resid_ld = p.resid_ld;
+    q.pbh = -p.tap_dh[0];
+    q.pbw = -p.tap_dw[0];
+    q.xs = y3_cdiv(p.OW, 32);
+    q.rg = y3_cdiv(p.OH, rows);
+    const long long groups = (long long)src->n * q.xs * q.rg;
+    Y3_CHECK_ARG(groups < 0x7fffffffLL, "conv2d_fwd_bf16: too many row groups");
+    q.groups = (int)groups;
+    q.dv_rg = y3_make_div(q.rg);
+    q.dv_xs = y3_make_div(q.xs);
+    q.flags = p.flags;
+    q.alpha = p.alpha;
+    d->route = route;
+    d->bm = 32 * rows;
+    d->bn = p.Nout;
+    d->bk = p.C;                        // (one tap of one pixel per K step)
+    d->grid = (unsigned)(groups < cap ? groups : cap);
+    d->threads = threads;
+    d->splits = 1;
+    d->chunk = p.K / d->bk;
+    d->patch_stride = p.sh;
+    d->patch_resid = route == Y3_BF16_ROUTE_C32 && q.resid ? 1 : 0;      // (a run-time branch of the 64 -> 128 kernel)
+    return Y3_OK;
+}
+
+// Host only: launches nothing and dereferences no pointer of the caller's (of src / dst / resid -> ptr, the weights, the bias and
+// the workspace only alignment and null-ness are read; scale / shift: null-ness).
+static int describe_bf16(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
+                         int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
+                         void* workspace, size_t workspace_bytes, Bf16Desc* d) {
     if (int e = check_bf16_tensor(src, "conv2d_fwd_bf16 src")) return e;
     if (int e = check_bf16_tensor(dst, "conv2d_fwd_bf16 dst")) return e;
     Y3_CHECK_ARG(wt_t_bf16, "conv2d_fwd_bf16: null weights");
@@ -1478,7 +1497,8 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
     const int OH = (src->h + stride - 1) / stride, OW = (src->w + stride - 1) / stride;
     Y3_CHECK_ARG(dst->n == src->n && dst->h == OH && dst->w == OW, "conv2d_fwd_bf16: dst geometry");
     Y3_CHECK_ARG((scale == nullptr) == (shift == nullptr), "conv2d_fwd_bf16: scale/shift must both be given");
-    Bf16Args p = {};
+    *d = Bf16Desc();
+    Bf16Args& p = d->a;
     const int taps = ksize * ksize;
     const int pbh = y3_same_pad_before(src->h, ksize, stride), pbw = y3_same_pad_before(src->w, ksize, stride);
     int min_off = 0;
@@ -1549,7 +1569,6 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
         if (resid) ok = ok && ((uintptr_t)resid->ptr & 15) == 0 && (resid->ld & 7) == 0;
         p.vec_ok = ok ? 1 : 0;
     }
-    hipStream_t st = (hipStream_t)stream;
     // Tile choice, measured in the network on MI355X (tools/infer_bench.py --layers, batch 8 of 416^2 and 608^2).  With
     // 16x the fp32 MFMA rate the kernel is bound by how well resident waves cover each other's LDS / L2 latency, not by
     // the matrix pipe, so the best shape follows the grid size: 256x128 tiles (8 waves, K steps of 64) where that gives
@@ -1559,154 +1578,122 @@ static int conv2d_fwd_bf16_impl(const y3_tensor* src, const void* wt_t_bf16, con
     const long long t128 = (long long)y3_cdiv(p.M, 128) * y3_cdiv(p.Nout, 128);
     // the 256 x 256 ping-pong kernel: whole 64-deep K tiles inside one tap, 16-byte rows for the epilogue, Cout in eights
     const long long tpp = (long long)y3_cdiv(p.M, 256) * y3_cdiv(p.Nout, 256);
-    if (p.C % 64 == 0 && p.Nout >= 256 && p.Nout % 8 == 0 && p.vec_ok && tpp >= 96) {
-        p.nbn = y3_cdiv(p.Nout, 256);
-        p.ohw = p.OH * p.OW;
-        p.dv_nbn = y3_make_div(p.nbn);
-        p.dv_ohw = y3_make_div(p.ohw);
-        p.dv_ow = y3_make_div(p.OW);
-        if (dry) {
-            bf16_dry_report(dry, p, Y3_BF16_ROUTE_PP, 256, 256, 64, tpp, 512, 1, p.K / 64, 0, 0, 0);
-            return Y3_OK;
-        }
-        hipLaunchKernelGGL(conv_bf16_pp_kernel, dim3((unsigned)tpp), dim3(512), 0, st, p);
-        Y3_CHECK_LAUNCH("conv_bf16_pp");
-        return Y3_OK;
-    }
-    // the patch kernel for the 32 -> 64 3x3 layers (conv_bf16_c32_kernel)
+    // the patch kernels for the 32 -> 64 and 64 -> 128 3x3 layers
     const bool patch_epi_ok = !(flags & Y3_BF16_NO_PATCH) && (!(flags & Y3_EPI_LRELU) || (alpha >= 0.f && alpha <= 1.f));   // their leaky-relu is max(x, alpha x)
-    if (patch_epi_ok && ksize == 3 && p.C == 32 && p.Nout == 64 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0 &&
-        (!bias || ((uintptr_t)bias & 3) == 0)) {
-        PatchArgs q = {};
-        q.src = (const u16*)src->ptr;
-        q.wt = (const u16*)wt_t_bf16;
-        q.dst = (u16*)dst->ptr;
-        q.bias = bias;
-        q.scale = scale;
-        q.shift = shift;
-        q.resid = p.resid;
-        q.src_bytes = (unsigned)((long long)src->n * src->h * src->w * src->ld * 2);
-        q.dst_bytes = p.dst_bytes;
-        q.resid_bytes = p.resid ? p.resid_bytes : 0u;
-        q.H = src->h;
-        q.W = src->w;
-        q.OH = OH;
-        q.OW = OW;
-        q.src_ld = src->ld;
-        q.dst_ld = dst->ld;
-        q.resid_ld = p.resid_ld;
-        q.pbh = pbh;
-        q.pbw = pbw;
-        q.xs = y3_cdiv(OW, 32);
-        q.rg = y3_cdiv(OH, stride == 1 ? 8 : 4);
-        const long long groups = (long long)src->n * q.xs * q.rg;
-        Y3_CHECK_ARG(groups < 0x7fffffffLL, "conv2d_fwd_bf16: too many row groups");
-        q.groups = (int)groups;
-        q.dv_rg = y3_make_div(q.rg);
-        q.dv_xs = y3_make_div(q.xs);
-        q.flags = flags;
-        q.alpha = alpha;
-        const unsigned grid = (unsigned)(groups < 512 ? groups : 512);       // two workgroups per CU, each a contiguous run of groups
-        if (dry) {      // (bm: the 32 x 8 / 32 x 4 output pixels of one row group)
-            bf16_dry_report(dry, p, Y3_BF16_ROUTE_C32, stride == 1 ? 256 : 128, 64, 32, grid, 256, 1, p.K / 32, stride, q.resid ? 1 : 0, 0);
-            return Y3_OK;
-        }
-        if (stride == 1 && q.resid)
-            hipLaunchKernelGGL((conv_bf16_c32_kernel<1, true>), dim3(grid), dim3(256), 0, st, q);
-        else if (stride == 1)
-            hipLaunchKernelGGL((conv_bf16_c32_kernel<1, false>), dim3(grid), dim3(256), 0, st, q);
-        else if (q.resid)
-            hipLaunchKernelGGL((conv_bf16_c32_kernel<2, true>), dim3(grid), dim3(256), 0, st, q);
-        else
-            hipLaunchKernelGGL((conv_bf16_c32_kernel<2, false>), dim3(grid), dim3(256), 0, st, q);
-        Y3_CHECK_LAUNCH("conv_bf16_c32");
-        return Y3_OK;
-    }
-    if (patch_epi_ok && ksize == 3 && p.C == 64 && p.Nout == 128 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0) {
-        PatchArgs q = {};
-        q.src = (const u16*)src->ptr;
-        q.wt = (const u16*)wt_t_bf16;
-        q.dst = (u16*)dst->ptr;
-        q.bias = bias;
-        q.scale = scale;
-        q.shift = shift;
-        q.resid = p.resid;
-        q.src_bytes = (unsigned)((long long)src->n * src->h * src->w * src->ld * 2);
-        q.dst_bytes = p.dst_bytes;
-        q.resid_bytes = p.resid ? p.resid_bytes : 0u;
-        q.H = src->h;
-        q.W = src->w;
-        q.OH = OH;
-        q.OW = OW;
-        q.src_ld = src->ld;
-        q.dst_ld = dst->ld;
-        q.resid_ld = p.resid_ld;
-        q.pbh = pbh;
-        q.pbw = pbw;
-        q.xs = y3_cdiv(OW, 32);
-        q.rg = y3_cdiv(OH, stride == 1 ? 4 : 2);
-        const long long groups = (long long)src->n * q.xs * q.rg;
-        Y3_CHECK_ARG(groups < 0x7fffffffLL, "conv2d_fwd_bf16: too many row groups");
-        q.groups = (int)groups;
-        q.dv_rg = y3_make_div(q.rg);
-        q.dv_xs = y3_make_div(q.xs);
-        q.flags = flags;
-        q.alpha = alpha;
-        const unsigned grid = (unsigned)(groups < 256 ? groups : 256);       // one workgroup of 8 waves per CU
-        if (dry) {      // (bm: the 32 x 4 / 32 x 2 output pixels of one row group; the residual is a run-time branch of this kernel)
-            bf16_dry_report(dry, p, Y3_BF16_ROUTE_C64, stride == 1 ? 128 : 64, 128, 64, grid, 512, 1, p.K / 64, stride, 0, 0);
-            return Y3_OK;
-        }
-        if (stride == 1)
-            hipLaunchKernelGGL(conv_bf16_c64_kernel<1>, dim3(grid), dim3(512), 0, st, q);
-        else
-            hipLaunchKernelGGL(conv_bf16_c64_kernel<2>, dim3(grid), dim3(512), 0, st, q);
-        Y3_CHECK_LAUNCH("conv_bf16_c64");
-        return Y3_OK;
-    }
-    if (p.Nout <= 32) {
-        p.nbn = 1;
-        launch_bf16<128, 32, 4, 1>(p, y3_cdiv(p.M, 128), st, dry);
+    const bool patch_ok = patch_epi_ok && ksize == 3 && !dst_is_f32 && p.vec_ok && ((uintptr_t)wt_t_bf16 & 15) == 0;
+    if (p.C % 64 == 0 && p.Nout >= 256 && p.Nout % 8 == 0 && p.vec_ok && tpp >= 96) {
+        set_tile(d, Y3_BF16_ROUTE_PP, 256, 256, 64, 512);
+    } else if (patch_ok && p.C == 32 && p.Nout == 64 && (!bias || ((uintptr_t)bias & 3) == 0)) {
+        // conv_bf16_c32_kernel: 8 / 4 output rows per group, two workgroups per CU
+        return set_patch(d, Y3_BF16_ROUTE_C32, src, stride == 1 ? 8 : 4, 512, 256);
+    } else if (patch_ok && p.C == 64 && p.Nout == 128) {
+        // conv_bf16_c64_kernel: 4 / 2 output rows per group, one workgroup of 8 waves per CU
+        return set_patch(d, Y3_BF16_ROUTE_C64, src, stride == 1 ? 4 : 2, 256, 512);
+    } else if (p.Nout <= 32) {
+        set_tile(d, Y3_BF16_ROUTE_RING, 128, 32, 32, 256);
     } else if (p.Nout <= 64) {
-        p.nbn = 1;
-        launch_bf16<128, 64, 4, 1>(p, y3_cdiv(p.M, 128), st, dry);
+        set_tile(d, Y3_BF16_ROUTE_RING, 128, 64, 32, 256);
     } else if (k64 && t256 >= 150 && t256 <= 300) {
-        p.nbn = y3_cdiv(p.Nout, 128);
         // (staged epilogue without a residual too, as for the 128 x 128 launches below: same box 8 x 608^2 2.552 -> 2.530 ms, 8 x 416^2
         // 1.729 -> 1.722, 25 / 45 tiles unchanged)
-        launch_bf16<256, 128, 4, 2, 64>(p, y3_cdiv(p.M, 256) * p.nbn, st, dry);
+        set_tile(d, Y3_BF16_ROUTE_RING, 256, 128, 64, 512);
     } else if (t128 >= 512) {
-        p.nbn = y3_cdiv(p.Nout, 128);
         // with or without a residual through the staged epilogue (16-byte stores over whole tile rows).  Round 2 preferred a direct
         // one (2-byte stores from registers, 3 waves per SIMD) where there is nothing to load; re-measured at the batches the tiled path
         // plans (45 x 608^2, same box): the ten 256 -> 128 1x1 launches of the 76^2 stage 60 -> 55 us, 512 -> 128 88 -> 76
-        launch_bf16<128, 128, 2, 2>(p, y3_cdiv(p.M, 128) * p.nbn, st, dry);
+        set_tile(d, Y3_BF16_ROUTE_RING, 128, 128, 32, 256);
     } else {
-        p.nbn = y3_cdiv(p.Nout, 64);
-        const int tiles = y3_cdiv(p.M, 64) * p.nbn;
+        set_tile(d, Y3_BF16_ROUTE_RING, 64, 64, 32, 256);
         const Bf16Split sk = plan_bf16_split(p.M, p.Nout, p.K);
         if (sk.splits > 1 && workspace && workspace_bytes >= sk.ws_bytes) {
-            p.sk_splits = sk.splits;
-            p.sk_chunk = sk.chunk;
+            d->grid *= sk.splits;
+            d->splits = p.sk_splits = sk.splits;
+            d->chunk = p.sk_chunk = sk.chunk;
+            d->ws = sk.ws_bytes;
             p.dv_sk = y3_make_div(sk.splits);
             p.tickets = (int*)workspace;
             p.slab = (float*)((char*)workspace + Y3_BF16_SK_HEADER);
-            p.ohw = p.OH * p.OW;
-            p.dv_nbn = y3_make_div(p.nbn);
-            p.dv_ohw = y3_make_div(p.ohw);
-            p.dv_ow = y3_make_div(p.OW);
-            if (dry) {
-                bf16_dry_report(dry, p, Y3_BF16_ROUTE_RING, 64, 64, 32, (long long)tiles * sk.splits, 256, sk.splits, sk.chunk, 0, 0, sk.ws_bytes);
-                return Y3_OK;
-            }
-            hipLaunchKernelGGL((conv_bf16_kernel<64, 64, 2, 2, 32, true>), dim3(tiles * sk.splits), dim3(256), 0, st, p);
-        } else {
-            launch_bf16<64, 64, 2, 2>(p, tiles, st, dry);
         }
     }
-    if (dry) return Y3_OK;
-    Y3_CHECK_LAUNCH("conv_bf16");
+    p.ohw = p.OH * p.OW;
+    p.dv_nbn = y3_make_div(p.nbn);
+    p.dv_ohw = y3_make_div(p.ohw);
+    p.dv_ow = y3_make_div(p.OW);
     return Y3_OK;
+}
+
+// the ring instantiation for d's tile, if this is it
+template <int BM, int BN, int WM, int WN, int BK = 32, bool SK = false>
+static bool issue_ring(const Bf16Desc& d, hipStream_t st) {
+    if (d.bm != BM || d.bn != BN || d.bk != BK || d.threads != 64 * WM * WN || (d.splits > 1) != SK) return false;
+    hipLaunchKernelGGL((conv_bf16_kernel<BM, BN, WM, WN, BK, SK>), dim3(d.grid), dim3(d.threads), 0, st, d.a);
+    return true;
+}
+
+// Issue one described launch: d as describe_bf16 filled it.
+static int issue_bf16(const Bf16Desc& d, hipStream_t st) {
+    const dim3 g(d.grid), b(d.threads);
+    const int s = d.patch_stride, r = d.patch_resid;
+    if (d.route == Y3_BF16_ROUTE_PP && d.bm == 256 && d.bn == 256 && d.bk == 64 && d.threads == 512 && d.splits == 1) {
+        hipLaunchKernelGGL(conv_bf16_pp_kernel, g, b, 0, st, d.a);
+        Y3_CHECK_LAUNCH("conv_bf16_pp");
+        return Y3_OK;
+    }
+    if (d.route == Y3_BF16_ROUTE_C32 && (s == 1 || s == 2) && d.bm == 256 / s && d.threads == 256) {
+        if (s == 1 && r)
+            hipLaunchKernelGGL((conv_bf16_c32_kernel<1, true>), g, b, 0, st, d.q);
+        else if (s == 1)
+            hipLaunchKernelGGL((conv_bf16_c32_kernel<1, false>), g, b, 0, st, d.q);
+        else if (r)
+            hipLaunchKernelGGL((conv_bf16_c32_kernel<2, true>), g, b, 0, st, d.q);
+        else
+            hipLaunchKernelGGL((conv_bf16_c32_kernel<2, false>), g, b, 0, st, d.q);
+        Y3_CHECK_LAUNCH("conv_bf16_c32");
+        return Y3_OK;
+    }
+    if (d.route == Y3_BF16_ROUTE_C64 && (s == 1 || s == 2) && d.bm == 128 / s && d.threads == 512) {
+        if (s == 1)
+            hipLaunchKernelGGL(conv_bf16_c64_kernel<1>, g, b, 0, st, d.q);
+        else
+            hipLaunchKernelGGL(conv_bf16_c64_kernel<2>, g, b, 0, st, d.q);
+        Y3_CHECK_LAUNCH("conv_bf16_c64");
+        return Y3_OK;
+    }
+    if (d.route == Y3_BF16_ROUTE_RING &&
+        (issue_ring<128, 32, 4, 1>(d, st) || issue_ring<128, 64, 4, 1>(d, st) || issue_ring<256, 128, 4, 2, 64>(d, st) ||
+         issue_ring<128, 128, 2, 2>(d, st) || issue_ring<64, 64, 2, 2, 32, true>(d, st) || issue_ring<64, 64, 2, 2>(d, st))) {
+        Y3_CHECK_LAUNCH("conv_bf16");
+        return Y3_OK;
+    }
+    y3_set_error("conv2d_fwd_bf16: no kernel for route %d, tile %dx%dx%d, %d threads, %d splits, patch stride %d", d.route, d.bm, d.bn, d.bk, d.threads, d.splits, s);
+    return Y3_EINVAL;
+}
+
+extern "C" int y3_conv2d_fwd_bf16(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
+                                  int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
+                                  y3_stream_t stream) {
+    Bf16Desc d;
+    if (int e = describe_bf16(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, nullptr, 0, &d)) return e;
+    return issue_bf16(d, (hipStream_t)stream);
+}
+extern "C" int y3_conv2d_fwd_bf16_ws(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
+                                     int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
+                                     void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    Bf16Desc d;
+    if (int e = describe_bf16(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, workspace, workspace_bytes, &d)) return e;
+    return issue_bf16(d, (hipStream_t)stream);
+}
+// the description of the launch above (host only; a refused launch: all zeros, y3_last_error() says why)
+extern "C" size_t y3_conv2d_fwd_bf16_plan(const y3_tensor* src, const void* wt_t_bf16, const float* bias, int ksize, int stride, const y3_tensor* dst,
+                                          int dst_is_f32, unsigned flags, float alpha, const float* scale, const float* shift, const y3_tensor* resid,
+                                          void* workspace, size_t workspace_bytes, int* out12) {
+    if (!out12) return 0;
+    for (int i = 0; i < 12; ++i) out12[i] = 0;
+    Bf16Desc d;
+    if (describe_bf16(src, wt_t_bf16, bias, ksize, stride, dst, dst_is_f32, flags, alpha, scale, shift, resid, workspace, workspace_bytes, &d) != Y3_OK) return 0;
+    const int v[12] = {d.route, d.bm, d.bn, d.bk, (int)d.grid, d.threads, d.splits, d.chunk, d.a.vec_ok, d.patch_stride, d.patch_resid, d.a.K / d.bk};
+    for (int i = 0; i < 12; ++i) out12[i] = v[i];
+    return d.ws;
 }
 
 extern "C" int y3_conv2d_first_bf16(const y3_tensor* src, const float* wt, const float* bias, const y3_tensor* dst, unsigned flags, float alpha,

@@ -1,10 +1,10 @@
 """The kernel routes of y3_conv2d_fwd_bf16_ws, and one real layer of the inference plan per route class (host only: no GPU).
 
-conv2d_fwd_bf16_impl (csrc/conv_bf16.hip) ends in an if-chain that picks, per launch, one of nine routes -- the 256 x 256
+describe_bf16 (csrc/conv_bf16.hip) ends in an if-chain that picks, per launch, one of nine routes -- the 256 x 256
 ping-pong kernel, the 32 -> 64 patch kernel (stride x residual: four instantiations), the 64 -> 128 patch kernel (stride: two), the
 LDS-DMA ring kernel on five tiles, split along K on the 64 x 64 one -- from the shape, the flags (Y3_BF16_NO_PATCH, which
-yolo3/model.py sets from its 300 MB traffic rule), alpha and the alignment of its operands.  y3_conv2d_fwd_bf16_plan is a dry run
-of that very code and reports the decision as twelve numbers
+yolo3/model.py sets from its 300 MB traffic rule), alpha and the alignment of its operands.  y3_conv2d_fwd_bf16_plan reports
+the description the entry point launches from as twelve numbers
     {route, bm, bn, bk, grid, threads, splits, chunk, vec_ok, patch stride, patch residual, nk}
 (include/yolo3hip.h).
 

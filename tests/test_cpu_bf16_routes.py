@@ -4,7 +4,7 @@ with -s to see the counts the README quotes."""
 import bf16_routes as br
 
 # The representatives at the commit that added the query, by id (class + layer shape).  A dispatch threshold of
-# conv2d_fwd_bf16_impl or BF16_PATCH_MIN_BYTES (yolo3/model.py) that moves shows up here: look at what migrated, check that every
+# describe_bf16 or BF16_PATCH_MIN_BYTES (yolo3/model.py) that moves shows up here: look at what migrated, check that every
 # kernel still has its fp64 case in test_gpu_bf16_routes.py, then regenerate with `python tests/bf16_routes.py`.
 EXPECTED = [
     'c32128x64k32-s2-whole-n10_608x608_32_64_k3_s2',

@@ -1,6 +1,6 @@
 """y3_conv2d_fwd_bf16_ws on every kernel route of the inference plan, against fp64.
 
-conv2d_fwd_bf16_impl picks one of nine launch routes per call (tests/bf16_routes.py says how, and which launches of the network
+describe_bf16 (csrc/conv_bf16.hip) picks one of nine launch routes per call (tests/bf16_routes.py says how, and which launches of the network
 fall into which class).  This file runs
 
 * the cheapest real layer of every class (test_route: id = class + layer shape), with the epilogue the model passes -- bias,
