@@ -566,6 +566,22 @@ int y3_augment_batch(const void* src, int dtype, int n, int h_in, int w_in, int 
                      float* out, void* workspace, y3_stream_t stream);
 size_t y3_augment_workspace_bytes(int n, int h_out, int w_out, int c);
 
+/* ---- ground-truth label tensors: ImageReader.__format_boxes (imagereader.py:252-324) on the device ------------------------
+ * For ImageReader(..., label_device='gpu') and multi-scale training: the boxes of a batch cross PCIe, the three
+ * label tensors are built where the loss reads them.  boxes: DEVICE int32 [n][max_boxes][5] = x, y, w, h, class with (x, y) the
+ * top-left corner (what format_boxes takes); counts: DEVICE int32 [n], image i uses boxes[i][0 .. counts[i]) (clamped to
+ * 0 .. max_boxes; boxes may be null when max_boxes == 0).  out1 / out2 / out3: float32 [n][G][G][A][5+K] for strides 32 / 16 / 8 of
+ * an img_h x img_w image (multiples of 32); every element is written by this one launch, zeros included.
+ * Bit-identical to format_boxes per image: box centre floor(xy + (wh - 1) / 2); best anchor by the IoU of co-centred (w, h) with
+ * np.argmax's first-maximum rule, written at the SAME anchor slot of all three scales (Q5); row = [cx, cy, w, h, 1, one-hot];
+ * boxes that share a cell and anchor behave like the host's sequential loop (coordinates of the last box in input order, the class
+ * bits of all of them).  The cell index is the float32 evaluation floor((c / size) * G) of imagereader.py:309-310 as NumPy >= 2
+ * performs it (IEEE float32 division, then float32 multiplication), NOT c / stride: they differ, e.g. size 352, stride 16, centre
+ * 208 -> cell 12.  A box whose cell or class falls outside the tensor (the host loop raises or wraps there) writes nothing.
+ * Deterministic: no atomics, each output word is owned by one workgroup.  No workspace.  anchors_host: host [A][2] (w, h). */
+int y3_format_labels(const int* boxes, const int* counts, int n, int max_boxes, const float* anchors_host, int num_anchors,
+                     int num_classes, int img_h, int img_w, float* out1, float* out2, float* out3, y3_stream_t stream);
+
 /* ---- detection accuracy: matching + 101-point AP (not in the reference; yolo3/metrics.py, evaluate.py) ----
  * Detections are the keep lists of y3_nms_per_class: per (image, class) segment s = img * K + c the first
  * min(keep_cnt[s], max_keep, max_det) entries of keep_idx / keep_score, in keep order (descending score, ties: higher row

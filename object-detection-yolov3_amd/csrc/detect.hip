@@ -923,3 +923,163 @@ extern "C" int y3_nms_single_class(const float* rows5, int m, float iou_thr, int
     return nms_launch(rows5, 1, m, 1, 1, Y3_NMS_HARD, -INFINITY, -INFINITY, iou_thr, 0.f, -1.f, -1.f, keep_idx, keep_cnt, keep_score, m,
                       workspace, workspace_bytes, stream);
 }
+
+// ---------------------------------------------------------------------------
+// ground-truth label tensors (ImageReader.__format_boxes, imagereader.py:252-324)
+// ---------------------------------------------------------------------------
+// One launch writes the three label tensors [N, G, G, A, 5+K] completely.  The flat tensor of a scale is cut into runs of whole
+// cells; a workgroup owns one run: it zero-fills it (16-byte stores between an unaligned head and tail), then walks the boxes of the
+// images its run touches, Y3_LABEL_CHUNK at a time and in input order, and writes the rows of the boxes whose cell lies in the run.
+// Nothing outside the run is written, so no workgroup depends on another and the result does not depend on the order waves run in.
+// Within a chunk the objectness and class stores all write 1.0 (any order gives the same bits); the four coordinates of a
+// (cell, anchor) are stored by the LAST box of the chunk that lands there (the keys of the chunk sit in LDS), and a barrier
+// between chunks puts a later chunk's stores after an earlier one's: the state the host's sequential loop leaves.
+//
+// Arithmetic: every step is the float32 operation NumPy performs in format_boxes, in its order, under -ffp-contract=off:
+// centre = floor(xy + (wh - 1) / 2); the anchor IoU as min / max / product / (sum - inter) / quotient with the first maximum
+// winning (np.argmax); the cell index as floor((c / size) * G) with `size` and `G` converted to float32 and an IEEE division
+// followed by an IEEE multiplication -- the FLOAT32 evaluation of `boxes[t, 1] / image_size[0] * g[0]` (NumPy 2 keeps a float32
+// scalar float32 against a Python int), which is neither c // stride nor the float64 evaluation: side 352, stride 16, centre
+// 208 gives cell 12, not 13.  No reciprocal, no fast-math.
+#define Y3_LABEL_CHUNK 256          // boxes per pass = threads per workgroup; max_boxes is not bounded by it
+#define Y3_LABEL_RUN_FLOATS 16384   // floats a workgroup owns (rounded to whole cells): 16 x 16-byte stores per thread
+
+struct LabelArgs {
+    const int* boxes;   // [N][max_boxes][5]
+    const int* counts;  // [N]
+    float* out[3];
+    int gh[3], gw[3];
+    int block_start[4];  // first workgroup of each scale
+    int N, max_boxes, A, K;
+    int cells_per_block;
+    float img_h, img_w;
+    float aw[Y3_MAX_ANCHORS], ah[Y3_MAX_ANCHORS];
+};
+
+__global__ __launch_bounds__(Y3_LABEL_CHUNK) void format_labels_kernel(const LabelArgs p) {
+    __shared__ int key[Y3_LABEL_CHUNK];
+    const int tid = threadIdx.x;
+    int s = 0;
+    while (s < 2 && (int)blockIdx.x >= p.block_start[s + 1]) ++s;
+    const int gh = p.gh[s], gw = p.gw[s];
+    const int D = 5 + p.K, AD = p.A * D;
+    const long long cells = (long long)gh * gw;
+    const long long total = cells * p.N;
+    const long long c0 = (long long)((int)blockIdx.x - p.block_start[s]) * p.cells_per_block;
+    const long long c1 = c0 + p.cells_per_block < total ? c0 + p.cells_per_block : total;
+    float* const base = p.out[s];
+
+    // zero fill of [c0, c1) cells
+    {
+        float* f = base + c0 * AD;
+        const long long cnt = (c1 - c0) * AD;
+        long long head = (long long)(((16u - (unsigned)((uintptr_t)f & 15u)) & 15u) >> 2);
+        if (head > cnt) head = cnt;
+        const long long nv = (cnt - head) >> 2;
+        float4* v = reinterpret_cast<float4*>(f + head);
+        for (long long i = tid; i < nv; i += Y3_LABEL_CHUNK) v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (tid < head) f[tid] = 0.f;
+        const long long tail0 = head + (nv << 2);
+        if (tail0 + tid < cnt) f[tail0 + tid] = 0.f;      // < 4 floats
+    }
+    __syncthreads();
+
+    const int n0 = (int)(c0 / cells), n1 = (int)((c1 - 1) / cells);
+    for (int n = n0; n <= n1; ++n) {
+        int cnt = p.counts[n];
+        cnt = cnt < 0 ? 0 : (cnt > p.max_boxes ? p.max_boxes : cnt);
+        const int* bx = p.boxes + (long long)n * p.max_boxes * 5;
+        for (int t0 = 0; t0 < cnt; t0 += Y3_LABEL_CHUNK) {
+            const int t = t0 + tid;
+            int k = -1, cls = 0;
+            float cx = 0.f, cy = 0.f, w = 0.f, h = 0.f;
+            if (t < cnt) {
+                const float x = (float)bx[t * 5 + 0], y = (float)bx[t * 5 + 1];
+                w = (float)bx[t * 5 + 2];
+                h = (float)bx[t * 5 + 3];
+                cls = bx[t * 5 + 4];
+                cx = floorf(x + (w - 1.f) / 2.0f);
+                cy = floorf(y + (h - 1.f) / 2.0f);
+                int best = 0;
+                float best_iou = 0.f;
+                for (int a = 0; a < p.A; ++a) {
+                    const float aw = p.aw[a], ah = p.ah[a];
+                    const float iw = fmaxf(fminf(w / 2.0f, aw / 2.0f) - fmaxf(-w / 2.0f, -aw / 2.0f), 0.0f);
+                    const float ih = fmaxf(fminf(h / 2.0f, ah / 2.0f) - fmaxf(-h / 2.0f, -ah / 2.0f), 0.0f);
+                    const float inter = iw * ih;
+                    const float iou = inter / (w * h + aw * ah - inter);
+                    if (a == 0 || iou > best_iou) {
+                        best = a;
+                        best_iou = iou;
+                    }
+                }
+                const float fi = floorf(cy / p.img_h * (float)gh);
+                const float fj = floorf(cx / p.img_w * (float)gw);
+                // a cell or class outside the tensor (where the host loop raises or wraps around) writes nothing
+                if (fi >= 0.f && fi < (float)gh && fj >= 0.f && fj < (float)gw && cls >= 0 && cls < p.K) {
+                    const long long cell = (long long)n * cells + (long long)((int)fi * gw + (int)fj);
+                    if (cell >= c0 && cell < c1) k = (int)(cell - c0) * p.A + best;
+                }
+            }
+            key[tid] = k;
+            __syncthreads();
+            if (k >= 0) {
+                float* row = base + c0 * AD + (long long)k * D;
+                bool last = true;
+                const int lim = cnt - t0 < Y3_LABEL_CHUNK ? cnt - t0 : Y3_LABEL_CHUNK;
+                for (int u = tid + 1; u < lim; ++u) last = last && key[u] != k;
+                if (last) {
+                    row[0] = cx;
+                    row[1] = cy;
+                    row[2] = w;
+                    row[3] = h;
+                }
+                row[4] = 1.0f;
+                row[5 + cls] = 1.0f;
+            }
+            __syncthreads();      // the next chunk's stores (and its keys) come after this chunk's
+        }
+    }
+}
+
+extern "C" int y3_format_labels(const int* boxes, const int* counts, int n, int max_boxes, const float* anchors_host, int num_anchors,
+                                int num_classes, int img_h, int img_w, float* out1, float* out2, float* out3, y3_stream_t stream) {
+    Y3_CHECK_ARG(counts && anchors_host && out1 && out2 && out3, "format_labels: null pointer");
+    Y3_CHECK_ARG(max_boxes >= 0 && (boxes || max_boxes == 0), "format_labels: max_boxes %d%s", max_boxes, boxes ? "" : " with null boxes");
+    Y3_CHECK_ARG(n >= 1 && num_anchors >= 1 && num_anchors <= Y3_MAX_ANCHORS && num_classes >= 1, "format_labels: n %d anchors %d classes %d", n,
+                 num_anchors, num_classes);
+    Y3_CHECK_ARG(img_h >= 32 && img_w >= 32 && img_h % 32 == 0 && img_w % 32 == 0 && img_h < (1 << 24) && img_w < (1 << 24),
+                 "format_labels: image %dx%d (multiples of 32)", img_h, img_w);
+    Y3_CHECK_ARG((long long)n * max_boxes * 5 < (1LL << 31), "format_labels: %d x %d boxes too many", n, max_boxes);
+    LabelArgs p = {};
+    p.boxes = boxes;
+    p.counts = counts;
+    p.out[0] = out1;
+    p.out[1] = out2;
+    p.out[2] = out3;
+    p.N = n;
+    p.max_boxes = max_boxes;
+    p.A = num_anchors;
+    p.K = num_classes;
+    p.img_h = (float)img_h;
+    p.img_w = (float)img_w;
+    const int AD = num_anchors * (5 + num_classes);
+    p.cells_per_block = Y3_LABEL_RUN_FLOATS / AD > 0 ? Y3_LABEL_RUN_FLOATS / AD : 1;
+    Y3_CHECK_ARG((long long)p.cells_per_block * AD < (1LL << 31), "format_labels: %d classes too many", num_classes);
+    long long blocks = 0;
+    for (int s = 0; s < 3; ++s) {
+        p.gh[s] = img_h / (32 >> s);
+        p.gw[s] = img_w / (32 >> s);
+        p.block_start[s] = (int)blocks;
+        blocks += ((long long)n * p.gh[s] * p.gw[s] + p.cells_per_block - 1) / p.cells_per_block;
+        Y3_CHECK_ARG(blocks < (1LL << 31), "format_labels: labels too large");
+    }
+    p.block_start[3] = (int)blocks;
+    for (int a = 0; a < num_anchors; ++a) {
+        p.aw[a] = anchors_host[2 * a];
+        p.ah[a] = anchors_host[2 * a + 1];
+    }
+    hipLaunchKernelGGL(format_labels_kernel, dim3((unsigned)blocks), dim3(Y3_LABEL_CHUNK), 0, (hipStream_t)stream, p);
+    Y3_CHECK_LAUNCH("format_labels");
+    return Y3_OK;
+}

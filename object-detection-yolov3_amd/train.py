@@ -19,6 +19,11 @@ with an IoU loss `loss_xy` carries the box term and `loss_wh` is 0.  The weight 
 replicas x N; a "step" of the loop, of --test_every_n_steps and of train.csv stays one batch) and --grad_clip_norm X bounds the
 global L2 norm of the (averaged) gradient at X; with either, <scalars>/grad_norm.csv gets one row per optimiser
 step: the train.csv step that completed it, the norm before clipping and the factor applied to the summed gradient.
+--multiscale_min A --multiscale_max B (with --augmentation_device gpu) trains at a changing square input size: every
+--multiscale_period batches (default 10) a side is drawn from the multiples of 32 in [A, B] as a pure function of
+--multiscale_seed and the batch count, the same on every rank; the batch is augmented straight to that size and its labels are
+built on the device at it.  <scalars>/train_size.csv gets one row per step.  The test reader, the test loss, the
+mAP pass, model selection, the checkpoint and the export stay at the size the images are stored at.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -115,6 +120,21 @@ def evaluate_test_map(yolo, strategy, database, batch_size, min_box_size, world,
     return res, ev.num_images, time.time() - t0
 
 
+def multiscale_sizes(multiscale_min, multiscale_max):
+    """The square sizes of --multiscale_min / --multiscale_max: every multiple of 32 in [min, max]; None when both are None (off).
+    ValueError when only one is given, either is no positive multiple of 32, or min > max."""
+    if multiscale_min is None and multiscale_max is None:
+        return None
+    if multiscale_min is None or multiscale_max is None:
+        raise ValueError('--multiscale_min and --multiscale_max go together')
+    lo, hi = int(multiscale_min), int(multiscale_max)
+    if lo < 32 or hi < 32 or lo % 32 or hi % 32:
+        raise ValueError('--multiscale_min / --multiscale_max must be positive multiples of 32, got {} / {}'.format(lo, hi))
+    if lo > hi:
+        raise ValueError('--multiscale_min {} is larger than --multiscale_max {}'.format(lo, hi))
+    return [(v, v) for v in range(lo, hi + 1, 32)]
+
+
 def abort_on_nan(loss_value, message):
     """train.py:124-125,151-152."""
     if np.isnan(float(loss_value)):
@@ -135,8 +155,14 @@ def effective_reader_count(requested, cpus, local_world):
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
-                box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None):
+                box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, multiscale_min=None, multiscale_max=None,
+                multiscale_period=10, multiscale_seed=0):
     test_map = effective_test_map(test_map, model_selection)
+    train_sizes = multiscale_sizes(multiscale_min, multiscale_max)
+    if train_sizes is not None and augmentation_device != 'gpu':
+        raise ValueError('multi-scale training needs augmentation_device gpu: the batches are resampled and labelled on the device')
+    if train_sizes is not None and int(multiscale_period) < 1:
+        raise ValueError('multiscale_period must be >= 1, got {!r}'.format(multiscale_period))
     from yolo3.model import check_box_loss_args, check_grad_args
     check_box_loss_args(box_loss, box_loss_weight)
     check_grad_args(accumulate_steps, grad_clip_norm)
@@ -167,7 +193,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     print('Test Reader has {} images'.format(test_reader.get_image_count()))
     print('Setting up training image reader')
     train_reader = imagereader.ImageReader(train_database_filepath, anchors, use_augmentation=use_augmentation, shuffle=True,
-                                           num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device)
+                                           num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device,
+                                           **(dict(label_device='gpu') if train_sizes is not None else {}))
     print('Train Reader has {} images'.format(train_reader.get_image_count()))
     training_checkpoint_filepath = None
     try:
@@ -200,12 +227,16 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
 
         train_dataset = train_reader.get_tf_dataset().batch(batch_size).prefetch(reader_count)
         test_dataset = test_reader.get_tf_dataset().batch(batch_size).prefetch(reader_count)
+        if train_sizes is not None:
+            train_dataset = train_dataset.multiscale(train_sizes, multiscale_period, multiscale_seed)
+            print('Multi-scale training: sizes {} drawn every {} batches (seed {}); testing, checkpoint and export stay at {}'.format(
+                [s[0] for s in train_sizes], multiscale_period, multiscale_seed, train_reader.get_image_size()[:2]))
 
         print('Creating model')
         number_classes = train_reader.get_number_classes()
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
-                            grad_clip_norm=grad_clip_norm)
+                            grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}))
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
@@ -245,6 +276,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             if log_grad_norm:
                 with open(os.path.join(log_dir, 'grad_norm.csv'), 'w') as fh:
                     fh.write('step,grad_norm,scale\n')
+            if train_sizes is not None:
+                with open(os.path.join(log_dir, 'train_size.csv'), 'w') as fh:
+                    fh.write('step,height,width\n')
 
         def log_scalars(split, step, metrics):
             if rank == 0:
@@ -272,6 +306,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 abort_on_nan(loss_value, 'Training Loss went to NaN, try a lower learning rate')
                 print('Train Epoch {}: Batch {}/{}: Loss {}'.format(epoch, step, train_epoch_size, train_metrics[0].result()))
                 log_scalars('train', int(epoch * train_epoch_size + step), train_metrics)
+                if train_sizes is not None and rank == 0:
+                    with open(os.path.join(log_dir, 'train_size.csv'), 'a') as fh:
+                        fh.write('{},{},{}\n'.format(int(epoch * train_epoch_size + step), int(batch_images.shape[2]), int(batch_images.shape[3])))
                 if log_grad_norm and rank == 0 and yolo.micro_step == 0:      # this batch completed an optimiser step
                     with open(os.path.join(log_dir, 'grad_norm.csv'), 'a') as fh:
                         fh.write('{},{!r},{!r}\n'.format(int(epoch * train_epoch_size + step), float(yolo.last_grad_norm),
@@ -392,8 +429,42 @@ def _grad_clip_norm_arg(text):
     return c
 
 
+def _multiscale_side_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a positive multiple of 32, got {!r}'.format(text))
+    if v < 32 or v % 32:
+        raise argparse.ArgumentTypeError('a positive multiple of 32, got {!r}'.format(text))
+    return v
+
+
+def _multiscale_period_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    if v < 1:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    return v
+
+
+class _Parser(argparse.ArgumentParser):
+    """The checks that span several flags: an argparse error like any other."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        try:
+            sizes = multiscale_sizes(a.multiscale_min, a.multiscale_max)
+        except ValueError as e:
+            self.error(str(e))
+        if sizes is not None and a.augmentation_device != 'gpu':
+            self.error('--multiscale_min / --multiscale_max need --augmentation_device gpu')
+        return a
+
+
 def build_parser():
-    parser = argparse.ArgumentParser(prog='train_yolo', description='Script which trains a yolo_v3 model')
+    parser = _Parser(prog='train_yolo', description='Script which trains a yolo_v3 model')
     parser.add_argument('--batch_size', dest='batch_size', type=int, help='training batch size', default=8)
     parser.add_argument('--learning_rate', dest='learning_rate', type=float, default=1e-4)
     parser.add_argument('--test_every_n_steps', dest='test_every_n_steps', type=int, help='number of gradient update steps to take between test epochs', default=1000)
@@ -434,6 +505,15 @@ def build_parser():
     parser.add_argument('--grad_clip_norm', dest='grad_clip_norm', type=_grad_clip_norm_arg, default=None,
                         help='(addition) off by default; X > 0: scale the gradient of an optimiser step so that its global L2 norm is at '
                              'most X (as Keras Adam(global_clipnorm=X))')
+    parser.add_argument('--multiscale_min', dest='multiscale_min', type=_multiscale_side_arg, default=None,
+                        help='(addition) with --multiscale_max: train at a changing square input size, every multiple of 32 from this side ... '
+                             '(needs --augmentation_device gpu; testing, checkpoint and export stay at the stored size)')
+    parser.add_argument('--multiscale_max', dest='multiscale_max', type=_multiscale_side_arg, default=None,
+                        help='(addition) ... to this side (a multiple of 32, >= --multiscale_min)')
+    parser.add_argument('--multiscale_period', dest='multiscale_period', type=_multiscale_period_arg, default=10,
+                        help='(addition) batches between two draws of the multi-scale size (default 10)')
+    parser.add_argument('--multiscale_seed', dest='multiscale_seed', type=int, default=0,
+                        help='(addition) seed of the multi-scale size schedule: the size of batch i is a pure function of (seed, i // period)')
     return parser
 
 
@@ -445,4 +525,5 @@ if __name__ == "__main__":
     train_model(a.batch_size, a.test_every_n_steps, a.train_database_filepath, a.test_database_filepath, a.output_folder,
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
-                a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm)
+                a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm, a.multiscale_min, a.multiscale_max,
+                a.multiscale_period, a.multiscale_seed)

@@ -202,3 +202,52 @@ def draw_augmentation(img_shape, boxes, rotation_flag=False, reflection_flag=Fal
     rec = np.zeros(1, AUG_RECORD)
     rec[0] = (H, W, rows, cols, dy, dx, int(reflect_x), int(reflect_y), noise, u_noise, sigma, 0, seed)
     return rec, boxes
+
+
+# ---- multi-scale training: the same augmented crop, resampled to another network input size ----------------
+def rescale_record(rec, crop_from, size):
+    """The record that makes y3_augment_batch(..., h_out=size[0], w_out=size[1]) produce the crop `rec` describes at
+    crop_from = (h, w), resampled to `size`: rows, cols, dy, dx scaled by size / crop_from and rounded to nearest (half up, in
+    exact integer arithmetic), rows' / cols' at least the new crop, dy' / dx' clamped so that the crop fits (dy' + size[0] <=
+    rows').  Flips, noise and the blur sigma are unchanged: sigma stays in OUTPUT pixels, so the kernel's radius limit holds.
+    rec: AUG_RECORD array of any shape; returns a new array, equal to rec when size == crop_from."""
+    out = np.array(rec, dtype=AUG_RECORD, copy=True)
+    for full, off, c, s in (('rows', 'dy', int(crop_from[0]), int(size[0])), ('cols', 'dx', int(crop_from[1]), int(size[1]))):
+        if s == c:
+            continue
+        n = np.maximum((2 * out[full].astype(np.int64) * s + c) // (2 * c), s)
+        o = np.minimum((2 * out[off].astype(np.int64) * s + c) // (2 * c), n - s)
+        out[full], out[off] = n, o
+    return out
+
+
+def scale_boxes(boxes, crop_from, size):
+    """The box side of rescale_record: [n,5] integer boxes (x, y, w, h, class; top-left corner) of a crop_from = (h, w) image
+    mapped into a `size` image.  Corner based and rounded OUTWARDS in exact integer arithmetic: the left / top edge x becomes
+    floor(x * s / c), the exclusive right / bottom edge x + w becomes ceil((x + w) * s / c); then the near edge is clamped to
+    [0, s - 1] and the far edge to [near + 1, s], so every box stays inside the new image with w, h >= 1, and a box covering the
+    whole crop covers the whole target.  An axis whose size does not change is returned as it came (the identity at equal
+    sizes, whatever the boxes).  None / empty input comes back unchanged."""
+    if boxes is None or boxes.shape[0] == 0:
+        return boxes
+    out = np.array(boxes, copy=True)
+    b = out.astype(np.int64)
+    for lo, ext, c, s in ((0, 2, int(crop_from[1]), int(size[1])), (1, 3, int(crop_from[0]), int(size[0]))):
+        if s == c:
+            continue
+        near = np.clip((b[:, lo] * s) // c, 0, s - 1)
+        far = np.clip(-((-(b[:, lo] + b[:, ext]) * s) // c), near + 1, s)
+        out[:, lo], out[:, ext] = near, far - near
+    return out
+
+
+def multiscale_choice(seed, block, count):
+    """Index in 0 .. count-1 of the size multi-scale training uses for the block-th run of `period` batches: a pure function of
+    (seed, block) -- splitmix64 of seed * 2^32 + block, reduced modulo count -- so every rank draws the same size and a run can
+    be repeated."""
+    m = (1 << 64) - 1
+    z = ((int(seed) << 32) + int(block) + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    z ^= z >> 31
+    return int(z % int(count))

@@ -8,6 +8,8 @@ augment_device    augment.py:30-125 on the device (csrc/augment.hip) for ImageRe
 format_image      imagereader.py:57-60
 format_boxes      ImageReader.__format_boxes, imagereader.py:252-324 (host NumPy,
                   as in the reference: it runs in the reader processes)
+format_labels_device  the same three label tensors built on the device from the boxes of a batch (y3_format_labels,
+                  csrc/detect.hip) for ImageReader(..., label_device='gpu') and Dataset.multiscale()
 """
 import multiprocessing
 import os
@@ -18,7 +20,7 @@ import traceback
 import numpy as np
 import torch
 
-from ._hip import lib, check
+from ._hip import lib, check, float_array
 from . import augment
 from . import lmdbio
 from .isg_ai_pb import ImageYoloBoxesPair
@@ -67,6 +69,44 @@ def augment_device(src, records, crop_to, ranges=False):
     bits = torch.where(bits >= 2**31, bits - 2**32, bits).to(torch.int32)
     val = bits.view(torch.float32)
     return out, -val[:, 1], val[:, 0]
+
+
+def format_labels_device(boxes, counts, image_size, anchors, number_classes):
+    """y3_format_labels: boxes CUDA int32 [B, M, 5] (x, y, w, h, class; top-left corner; M may be 0), counts CUDA int32 [B] ->
+    the three float32 label tensors [B, G, G, A, 5+K] of format_boxes (bit-identical per image), written completely by one
+    launch on the current stream."""
+    assert boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 3 and boxes.shape[2] == 5, (boxes.dtype, tuple(boxes.shape))
+    assert counts.is_cuda and counts.dtype == torch.int32 and counts.shape == (boxes.shape[0],), (counts.dtype, tuple(counts.shape))
+    boxes, counts = boxes.contiguous(), counts.contiguous()
+    b, m = int(boxes.shape[0]), int(boxes.shape[1])
+    h, w = int(image_size[0]), int(image_size[1])
+    a, k = len(anchors), int(number_classes)
+    f = NETWORK_DOWNSAMPLE_FACTOR
+    out = [torch.empty((b, h // (f >> s), w // (f >> s), a, 5 + k), dtype=torch.float32, device=boxes.device) for s in range(3)]
+    anchors_c = float_array([float(v) for an in anchors for v in an])
+    st = torch.cuda.current_stream(boxes.device).cuda_stream
+    check(lib.y3_format_labels(boxes.data_ptr() if m else None, counts.data_ptr(), b, m, anchors_c, a, k, h, w,
+                               out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st), 'y3_format_labels')
+    return out
+
+
+def collate_boxes(box_lists, out=None):
+    """Boxes of a batch, [k_i, 5] each (None = none) -> (boxes int32 [B, M, 5] zero-padded, counts int32 [B]) with M the batch
+    maximum (at least 1): nothing is dropped.  out: optional (boxes, counts) arrays to fill, boxes with room for M."""
+    counts = np.array([0 if b is None else len(b) for b in box_lists], np.int32)
+    m = max(1, int(counts.max()) if len(counts) else 1)
+    if out is None:
+        boxes = np.zeros((len(box_lists), m, 5), np.int32)
+    else:
+        boxes, cdst = out
+        assert boxes.shape[1] >= m
+        boxes[...] = 0
+        cdst[...] = counts
+        counts = cdst
+    for i, b in enumerate(box_lists):
+        if counts[i]:
+            boxes[i, :counts[i]] = b
+    return boxes, counts
 
 
 def zscore_normalize(image_data):
@@ -148,16 +188,55 @@ class Dataset:
     n examples and moves them to the GPU, where the images are z-scored by the HIP kernel (the reference z-scores in
     the reader processes on the CPU, imagereader.py:398); ``prefetch(d)`` assembles up to d batches ahead in pinned host
     memory on a background thread (tf.data's prefetch, train.py:61), so that taking examples off the worker queue and
-    stacking them overlaps the GPU step instead of preceding it."""
+    stacking them overlaps the GPU step instead of preceding it.
+    With a label_device='gpu' reader the examples carry their boxes; a batch pads them to its own maximum (with counts) and
+    y3_format_labels builds the label tensors on the device.  ``multiscale(sizes, period, seed)`` (such a reader only, DESIGN
+    §3.11) gives batch i -- counted over the life of this object, not per epoch -- the size sizes[j], j a pure function of
+    (seed, i // period): the batch is augmented straight to that size and its labels are built at it."""
 
-    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0):
+    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None):
         self.reader, self.batch_size, self.device, self.prefetch_depth = reader, batch_size, device, prefetch_depth
+        self.multiscale_cfg = multiscale       # None or (sizes [(h, w)], period, seed)
+        self.batches = 0                       # batches handed out so far, over every iteration of this object
 
     def batch(self, n):
-        return Dataset(self.reader, int(n), self.device, self.prefetch_depth)
+        return Dataset(self.reader, int(n), self.device, self.prefetch_depth, self.multiscale_cfg)
 
     def prefetch(self, n):
-        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)))     # batches, not examples: 4 is plenty
+        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)), self.multiscale_cfg)     # batches, not examples: 4 is plenty
+
+    def multiscale(self, sizes, period, seed=0):
+        """Multi-scale training: see the class docstring.  sizes: (h, w) pairs, multiples of 32; period: batches per draw."""
+        if getattr(self.reader, 'label_device', 'cpu') != 'gpu':
+            raise ValueError("multiscale() needs a reader with label_device='gpu': the labels are built at the drawn size")
+        sizes = [(int(s[0]), int(s[1])) for s in sizes]
+        if not sizes or any(h < 32 or w < 32 or h % 32 or w % 32 for h, w in sizes):
+            raise ValueError('multiscale sizes must be (h, w) multiples of {}, got {!r}'.format(NETWORK_DOWNSAMPLE_FACTOR, sizes))
+        if isinstance(period, bool) or int(period) != period or int(period) < 1:
+            raise ValueError('multiscale period must be an integer >= 1, got {!r}'.format(period))
+        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, (sizes, int(period), int(seed)))
+
+    def size_of_batch(self, i):
+        """(h, w) of batch i of this dataset: the reader's stored size unless multiscale() is on."""
+        if self.multiscale_cfg is None:
+            return tuple(self.reader.image_size[:2])
+        sizes, period, seed = self.multiscale_cfg
+        return sizes[augment.multiscale_choice(seed, int(i) // period, len(sizes))]
+
+    def _device_batch(self, dev, imgs, records, boxes, counts):
+        """A label_device='gpu' batch on the device: imgs the raw pixels (already there), records host AUG_RECORD [B], boxes /
+        counts host int32 (NumPy arrays or pinned tensors).  Augments to this batch's size, z-scores, builds the labels."""
+        crop = tuple(self.reader.image_size[:2])
+        size = self.size_of_batch(self.batches)
+        self.batches += 1
+        if size != crop:
+            records = augment.rescale_record(records, crop, size)
+            b = boxes.numpy() if torch.is_tensor(boxes) else boxes
+            boxes = augment.scale_boxes(b.reshape(-1, 5), crop, size).reshape(b.shape)      # (padding rows are never read)
+        as_t = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True)
+        labels = format_labels_device(as_t(boxes), as_t(counts), (size[0], size[1], self.reader.image_size[2]), self.reader.anchors,
+                                      self.reader.number_classes)
+        return (zscore_normalize_device(augment_device(imgs, records, size)), *labels)
 
     def shard(self, num_shards, index):
         """experimental_distribute_dataset (train.py:62,66): every replica reads its own examples.  The reader's
@@ -185,10 +264,14 @@ class Dataset:
             return
         dev = self.device or torch.device('cuda', torch.cuda.current_device())
         on_gpu = self.reader.augmentation_device == 'gpu'     # examples carry raw HWC pixels + an AUG_RECORD (ImageReader)
+        lab_gpu = getattr(self.reader, 'label_device', 'cpu') == 'gpu'     # examples are (pixels, boxes, AUG_RECORD): labels built here
         crop = self.reader.image_size[:2]
         if not self.prefetch_depth:
             for ex in self._examples():
                 imgs = torch.from_numpy(np.stack([e[0] for e in ex])).to(dev, non_blocking=True)
+                if lab_gpu:
+                    yield self._device_batch(dev, imgs, np.concatenate([e[2] for e in ex]), *collate_boxes([e[1] for e in ex]))
+                    continue
                 labels = [torch.from_numpy(np.stack([e[i] for e in ex])).to(dev, non_blocking=True) for i in (1, 2, 3)]
                 if on_gpu:
                     imgs = augment_device(imgs, np.concatenate([e[4] for e in ex]), crop)
@@ -217,6 +300,20 @@ class Dataset:
                     slot = ring[i % len(ring)]
                     if slot['event'] is not None:
                         slot['event'].synchronize()          # the upload that last used these pinned buffers has finished
+                    if lab_gpu:
+                        if slot['bufs'] is None:
+                            slot['bufs'] = [torch.empty((len(ex),) + ex[0][0].shape, dtype=torch.from_numpy(ex[0][0]).dtype, pin_memory=True),
+                                            None, torch.empty(len(ex), dtype=torch.int32, pin_memory=True)]
+                        np.stack([e[0] for e in ex], out=slot['bufs'][0].numpy())
+                        need = max([1] + [len(e[1]) for e in ex])
+                        if slot['bufs'][1] is None or slot['bufs'][1].shape[1] < need:       # the box buffer grows: no fixed cap, nothing dropped
+                            cap = 1 << (need - 1).bit_length()
+                            slot['bufs'][1] = torch.empty((len(ex), cap, 5), dtype=torch.int32, pin_memory=True)
+                        collate_boxes([e[1] for e in ex], out=(slot['bufs'][1].numpy(), slot['bufs'][2].numpy()))
+                        slot['records'] = np.concatenate([e[2] for e in ex])
+                        if not hand_over(slot):
+                            return
+                        continue
                     if slot['bufs'] is None:
                         slot['bufs'] = [torch.empty((len(ex),) + ex[0][j].shape, dtype=torch.from_numpy(ex[0][j]).dtype, pin_memory=True)
                                         for j in range(4)]
@@ -235,6 +332,13 @@ class Dataset:
                 slot = ready.get()
                 if slot is None:
                     return
+                if lab_gpu:
+                    out = self._device_batch(dev, slot['bufs'][0].to(dev, non_blocking=True), slot['records'], slot['bufs'][1], slot['bufs'][2])
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(dev))      # behind the uploads from the pinned buffers
+                    slot['event'] = ev
+                    yield out
+                    continue
                 dev_t = [b.to(dev, non_blocking=True) for b in slot['bufs']]
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(dev))
@@ -250,15 +354,23 @@ class ImageReader:
     get_number_classes / get_image_count / get_example / generator; get_tf_dataset() returns a ``Dataset``."""
 
     def __init__(self, img_db, anchors, use_augmentation=True, balance_classes=False, shuffle=True, num_workers=1, num_shards=1, shard_index=0,
-                 augmentation_device='cpu'):
+                 augmentation_device='cpu', label_device='cpu'):
         """num_shards / shard_index (addition): with one process per GPU every rank owns a reader; an unshuffled reader
         (the test set) then serves every num_shards-th stride of the key list, so the ranks evaluate disjoint images like
         the replicas of the reference's one distributed test batch.
         augmentation_device (addition): 'cpu' augments in the worker processes (augment.augment_image_box_pair, the
         reference's design); 'gpu' has the workers draw only the random decisions (augment.draw_augmentation) and hand out
-        the stored pixels, which the batches then augment on the device (augment_device, csrc/augment.hip)."""
+        the stored pixels, which the batches then augment on the device (augment_device, csrc/augment.hip).
+        label_device (addition): 'cpu' builds the three label tensors in the worker processes (format_boxes, the reference's
+        design); 'gpu' (needs augmentation_device='gpu') has the workers hand out the transformed boxes, [k, 5] int32, and the
+        batches build the labels on the device (format_labels_device): the same tensors, a few dozen boxes over PCIe instead."""
         assert augmentation_device in ('cpu', 'gpu'), augmentation_device
+        if label_device not in ('cpu', 'gpu'):
+            raise ValueError("label_device must be 'cpu' or 'gpu', got {!r}".format(label_device))
+        if label_device == 'gpu' and augmentation_device != 'gpu':
+            raise ValueError("label_device='gpu' needs augmentation_device='gpu': the workers then hand out boxes and records, not tensors")
         self.augmentation_device = augmentation_device
+        self.label_device = label_device
         self.num_shards, self.shard_index = int(num_shards), int(shard_index)
         assert 0 <= self.shard_index < self.num_shards
         self.image_db = img_db
@@ -371,7 +483,8 @@ class ImageReader:
 
     def load_example(self, key, env):
         """One example as the workers produce it: (image[C,H,W] float32 NOT yet z-scored, label_1, label_2, label_3); with
-        augmentation_device='gpu': (image[H,W,C] as stored, label_1, label_2, label_3, AUG_RECORD [1])."""
+        augmentation_device='gpu': (image[H,W,C] as stored, label_1, label_2, label_3, AUG_RECORD [1]); with label_device='gpu'
+        as well: (image[H,W,C] as stored, boxes [k,5] int32 -- what format_boxes would have been given -- , AUG_RECORD [1])."""
         datum = ImageYoloBoxesPair().ParseFromString(env.get(key))
         img, boxes = datum.to_arrays()
         if list(img.shape) != list(self.image_size):
@@ -383,6 +496,9 @@ class ImageReader:
                 rec, boxes = augment.draw_augmentation(img.shape, boxes, crop_to=crop_to, **TRAIN_AUGMENTATION)
             else:
                 rec = augment.identity_record(img.shape, crop_to)
+            if self.label_device == 'gpu':
+                boxes = np.zeros((0, 5), np.int32) if boxes is None else np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 5)
+                return (np.ascontiguousarray(img), boxes, rec)
             labels = format_boxes(boxes, self.image_size, self.anchors, self.number_classes)
             return (np.ascontiguousarray(img), labels[0], labels[1], labels[2], rec)
         if self.use_augmentation:                               # severities of imagereader.py:369-391
@@ -431,6 +547,13 @@ class ImageReader:
         example = self._get_raw()
         if example is None:
             return None
+        if self.label_device == 'gpu':                         # a batch of one through the device path, labels included
+            src = torch.from_numpy(example[0][None]).cuda()
+            img = zscore_normalize_device(augment_device(src, example[2], self.image_size[:2]))[0].cpu().numpy()
+            boxes, counts = collate_boxes([example[1]])
+            labels = format_labels_device(torch.from_numpy(boxes).cuda(), torch.from_numpy(counts).cuda(), self.image_size, self.anchors,
+                                          self.number_classes)
+            return (img,) + tuple(l[0].cpu().numpy() for l in labels)
         if self.augmentation_device == 'gpu':                  # a batch of one through the device path
             src = torch.from_numpy(example[0][None]).cuda()
             img = zscore_normalize_device(augment_device(src, example[4], self.image_size[:2]))[0].cpu().numpy()

@@ -82,6 +82,27 @@ def clip_scale(norm, clip, k):
     return np.float32(s)
 
 
+def check_train_sizes(img_size, train_sizes):
+    """Host-side validation of the network input sizes train_step / test_step accept (multi-scale training).  None:
+    the constructed size only, returned as [(H, W)].  Otherwise a list of (H, W), each a positive multiple of 32; the constructed
+    img_size is always included (first).  ValueError otherwise."""
+    own = (int(img_size[0]), int(img_size[1]))
+    if train_sizes is None:
+        return [own]
+    out = [own]
+    try:
+        pairs = [(s[0], s[1], len(s)) for s in train_sizes]
+    except (TypeError, IndexError):
+        raise ValueError('train_sizes must be None or a list of (H, W) pairs, got {!r}'.format(train_sizes))
+    for h, w, n in pairs:
+        ok = n == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (h, w))
+        if not ok or h < 32 or w < 32 or h % 32 or w % 32:
+            raise ValueError('train_sizes must hold (H, W) pairs of positive multiples of 32, got {!r}'.format((h, w) if n == 2 else train_sizes))
+        if (int(h), int(w)) not in out:
+            out.append((int(h), int(w)))
+    return out
+
+
 def _round_up(v, a):
     return (v + a - 1) // a * a
 
@@ -221,10 +242,13 @@ class Mean:
 
 
 class _Plan:
-    """Static launch list for one (batch size, mode)."""
+    """Static launch list for one (batch size, mode, input size).  A plan owns everything whose shape follows the input: activations
+    and their gradients, the label tensors, BatchNorm partial rows, the conv / kernel-gradient workspaces, its captured graphs.
+    What depends on the weights alone (arenas, transposed and split copies, per-channel BatchNorm blocks) stays on the model."""
 
-    def __init__(self, model, n, training, bf16=False):
+    def __init__(self, model, n, training, bf16=False, size=None):
         self.model = model
+        self.size = (int(size[0]), int(size[1])) if size is not None else (model.img_size[0], model.img_size[1])
         self.n = n
         self.training = training
         self.bf16 = bool(bf16) and not training     # reduced-precision conv path: inference only (BASELINE config 5)
@@ -276,7 +300,7 @@ class _Plan:
         mdl = self.model
         dev = mdl.device
         N = self.n
-        H, W, C = mdl.img_size
+        (H, W), C = self.size, mdl.img_size[2]
         A, K = mdl.number_anchors, mdl.number_classes
         D = A * (5 + K)
         Dld = _round_up(D, 4)
@@ -733,7 +757,9 @@ class YoloV3:
 
     def __init__(self, global_batch_size, img_size, number_classes, anchors=None, learning_rate=1e-4, device=None, seed=None,
                  use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
-                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None):
+                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None):
+        # input sizes train_step / test_step accept: None = img_size only; checked before the device is needed
+        self.train_sizes = check_train_sizes(img_size, train_sizes)
         # gradient accumulation and global-norm clipping: 1 / None = off; checked before the device is needed
         check_grad_args(accumulate_steps, grad_clip_norm)
         self.accumulate_steps = int(accumulate_steps)
@@ -1092,20 +1118,30 @@ class YoloV3:
         return self.learning_rate
 
     # ---- execution -------------------------------------------------------------------------
-    def _plan(self, n, training, bf16=False, slot=0):
+    def _plan(self, n, training, bf16=False, slot=0, size=None):
         bf16 = bool(bf16) and not training
-        key = (int(n), bool(training), bf16, int(slot))
+        size = (int(size[0]), int(size[1])) if size is not None else (self.img_size[0], self.img_size[1])
+        key = (int(n), bool(training), bf16, int(slot), size)
         if bf16:
             self._refresh_bf16()
         if key not in self._plans:
-            self._plans[key] = _Plan(self, int(n), bool(training), bf16)
+            self._plans[key] = _Plan(self, int(n), bool(training), bf16, size)
         return self._plans[key]
+
+    def _step_size(self, images):
+        """(H, W) of a train_step / test_step batch: one of train_sizes (the constructed size alone without multi-scale training)."""
+        shape = tuple(images.shape)
+        if len(shape) == 4 and shape[1] == self.img_size[2] and (int(shape[2]), int(shape[3])) in self.train_sizes:
+            return (int(shape[2]), int(shape[3]))
+        raise ValueError('input shape %s does not match the model input (C,H,W)=%s (Q18: fixed at construction)%s'
+                         % (shape, (self.img_size[2], self.img_size[0], self.img_size[1]),
+                            '' if len(self.train_sizes) == 1 else ' or another of its train_sizes %s' % (self.train_sizes,)))
 
     def _load_inputs(self, plan, images, gt_data=None):
         images = torch.as_tensor(images)
-        if tuple(images.shape[1:]) != (self.img_size[2], self.img_size[0], self.img_size[1]):
+        if tuple(images.shape[1:]) != (self.img_size[2], plan.size[0], plan.size[1]):
             raise ValueError('input shape %s does not match the model input (C,H,W)=%s (Q18: fixed at construction)'
-                             % (tuple(images.shape), (self.img_size[2], self.img_size[0], self.img_size[1])))
+                             % (tuple(images.shape), (self.img_size[2], plan.size[0], plan.size[1])))
         plan.in_nchw.copy_(images.to(torch.float32), non_blocking=True)
         if gt_data is not None:
             for dst, src in zip(plan.gt, gt_data):
@@ -1246,13 +1282,15 @@ class YoloV3:
         loss_metric, loss_xy_metric, loss_wh_metric, loss_obj_metric, loss_class_metric);
         metrics may be None.  Returns the loss value as a 0-d device tensor.
         With accumulate_steps = k > 1 this is one MICRO-step: forward, loss, backward (and all-reduce) as ever, grads folded into
-        the accumulator; only the k-th call in a row advances `iterations` and updates weights, moments and EMA."""
+        the accumulator; only the k-th call in a row advances `iterations` and updates weights, moments and EMA.
+        With train_sizes the images may have any listed (H, W), the labels the matching grids: every size has its own plan (and
+        captured graphs), the weights, moments, accumulator and BatchNorm statistics are the model's."""
         images, gt_data = inputs[0], inputs[1]
         metrics = list(inputs[2:]) + [None] * 5
         n = int(images.shape[0])
         if self._ema_swapped:
             raise RuntimeError('train_step inside ema_weights(): the live weights are parked')
-        plan = self._plan(n, True)
+        plan = self._plan(n, True, size=self._step_size(images))
         self._load_inputs(plan, images, gt_data)
         last = self.micro_step == self.accumulate_steps - 1          # always, without accumulation
         if last:
@@ -1325,7 +1363,7 @@ class YoloV3:
         images, gt_data = inputs[0], inputs[1]
         metrics = list(inputs[2:]) + [None] * 5
         n = int(images.shape[0])
-        plan = self._plan(n, False)
+        plan = self._plan(n, False, size=self._step_size(images))
         self._load_inputs(plan, images, gt_data)
         st = self._stream()
         plan.run_forward(st)
