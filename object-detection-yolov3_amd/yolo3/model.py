@@ -11,7 +11,9 @@ order, and each step is a static list of kernel launches (replayable as one
 HIP graph).  torch is used for device memory, streams and the RCCL all-reduce
 only; there is no torch.nn / autograd / CPU fallback on this path.
 """
+import collections
 import contextlib
+import functools
 import math
 import os
 
@@ -241,14 +243,32 @@ class Mean:
         self.count = 0
 
 
+def _pixels(v):
+    return v.n * v.h * v.w
+
+
+# ticketed conv launch -> the library's workspace query, fed with the launch's own arguments (those before the workspace)
+_WS_QUERY = {
+    'y3_conv2d_fwd': lambda src, wt, bias, k, s, dst, flags, *_: lib.y3_conv2d_fwd_workspace_x(_pixels(dst), src.c, k, dst.c, flags),
+    'y3_conv2d_fwd_bf16_ws': lambda src, wt, bias, k, s, dst, *_: lib.y3_conv2d_fwd_bf16_workspace(_pixels(dst), src.c, k, dst.c),
+    'y3_conv2d_dgrad': lambda ddst, wt, k, s, dsrc, flags: lib.y3_conv2d_dgrad_workspace_x(ddst, k, s, dsrc, flags),
+    'y3_conv2d_dgrad_bn': lambda ddst, wt, k, s, dsrc, flags, *_: lib.y3_conv2d_dgrad_workspace_x(ddst, k, s, dsrc, flags),
+}
+
+# What the forward walk decides once for a layer and keeps as the last element of its op.  fwd / dgrad / wgrad: whether that launch
+# runs the x3 kernels, CONV_X3 or 0 each; everything sized or emitted for the layer reads it from there.  bn: the addresses
+# (save_mean, save_rstd, coef) of a BatchNorm layer's per-channel block, None for a head.
+_Layer = collections.namedtuple('_Layer', 'fwd dgrad wgrad bn')
+
+
 class _Plan:
     """Static launch list for one (batch size, mode, input size).  A plan owns everything whose shape follows the input: activations
     and their gradients, the label tensors, BatchNorm partial rows, the conv / kernel-gradient workspaces, its captured graphs.
     What depends on the weights alone (arenas, transposed and split copies, per-channel BatchNorm blocks) stays on the model."""
 
-    def __init__(self, model, n, training, bf16=False, size=None):
+    def __init__(self, model, n, training, bf16, size):
         self.model = model
-        self.size = (int(size[0]), int(size[1])) if size is not None else (model.img_size[0], model.img_size[1])
+        self.size = size             # (H, W), as YoloV3._plan normalised it
         self.n = n
         self.training = training
         self.bf16 = bool(bf16) and not training     # reduced-precision conv path: inference only (BASELINE config 5)
@@ -276,11 +296,17 @@ class _Plan:
         self.keep.append(args)
         lst.append((fn, args))
 
-    def _conv_call(self, lst, m, sp, fn, *args, need=None):
-        """Emit a conv launch that may use the shared split-K workspace (allocated after the walk)."""
-        if need is None:
-            need = int(lib.y3_conv2d_fwd_workspace(m, sp.cin_pad, sp.k, sp.cout))
-        self.conv_ws_bytes = max(self.conv_ws_bytes, need)
+    def _at(self, arena, off):
+        """Device address of float offset `off` (LayerSpec.*_off and their like) in one of the model's or the plan's flat buffers:
+        an fp32 arena, the bf16 copy of one, or the piece planes (three bf16 planes per kernel, y3_x3_split_weights)."""
+        pieces = 3 if arena is self.model.planes or arena is self.model.planes_t else 1
+        return arena.data_ptr() + arena.element_size() * pieces * off
+
+    def _conv_call(self, lst, fn, *args):
+        """Emit a conv launch that may use the shared split-K workspace (allocated after the walk).  Its need is asked with the
+        launch's own arguments, flags included (Y3_CONV_X3 changes the tile and the split-K plan): with fewer bytes than that
+        the library quietly drops the split (yolo3hip.h)."""
+        self.conv_ws_bytes = max(self.conv_ws_bytes, int(_WS_QUERY[fn.__name__](*args)))
         entry = [fn, args]
         self._conv_ws_users.append(entry)
         lst.append(entry)
@@ -335,13 +361,7 @@ class _Plan:
             self.dz = torch.empty(max_mc, dtype=torch.float32, device=dev)
             # y3_bn_bwd_workspace(): 1 KiB of tickets (zero before the first launch) + <= 512 x 6 x 64 fp64 partials
             self.bnb_ws = torch.zeros(1024 + 512 * 6 * 64 * 8, dtype=torch.uint8, device=dev)
-            self.wg_ws_bytes = 0
-
-        def ptr(off):
-            return P.data_ptr() + 4 * off
-
-        def wbf(off):
-            return mdl.params_t_bf16.data_ptr() + 2 * off
+        ptr = functools.partial(self._at, P)
 
         def conv_layer(src, out=None, resid=None):
             """model.py:29-39 (+ the tf.add of model.py:47 when resid is given)."""
@@ -350,49 +370,50 @@ class _Plan:
             sp = specs[i]
             oh, ow = -(-src.h // sp.s), -(-src.w // sp.s)
             y = out if out is not None else self._new(N, oh, ow, sp.cout, dtype=act)
-            ch = mdl.chan.data_ptr() + 4 * sp.ch_off       # per-layer [scale|shift|mean|rstd|coef(3)] block
+            a = self._new(N, oh, ow, sp.cout) if tr else None      # the convolution's own output: BatchNorm reads it again in backward
+            rv = resid.v if resid is not None else None
+            ch = self._at(mdl.chan, sp.ch_off)       # per-layer [scale|shift|mean|rstd|coef(3)] block
             cs = sp.cout * 4
             scale, shift, smean, srstd, coef = ch, ch + cs, ch + 2 * cs, ch + 3 * cs, ch + 4 * cs
-            mmean = mdl.moving.data_ptr() + 4 * sp.mv_off
-            mvar = mdl.moving.data_ptr() + 4 * (mdl.moving_stride + sp.mv_off)
-            # fp32 arithmetic as three bf16 pieces per operand (conv_x3.hip) for the layers the model's policy names: the kernel then
-            # wants the copy of the weights with K contiguous per output column, i.e. the TRANSPOSED arena in the forward pass
-            x3 = CONV_X3 if (not bf and mdl.x3_forward(sp, N * oh * ow)) else 0
-            wfwd = (mdl.planes_t.data_ptr() + 2 * 3 * sp.w_off) if x3 else ptr(sp.w_off)      # x3: the three bf16 planes of the transposed kernel
-            fneed = int(lib.y3_conv2d_fwd_workspace_x(N * oh * ow, sp.cin_pad, sp.k, sp.cout, x3))
-            if x3:
+            # fp32 arithmetic as three bf16 pieces per operand (conv_x3.hip) for the launches the model's policy names.  The gradients
+            # have their activations' geometry, which is all the data-gradient query reads; the first layer has no data gradient.
+            x3 = _Layer(CONV_X3 if not bf and mdl.x3_forward(sp, N * oh * ow) else 0,
+                        CONV_X3 if tr and src is not x0 and mdl.x3_dgrad(a.v, sp.k, sp.s, src.v) else 0,
+                        CONV_X3 if tr and mdl.x3_wgrad(sp, N * oh * ow) else 0, (smean, srstd, coef))
+            if x3.fwd:
                 self.x3_fwd.append(i)
+            # the x3 kernel wants the copy of the weights with K contiguous per output column, i.e. the three bf16 planes of the
+            # TRANSPOSED kernel in the forward pass
+            wfwd = self._at(mdl.planes_t, sp.w_off) if x3.fwd else ptr(sp.w_off)
             if tr:
-                a = self._new(N, oh, ow, sp.cout)
-                tiles = lib.y3_conv2d_stats_tiles_x(a.m, sp.cin_pad, sp.k, sp.cout, x3)
+                tiles = lib.y3_conv2d_stats_tiles_x(a.m, sp.cin_pad, sp.k, sp.cout, x3.fwd)
                 assert tiles * 2 * sp.cout <= self.stats_ws.numel()
-                self._conv_call(self.fwd, a.m, sp, lib.y3_conv2d_fwd, src.v, wfwd, ptr(sp.b_off), sp.k, sp.s, a.v, EPI_LRELU | x3,
-                                LRELU_ALPHA, None, None, None, self.stats_ws.data_ptr(), need=fneed)
+                self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, wfwd, ptr(sp.b_off), sp.k, sp.s, a.v, EPI_LRELU | x3.fwd,
+                                LRELU_ALPHA, None, None, None, self.stats_ws.data_ptr())
                 self._emit(self.fwd, lib.y3_bn_stats_finalize, self.stats_ws.data_ptr(), tiles, sp.cout, a.m, ptr(sp.g_off), ptr(sp.be_off),
-                           BN_EPS, BN_MOMENTUM, mmean, mvar, smean, srstd, scale, shift)
-                self._emit(self.fwd, lib.y3_bn_apply, a.v, scale, shift, resid.v if resid is not None else None, y.v)
-                self.ops.append(('conv_layer', i, src, a, y, resid, (smean, srstd, coef)))
+                           BN_EPS, BN_MOMENTUM, self._at(mdl.moving, sp.mv_off), self._at(mdl.moving, mdl.moving_stride + sp.mv_off),
+                           smean, srstd, scale, shift)
+                self._emit(self.fwd, lib.y3_bn_apply, a.v, scale, shift, rv, y.v)
+                self.ops.append(('conv_layer', i, src, a, y, resid, x3))
             elif bf and i > 0:
                 # (the shared conv workspace: small-M layers are split along K, y3_conv2d_fwd_bf16_workspace)
                 # the patch kernels of the early 3x3 layers only where the layer streams from HBM (yolo3hip.h, Y3_BF16_NO_PATCH;
                 # same box, graph replay: 25 x 608^2 6.54 -> 6.25 ms with them, 8 x 608^2 2.56 -> 2.61, 8 x 416^2 1.74 -> 1.78)
                 moved = 2 * y.m * (sp.s * sp.s * sp.cin_pad + sp.cout * (2 if resid is not None else 1))
-                self._conv_call(self.fwd, y.m, sp, lib.y3_conv2d_fwd_bf16_ws, src.v, wbf(sp.w_off), ptr(sp.b_off), sp.k, sp.s, y.v, 0,
-                                EPI_LRELU | (0 if moved >= BF16_PATCH_MIN_BYTES else BF16_NO_PATCH),
-                                LRELU_ALPHA, scale, shift, resid.v if resid is not None else None,
-                                need=int(lib.y3_conv2d_fwd_bf16_workspace(y.m, sp.cin_pad, sp.k, sp.cout)))
+                self._conv_call(self.fwd, lib.y3_conv2d_fwd_bf16_ws, src.v, self._at(mdl.params_t_bf16, sp.w_off), ptr(sp.b_off), sp.k, sp.s, y.v, 0,
+                                EPI_LRELU | (0 if moved >= BF16_PATCH_MIN_BYTES else BF16_NO_PATCH), LRELU_ALPHA, scale, shift, rv)
             elif bf and sp.cin_pad == 4 and sp.cout == 32 and sp.k == 3 and sp.s == 1:
                 # the RGB layer: fp32 direct convolution, one rounding on the bf16 store
                 self._emit(self.fwd, lib.y3_conv2d_first_bf16, src.v, ptr(sp.w_off), ptr(sp.b_off), y.v, EPI_LRELU, LRELU_ALPHA, scale, shift)
             elif bf:
                 # (other first-layer shapes) fp32 MFMA kernel, output rounded to bf16 once
                 y32 = self._new(N, oh, ow, sp.cout)
-                self._conv_call(self.fwd, y.m, sp, lib.y3_conv2d_fwd, src.v, ptr(sp.w_off), ptr(sp.b_off), sp.k, sp.s, y32.v, EPI_LRELU,
+                self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, ptr(sp.w_off), ptr(sp.b_off), sp.k, sp.s, y32.v, EPI_LRELU,
                                 LRELU_ALPHA, scale, shift, None, None)
                 self._emit(self.fwd, lib.y3_f32_to_bf16, y32.buf.data_ptr(), y.buf.data_ptr(), y.buf.numel())
             else:
-                self._conv_call(self.fwd, y.m, sp, lib.y3_conv2d_fwd, src.v, wfwd, ptr(sp.b_off), sp.k, sp.s, y.v, EPI_LRELU | x3,
-                                LRELU_ALPHA, scale, shift, resid.v if resid is not None else None, None, need=fneed)
+                self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, wfwd, ptr(sp.b_off), sp.k, sp.s, y.v, EPI_LRELU | x3.fwd,
+                                LRELU_ALPHA, scale, shift, rv, None)
             self.layer_out.append(y)
             return y
 
@@ -416,11 +437,11 @@ class _Plan:
             sp = specs[i]
             fm = self._new(N, src.h, src.w, D, Dld, zero=True)
             if bf:      # bf16 operands, fp32 feature map: decode / loss / NMS stay fp32
-                self._conv_call(self.fwd, fm.m, sp, lib.y3_conv2d_fwd_bf16_ws, src.v, wbf(sp.w_off), ptr(sp.b_off), 1, 1, fm.v, 1, 0, 0.0, None, None, None,
-                                need=int(lib.y3_conv2d_fwd_bf16_workspace(fm.m, sp.cin_pad, 1, sp.cout)))
+                self._conv_call(self.fwd, lib.y3_conv2d_fwd_bf16_ws, src.v, self._at(mdl.params_t_bf16, sp.w_off), ptr(sp.b_off), 1, 1, fm.v, 1, 0, 0.0,
+                                None, None, None)
                 return fm
-            self._conv_call(self.fwd, fm.m, sp, lib.y3_conv2d_fwd, src.v, ptr(sp.w_off), ptr(sp.b_off), 1, 1, fm.v, 0, 0.0, None, None, None, None)
-            self.ops.append(('head', i, src, fm))
+            self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, ptr(sp.w_off), ptr(sp.b_off), 1, 1, fm.v, 0, 0.0, None, None, None, None)
+            self.ops.append(('head', i, src, fm, _Layer(0, 0, 0, None)))      # the heads stay on the fp32 kernels
             return fm
 
         def upsample_into(src, dst):
@@ -458,7 +479,6 @@ class _Plan:
         fm3 = head(x, 2)
         assert li[0] == len(specs)
         self.fms = [fm1, fm2, fm3]
-        self.x0 = x0
 
         # decode (model.py:169-212)
         self.nb = sum(f.h * f.w * A for f in self.fms)
@@ -476,7 +496,7 @@ class _Plan:
         self.loss_calls = []
         for si, (f, g) in enumerate(zip(self.fms, self.gt)):
             f.grad = self._new(N, f.h, f.w, D, Dld, zero=True)
-            ws = self.loss_ws.data_ptr() + 4 * si * ws_floats
+            ws = self._at(self.loss_ws, si * ws_floats)
             if mdl.box_loss == 'mse':    # the reference's loss: the call list of a model built without box-loss arguments
                 self.loss_calls.append((lib.y3_loss_fwd_bwd, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
                                                               self.loss4.data_ptr(), f.grad.v, ws)))
@@ -502,26 +522,36 @@ class _Plan:
                 ch.grad = _T(t.grad.buf, ch.n, ch.h, ch.w, ch.c, ch.ld, ch.off)
         return t.grad
 
+    def _kernel_grad(self, fn, *args):
+        """Emit a kernel gradient (args up to the workspace): on the main stream, or with a side stream there, between an event the
+        main stream records now (the operands are complete) and one the side stream records behind the launch.  Every kernel
+        gradient goes the same way: they share one slab workspace, in stream order.  Returns the index of that second event (None
+        on the main stream): whoever overwrites an operand, or reads the result, waits for it."""
+        args += (self.wg_ws.data_ptr(), self.wg_ws_bytes)
+        if self.side is None:
+            self._emit(self.bwd, fn, *args)
+            return None
+        self.events += [torch.cuda.Event(), torch.cuda.Event()]
+        e_go, e_wg = len(self.events) - 2, len(self.events) - 1
+        self.bwd.append(('record', e_go))
+        self.keep.append(args)
+        self.bwd.append(('side_call', (fn, args, e_go, e_wg)))
+        return e_wg
+
+    def _main_wait(self, e):
+        if e is not None:
+            self.bwd.append(('main_wait', e))
+
     def _build_backward(self):
         mdl = self.model
         specs = mdl.specs
-        G = mdl.grads
-        Wt = mdl.params_t
-        N = self.n
+        gptr = functools.partial(self._at, mdl.grads)
 
-        def gptr(off):
-            return G.data_ptr() + 4 * off
-
-        # concat parents own the gradient storage of their slices
         wg_need = 0
         for op in self.ops:
             if op[0] in ('conv_layer', 'head'):
                 sp = specs[op[1]]
-                src = op[2]
-                dd = op[3]
-                need = lib.y3_conv2d_wgrad_workspace_x(src.v, view(self.dz, dd.n, dd.h, dd.w, sp.cout), sp.k, sp.s,
-                                                       CONV_X3 if (op[0] == 'conv_layer' and mdl.x3_wgrad(sp, dd.m)) else 0)
-                wg_need = max(wg_need, int(need))
+                wg_need = max(wg_need, int(lib.y3_conv2d_wgrad_workspace_x(op[2].v, op[3].v, sp.k, sp.s, op[-1].wgrad)))     # (dz has op[3]'s geometry)
         self.wg_ws = torch.zeros(max(wg_need // 4, 4), dtype=torch.float32, device=mdl.device)      # tickets + slabs, zeroed once
         self.wg_ws_bytes = wg_need
 
@@ -550,21 +580,18 @@ class _Plan:
         for op in self.ops:
             if op[0] != 'conv_layer':
                 continue
-            _, i, src, a, y, resid, _ = op
+            a, y = op[3], op[4]
             cons = first_consumer.get(id(y))
             if cons is None or cons[0] != 'conv_layer' or cons[2] is not y or y.children or y is self.x0:
                 continue      # (a concat SLICE qualifies: later readers of the whole concat are visited earlier by the reversed walk)
             csp = specs[cons[1]]
-            ca = cons[3]
-            dd = view(self.dz, ca.n, ca.h, ca.w, csp.cout)
-            tiles = int(lib.y3_conv2d_dgrad_bn_tiles_x(dd, csp.k, csp.s, y.v, CONV_X3 if mdl.x3_dgrad(csp, y.m) else 0))
+            tiles = int(lib.y3_conv2d_dgrad_bn_tiles_x(cons[3].v, csp.k, csp.s, y.v, cons[-1].dgrad))      # (geometry only, as in conv_layer)
             if tiles <= 0:
                 continue
             part = torch.empty(tiles * 6 * y.c, dtype=torch.float32, device=mdl.device)
             epi_of[id(cons)] = (a, part, tiles)
             epi_for[id(op)] = (part, tiles)
         self.epilogue_stats_layers = len(epi_for)
-        first_src = self.x0
         # The kernel gradient of a layer and its data gradient both start from dz and are independent.  Each is a single
         # round of workgroups with ~8 us of prologue + epilogue in which the matrix pipe idles, so the kernel gradients go to
         # a second stream and fill those bubbles: 23.3 -> 21.4 ms per step with host launches.  (Replayed as a HIP graph
@@ -575,28 +602,18 @@ class _Plan:
         self.events = []
         dz_bufs = [self.dz, torch.empty_like(self.dz)] if two else [self.dz]
         dz_busy = [None, None]          # event index of the wgrad still reading each dz buffer
-        head_wg = []
+        head_wg = None                  # ... of the newest head's
         nconv = 0
         for op in reversed(self.ops):
             kind = op[0]
             if kind == 'head':
-                _, i, src, fm = op
+                _, i, src, fm, _ = op
                 sp = specs[i]
                 dfm = fm.grad
                 self._emit(self.bwd, lib.y3_colsum, dfm.v, gptr(sp.b_off))
-                if two:     # every kernel gradient goes through the side stream: they share one slab workspace, in stream order
-                    self.events += [torch.cuda.Event(), torch.cuda.Event()]
-                    e_go, e_wg = len(self.events) - 2, len(self.events) - 1
-                    self.bwd.append(('record', e_go))
-                    wargs = (src.v, dfm.v, 1, 1, gptr(sp.w_off), self.wg_ws.data_ptr(), self.wg_ws_bytes)
-                    self.keep.append(wargs)
-                    self.bwd.append(('side_call', (lib.y3_conv2d_wgrad, wargs, e_go, e_wg)))
-                    head_wg.append(e_wg)
-                else:
-                    self._emit(self.bwd, lib.y3_conv2d_wgrad, src.v, dfm.v, 1, 1, gptr(sp.w_off), self.wg_ws.data_ptr(), self.wg_ws_bytes)
+                head_wg = self._kernel_grad(lib.y3_conv2d_wgrad, src.v, dfm.v, 1, 1, gptr(sp.w_off))
                 ds = self._grad_of(src)
-                self._conv_call(self.bwd, ds.m, sp, lib.y3_conv2d_dgrad, dfm.v, Wt.data_ptr() + 4 * sp.w_off, 1, 1, ds.v, EPI_ACCUM if src.gw else 0,
-                                need=int(lib.y3_conv2d_dgrad_workspace(dfm.v, 1, 1, ds.v)))
+                self._conv_call(self.bwd, lib.y3_conv2d_dgrad, dfm.v, self._at(mdl.params_t, sp.w_off), 1, 1, ds.v, EPI_ACCUM if src.gw else 0)
                 src.mark_written()
                 self.bwd.append(('layer_done', i))
             elif kind == 'upsample':
@@ -606,11 +623,13 @@ class _Plan:
                 self._emit(self.bwd, lib.y3_upsample_sum2x_bwd, dst.grad.v, ds.v)
                 src.mark_written()
             else:
-                _, i, src, a, y, resid, (smean, srstd, coef) = op
+                _, i, src, a, y, resid, x3 = op
+                smean, srstd, coef = x3.bn
                 sp = specs[i]
                 assert y.gw, 'gradient of layer %d output never produced' % i
                 dy = y.grad
                 dr = None
+                dr_acc = 0
                 if resid is not None:                       # out = resid + y  ->  d resid += d out, fused into the pass that reads dy anyway
                     dr = self._grad_of(resid)
                     dr_acc = 1 if resid.gw else 0
@@ -619,72 +638,56 @@ class _Plan:
                 nconv += 1
                 dz = _T(dz_bufs[slot], a.n, a.h, a.w, sp.cout)
                 self.keep.append(dz)
-                if id(op) in epi_for:
+                epi = epi_for.get(id(op))
+                if epi is not None:
                     # the statistics were summed by the data gradient that completed dy: finalize, then apply (+ residual fan-in)
-                    part, tiles = epi_for[id(op)]
-                    self._emit(self.bwd, lib.y3_bn_bwd_finalize_tiles, part.data_ptr(), tiles, sp.cout, a.m, mdl.params.data_ptr() + 4 * sp.g_off,
+                    part, tiles = epi
+                    self._emit(self.bwd, lib.y3_bn_bwd_finalize_tiles, part.data_ptr(), tiles, sp.cout, a.m, self._at(mdl.params, sp.g_off),
                                smean, srstd, LRELU_ALPHA, gptr(sp.g_off), gptr(sp.be_off), gptr(sp.b_off), coef)
-                    if two and dz_busy[slot] is not None:
-                        self.bwd.append(('main_wait', dz_busy[slot]))
-                    if dr is not None:
-                        self._emit(self.bwd, lib.y3_bn_bwd_apply_fanin, dy.v, a.v, coef, LRELU_ALPHA, dz.v, dr.v, dr_acc)
-                    else:
-                        self._emit(self.bwd, lib.y3_bn_bwd_apply, dy.v, a.v, coef, LRELU_ALPHA, dz.v)
                 else:
                     assert int(lib.y3_bn_bwd_workspace(a.m, sp.cout)) <= self.bnb_ws.numel()
-                    self._emit(self.bwd, lib.y3_bn_bwd_stats, dy.v, a.v, dr.v if dr is not None else None, dr_acc if dr is not None else 0,
-                               mdl.params.data_ptr() + 4 * sp.g_off, smean, srstd, LRELU_ALPHA, gptr(sp.g_off), gptr(sp.be_off), gptr(sp.b_off), coef,
+                    self._emit(self.bwd, lib.y3_bn_bwd_stats, dy.v, a.v, dr.v if dr is not None else None, dr_acc,
+                               self._at(mdl.params, sp.g_off), smean, srstd, LRELU_ALPHA, gptr(sp.g_off), gptr(sp.be_off), gptr(sp.b_off), coef,
                                self.bnb_ws.data_ptr(), self.bnb_ws.numel())
-                    if two and dz_busy[slot] is not None:
-                        self.bwd.append(('main_wait', dz_busy[slot]))
-                    self._emit(self.bwd, lib.y3_bn_bwd_apply, dy.v, a.v, coef, LRELU_ALPHA, dz.v)
-                wx3 = CONV_X3 if mdl.x3_wgrad(sp, a.m) else 0      # kernel gradient on the x3 arithmetic (both operands are activations: no weight copy involved)
-                if wx3:
-                    self.x3_wgrad.append(i)
-                if two:
-                    self.events += [torch.cuda.Event(), torch.cuda.Event()]
-                    e_dz, e_wg = len(self.events) - 2, len(self.events) - 1
-                    self.bwd.append(('record', e_dz))
-                    wargs = (src.v, dz.v, sp.k, sp.s, gptr(sp.w_off), wx3, self.wg_ws.data_ptr(), self.wg_ws_bytes)
-                    self.keep.append(wargs)
-                    self.bwd.append(('side_call', (lib.y3_conv2d_wgrad_x, wargs, e_dz, e_wg)))
-                    dz_busy[slot] = e_wg
+                self._main_wait(dz_busy[slot])      # the kernel gradient of two layers ago still reads this dz buffer
+                if epi is not None and dr is not None:
+                    self._emit(self.bwd, lib.y3_bn_bwd_apply_fanin, dy.v, a.v, coef, LRELU_ALPHA, dz.v, dr.v, dr_acc)
                 else:
-                    self._emit(self.bwd, lib.y3_conv2d_wgrad_x, src.v, dz.v, sp.k, sp.s, gptr(sp.w_off), wx3, self.wg_ws.data_ptr(), self.wg_ws_bytes)
-                if src is not first_src:
+                    self._emit(self.bwd, lib.y3_bn_bwd_apply, dy.v, a.v, coef, LRELU_ALPHA, dz.v)
+                # (kernel gradient on the x3 arithmetic: both operands are activations, no weight copy involved)
+                dz_busy[slot] = self._kernel_grad(lib.y3_conv2d_wgrad_x, src.v, dz.v, sp.k, sp.s, gptr(sp.w_off), x3.wgrad)
+                if x3.wgrad:
+                    self.x3_wgrad.append(i)
+                if src is not self.x0:
                     ds = self._grad_of(src)
-                    # x3 data gradient: the kernel wants K (= this layer's output channels) contiguous per column: the Keras arena
-                    x3 = CONV_X3 if mdl.x3_dgrad(sp, ds.m) else 0
-                    wdg = (mdl.planes.data_ptr() + 2 * 3 * sp.w_off) if x3 else (Wt.data_ptr() + 4 * sp.w_off)      # x3: planes of the Keras kernel
-                    dflags = (EPI_ACCUM if src.gw else 0) | x3
-                    dneed = int(lib.y3_conv2d_dgrad_workspace_x(dz.v, sp.k, sp.s, ds.v, x3))
-                    if x3:
+                    # x3 data gradient: the kernel wants K (= this layer's output channels) contiguous per column: the planes of the Keras arena
+                    wdg = self._at(mdl.planes, sp.w_off) if x3.dgrad else self._at(mdl.params_t, sp.w_off)
+                    dflags = (EPI_ACCUM if src.gw else 0) | x3.dgrad
+                    if x3.dgrad:
                         self.x3_dgrad.append(i)
                     if id(op) in epi_of:      # this launch completes d(src): it also sums the BatchNorm-backward moments of the producer
                         pa, part, _ = epi_of[id(op)]
-                        self._conv_call(self.bwd, ds.m, sp, lib.y3_conv2d_dgrad_bn, dz.v, wdg, sp.k, sp.s, ds.v, dflags, pa.v, part.data_ptr(), need=dneed)
+                        self._conv_call(self.bwd, lib.y3_conv2d_dgrad_bn, dz.v, wdg, sp.k, sp.s, ds.v, dflags, pa.v, part.data_ptr())
                         self.keep.append(part)
                     else:
-                        self._conv_call(self.bwd, ds.m, sp, lib.y3_conv2d_dgrad, dz.v, wdg, sp.k, sp.s, ds.v, dflags, need=dneed)
+                        self._conv_call(self.bwd, lib.y3_conv2d_dgrad, dz.v, wdg, sp.k, sp.s, ds.v, dflags)
                     src.mark_written()
                 self.bwd.append(('layer_done', i))
-        for e in dz_busy + head_wg[-1:]:
-            if two and e is not None:
-                self.bwd.append(('main_wait', e))
+        for e in dz_busy + [head_wg]:
+            self._main_wait(e)
 
     # -- execution -------------------------------------------------------------------
-    def _run(self, lst, stream, hook=None):
+    def _run(self, lst, stream, dist=None):
         main = None
         pending = []                   # kernel gradients in flight on the side stream (event indices)
         for fn, args in lst:
             if fn == 'layer_done':
-                if hook is not None:
-                    dist_ = self.model.dist
-                    if pending and (dist_ is None or args in getattr(dist_, '_by_layer', {args: 1})):
+                if dist is not None:
+                    if pending and dist.ends_bucket(args):
                         for e in pending:          # a gradient bucket is about to be all-reduced: its kernel gradients must be in
                             main.wait_event(self.events[e])
                         pending = []
-                    hook(args)
+                    dist.on_layer_done(args)
                 continue
             if fn in ('record', 'main_wait', 'side_call'):
                 if main is None:
@@ -713,14 +716,19 @@ class _Plan:
         fn, args = self.decode_call
         check(fn(*args, stream), 'y3_decode_fwd')
 
+    def run_inference(self, stream, skip_input=False):
+        self.run_forward(stream, skip_input)
+        self.run_decode(stream)
+
     def run_loss(self, stream):
         # (a kernel launch, not tensor.zero_(): inside a captured step nothing may turn into a memset node -- DESIGN 9)
         check(lib.y3_fill(self.loss4.data_ptr(), 4, 0.0, stream), 'y3_fill')
         for fn, args in self.loss_calls:
             check(fn(*args, stream), 'y3_loss_fwd_bwd')
 
-    def run_backward(self, stream, hook=None):
-        self._run(self.bwd, stream, hook)
+    def run_backward(self, stream, dist=None):
+        """dist: the model's DataParallel (all-reduces each gradient bucket as its last layer completes), or None."""
+        self._run(self.bwd, stream, dist)
 
 
 class _CallableModel:
@@ -856,37 +864,37 @@ class YoloV3:
         self._plans = {}
         self._tr_table = None
         self._fold_table = None
+        self._adam_call = self._adam_launch()
         self._init_weights(seed)
         self.model = _CallableModel(self, False)
         self.model_feature_maps = _CallableModel(self, True)
         self.optimizer = self
 
     # ---- which launches run the x3 kernels ---------------------------------------
-    def _x3_policy(self, c, ntaps, nout, m, stride, forward):
-        if self.conv_arithmetic == 'f32' or not lib.y3_conv2d_x3_ok(m, c, ntaps, nout) or (stride != 1 and not forward):
+    def x3_forward(self, sp, m_out):
+        if self.conv_arithmetic == 'f32' or not lib.y3_conv2d_x3_ok(m_out, sp.cin_pad, sp.k * sp.k, sp.cout):
+            return False
+        # measured (tools/x3_check.py --all, tools/layer_times.py; batch 8 at 416^2, launch by launch and inside the step): the 3x3
+        # layers gain -- every one the kernels take (>= 32 input channels): 208^2 32->64 140 -> 116 us, the others 1.5-1.8x; the 1x1
+        # layers (4-64 K steps: prologue + epilogue bound) do not
+        return self.conv_arithmetic == 'x3-all' or sp.k == 3
+
+    def x3_dgrad(self, ddst, k, s, dsrc):
+        """ddst, dsrc: views with the geometry of the gradients of the layer's output (its channels are contracted) and input.  The
+        shapes the kernels take are the library's to say, for both strides; the policy below is measured."""
+        if self.conv_arithmetic == 'f32' or not lib.y3_conv2d_dgrad_x3_ok(ddst, k, s, dsrc):
             return False
         if self.conv_arithmetic == 'x3-all':
             return True
-        # measured (tools/x3_check.py --all, tools/layer_times.py; batch 8 at 416^2, launch by launch and inside the step): the 3x3
-        # layers gain -- forward 1.2-1.8x, stride-1 data gradients 1.1-1.7x with >= 128 contracted channels and >= 64 outputs
-        # (0.79x for the 64 -> 32 one); the 1x1 layers (4-64 K steps: prologue + epilogue bound) do not
-        if ntaps != 9:
-            return False
-        if forward:
-            return True          # every 3x3 layer the kernels take (>= 32 input channels): 208^2 32->64 140 -> 116 us, the others 1.5-1.8x
-        return c >= 128 and nout >= 64
-
-    def x3_forward(self, sp, m_out):
-        return self._x3_policy(sp.cin_pad, sp.k * sp.k, sp.cout, m_out, sp.s, True)
-
-    def x3_dgrad(self, sp, m_in):
-        if sp.s == 2:
-            # the merged launch of the four parity classes (y3_conv2d_dgrad_x3_ok): >= 64 input channels, output channels a power of two
-            if self.conv_arithmetic == 'f32' or sp.k != 3 or sp.cin_pad < 64 or sp.cout % 16 or (sp.cout & (sp.cout - 1)):
-                return False
-            # measured (tools/layer_times.py): 163 -> 125, 151 -> 124, 142 -> 103 us at 13^2 / 26^2 / 52^2 output; 152 -> 151 for the 64-channel layer
-            return self.conv_arithmetic == 'x3-all' or sp.cin_pad >= 128
-        return self._x3_policy(sp.cout, sp.k * sp.k, sp.cin_pad, m_in, sp.s, False)
+        if k != 3:
+            return False      # the 1x1 layers do not gain (x3_forward)
+        if s == 2:
+            # the merged launch of the four parity classes; measured (tools/layer_times.py): 163 -> 125, 151 -> 124, 142 -> 103 us at
+            # 13^2 / 26^2 / 52^2 output; 152 -> 151 for the 64-channel layer
+            return dsrc.c >= 128
+        # measured (as x3_forward): stride-1 data gradients 1.1-1.7x with >= 128 contracted channels and >= 64 outputs (0.79x for the
+        # 64 -> 32 one)
+        return ddst.c >= 128 and dsrc.c >= 64
 
     def x3_wgrad(self, sp, m_out):
         if self.conv_arithmetic == 'f32' or not lib.y3_conv2d_wgrad_x3_ok(m_out, sp.cin_pad, sp.k, sp.cout):
@@ -1120,7 +1128,7 @@ class YoloV3:
     # ---- execution -------------------------------------------------------------------------
     def _plan(self, n, training, bf16=False, slot=0, size=None):
         bf16 = bool(bf16) and not training
-        size = (int(size[0]), int(size[1])) if size is not None else (self.img_size[0], self.img_size[1])
+        size = (int(size[0]), int(size[1])) if size is not None else self.train_sizes[0]      # (the constructed size)
         key = (int(n), bool(training), bf16, int(slot), size)
         if bf16:
             self._refresh_bf16()
@@ -1128,41 +1136,47 @@ class YoloV3:
             self._plans[key] = _Plan(self, int(n), bool(training), bf16, size)
         return self._plans[key]
 
-    def _step_size(self, images):
-        """(H, W) of a train_step / test_step batch: one of train_sizes (the constructed size alone without multi-scale training)."""
+    def _input_size(self, images, sizes=None):
+        """(H, W) of an NCHW batch, which must be one of `sizes`: train_sizes for train_step / test_step, by default the constructed
+        size alone.  Checked before a plan is looked up, so a refused batch leaves none behind."""
+        sizes = self.train_sizes[:1] if sizes is None else sizes
         shape = tuple(images.shape)
-        if len(shape) == 4 and shape[1] == self.img_size[2] and (int(shape[2]), int(shape[3])) in self.train_sizes:
+        if len(shape) == 4 and shape[1] == self.img_size[2] and (int(shape[2]), int(shape[3])) in sizes:
             return (int(shape[2]), int(shape[3]))
         raise ValueError('input shape %s does not match the model input (C,H,W)=%s (Q18: fixed at construction)%s'
                          % (shape, (self.img_size[2], self.img_size[0], self.img_size[1]),
-                            '' if len(self.train_sizes) == 1 else ' or another of its train_sizes %s' % (self.train_sizes,)))
+                            '' if len(sizes) == 1 else ' or another of its train_sizes %s' % (sizes,)))
 
     def _load_inputs(self, plan, images, gt_data=None):
-        images = torch.as_tensor(images)
-        if tuple(images.shape[1:]) != (self.img_size[2], plan.size[0], plan.size[1]):
-            raise ValueError('input shape %s does not match the model input (C,H,W)=%s (Q18: fixed at construction)'
-                             % (tuple(images.shape), (self.img_size[2], plan.size[0], plan.size[1])))
-        plan.in_nchw.copy_(images.to(torch.float32), non_blocking=True)
+        plan.in_nchw.copy_(torch.as_tensor(images).to(torch.float32), non_blocking=True)
         if gt_data is not None:
             for dst, src in zip(plan.gt, gt_data):
                 dst.copy_(torch.as_tensor(src).to(torch.float32).reshape(dst.shape), non_blocking=True)
+
+    def _graph_of(self, body, warm=None):
+        """body(stream) as a HIP graph (the launch lists are static and read no host state).  A warm-up call -- `warm`, by default
+        body itself -- runs first, so that lazy initialisation happens outside the capture."""
+        (warm or body)(self._stream())
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode='thread_local'):      # the prefetch thread may allocate pinned memory meanwhile
+            body(self._stream())
+        return g
 
     def predict(self, images, precision=None, slot=0):
         """The saved 'yolov3' model (model.py:463): NCHW in -> [N, Nb, 5+K].  precision 'bf16' runs every conv after
         the RGB layer on the bf16 MFMA path (fp32 accumulate, fp32 heads / decode); default self.inference_precision.
         Calls with different ``slot`` use separate activation / output buffers and may run concurrently on different
         streams (inference_tiled does that); calls with the same slot must be stream-ordered."""
-        n = int(images.shape[0])
-        plan = self._plan(n, False, (precision or self.inference_precision) == 'bf16', slot)
+        self._input_size(images)
+        plan = self._plan(int(images.shape[0]), False, (precision or self.inference_precision) == 'bf16', slot)
         self._load_inputs(plan, images)
         if self.use_graph:
             if plan.infer_graph is None:
-                self._capture_inference(plan)
+                plan.infer_graph = self._graph_of(plan.run_inference)
             plan.infer_graph.replay()
         else:
-            st = self._stream()
-            plan.run_forward(st)
-            plan.run_decode(st)
+            plan.run_inference(self._stream())
         return plan.boxes
 
     def predict_tiles(self, img_dev, dtype_code, img_shape, table_ptr, count, tile_size=None, precision=None, slot=0):
@@ -1180,39 +1194,17 @@ class YoloV3:
         check(lib.y3_tile_gather_zscore_nhwc(img_dev.data_ptr(), int(dtype_code), h, w, c, table_ptr, count, self.img_size[0], self.img_size[1],
                                              plan.x0.buf.data_ptr(), plan.x0.ld, plan.zs_ws.data_ptr(), st), 'y3_tile_gather_zscore_nhwc')
         if self.use_graph:
-            if plan.infer_graph_tiles is None:
-                plan.run_forward(st, skip_input=True)
-                plan.run_decode(st)
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode='thread_local'):
-                    st2 = self._stream()
-                    plan.run_forward(st2, skip_input=True)
-                    plan.run_decode(st2)
-                plan.infer_graph_tiles = g
+            if plan.infer_graph_tiles is None:      # forward without the input transpose: the gather above wrote x0
+                plan.infer_graph_tiles = self._graph_of(functools.partial(plan.run_inference, skip_input=True))
             plan.infer_graph_tiles.replay()
         else:
-            plan.run_forward(st, skip_input=True)
-            plan.run_decode(st)
+            plan.run_inference(st, skip_input=True)
         return plan.boxes
-
-    def _capture_inference(self, plan):
-        """forward + decode of one inference plan as a HIP graph (the launch lists are static and read no host state)."""
-        st = self._stream()
-        plan.run_forward(st)
-        plan.run_decode(st)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode='thread_local'):      # the prefetch thread may allocate pinned memory meanwhile
-            st = self._stream()
-            plan.run_forward(st)
-            plan.run_decode(st)
-        plan.infer_graph = g
 
     def feature_maps(self, images, training=False, precision=None):
         """The 'yolov3_fm' model (model.py:462): three NCHW feature maps (fp32 unless precision='bf16' is asked for)."""
-        n = int(images.shape[0])
-        plan = self._plan(n, training, precision == 'bf16')
+        self._input_size(images)
+        plan = self._plan(int(images.shape[0]), training, precision == 'bf16')
         self._load_inputs(plan, images)
         st = self._stream()
         plan.run_forward(st)
@@ -1233,10 +1225,9 @@ class YoloV3:
     def _fwd_bwd(self, plan, st):
         plan.run_forward(st)
         plan.run_loss(st)
-        hook = self.dist.on_layer_done if self.dist is not None else None
         if self.dist is not None:
             self.dist.begin_step()
-        plan.run_backward(st, hook)
+        plan.run_backward(st, self.dist)
 
     def _grad_passes(self, st, last):
         """After the backward pass of a micro-step (kernel gradients joined into `st` by run_backward, all-reduce by finish_step):
@@ -1252,30 +1243,38 @@ class YoloV3:
             check(lib.y3_grad_clip_scale(self._grad_ws.data_ptr(), n, self.accumulate_steps, clip, self.last_grad_norm.data_ptr(),
                                          self.grad_scale_dev.data_ptr(), st), 'y3_grad_clip_scale')
 
-    def _adam(self, st):
+    def _adam_launch(self):
+        """(entry point, arguments up to the stream) of the optimiser step.  Every buffer it names is allocated by the constructor
+        and only ever written in place, so the constructor calls this once; what changes per step (lr_t, the EMA factor, the
+        gradient scale) is read from device memory."""
+        g = self.grad_acc if self.grad_acc is not None else self.grads
+        name = 'y3_adam_step'
+        args = [self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.arena_floats,
+                self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps]
+        if self.ema_decay is not None:
+            # the same Adam step + the weight / moving-statistics average in the same pass (DESIGN §3.7)
+            name += '_ema'
+            args += [self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr(), self.moving.numel(), self.ema_omd_dev.data_ptr()]
         if self._grad_ws is not None:
             # accumulation / clipping on: the same update on (accumulated gradient) * scale (DESIGN §3.10)
-            g = self.grad_acc if self.grad_acc is not None else self.grads
-            if self.ema_decay is None:
-                check(lib.y3_adam_step_scaled(self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
-                                              self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps,
-                                              self.grad_scale_dev.data_ptr(), st), 'y3_adam_step_scaled')
-            else:
-                check(lib.y3_adam_step_ema_scaled(self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
-                                                  self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps,
-                                                  self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr(),
-                                                  self.moving.numel(), self.ema_omd_dev.data_ptr(), self.grad_scale_dev.data_ptr(), st),
-                      'y3_adam_step_ema_scaled')
-        elif self.ema_decay is None:
-            check(lib.y3_adam_step(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
-                                   self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps, st), 'y3_adam_step')
-        else:
-            # the same Adam step + the weight / moving-statistics average in the same pass
-            check(lib.y3_adam_step_ema(self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(),
-                                       self.arena_floats, self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps,
-                                       self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr(), self.moving.numel(),
-                                       self.ema_omd_dev.data_ptr(), st), 'y3_adam_step_ema')
+            name += '_scaled'
+            args += [self.grad_scale_dev.data_ptr()]
+        return getattr(lib, name), tuple(args)
+
+    def _adam(self, st):
+        fn, args = self._adam_call
+        check(fn(*args, st), fn.__name__)
         self._refresh_transposed()
+
+    def _loss_out(self, plan, metrics):
+        """plan.loss4 of the step just enqueued -> the loss the step returns (0-d device tensor), fed with its four parts to the
+        metrics (loss, xy, wh, obj, class; fewer or None = not wanted)."""
+        parts = plan.loss4.clone()
+        loss_value = parts.sum() / float(self.global_batch_size)
+        for mtr, val in zip(metrics, [loss_value, parts[0], parts[1], parts[2], parts[3]]):
+            if mtr is not None:
+                mtr.update_state(val)
+        return loss_value
 
     def train_step(self, inputs):
         """model.py:481-508 for this replica.  inputs = (images, (gt1, gt2, gt3),
@@ -1286,11 +1285,9 @@ class YoloV3:
         With train_sizes the images may have any listed (H, W), the labels the matching grids: every size has its own plan (and
         captured graphs), the weights, moments, accumulator and BatchNorm statistics are the model's."""
         images, gt_data = inputs[0], inputs[1]
-        metrics = list(inputs[2:]) + [None] * 5
-        n = int(images.shape[0])
         if self._ema_swapped:
             raise RuntimeError('train_step inside ema_weights(): the live weights are parked')
-        plan = self._plan(n, True, size=self._step_size(images))
+        plan = self._plan(int(images.shape[0]), True, size=self._input_size(images, self.train_sizes))
         self._load_inputs(plan, images, gt_data)
         last = self.micro_step == self.accumulate_steps - 1          # always, without accumulation
         if last:
@@ -1316,12 +1313,7 @@ class YoloV3:
             if last:
                 self._adam(st)
         self.micro_step = 0 if last else self.micro_step + 1
-        parts = plan.loss4.clone()
-        loss_value = parts.sum() / float(self.global_batch_size)
-        for mtr, val in zip(metrics[:5], [loss_value, parts[0], parts[1], parts[2], parts[3]]):
-            if mtr is not None:
-                mtr.update_state(val)
-        return loss_value
+        return self._loss_out(plan, inputs[2:])
 
     def _capture(self, plan, last=True):
         """Capture forward + loss + backward + Adam of one step into a HIP graph.
@@ -1332,24 +1324,24 @@ class YoloV3:
         micro-step that only folds its gradients into the accumulator (`first`
         comes from device memory, so one graph serves micro-steps 1 .. k-1),
         last=True adds the norm, the scale and the scaled Adam step."""
-        moving = self.moving.clone()
-        st = self._stream()
-        plan.run_forward(st)
-        plan.run_loss(st)
-        plan.run_backward(st)
-        self.moving.copy_(moving)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode='thread_local'):      # the prefetch thread may allocate pinned memory meanwhile
-            st = self._stream()
+        def fwd_bwd(st):      # (a captured step has no data parallelism: train_step)
             plan.run_forward(st)
             plan.run_loss(st)
             plan.run_backward(st)
+
+        def warm(st):
+            moving = self.moving.clone()
+            fwd_bwd(st)
+            self.moving.copy_(moving)
+
+        def step(st):
+            fwd_bwd(st)
             if self._grad_ws is not None:
                 self._grad_passes(st, last)
             if last:
                 self._adam(st)
-        setattr(plan, 'graph' if last else 'graph_micro', g)
+
+        setattr(plan, 'graph' if last else 'graph_micro', self._graph_of(step, warm))
 
     def dist_train_step(self, dist_strategy, inputs):
         """model.py:510-515: per-replica step + SUM of the per-replica losses."""
@@ -1361,19 +1353,12 @@ class YoloV3:
     def test_step(self, inputs):
         """model.py:517-534: BN in inference mode, loss + metrics, no update."""
         images, gt_data = inputs[0], inputs[1]
-        metrics = list(inputs[2:]) + [None] * 5
-        n = int(images.shape[0])
-        plan = self._plan(n, False, size=self._step_size(images))
+        plan = self._plan(int(images.shape[0]), False, size=self._input_size(images, self.train_sizes))
         self._load_inputs(plan, images, gt_data)
         st = self._stream()
         plan.run_forward(st)
         plan.run_loss(st)
-        parts = plan.loss4.clone()
-        loss_value = parts.sum() / float(self.global_batch_size)
-        for mtr, val in zip(metrics[:5], [loss_value, parts[0], parts[1], parts[2], parts[3]]):
-            if mtr is not None:
-                mtr.update_state(val)
-        return loss_value
+        return self._loss_out(plan, inputs[2:])
 
     def dist_test_step(self, dist_strategy, inputs):
         """model.py:536-540."""

@@ -207,11 +207,14 @@ class DataParallel:
             return None
         return w              # gloo: finish_step waits on the host
 
+    def ends_bucket(self, layer_idx):
+        """Whether backward completes a gradient bucket with this layer (its lowest): on_layer_done then all-reduces it."""
+        return layer_idx in self._by_layer
+
     def on_layer_done(self, layer_idx):
-        b = self._by_layer.get(layer_idx)
-        if b is None or not self.active:
+        if not (self.active and self.ends_bucket(layer_idx)):
             return
-        lo, hi, _ = b
+        lo, hi, _ = self._by_layer[layer_idx]
         g = self.model.grads[lo:hi]
         if self.comm is None:            # host tensors (CPU tests)
             self._works.append(dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.group, async_op=True))

@@ -241,6 +241,87 @@ def test_bf16_layers_teacher_forced(img, n):
         assert bool(assert_fm), 'head %d' % j
 
 
+@pytest.mark.parametrize('conv_arithmetic', ['f32', 'x3', 'x3-all'])
+def test_every_emitted_launch_fits_what_was_sized_for_it(conv_arithmetic, monkeypatch):
+    """The plan decides per layer which launches run the x3 kernels and sizes workspaces, picks weight operands and fills its x3
+    lists from that decision.  Here every conv launch the plans emit (training with the side stream and for graph capture,
+    inference fp32 and bf16; nothing is launched) is held against the library's own word for ITS arguments and flags:
+      * the workspace query of the entry point, asked with the entry's own arguments, needs no more than the entry carries;
+      * the weight operand lies in the piece planes (planes_t forward, planes data gradient) exactly when the flags hold
+        CONV_X3, else in params (forward) / params_t (data gradient) / the bf16 copy (bf16 forward);
+      * plan.x3_fwd / x3_dgrad / x3_wgrad name exactly the layers whose launch carries the flag.
+    Batch 4 at 96^2 is the smallest case at which all three kinds have x3 launches (test_gpu_teacher_forced.py)."""
+    from yolo3 import _hip
+    from yolo3.model import YoloV3
+    lib, X3 = _hip.lib, _hip.CONV_X3
+    monkeypatch.delenv('Y3_WGRAD_STREAM', raising=False)
+    n, img = 4, 96
+    yolo = YoloV3(n, [img, img, 3], K, ANCHORS, conv_arithmetic=conv_arithmetic, seed=1)
+    side = yolo._plan(n, True)
+    yolo._plans.clear()
+    yolo.use_graph = True
+    plans = {'side': side, 'graph': yolo._plan(n, True), 'fp32': yolo._plan(n, False), 'bf16': yolo._plan(n, False, True)}
+    assert side.side is not None and plans['graph'].side is None
+    assert any(fn == 'side_call' for fn, _ in side.bwd) and not any(fn == 'side_call' for fn, _ in plans['graph'].bwd)
+
+    def layer_at(addr, arena, per_float):
+        """Layer whose kernel starts at `addr` of `arena` (per_float bytes per arena float); None if addr is not in it."""
+        if arena is None or not 0 <= addr - arena.data_ptr() < arena.numel() * arena.element_size():
+            return None
+        return {sp.w_off * per_float: i for i, sp in enumerate(yolo.specs)}[addr - arena.data_ptr()]
+
+    def pixels(v):
+        return v.n * v.h * v.w
+
+    for name, plan in plans.items():
+        got = {'fwd': [], 'dgrad': [], 'wgrad': []}
+        count = dict.fromkeys(('y3_conv2d_fwd', 'y3_conv2d_dgrad', 'y3_conv2d_dgrad_bn', 'y3_conv2d_wgrad', 'y3_conv2d_wgrad_x',
+                               'y3_conv2d_fwd_bf16_ws'), 0)
+        for fn, args in plan.fwd + plan.bwd:
+            if fn == 'side_call':
+                fn, args = args[0], args[1]
+            if isinstance(fn, str) or fn.__name__ not in count:
+                continue
+            what = fn.__name__
+            count[what] += 1
+            if what == 'y3_conv2d_fwd':
+                src, wt, _, k, s, dst, flags = args[:7]
+                need = lib.y3_conv2d_fwd_workspace_x(pixels(dst), src.c, k, dst.c, flags)
+                arenas, kind = ((yolo.planes_t, 6), (yolo.params, 4)), 'fwd'
+            elif what == 'y3_conv2d_fwd_bf16_ws':
+                src, wt, _, k, s, dst, _, flags = args[:8]
+                need = lib.y3_conv2d_fwd_bf16_workspace(pixels(dst), src.c, k, dst.c)
+                assert not flags & X3
+                arenas, kind = ((None, 6), (yolo.params_t_bf16, 2)), 'fwd'
+            elif what in ('y3_conv2d_dgrad', 'y3_conv2d_dgrad_bn'):
+                ddst, wt, k, s, dsrc, flags = args[:6]
+                need = lib.y3_conv2d_dgrad_workspace_x(ddst, k, s, dsrc, flags)
+                arenas, kind = ((yolo.planes, 6), (yolo.params_t, 4)), 'dgrad'
+            else:
+                src, ddst, k, s, wt = args[:5]
+                flags = args[5] if what == 'y3_conv2d_wgrad_x' else 0
+                need = lib.y3_conv2d_wgrad_workspace_x(src, ddst, k, s, flags)
+                arenas, kind = ((None, 6), (yolo.grads, 4)), 'wgrad'      # (no weight operand: the address is the gradient's)
+            assert args[-2] and int(need) <= args[-1], (name, what, int(need), args[-1])
+            (x3_arena, x3_bytes), (arena, nbytes) = arenas
+            in_x3, in_plain = layer_at(wt, x3_arena, x3_bytes), layer_at(wt, arena, nbytes)
+            if flags & X3 and kind != 'wgrad':
+                assert in_x3 is not None and in_plain is None, (name, what, flags)
+            else:
+                assert in_plain is not None and in_x3 is None, (name, what, flags)
+            if flags & X3:
+                got[kind].append(in_x3 if in_x3 is not None else in_plain)
+        for kind, lst in (('fwd', plan.x3_fwd), ('dgrad', plan.x3_dgrad), ('wgrad', plan.x3_wgrad)):
+            assert sorted(lst) == sorted(got[kind]) and len(set(lst)) == len(lst), (name, kind, lst, got[kind])
+        if name in ('side', 'graph'):
+            assert count['y3_conv2d_fwd'] == 75 and count['y3_conv2d_wgrad'] == 3 and count['y3_conv2d_wgrad_x'] == 72
+            assert count['y3_conv2d_dgrad'] + count['y3_conv2d_dgrad_bn'] == 74 and count['y3_conv2d_dgrad_bn'] == plan.epilogue_stats_layers
+            assert all(bool(got[kind]) == (conv_arithmetic != 'f32') for kind in got), (name, got)
+        else:
+            assert count['y3_conv2d_fwd'] + count['y3_conv2d_fwd_bf16_ws'] == (74 if name == 'bf16' else 75)
+            assert bool(got['fwd']) == (conv_arithmetic != 'f32' and name == 'fp32') and not got['dgrad'] and not got['wgrad']
+
+
 _ORACLE_STEPS = {}
 
 
