@@ -231,7 +231,7 @@ int y3_bn_apply(const y3_tensor* a, const float* scale, const float* shift, cons
  *                    arrives last, inside the same launch -- dgamma, dbeta, dbias (bias gradient of the conv) and the
  *                    per-channel coefficients k1,k2,k3 (coef[3][c]).  Optionally the residual fan-in of model.py:47
  *                    rides along while dy streams through: dres = dy (dres_accumulate == 0) or dres += dy.
- *                    Channels: a multiple of 64 up to 1024, or 4 / 8 / 16 / 32 (every layer of this network).
+ *                    Channels: 4 / 8 / 16, or a multiple of 32 up to 1024 (every layer of this network).
  *                    `workspace`: y3_bn_bwd_workspace(m, c) bytes, 16-byte aligned; its first 1 KiB (tickets) must be
  *                    zero before the FIRST call -- every call leaves it zero again.
  *   step 2 (apply):  dz = (k1*dy + k2*a + k3) * (a > 0 ? 1 : alpha)

@@ -174,7 +174,7 @@ extern "C" int y3_bn_apply(const y3_tensor* a, const float* scale, const float* 
 // ---------------------------------------------------------------------------
 #define Y3_BNB_SUMS 6
 #define Y3_BNB_BLOCKS 256             // workgroups per launch (one per CU): 512 stream no faster and double the last arrival's work (measured)
-#define Y3_BNB_TICKETS 1024           // bytes of tickets (one int per channel slice, <= 16 slices) at the head of the workspace
+#define Y3_BNB_TICKETS 1024           // bytes of tickets (one int per channel slice, <= 32 slices) at the head of the workspace
 
 // A workgroup streams a band of rows of ONE channel slice: lc float4 lanes (<= 8: 32 channels) x 256/lc row groups.  Slicing
 // the channels keeps the fp64 partials at parts * slices * 6 * 32 doubles <= 384 KiB whatever C is (whole-row workgroups
@@ -432,7 +432,7 @@ extern "C" int y3_bn_bwd_stats(const y3_tensor* dy, const y3_tensor* a, const y3
         Y3_CHECK_ARG(same_geom(dy, dres), "bn_bwd_stats: dres geometry");
     }
     BnbPlan pl;
-    Y3_CHECK_ARG(plan_bnb(pixels(a), a->c, &pl), "bn_bwd_stats: channels %d unsupported (a multiple of 64 up to 1024, or 4 / 8 / 16 / 32)", a->c);
+    Y3_CHECK_ARG(plan_bnb(pixels(a), a->c, &pl), "bn_bwd_stats: channels %d unsupported (4 / 8 / 16, or a multiple of 32 up to 1024)", a->c);
     const size_t need = (size_t)Y3_BNB_TICKETS + (size_t)pl.parts * pl.slices * Y3_BNB_SUMS * pl.sw * sizeof(double);
     Y3_CHECK_ARG(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, "bn_bwd_stats: workspace %zu bytes, %zu needed (16-byte aligned)",
                  workspace_bytes, need);
