@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "common.h"
+#include "conv_plan.h"   // Y3_WS_HEADER, Y3_WG_TABLE, Y3_WG_FANIN
 
 // Fast path of the same gather-GEMM (taken when C % BK == 0, i.e. every layer except the first conv; the 14-channel
 // heads included -- see make_fast): a K step never straddles a tap, so the tap and the channel
@@ -111,7 +112,6 @@ __device__ __forceinline__ void y3_sgb_pairs() {   // COUNT x { MFMAS matrix ins
 }
 
 // kernel gradient (conv.hip: conv_wgrad_kernel; conv_x3.hip: conv_wgrad_x3_kernel)
-#define Y3_WG_FANIN 8   // kernel-gradient slab reduction: fan-in of the in-kernel tree
 struct WgradArgs {
     const float* src;
     const float* ddst;
@@ -129,9 +129,6 @@ struct WgradArgs {
     Y3Div dv_tiles, dv_nbn, dv_ohw, dv_ow;   // index decode without run-time divides (y3_make_div)
 };
 
-#ifndef Y3_WG_TABLE
-#define Y3_WG_TABLE 2048      // pixels per split the LDS pixel table holds (plan_wgrad keeps chunks below it)
-#endif
 bool y3_wgrad_x3_launch(const WgradArgs& p, int bkr, int bn, unsigned grid, hipStream_t st);
 
 // conv_x3.hip: launch of the x3 kernel for a planned tile (false: no kernel built for it)

@@ -1,5 +1,7 @@
 // Error channel and version of libyolo3hip.so.
-#include "common.h"
+#include <stdarg.h>
+
+#include "host.h"
 
 static thread_local char g_err[512] = "";
 

@@ -2,7 +2,7 @@
 form, and the inputs and fp64 references their tests share (host only: no GPU).  The companion of plan_forms.py, whose layer table,
 envelope (batch 1-16 x image side 320-608), cost cap and tie-breaking order it imports.
 
-ENTRY 'wgrad'.  plan_wgrad / plan_wgrad_x3 (csrc/conv.hip) choose from (m, cin, ksize, cout) the tile bkr x bn of the [K][cout] gradient
+ENTRY 'wgrad'.  plan_wgrad / plan_wgrad_x3 (csrc/conv_plan.cpp) choose from (m, cin, ksize, cout) the tile bkr x bn of the [K][cout] gradient
 and cut the m = N*OH*OW pixels into `splits` runs of `chunk`; y3_conv2d_wgrad_plan_x reports {bkr, bn, splits, chunk, tiles, in_kernel,
 grid, pixel_table}.  THE SIGNATURE of a kernel-gradient launch is
 

@@ -1,6 +1,6 @@
 """The plan forms of y3_conv2d_fwd and the stride-1 y3_conv2d_dgrad, and one real layer per form (host only: no GPU).
 
-plan_conv / plan_conv_x3 (csrc/conv.hip) decide per launch, from m = N*OH*OW, cin, ksize and cout, which kernel runs, on which
+plan_conv / plan_conv_x3 (csrc/conv_plan.cpp) decide per launch, from m = N*OH*OW, cin, ksize and cout, which kernel runs, on which
 tile, and how the tiles are cut along K.  y3_conv2d_plan_x reports the decision as thirteen numbers
     {bm, bn, bk, tiles, f, s0, s1, chunk0, chunk1, grid, stats_tiles, fast, nk}
 (include/yolo3hip.h): tiles [0, f) run s0 K slices of chunk0 steps, tiles [f, tiles) s1 slices of chunk1, nk steps in all.

@@ -2,7 +2,7 @@
 
 conv_wgrad_x3_kernel is the largest line of the training profile; test_conv_wgrad covers it on small ad-hoc shapes only.  Here:
 every Appendix-A shape at batch 8 (the training batch: up to 86 528 pixels summed per weight) and the 13^2 / 26^2 shapes at batch 1
-(small-batch training), which between them reach all four reduction forms of plan_wgrad_x3 (conv.hip) -- one pixel run, the
+(small-batch training), which between them reach all four reduction forms of plan_wgrad_x3 (conv_plan.cpp) -- one pixel run, the
 in-kernel ticket reduction, the slab reduction with XCD-remapped items, the slab reduction with the XCD-strided padded grid.
 test_wgrad_cases_cover_every_reduction_form reads the plans back, so the claim holds if the planner moves.  Inputs look like
 activations (mostly positive, non-zero mean: a wrong tap offset at the SAME-pad border changes the sums), src is a channel slice

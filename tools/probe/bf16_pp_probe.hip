@@ -2,7 +2,7 @@
 // (results become wrong, timing stays meaningful): 1 = no LDS-DMA in the loop, 2 = no fragment reads, 4 = no MFMAs,
 // 8 = no vmcnt wait.  Builds conv_bf16.hip with -DY3_TIMING:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DY3_TIMING -I include -I object-detection-yolov3_amd/csrc \
-//         tools/probe/bf16_pp_probe.hip object-detection-yolov3_amd/csrc/core.hip -o tools/probe/bf16_pp_probe
+//         tools/probe/bf16_pp_probe.hip object-detection-yolov3_amd/csrc/core.cpp -o tools/probe/bf16_pp_probe
 //   tools/probe/bf16_pp_probe [n h cin cout k]
 #include "../../object-detection-yolov3_amd/csrc/conv_bf16.hip"
 #include <algorithm>

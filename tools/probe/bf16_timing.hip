@@ -1,7 +1,7 @@
 // Probe: where does a bf16 conv workgroup spend its time?  Builds conv_bf16.hip with -DY3_TIMING (per-workgroup
 // s_memtime stamps: start, after prologue, after main loop, after epilogue; HW_ID, XCC_ID) and prints the distribution.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DY3_TIMING -I include -I object-detection-yolov3_amd/csrc \
-//         tools/probe/bf16_timing.hip object-detection-yolov3_amd/csrc/core.hip -o tools/probe/bf16_timing
+//         tools/probe/bf16_timing.hip object-detection-yolov3_amd/csrc/core.cpp -o tools/probe/bf16_timing
 #include "../../object-detection-yolov3_amd/csrc/conv_bf16.hip"
 #include <algorithm>
 #include <cstdio>

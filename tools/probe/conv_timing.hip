@@ -2,7 +2,7 @@
 // Builds conv.hip with -DY3_TIMING (per-workgroup s_memtime stamps: start, after prologue, after main loop, end; HW_ID,
 // XCC_ID, s_memrealtime at both ends) and prints the distributions, the workgroups per CU and the clock the chip held.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -DY3_TIMING -I include -I object-detection-yolov3_amd/csrc \
-//         tools/probe/conv_timing.hip object-detection-yolov3_amd/csrc/core.hip -o tools/probe/conv_timing
+//         tools/probe/conv_timing.hip object-detection-yolov3_amd/csrc/conv_plan.cpp object-detection-yolov3_amd/csrc/core.cpp -o tools/probe/conv_timing
 //   tools/probe/conv_timing [n h cin cout k [x3]]   (forward, stride 1; x3 = 1: the Y3_CONV_X3 kernel; env Y3_ABL applies)
 // The stamped launch is the last of 200 back-to-back stamped launches, so the clock it reports is the clock the chip HOLDS under
 // this kernel (and under the ablation Y3_ABL selects), not the clock of a first launch on an idle chip.
