@@ -566,6 +566,28 @@ int y3_augment_batch(const void* src, int dtype, int n, int h_in, int w_in, int 
                      float* out, void* workspace, y3_stream_t stream);
 size_t y3_augment_workspace_bytes(int n, int h_out, int w_out, int c);
 
+/* ---- mosaic augmentation (not in the reference; yolo3/augment.py draw_mosaic / mosaic_boxes) -----------------
+ * Every output image is put together from windows of up to four images of the SAME batch, one per quadrant around a seam
+ * (cy, cx).  Quadrant q of output image i: 0 = rows [0,cy) x columns [0,cx), 1 = [0,cy) x [cx,w), 2 = [cy,h) x [0,cx),
+ * 3 = [cy,h) x [cx,w); with (qy, qx) its origin and (qh, qw) its size,
+ *     out[i][ch][y][x] = src[src[q]][ch][y - qy + oy[q]][x - qx + ox[q]]        for (y, x) in quadrant q, every channel ch.
+ * A pure copy: the output bits are the input bits (NaN payloads and -0.0 included).  An empty quadrant (qh == 0 or qw == 0) reads
+ * nothing and its fields are ignored.  cy = h, cx = w, src[0] = i, oy[0] = ox[0] = 0 copies image i through unchanged.
+ * src, out: DEVICE float32 [n][c][h][w], c = 1 or 3, any h, w >= 1 (h * w < 2^31 - 8), 4-byte aligned; the ranges must not
+ * overlap (the pass cannot run in place).  records: HOST array of n records, validated before any launch (Y3_EINVAL + message:
+ * seam outside [0,h] x [0,w]; for a non-empty quadrant a source outside [0,n) or a window that leaves the source -- oy < 0,
+ * oy + qh > h, likewise in x --; non-zero reserved; bad c, n, h, w; overlapping src / out) and handed to the kernel as kernel
+ * arguments, 32 output images per launch; a source index may point anywhere in the batch.  Every output element is written by
+ * exactly one thread: no atomics, no workspace, the same bits on every launch. */
+typedef struct y3_mosaic_record {   /* 64 bytes, one per OUTPUT image */
+    int32_t cy, cx;                 /* seam: 0 <= cy <= h, 0 <= cx <= w */
+    int32_t src[4];                 /* source image of quadrant q, 0 <= src < n */
+    int32_t oy[4], ox[4];           /* top-left corner of the window taken from that source */
+    int32_t reserved[2];            /* 0 */
+} y3_mosaic_record;
+int y3_mosaic_batch(const float* src, int n, int c, int h, int w, const y3_mosaic_record* records_host, float* out,
+                    y3_stream_t stream);
+
 /* ---- ground-truth label tensors: ImageReader.__format_boxes (imagereader.py:252-324) on the device ------------------------
  * For ImageReader(..., label_device='gpu') and multi-scale training: the boxes of a batch cross PCIe, the three
  * label tensors are built where the loss reads them.  boxes: DEVICE int32 [n][max_boxes][5] = x, y, w, h, class with (x, y) the

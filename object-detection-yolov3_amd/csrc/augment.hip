@@ -11,6 +11,13 @@
 //                 mirrors), filters along W and mixes the channels with the folded C x C matrix.  Without blur it writes
 //                 back in place, with blur into the workspace.
 //   aug_col       only for images with blur: 64-column x 32-row tiles with a row halo in LDS, filter along H -> `out`.
+//
+// Mosaic (not in the reference; y3_mosaic_batch, semantics in yolo3hip.h): a second, separate pass that recombines
+// the augmented batch, four windows of four images per output image.
+//   mosaic        one thread per 16-byte-aligned group of four destination floats of one (image, channel) plane.  A group that
+//                 lies inside one span (one row, one side of the seam column) is one 16-byte load at 4-byte alignment -- the
+//                 source is shifted against the destination by ox - qx, any residue mod 4 -- and one aligned 16-byte store; the
+//                 at most three groups a row has at its seam and its ends copy their floats one by one.
 #include "common.h"
 #include <math.h>
 #include <algorithm>
@@ -363,6 +370,103 @@ extern "C" int y3_augment_batch(const void* src, int dtype, int n, int h_in, int
             hipLaunchKernelGGL(aug_col_kernel, dim3(tilesx * tilesy * c, nb), dim3(256), 0, st, (const float*)t, o, tab, c, h_out, w_out, tilesx, tilesy);
             Y3_CHECK_LAUNCH("augment_batch: column blur");
         }
+    }
+    return Y3_OK;
+}
+
+// ---- mosaic: four windows of four augmented images per output image (not in the reference) ---------------------------------
+struct MosImg {                // 48 bytes
+    long long delta[4];        // quadrant q: source element = delta[q] + ch * h * w + (y * w + x); src * c * h * w + (oy - qy) * w + ox - qx
+    int cy, cx;
+    int pad0, pad1;
+};
+struct MosTable {
+    MosImg img[Y3_AUG_CHUNK];
+};
+typedef float mos_f4 __attribute__((ext_vector_type(4)));
+typedef float mos_f4u __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes at 4-byte alignment: one global_load_dwordx4
+
+// grid (groups of a plane / 256, c, images of the chunk).  `out` is the chunk's first output image, `src` the whole batch.
+// e / W for 0 <= e < 2^31 is (e * div_mul) >> div_shift (Granlund & Montgomery, PLDI'94: l = ceil(log2 W), div_mul =
+// floor(2^(31+l) / W) + 1 < 2^32, div_shift = 31 + l), a multiply in place of the division every thread would start with.
+__global__ __launch_bounds__(256) void mosaic_kernel(const float* __restrict__ src, float* __restrict__ out, MosTable tab, int C, int H, int W,
+                                                     unsigned div_mul, int div_shift) {
+    const MosImg& m = tab.img[blockIdx.z];
+    const int P = H * W;
+    float* o = out + ((size_t)blockIdx.z * C + blockIdx.y) * (size_t)P;
+    const float* s = src + (size_t)blockIdx.y * (size_t)P;
+    const float *s0 = s + m.delta[0], *s1 = s + m.delta[1], *s2 = s + m.delta[2], *s3 = s + m.delta[3];      // uniform: scalar registers
+#define MOS_SRC(row, x) ((row) >= m.cy ? ((x) >= m.cx ? s3 : s2) : ((x) >= m.cx ? s1 : s0))
+    const int a = (int)(((size_t)o >> 2) & 3);                     // the plane starts `a` floats into a 16-byte group
+    const int e0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4 - a;  // first element of this thread's group, -3 .. P-1
+    if (e0 >= P) return;
+    const int e = max(e0, 0), end = min(e0 + 4, P);
+    int row = (int)(((unsigned long long)(unsigned)e * div_mul) >> div_shift), x = e - row * W;
+    const bool whole = e0 >= 0 && e0 + 4 <= P && x + 4 <= W && (x + 4 <= m.cx || x >= m.cx);      // one span: y * w + x = e0 on both sides
+    mos_f4 v;
+    if (whole) {
+        v = *(const mos_f4u*)(MOS_SRC(row, x) + e0);
+    } else {                                                        // a row end, the seam, or the plane's first / last group:
+#pragma unroll
+        for (int k = 0; k < 4; ++k)                                 // its (up to) four loads issued back to back, its stores after them
+            if (e0 + k >= e && e0 + k < end) {
+                v[k] = MOS_SRC(row, x)[e0 + k];
+                if (++x == W) {
+                    x = 0;
+                    ++row;
+                }
+            }
+    }
+    if (whole) {
+        *(mos_f4*)(o + e0) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (e0 + k >= e && e0 + k < end) o[e0 + k] = v[k];
+    }
+#undef MOS_SRC
+}
+
+extern "C" int y3_mosaic_batch(const float* src, int n, int c, int h, int w, const y3_mosaic_record* records, float* out, y3_stream_t stream) {
+    Y3_CHECK_ARG(src && records && out, "mosaic_batch: null pointer");
+    Y3_CHECK_ARG(c == 1 || c == 3, "mosaic_batch: channels %d (1 or 3)", c);
+    Y3_CHECK_ARG(n > 0 && h > 0 && w > 0, "mosaic_batch: bad dims n %d, %dx%d", n, h, w);
+    Y3_CHECK_ARG((long long)h * w < (1LL << 31) - 8, "mosaic_batch: plane %dx%d too large", h, w);
+    const size_t plane = (size_t)h * w, image = plane * c, bytes = (size_t)n * image * sizeof(float);
+    Y3_CHECK_ARG((((size_t)src | (size_t)out) & 3) == 0, "mosaic_batch: src / out not 4-byte aligned");
+    Y3_CHECK_ARG((size_t)src + bytes <= (size_t)out || (size_t)out + bytes <= (size_t)src, "mosaic_batch: src and out overlap (the pass cannot run in place)");
+    for (int i = 0; i < n; ++i) {
+        const y3_mosaic_record& r = records[i];
+        Y3_CHECK_ARG(r.cy >= 0 && r.cy <= h && r.cx >= 0 && r.cx <= w, "mosaic_batch: record %d: seam (%d, %d) outside [0, %d] x [0, %d]", i, r.cy, r.cx, h, w);
+        Y3_CHECK_ARG(r.reserved[0] == 0 && r.reserved[1] == 0, "mosaic_batch: record %d: reserved words %d %d", i, r.reserved[0], r.reserved[1]);
+        for (int q = 0; q < 4; ++q) {
+            const int qh = (q & 2) ? h - r.cy : r.cy, qw = (q & 1) ? w - r.cx : r.cx;
+            if (qh == 0 || qw == 0) continue;
+            Y3_CHECK_ARG(r.src[q] >= 0 && r.src[q] < n, "mosaic_batch: record %d: quadrant %d: source image %d of %d", i, q, r.src[q], n);
+            Y3_CHECK_ARG(r.oy[q] >= 0 && r.ox[q] >= 0 && (long long)r.oy[q] + qh <= h && (long long)r.ox[q] + qw <= w,
+                         "mosaic_batch: record %d: quadrant %d: window %d+%d x %d+%d leaves the %dx%d source", i, q, r.oy[q], qh, r.ox[q], qw, h, w);
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int groups = y3_cdiv((long long)plane + 3, 4);
+    const int div_shift = 31 + y3_ilog2(w);
+    const unsigned div_mul = (unsigned)((1ULL << div_shift) / (unsigned long long)w + 1);
+    for (int base = 0; base < n; base += Y3_AUG_CHUNK) {
+        const int nb = std::min(Y3_AUG_CHUNK, n - base);
+        MosTable tab = {};
+        for (int i = 0; i < nb; ++i) {
+            const y3_mosaic_record& r = records[base + i];
+            MosImg& m = tab.img[i];
+            m.cy = r.cy;
+            m.cx = r.cx;
+            for (int q = 0; q < 4; ++q) {
+                const int qy = (q & 2) ? r.cy : 0, qx = (q & 1) ? r.cx : 0;
+                if (((q & 2) ? h - r.cy : r.cy) == 0 || ((q & 1) ? w - r.cx : r.cx) == 0) continue;      // empty: no element selects it
+                m.delta[q] = (long long)r.src[q] * (long long)image + ((long long)r.oy[q] - qy) * w + ((long long)r.ox[q] - qx);
+            }
+        }
+        hipLaunchKernelGGL(mosaic_kernel, dim3(y3_cdiv(groups, 256), c, nb), dim3(256), 0, st, src, out + (size_t)base * image, tab, c, h, w, div_mul, div_shift);
+        Y3_CHECK_LAUNCH("mosaic_batch");
     }
     return Y3_OK;
 }

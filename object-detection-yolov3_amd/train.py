@@ -24,6 +24,10 @@ step: the train.csv step that completed it, the norm before clipping and the fac
 --multiscale_seed and the batch count, the same on every rank; the batch is augmented straight to that size and its labels are
 built on the device at it.  <scalars>/train_size.csv gets one row per step.  The test reader, the test loss, the
 mAP pass, model selection, the checkpoint and the export stay at the size the images are stored at.
+--mosaic_prob P (with --augmentation_device gpu; 0 = off) turns each training image, with probability P, into a mosaic of itself
+and three other images of its batch, composed on the device after the augmentation; the draws are a pure function
+of --mosaic_seed, the rank and the batch count, and a box stays when at least --mosaic_min_visible of its area is still visible.
+Composes with the --multiscale_* flags; the test reader, the mAP pass, the checkpoint and the export are untouched.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -152,12 +156,25 @@ def effective_reader_count(requested, cpus, local_world):
     return max(1, min(int(requested), share))
 
 
+def check_mosaic_args(mosaic_prob, mosaic_min_visible):
+    """--mosaic_prob / --mosaic_min_visible -> the probability as a float (0.0 = off).  ValueError outside [0, 1]."""
+    p = float(mosaic_prob or 0.0)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('--mosaic_prob must be in [0, 1], got {!r}'.format(mosaic_prob))
+    if not 0.0 <= float(mosaic_min_visible) <= 1.0:
+        raise ValueError('--mosaic_min_visible must be in [0, 1], got {!r}'.format(mosaic_min_visible))
+    return p
+
+
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, multiscale_min=None, multiscale_max=None,
-                multiscale_period=10, multiscale_seed=0):
+                multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25):
     test_map = effective_test_map(test_map, model_selection)
+    mosaic_prob = check_mosaic_args(mosaic_prob, mosaic_min_visible)
+    if mosaic_prob and augmentation_device != 'gpu':
+        raise ValueError('mosaic augmentation needs augmentation_device gpu: the batches are composed and labelled on the device')
     train_sizes = multiscale_sizes(multiscale_min, multiscale_max)
     if train_sizes is not None and augmentation_device != 'gpu':
         raise ValueError('multi-scale training needs augmentation_device gpu: the batches are resampled and labelled on the device')
@@ -194,7 +211,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     print('Setting up training image reader')
     train_reader = imagereader.ImageReader(train_database_filepath, anchors, use_augmentation=use_augmentation, shuffle=True,
                                            num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device,
-                                           **(dict(label_device='gpu') if train_sizes is not None else {}))
+                                           **(dict(label_device='gpu') if train_sizes is not None or mosaic_prob else {}),
+                                           # (a shuffled reader ignores its shard when it picks keys; the mosaic draws are keyed by it)
+                                           **(dict(num_shards=world, shard_index=rank) if mosaic_prob else {}))
     print('Train Reader has {} images'.format(train_reader.get_image_count()))
     training_checkpoint_filepath = None
     try:
@@ -231,6 +250,10 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             train_dataset = train_dataset.multiscale(train_sizes, multiscale_period, multiscale_seed)
             print('Multi-scale training: sizes {} drawn every {} batches (seed {}); testing, checkpoint and export stay at {}'.format(
                 [s[0] for s in train_sizes], multiscale_period, multiscale_seed, train_reader.get_image_size()[:2]))
+        if mosaic_prob:
+            train_dataset = train_dataset.mosaic(mosaic_prob, mosaic_seed, mosaic_min_visible)
+            print('Mosaic augmentation: probability {:g} per image, four images of the batch per mosaic (seed {}); boxes with less than '
+                  '{:g} of their area visible are dropped; the test reader is untouched'.format(mosaic_prob, mosaic_seed, mosaic_min_visible))
 
         print('Creating model')
         number_classes = train_reader.get_number_classes()
@@ -460,6 +483,12 @@ class _Parser(argparse.ArgumentParser):
             self.error(str(e))
         if sizes is not None and a.augmentation_device != 'gpu':
             self.error('--multiscale_min / --multiscale_max need --augmentation_device gpu')
+        try:
+            prob = check_mosaic_args(a.mosaic_prob, a.mosaic_min_visible)
+        except ValueError as e:
+            self.error(str(e))
+        if prob and a.augmentation_device != 'gpu':
+            self.error('--mosaic_prob needs --augmentation_device gpu')
         return a
 
 
@@ -514,6 +543,13 @@ def build_parser():
                         help='(addition) batches between two draws of the multi-scale size (default 10)')
     parser.add_argument('--multiscale_seed', dest='multiscale_seed', type=int, default=0,
                         help='(addition) seed of the multi-scale size schedule: the size of batch i is a pure function of (seed, i // period)')
+    parser.add_argument('--mosaic_prob', dest='mosaic_prob', type=float, default=0.0,
+                        help='(addition) off by default; P in (0, 1]: each training image becomes, with probability P, a mosaic of itself and '
+                             'three other images of its batch (needs --augmentation_device gpu; composes with --multiscale_*; the test reader is untouched)')
+    parser.add_argument('--mosaic_seed', dest='mosaic_seed', type=int, default=0,
+                        help='(addition) seed of the mosaic draws: a pure function of (seed, rank, batch count, image)')
+    parser.add_argument('--mosaic_min_visible', dest='mosaic_min_visible', type=float, default=0.25,
+                        help='(addition) a box of a mosaic stays when at least this share of its area lies in the window taken from its image (default 0.25)')
     return parser
 
 
@@ -526,4 +562,4 @@ if __name__ == "__main__":
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
                 a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm, a.multiscale_min, a.multiscale_max,
-                a.multiscale_period, a.multiscale_seed)
+                a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible)

@@ -251,3 +251,126 @@ def multiscale_choice(seed, block, count):
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
     z ^= z >> 31
     return int(z % int(count))
+
+
+# ---- mosaic (not in the reference): every output image put together from four images of its own batch -------
+# y3_mosaic_record (include/yolo3hip.h), one per OUTPUT image of a y3_mosaic_batch call
+MOSAIC_RECORD = np.dtype([('cy', '<i4'), ('cx', '<i4'), ('src', '<i4', (4,)), ('oy', '<i4', (4,)), ('ox', '<i4', (4,)), ('reserved', '<i4', (2,))])
+assert MOSAIC_RECORD.itemsize == 64
+
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(z):
+    """splitmix64's output function (the one multiscale_choice uses)."""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _quadrants(cy, cx, h, w):
+    """(qy, qx, qh, qw) of quadrants 0..3 around the seam (cy, cx) of an h x w image."""
+    return ((0, 0, cy, cx), (0, cx, cy, w - cx), (cy, 0, h - cy, cx), (cy, cx, h - cy, w - cx))
+
+
+def draw_mosaic(seed, shard, batch_index, n, size, prob):
+    """MOSAIC_RECORD [n] for the batch_index-th batch of n images of size = (h, w) on reader shard `shard`: a pure function of its
+    arguments (no global np.random: the prefetch thread and a rerun draw the same batch; another shard, batch or seed another).
+
+    Draws are counter based.  Output image i owns the stream key_i = the splitmix64 output function folded over (seed, shard,
+    batch_index, i) -- k = 0; for v in those four: k = mix((k ^ v) + 0x9E3779B97F4A7C15) -- and its j-th draw is the 64-bit word
+    u_j = mix(key_i + (j + 1) * 0x9E3779B97F4A7C15), i.e. splitmix64 seeded with key_i.  A uniform integer in [lo, hi] is
+    lo + u % (hi - lo + 1) (the modulo bias is below 2^-50 for any image size).  Exact draw order per image:
+      u_0        the image is a mosaic when (u_0 >> 11) * 2^-53 < prob; otherwise the identity record (cy = h, cx = w, src[0] = i,
+                 windows at 0) is emitted and the remaining words are not used
+      u_1, u_2   cy in [h//4, h - h//4], cx in [w//4, w - w//4]
+      u_3..u_5   src[1], src[2], src[3] (src[0] = i).  n >= 4: without replacement from the other n - 1 images in ascending
+                 order -- u_j % (number left) indexes the list of images not yet taken --, so the four are distinct.  n = 2, 3:
+                 each from the other n - 1 images, repetition allowed.  n = 1: image 0
+      u_6..u_13  oy[0], ox[0], oy[1], ox[1], ..., oy[3], ox[3]: oy[q] in [0, h - qh], ox[q] in [0, w - qw], the positions where
+                 the quadrant's qh x qw window fits into its source."""
+    h, w = int(size[0]), int(size[1])
+    n = int(n)
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError('draw_mosaic: n, h, w must be >= 1, got {} {} {}'.format(n, h, w))
+    rec = np.zeros(n, MOSAIC_RECORD)
+    for i in range(n):
+        key = 0
+        for v in (seed, shard, batch_index, i):
+            key = _mix64((key ^ (int(v) & _M64)) + _GOLDEN)
+        u = lambda j: _mix64(key + (j + 1) * _GOLDEN)
+        r = rec[i]
+        if not (u(0) >> 11) * 2.0 ** -53 < prob:
+            r['cy'], r['cx'], r['src'][0] = h, w, i
+            continue
+        cy = h // 4 + u(1) % (h - 2 * (h // 4) + 1)
+        cx = w // 4 + u(2) % (w - 2 * (w // 4) + 1)
+        r['cy'], r['cx'], r['src'][0] = cy, cx, i
+        others = [k for k in range(n) if k != i]
+        for q in (1, 2, 3):
+            if n >= 4:
+                r['src'][q] = others.pop(u(2 + q) % len(others))
+            elif n >= 2:
+                r['src'][q] = others[u(2 + q) % len(others)]
+        for q, (_, _, qh, qw) in enumerate(_quadrants(cy, cx, h, w)):
+            r['oy'][q] = u(6 + 2 * q) % (h - qh + 1)
+            r['ox'][q] = u(7 + 2 * q) % (w - qw + 1)
+    return rec
+
+
+def _is_identity(r, i, h, w):
+    return r['cy'] == h and r['cx'] == w and r['src'][0] == i and r['oy'][0] == 0 and r['ox'][0] == 0
+
+
+def mosaic_boxes(box_lists, records, size, min_visible=0.25):
+    """The boxes of the output images of y3_mosaic_batch(records) from the boxes of its input images.  box_lists: one int32 [k, 5]
+    array per input image (x, y, w, h, class; top-left corner; the box covers [x, x+w) x [y, y+h)), None or empty = no boxes.
+    Returns one int32 [k', 5] array per output image ([0, 5] when empty).
+
+    Per output image, quadrants 0..3 in order and within a quadrant the boxes of its source in their order: the box is
+    intersected with the source window [ox, ox+qw) x [oy, oy+qh); dropped when the clipped w' < 1 or h' < 1; dropped when
+    w' * h' < min_visible * (w * h) (exact integer products, compared in float64: a visible fraction of exactly min_visible
+    stays); otherwise shifted by (qx - ox, qy - oy).  The class is unchanged.  An image with the identity record keeps its
+    boxes exactly as they came, order included (no clipping is applied to it).  min_visible = 0.25 is a default, not a tuned
+    value."""
+    h, w = int(size[0]), int(size[1])
+    empty = np.zeros((0, 5), np.int32)
+    src = [empty if b is None or len(b) == 0 else np.asarray(b, np.int32).reshape(-1, 5) for b in box_lists]
+    assert len(records) == len(src), (len(records), len(src))
+    out = []
+    for i, r in enumerate(records):
+        if _is_identity(r, i, h, w):
+            out.append(src[i].copy())
+            continue
+        kept = []
+        for q, (qy, qx, qh, qw) in enumerate(_quadrants(int(r['cy']), int(r['cx']), h, w)):
+            if qh == 0 or qw == 0:
+                continue
+            oy, ox = int(r['oy'][q]), int(r['ox'][q])
+            for bx, by, bw, bh, cls in src[int(r['src'][q])].tolist():
+                x0, y0 = max(bx, ox), max(by, oy)
+                x1, y1 = min(bx + bw, ox + qw), min(by + bh, oy + qh)
+                if x1 - x0 < 1 or y1 - y0 < 1:
+                    continue
+                if float((x1 - x0) * (y1 - y0)) < np.float64(min_visible) * float(bw * bh):
+                    continue
+                kept.append((x0 + qx - ox, y0 + qy - oy, x1 - x0, y1 - y0, cls))
+        out.append(np.array(kept, np.int32).reshape(-1, 5))
+    return out
+
+
+def mosaic_reference(batch, records):
+    """y3_mosaic_batch restated in NumPy slices (the oracle of the GPU tests): batch [n, c, h, w] of any dtype -> a new array."""
+    batch = np.asarray(batch)
+    n, _, h, w = batch.shape
+    assert len(records) == n
+    out = np.empty_like(batch)
+    for i, r in enumerate(records):
+        for q, (qy, qx, qh, qw) in enumerate(_quadrants(int(r['cy']), int(r['cx']), h, w)):
+            if qh == 0 or qw == 0:
+                continue
+            oy, ox = int(r['oy'][q]), int(r['ox'][q])
+            out[i, :, qy:qy + qh, qx:qx + qw] = batch[int(r['src'][q]), :, oy:oy + qh, ox:ox + qw]
+    return out

@@ -8,6 +8,8 @@ augment_device    augment.py:30-125 on the device (csrc/augment.hip) for ImageRe
 format_image      imagereader.py:57-60
 format_boxes      ImageReader.__format_boxes, imagereader.py:252-324 (host NumPy,
                   as in the reference: it runs in the reader processes)
+mosaic_device     y3_mosaic_batch (csrc/augment.hip): the augmented batch recombined, four windows per output image, for
+                  Dataset.mosaic() (not in the reference)
 format_labels_device  the same three label tensors built on the device from the boxes of a batch (y3_format_labels,
                   csrc/detect.hip) for ImageReader(..., label_device='gpu') and Dataset.multiscale()
 """
@@ -69,6 +71,21 @@ def augment_device(src, records, crop_to, ranges=False):
     bits = torch.where(bits >= 2**31, bits - 2**32, bits).to(torch.int32)
     val = bits.view(torch.float32)
     return out, -val[:, 1], val[:, 0]
+
+
+def mosaic_device(x, records):
+    """y3_mosaic_batch: x CUDA float32 [B, C, H, W] (C = 1 or 3), records MOSAIC_RECORD [B] (host; see augment.draw_mosaic) -> a new
+    tensor of the same shape, every output image copied together from windows of up to four images of x.  Enqueued on the current
+    stream."""
+    assert x.is_cuda and x.dim() == 4 and x.dtype == torch.float32, (x.dtype, tuple(x.shape))
+    x = x.contiguous()
+    records = np.ascontiguousarray(records, dtype=augment.MOSAIC_RECORD)
+    b, c, h, w = x.shape
+    assert records.shape == (b,)
+    out = torch.empty_like(x)
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    check(lib.y3_mosaic_batch(x.data_ptr(), b, c, h, w, records.ctypes.data, out.data_ptr(), st), 'y3_mosaic_batch')
+    return out
 
 
 def format_labels_device(boxes, counts, image_size, anchors, number_classes):
@@ -192,18 +209,22 @@ class Dataset:
     With a label_device='gpu' reader the examples carry their boxes; a batch pads them to its own maximum (with counts) and
     y3_format_labels builds the label tensors on the device.  ``multiscale(sizes, period, seed)`` (such a reader only, DESIGN
     §3.11) gives batch i -- counted over the life of this object, not per epoch -- the size sizes[j], j a pure function of
-    (seed, i // period): the batch is augmented straight to that size and its labels are built at it."""
+    (seed, i // period): the batch is augmented straight to that size and its labels are built at it.
+    ``mosaic(prob, seed, min_visible)`` (such a reader only) turns each image of a batch, with probability prob, into a
+    mosaic of itself and three other images of the same batch: drawn as a pure function of (seed, the reader's shard, i), composed
+    on the device after the augmentation at the batch's size, the boxes remapped on the host before they are uploaded."""
 
-    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None):
+    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None, mosaic=None):
         self.reader, self.batch_size, self.device, self.prefetch_depth = reader, batch_size, device, prefetch_depth
         self.multiscale_cfg = multiscale       # None or (sizes [(h, w)], period, seed)
+        self.mosaic_cfg = mosaic               # None or (prob, seed, min_visible)
         self.batches = 0                       # batches handed out so far, over every iteration of this object
 
     def batch(self, n):
-        return Dataset(self.reader, int(n), self.device, self.prefetch_depth, self.multiscale_cfg)
+        return Dataset(self.reader, int(n), self.device, self.prefetch_depth, self.multiscale_cfg, self.mosaic_cfg)
 
     def prefetch(self, n):
-        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)), self.multiscale_cfg)     # batches, not examples: 4 is plenty
+        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)), self.multiscale_cfg, self.mosaic_cfg)     # batches, not examples: 4 is plenty
 
     def multiscale(self, sizes, period, seed=0):
         """Multi-scale training: see the class docstring.  sizes: (h, w) pairs, multiples of 32; period: batches per draw."""
@@ -214,7 +235,18 @@ class Dataset:
             raise ValueError('multiscale sizes must be (h, w) multiples of {}, got {!r}'.format(NETWORK_DOWNSAMPLE_FACTOR, sizes))
         if isinstance(period, bool) or int(period) != period or int(period) < 1:
             raise ValueError('multiscale period must be an integer >= 1, got {!r}'.format(period))
-        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, (sizes, int(period), int(seed)))
+        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, (sizes, int(period), int(seed)), self.mosaic_cfg)
+
+    def mosaic(self, prob, seed=0, min_visible=0.25):
+        """Mosaic augmentation: see the class docstring.  prob: share of mosaic images, 0 < prob <= 1; min_visible: a box stays when
+        at least this share of its area lies in the window taken from its image (augment.mosaic_boxes)."""
+        if getattr(self.reader, 'label_device', 'cpu') != 'gpu':
+            raise ValueError("mosaic() needs a reader with label_device='gpu': label tensors built in the workers cannot be remapped")
+        if isinstance(prob, bool) or not 0 < float(prob) <= 1:
+            raise ValueError('mosaic prob must be in (0, 1], got {!r}'.format(prob))
+        if isinstance(min_visible, bool) or not 0 <= float(min_visible) <= 1:
+            raise ValueError('mosaic min_visible must be in [0, 1], got {!r}'.format(min_visible))
+        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, self.multiscale_cfg, (float(prob), int(seed), float(min_visible)))
 
     def size_of_batch(self, i):
         """(h, w) of batch i of this dataset: the reader's stored size unless multiscale() is on."""
@@ -225,18 +257,31 @@ class Dataset:
 
     def _device_batch(self, dev, imgs, records, boxes, counts):
         """A label_device='gpu' batch on the device: imgs the raw pixels (already there), records host AUG_RECORD [B], boxes /
-        counts host int32 (NumPy arrays or pinned tensors).  Augments to this batch's size, z-scores, builds the labels."""
+        counts host int32 (NumPy arrays or pinned tensors).  Augments to this batch's size, z-scores, builds the labels; with
+        mosaic() on, the records of this batch are drawn here, the boxes remapped on the host and the augmented images recombined
+        before the z-score."""
         crop = tuple(self.reader.image_size[:2])
-        size = self.size_of_batch(self.batches)
+        index = self.batches
+        size = self.size_of_batch(index)
         self.batches += 1
         if size != crop:
             records = augment.rescale_record(records, crop, size)
             b = boxes.numpy() if torch.is_tensor(boxes) else boxes
             boxes = augment.scale_boxes(b.reshape(-1, 5), crop, size).reshape(b.shape)      # (padding rows are never read)
+        mosaic = None
+        if self.mosaic_cfg is not None:
+            prob, seed, min_visible = self.mosaic_cfg
+            mosaic = augment.draw_mosaic(seed, self.reader.shard_index, index, len(records), size, prob)
+            b, c = (x.numpy() if torch.is_tensor(x) else x for x in (boxes, counts))
+            # an output image can hold the boxes of four inputs: collated afresh (never into the pinned prefetch buffer)
+            boxes, counts = collate_boxes(augment.mosaic_boxes([b[i, :c[i]] for i in range(len(c))], mosaic, size, min_visible))
         as_t = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True)
         labels = format_labels_device(as_t(boxes), as_t(counts), (size[0], size[1], self.reader.image_size[2]), self.reader.anchors,
                                       self.reader.number_classes)
-        return (zscore_normalize_device(augment_device(imgs, records, size)), *labels)
+        imgs = augment_device(imgs, records, size)
+        if mosaic is not None:
+            imgs = mosaic_device(imgs, mosaic)
+        return (zscore_normalize_device(imgs), *labels)
 
     def shard(self, num_shards, index):
         """experimental_distribute_dataset (train.py:62,66): every replica reads its own examples.  The reader's
@@ -260,6 +305,8 @@ class Dataset:
 
     def __iter__(self):
         if self.batch_size is None:
+            if self.mosaic_cfg is not None:
+                raise ValueError('mosaic() combines the images of a batch: call batch(n) before iterating')
             yield from self.reader.generator()           # z-scored examples, as the reference's unbatched dataset yields them
             return
         dev = self.device or torch.device('cuda', torch.cuda.current_device())
