@@ -490,6 +490,54 @@ size_t y3_nms_workspace_bytes_ex(int n, int nb, int num_classes, int method);
 int y3_nms_single_class(const float* rows5, int m, float iou_thr, int* keep_idx, int* keep_cnt,
                         float* keep_score, void* workspace, size_t workspace_bytes, y3_stream_t stream);
 
+/* ---- tiled inference: merge of the tiles' detections on the device (inference_tiled.py:230-301) -----
+ * y3_tile_merge appends the detections of one batch of n tiles to a pool of whole-image detections, in the order the host
+ * loop produces them: tile order, class-major inside a tile, keep order inside a class; calls append in call order.
+ * rows [n, nb, ld] / keep_idx [n,K,max_keep] / keep_cnt [n,K] / keep_score [n,K,max_keep]: the decode rows and the outputs of
+ * y3_nms_per_class(_ex) for them (no clip).  table_dev: DEVICE int32 [n][6], the rows {y0, ny, pre_y, x0, nx, pre_x} of
+ * y3_tile_gather's table for these tiles; y0 / x0 are the CLAMPED origins the merge shifts by (Q12).  For every kept entry
+ * with box b0,b1,b2,b3 of tile (ty, tx), fp32 in the order written, no contraction (E = edge, th x tw = tile, H x W = image):
+ *   cx = (b2 + b0) / 2, cxg = cx + tx;  cy = (b3 + b1) / 2, cyg = cy + ty;
+ *   dropped (centre in a ghost band) when  (cyg > E && cy < E - margin) || (cyg <= H - E && cy >= (th - E) + margin)
+ *                                       || (cxg > E && cx < E - margin) || (cxg <= W - E && cx >= (tw - E) + margin);
+ *     E - margin and (th - E) + margin are fp32 operations on (float)E, margin, (float)(th - E); margin == 0 is bit for bit
+ *     merge_tile_detections' test, margin > 0 lets both tiles keep an object whose centre lies within margin of their
+ *     zone boundary (y3_nms_labelled then removes the duplicate);
+ *   x0 = int32(rint(b0 + tx)), y0 = int32(rint(b1 + ty)), x1 = int32(rint(b2 + tx)), y1 = int32(rint(b3 + ty))  (np.round:
+ *     half to even; a value outside int32 converts to INT_MIN as NumPy's x86-64 cast does);
+ *   dropped (centre outside the image) when x0 + x1 < 0 || x0 + x1 >= 2 W, likewise y (the int32 sums, which is what
+ *     finalize_predictions' float64 (x1 + x0) / 2.0 comparison decides);
+ *   pool row = clamp(x0, 0, W-1), clamp(y0, 0, H-1), clamp(x1, 0, W-1), clamp(y1, 0, H-1), keep_score, class index.
+ * The coordinates are stored as fp32, exact below 2^24: img_h, img_w <= 2^24 (Y3_EINVAL above).
+ * pool: fp32 [cap][6].  pool_count: DEVICE int32 [2] = {rows written so far, rows needed so far}; zero it before the first
+ * batch of an image.  A call adds its survivors to pool_count[1] whatever cap is, writes only the rows at positions < cap
+ * and sets pool_count[0] = min(pool_count[1], cap): when pool_count[1] > cap the caller re-merges into a larger pool.
+ * Two launches (count per (tile, class) segment; exclusive prefix + ordered write by ballot ranks).  No atomics, nothing
+ * read back by the host.  0 <= margin < edge.  n * num_classes <= Y3_TILE_MERGE_MAX_SEGMENTS per call (every workgroup of
+ * the second launch sums the counts before its segment itself; split a larger batch into several calls) and
+ * n * num_classes * max_keep < 2^31.  pool_count[1] saturates at INT_MAX (2^31 - 1) when the batches of an image add up to
+ * more: treat that value as an error.  workspace: y3_tile_merge_workspace_bytes(n, num_classes). */
+#define Y3_TILE_MERGE_MAX_SEGMENTS 65536
+int y3_tile_merge(const float* rows, int n, int nb, int ld, int num_classes, const int* keep_idx, const int* keep_cnt,
+                  const float* keep_score, int max_keep, const int* table_dev, int tile_h, int tile_w, int img_h, int img_w,
+                  int edge, float margin, float* pool, int cap, int* pool_count, void* workspace, size_t workspace_bytes,
+                  y3_stream_t stream);
+size_t y3_tile_merge_workspace_bytes(int n, int num_classes);
+
+/* y3_nms_labelled: class-wise NMS over such a pool.  pool [m][6] = x0,y0,x1,y1,score,class; workgroup c takes the rows whose
+ * column 5 == (float)c (a label outside 0..K-1 belongs to no class) with score > 0 and score >= score_thr as candidates, the
+ * score as is (the order key is the score's bit pattern, so a row with a zero, negative or NaN score is never a candidate,
+ * whatever the method), and runs y3_nms_per_class_ex's method on them: the same
+ * kernels, key order (larger score first, equal scores: higher row first), IoU, DIoU and soft decay.  Y3_NMS_NONE: no
+ * suppression at all -- the candidates in key order, no IoU formed (two zero-area boxes have IoU 0/0 and would drop each other
+ * under any threshold).  keep_idx [K][max_keep] pool row indices, keep_cnt [K], keep_score [K][max_keep]: the layout
+ * y3_eval_match reads for n = 1.  m >= 1.  workspace: y3_nms_workspace_bytes_ex(1, m, num_classes, method) (Y3_NMS_NONE:
+ * y3_nms_workspace_bytes(1, m, num_classes)). */
+#define Y3_NMS_NONE 4   /* y3_nms_labelled only */
+int y3_nms_labelled(const float* pool, int m, int num_classes, int method, float score_thr, float iou_thr, float sigma,
+                    int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace, size_t workspace_bytes,
+                    y3_stream_t stream);
+
 /* bbox_utils.filter_small_boxes (bbox_utils.py:274-281): keep_idx[0..*keep_cnt) = indices, in row order, of the rows
  * [x0,y0,x1,y1,...] (pitch ld floats) with (x1-x0) > min_size and (y1-y0) > min_size (strict, Q19).  keep_idx holds m ints. */
 int y3_filter_small_boxes(const float* rows, int m, int ld, float min_size, int* keep_idx, int* keep_cnt, y3_stream_t stream);

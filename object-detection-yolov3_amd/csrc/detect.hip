@@ -394,7 +394,8 @@ struct NmsArgs {
     int* keep_cnt;
     float* keep_score;
     int max_keep;
-    int raw;  // 1: rows are [x0,y0,x1,y1,score] and the score is used as is (single_class_nms)
+    int raw;  // 1: rows are [x0,y0,x1,y1,score] and the score is used as is (single_class_nms); 2: [x0,y0,x1,y1,score,class], the
+              // score as is, and a row is a candidate of its own class only (y3_nms_labelled)
     int cap;  // capacity (power of two) of the per-block key array
     unsigned char* ws;
     size_t ws_per_block;
@@ -522,10 +523,14 @@ __device__ __forceinline__ bool nms_candidate(const NmsArgs& p, const float* r, 
     nms_load_box(p, r, x0, y0, x1, y1);
     const float w = x1 - x0, h = y1 - y0;
     score = p.raw ? r[4] : sqrtf(r[5 + cls] * r[4]);
+    // labelled rows: column 5 names the one class the row belongs to; the order key is the score's bit pattern, so only a
+    // positive score is a candidate (0 would give row 0 the padding key, a negative one would sort first; NaN fails too)
+    if (p.raw == 2 && !(r[5] == (float)cls && score > 0.f)) return false;
     return w > p.min_box && h > p.min_box && score >= p.score_thr;
 }
 
-// CRIT: Y3_NMS_HARD (nms_suppressed) or Y3_NMS_DIOU (nms_suppressed_diou); the greedy rounds are the same
+// CRIT: Y3_NMS_HARD (nms_suppressed) or Y3_NMS_DIOU (nms_suppressed_diou); the greedy rounds are the same.  Y3_NMS_NONE (y3_nms_labelled
+// only): sort, then every candidate is kept
 template <bool LDS_KEYS, int CRIT>
 __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -584,76 +589,89 @@ __global__ __launch_bounds__(1024) void nms_kernel(const NmsArgs p) {
         }
     }
 
-    // 3. gather the sorted boxes (SoA) and their areas
-    for (int i = tid; i < count; i += 1024) {
-        float x0, y0, x1, y1;
-        nms_load_box(p, rows + (long long)(unsigned)(keys[i] & 0xffffffffull) * p.D, x0, y0, x1, y1);
-        bx0[i] = x0;
-        by0[i] = y0;
-        bx1[i] = x1;
-        by1[i] = y1;
-        bar[i] = (x1 - x0) * (y1 - y0);
-    }
-    __syncthreads();
+    // Y3_NMS_NONE: the sorted candidates are the keep list (no IoU is formed, so degenerate boxes cannot drop anything); the greedy
+    // rounds are not instantiated
+    if constexpr (CRIT == Y3_NMS_NONE) {
+        int* o_idx = p.keep_idx + (long long)blockIdx.x * p.max_keep;
+        float* o_sc = p.keep_score + (long long)blockIdx.x * p.max_keep;
+        const int m = count < p.max_keep ? count : p.max_keep;
+        for (int i = tid; i < m; i += 1024) {
+            o_idx[i] = (int)(unsigned)(keys[i] & 0xffffffffull);
+            o_sc[i] = __uint_as_float((unsigned)(keys[i] >> 32));
+        }
+        if (tid == 0) p.keep_cnt[blockIdx.x] = m;
+    } else {
+        // 3. gather the sorted boxes (SoA) and their areas
+        for (int i = tid; i < count; i += 1024) {
+            float x0, y0, x1, y1;
+            nms_load_box(p, rows + (long long)(unsigned)(keys[i] & 0xffffffffull) * p.D, x0, y0, x1, y1);
+            bx0[i] = x0;
+            by0[i] = y0;
+            bx1[i] = x1;
+            by1[i] = y1;
+            bar[i] = (x1 - x0) * (y1 - y0);
+        }
+        __syncthreads();
 
-    // 4. greedy suppression in sorted order, 64 candidates per round
-    int* out_idx = p.keep_idx + (long long)blockIdx.x * p.max_keep;
-    float* out_sc = p.keep_score + (long long)blockIdx.x * p.max_keep;
-    for (int base = 0; base < count; base += 64) {
-        if (tid < 64) {
-            const int j = base + tid;
-            const bool valid = j < count;
-            bool alive = valid && !dead[j];
-            float x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f, ar = 0.f;
-            if (valid) {
-                x0 = bx0[j];
-                y0 = by0[j];
-                x1 = bx1[j];
-                y1 = by1[j];
-                ar = bar[j];
+        // 4. greedy suppression in sorted order, 64 candidates per round
+        int* out_idx = p.keep_idx + (long long)blockIdx.x * p.max_keep;
+        float* out_sc = p.keep_score + (long long)blockIdx.x * p.max_keep;
+        for (int base = 0; base < count; base += 64) {
+            if (tid < 64) {
+                const int j = base + tid;
+                const bool valid = j < count;
+                bool alive = valid && !dead[j];
+                float x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f, ar = 0.f;
+                if (valid) {
+                    x0 = bx0[j];
+                    y0 = by0[j];
+                    x1 = bx1[j];
+                    y1 = by1[j];
+                    ar = bar[j];
+                }
+                unsigned long long mask = __ballot(alive);
+                unsigned long long kept = 0ull;
+                while (mask) {
+                    const int k = __ffsll((long long)mask) - 1;
+                    kept |= 1ull << k;
+                    const float kx0 = __shfl(x0, k), ky0 = __shfl(y0, k), kx1 = __shfl(x1, k), ky1 = __shfl(y1, k), kar = __shfl(ar, k);
+                    if (alive && tid > k && nms_test<CRIT>(kx0, ky0, kx1, ky1, kar, x0, y0, x1, y1, ar, p.iou_thr)) alive = false;
+                    mask = __ballot(alive) & ~((2ull << k) - 1ull);
+                }
+                const int nk = __popcll(kept);
+                if ((kept >> tid) & 1ull) {
+                    const int rank = __popcll(kept & ((1ull << tid) - 1ull));
+                    s_kb[0][rank] = x0;
+                    s_kb[1][rank] = y0;
+                    s_kb[2][rank] = x1;
+                    s_kb[3][rank] = y1;
+                    s_kb[4][rank] = ar;
+                    const int o = s_kept + rank;
+                    if (o < p.max_keep) {
+                        out_idx[o] = (int)(unsigned)(keys[j] & 0xffffffffull);
+                        out_sc[o] = __uint_as_float((unsigned)(keys[j] >> 32));
+                    }
+                }
+                if (tid == 0) s_nk = nk;
             }
-            unsigned long long mask = __ballot(alive);
-            unsigned long long kept = 0ull;
-            while (mask) {
-                const int k = __ffsll((long long)mask) - 1;
-                kept |= 1ull << k;
-                const float kx0 = __shfl(x0, k), ky0 = __shfl(y0, k), kx1 = __shfl(x1, k), ky1 = __shfl(y1, k), kar = __shfl(ar, k);
-                if (alive && tid > k && nms_test<CRIT>(kx0, ky0, kx1, ky1, kar, x0, y0, x1, y1, ar, p.iou_thr)) alive = false;
-                mask = __ballot(alive) & ~((2ull << k) - 1ull);
-            }
-            const int nk = __popcll(kept);
-            if ((kept >> tid) & 1ull) {
-                const int rank = __popcll(kept & ((1ull << tid) - 1ull));
-                s_kb[0][rank] = x0;
-                s_kb[1][rank] = y0;
-                s_kb[2][rank] = x1;
-                s_kb[3][rank] = y1;
-                s_kb[4][rank] = ar;
-                const int o = s_kept + rank;
-                if (o < p.max_keep) {
-                    out_idx[o] = (int)(unsigned)(keys[j] & 0xffffffffull);
-                    out_sc[o] = __uint_as_float((unsigned)(keys[j] >> 32));
+            __syncthreads();
+            const int nk = s_nk;
+            if (tid == 0) s_kept += nk;
+            if (nk > 0) {
+                for (int j = base + 64 + tid; j < count; j += 1024) {
+                    if (dead[j]) continue;
+                    const float x0 = bx0[j], y0 = by0[j], x1 = bx1[j], y1 = by1[j], ar = bar[j];
+                    for (int q = 0; q < nk; ++q)
+                        if (nms_test<CRIT>(s_kb[0][q], s_kb[1][q], s_kb[2][q], s_kb[3][q], s_kb[4][q], x0, y0, x1, y1, ar, p.iou_thr)) {
+                            dead[j] = 1;
+                            break;
+                        }
                 }
             }
-            if (tid == 0) s_nk = nk;
+            __syncthreads();
         }
-        __syncthreads();
-        const int nk = s_nk;
-        if (tid == 0) s_kept += nk;
-        if (nk > 0) {
-            for (int j = base + 64 + tid; j < count; j += 1024) {
-                if (dead[j]) continue;
-                const float x0 = bx0[j], y0 = by0[j], x1 = bx1[j], y1 = by1[j], ar = bar[j];
-                for (int q = 0; q < nk; ++q)
-                    if (nms_test<CRIT>(s_kb[0][q], s_kb[1][q], s_kb[2][q], s_kb[3][q], s_kb[4][q], x0, y0, x1, y1, ar, p.iou_thr)) {
-                        dead[j] = 1;
-                        break;
-                    }
-            }
-        }
-        __syncthreads();
+        if (tid == 0) p.keep_cnt[blockIdx.x] = s_kept < p.max_keep ? s_kept : p.max_keep;
     }
-    if (tid == 0) p.keep_cnt[blockIdx.x] = s_kept < p.max_keep ? s_kept : p.max_keep;
 }
 
 // ---------------------------------------------------------------------------
@@ -858,7 +876,7 @@ static void nms_greedy_launch(const NmsArgs& p, int blocks, hipStream_t st, bool
 static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw, int method, float min_box, float score_thr, float iou_thr,
                       float sigma, float clip_w, float clip_h, int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace,
                       size_t workspace_bytes, y3_stream_t stream) {
-    Y3_CHECK_ARG(method >= Y3_NMS_HARD && method <= Y3_NMS_SOFT_GAUSSIAN, "nms: unknown method %d", method);
+    Y3_CHECK_ARG(method >= Y3_NMS_HARD && method <= (raw == 2 ? Y3_NMS_NONE : Y3_NMS_SOFT_GAUSSIAN), "nms: unknown method %d", method);
     Y3_CHECK_ARG(!nms_soft(method) || score_thr > 0.f, "nms: soft-NMS needs score_thr > 0 (got %g)", (double)score_thr);
     Y3_CHECK_ARG(method != Y3_NMS_SOFT_GAUSSIAN || sigma > 0.f, "nms: Gaussian soft-NMS needs sigma > 0 (got %g)", (double)sigma);
     const size_t need = y3_nms_workspace_bytes_ex(n, nb, num_classes, method);
@@ -868,7 +886,7 @@ static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw
     NmsArgs p = {};
     p.rows = rows;
     p.nb = nb;
-    p.D = raw ? 5 : 5 + num_classes;
+    p.D = raw == 1 ? 5 : (raw == 2 ? 6 : 5 + num_classes);
     p.K = num_classes;
     p.raw = raw;
     p.min_box = min_box;
@@ -892,6 +910,8 @@ static int nms_launch(const float* rows, int n, int nb, int num_classes, int raw
         nms_greedy_launch<Y3_NMS_HARD>(p, blocks, st, &attr_failed);
     else if (method == Y3_NMS_DIOU)
         nms_greedy_launch<Y3_NMS_DIOU>(p, blocks, st, &attr_failed);
+    else if (method == Y3_NMS_NONE)
+        nms_greedy_launch<Y3_NMS_NONE>(p, blocks, st, &attr_failed);
     else if (nb <= Y3_SOFT_REG_ROWS)
         hipLaunchKernelGGL((soft_nms_kernel<Y3_SOFT_REG_ROWS / 1024>), dim3(blocks), dim3(1024), 0, st, p);
     else
@@ -922,6 +942,14 @@ extern "C" int y3_nms_single_class(const float* rows5, int m, float iou_thr, int
                                    size_t workspace_bytes, y3_stream_t stream) {
     return nms_launch(rows5, 1, m, 1, 1, Y3_NMS_HARD, -INFINITY, -INFINITY, iou_thr, 0.f, -1.f, -1.f, keep_idx, keep_cnt, keep_score, m,
                       workspace, workspace_bytes, stream);
+}
+
+// Class-wise NMS over a pool of labelled detections (the merged tiles of one image): block c takes the rows whose column 5 == c
+extern "C" int y3_nms_labelled(const float* pool, int m, int num_classes, int method, float score_thr, float iou_thr, float sigma,
+                               int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace, size_t workspace_bytes,
+                               y3_stream_t stream) {
+    return nms_launch(pool, 1, m, num_classes, 2, method, -INFINITY, score_thr, iou_thr, sigma, -1.f, -1.f, keep_idx, keep_cnt, keep_score,
+                      max_keep, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------

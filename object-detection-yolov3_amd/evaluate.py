@@ -61,6 +61,33 @@ def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', bat
     return res, ev.num_images, time.perf_counter() - t0
 
 
+def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, precision='fp32', batch_size=None,
+                   iou_thresholds=metrics.COCO_IOU_THRESHOLDS, max_detections=None, distributed=False, nms='hard', nms_sigma=0.5,
+                   seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5):
+    """``evaluate`` for the tiled pipeline (inference_tiled.py with --merge-device gpu): every image, of any size, is cut
+    into tiles, the tiles' detections are merged on the device (seam_margin) and the pool is matched against the
+    whole-image ground truth there (DetectionEvaluator.add_pool with nms=merge_nms).  batch_size: tiles per network launch
+    (None: inference_tiled's default).  Returns (result dict, number of images, seconds)."""
+    import inference_tiled
+    bbox_utils.check_nms_args(nms, nms_sigma)
+    bbox_utils.check_merge_args('gpu', seam_margin, merge_nms, merge_nms_sigma, inference_tiled.EDGE_EFFECT_RANGE)
+    yolo = load_model(saved_model_filepath)
+    yolo.inference_precision = precision
+    if list(tile_size) != list(yolo.img_size[:2]):
+        raise RuntimeError('tile size {} must equal the size the model was trained at {} (Q18)'.format(list(tile_size), yolo.img_size[:2]))
+    model = yolo.get_keras_model()
+    ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
+    t0 = time.perf_counter()
+    for _, img, gt in examples:
+        pool, count, _ = inference_tiled.tiled_pool_device(model, img, tile_size, min_box_size, batch_size, nms, nms_sigma, seam_margin)
+        ev.add_pool(pool, count, gt, nms=merge_nms, nms_sigma=merge_nms_sigma)
+    if distributed:
+        ev = metrics.all_gather_evaluator(ev)
+    res = ev.result()
+    torch.cuda.synchronize()
+    return res, ev.num_images, time.perf_counter() - t0
+
+
 def _fmt(v):
     return '' if isinstance(v, float) and math.isnan(v) else repr(float(v))
 
@@ -102,7 +129,8 @@ if __name__ == '__main__':
     parser.add_argument('--image-format', dest='image_format', type=str, default='tif')
     parser.add_argument('--min-box-size', type=int, default=32, help='Smallest detection to consider. Default (32, 32).')
     parser.add_argument('--precision', choices=['fp32', 'bf16'], default='fp32', help='conv arithmetic')
-    parser.add_argument('--batch-size', type=int, default=8, help='images per model call')
+    parser.add_argument('--batch-size', type=int, default=None, help='images per model call (default 8); with --tiled: tiles per network '
+                        'launch (default: inference_tiled.py\'s)')
     parser.add_argument('--iou-thresholds', type=float, nargs='+', default=None,
                         help='IoU thresholds (1..32 values in (0, 1]); default 0.50:0.05:0.95')
     parser.add_argument('--max-detections', type=int, default=None, help='detections kept per image and class (default: all NMS keeps)')
@@ -110,6 +138,15 @@ if __name__ == '__main__':
     parser.add_argument('--nms', choices=list(bbox_utils.NMS_METHODS), default='hard',
                         help='NMS method (extension): hard (the reference\'s greedy NMS, default), diou, soft-linear or soft-gaussian')
     parser.add_argument('--nms-sigma', dest='nms_sigma', type=float, default=0.5, help='sigma of --nms soft-gaussian (> 0)')
+    parser.add_argument('--tiled', action='store_true', help='score the tiled pipeline (inference_tiled.py --merge-device gpu) on images of any '
+                        'size from --image-folder / --csv-folder; needs --tile-height and --tile-width (the size the model was trained at)')
+    parser.add_argument('--tile-height', type=int, default=None)
+    parser.add_argument('--tile-width', type=int, default=None)
+    parser.add_argument('--seam-margin', dest='seam_margin', type=float, default=0.0, metavar='PX',
+                        help='--tiled: a tile also keeps centres up to PX inside its ghost band (0 <= PX < 96)')
+    parser.add_argument('--merge-nms', dest='merge_nms', choices=list(bbox_utils.MERGE_NMS_METHODS), default='none',
+                        help='--tiled: class-wise NMS over the merged detections of the whole image')
+    parser.add_argument('--merge-nms-sigma', dest='merge_nms_sigma', type=float, default=0.5, help='sigma of --merge-nms soft-gaussian (> 0)')
     parser.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend under torch.distributed.run: nccl (= RCCL, '
                         'one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
     a = parser.parse_args()
@@ -117,7 +154,20 @@ if __name__ == '__main__':
         parser.error('give exactly one data source: --database, or --image-folder with --csv-folder')
     if a.database is None and (a.image_folder is None or a.csv_folder is None):
         parser.error('--image-folder and --csv-folder go together')
-    if a.batch_size < 1:
+    if a.tiled:
+        if a.database is not None:
+            parser.error('--tiled reads whole images: give --image-folder with --csv-folder, not --database')
+        if a.tile_height is None or a.tile_width is None:
+            parser.error('--tiled needs --tile-height and --tile-width')
+        try:
+            bbox_utils.check_merge_args('gpu', a.seam_margin, a.merge_nms, a.merge_nms_sigma)
+        except ValueError as e:
+            parser.error(str(e))
+    elif a.tile_height is not None or a.tile_width is not None or a.seam_margin != 0 or a.merge_nms != 'none':
+        parser.error('--tile-height, --tile-width, --seam-margin and --merge-nms go with --tiled')
+    if a.batch_size is None and not a.tiled:
+        a.batch_size = 8
+    if a.batch_size is not None and a.batch_size < 1:
         parser.error('--batch-size must be >= 1')
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
         parser.error('--nms-sigma must be > 0')
@@ -143,11 +193,18 @@ if __name__ == '__main__':
         examples = database_examples(a.database, world, rank)
     else:
         examples = folder_examples(a.image_folder, a.csv_folder, a.image_format, world, rank)
-    res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
-                                distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma)
+    if a.tiled:
+        res, count, secs = evaluate_tiled(examples, a.saved_model_filepath, [a.tile_height, a.tile_width], a.min_box_size, a.precision,
+                                          a.batch_size, thresholds, a.max_detections, distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma,
+                                          seam_margin=a.seam_margin, merge_nms=a.merge_nms, merge_nms_sigma=a.merge_nms_sigma)
+    else:
+        res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
+                                    distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma)
     if rank == 0:
         print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
         print('NMS: {}'.format(a.nms + (' (sigma {:g})'.format(a.nms_sigma) if a.nms == 'soft-gaussian' else '')))
+        if a.tiled:
+            print('Tiled: {} x {} tiles, seam margin {:g}, merge NMS {}'.format(a.tile_height, a.tile_width, a.seam_margin, a.merge_nms))
         print_table(res)
         if a.output_file:
             write_csv(res, a.output_file)

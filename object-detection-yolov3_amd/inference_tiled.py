@@ -184,12 +184,44 @@ def upload_bands(table, sizes, height):
     return out
 
 
-def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5):
+def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5, merge_device='cpu',
+                          seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5):
     """inference_tiled.py:185-310.  ``yolo_model(batch, training=False)`` maps CUDA float32 [B,C,h,w] (z-scored) to
     rows [B, Nb, 5+K] (CUDA tensor or ndarray).  batch_size None: BATCH_SIZE tiles per launch on the fp32 path,
     plan_tile_batches() on the bf16 path.  nms / nms_sigma: the per-tile NMS method (bbox_utils.NMS_METHODS) and its
-    Gaussian parameter; the merge of the tiles' detections does not depend on it."""
+    Gaussian parameter; the merge of the tiles' detections does not depend on it.
+
+    merge_device 'cpu' (default): the per-tile detections are copied back and merged by merge_tile_detections /
+    finalize_predictions.  'gpu' (extension): they are merged on the device (tiled_pool_device) and come back
+    once; with the other merge options at their defaults the returned float64 [M, 6] array is the host path's, order
+    included.  seam_margin (pixels, 0 <= margin < EDGE_EFFECT_RANGE, needs 'gpu'): a tile also keeps a detection whose
+    centre lies up to this far inside its ghost band, so an object on a zone boundary is reported by both neighbours
+    instead of by chance.  merge_nms ('none' or one of bbox_utils.NMS_METHODS, needs 'gpu'; merge_nms_sigma: Gaussian
+    parameter): class-wise NMS over the whole image's detections (IoU threshold 0.3; the soft methods drop below the per-tile
+    score threshold 0.1 and return decayed scores), which removes those duplicates.  With a merge NMS the rows come back
+    class-major, in keep order (score descending) inside a class, not in tile order."""
     bbox_utils.check_nms_args(nms, nms_sigma)
+    bbox_utils.check_merge_args(merge_device, seam_margin, merge_nms, merge_nms_sigma, EDGE_EFFECT_RANGE)
+    if merge_device == 'gpu':
+        pool, count, classes = tiled_pool_device(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, seam_margin)
+        if merge_nms != 'none':
+            pool = bbox_utils.gather_kept(pool, *bbox_utils.nms_labelled_device(pool, classes, merge_nms, sigma=merge_nms_sigma))
+        predictions = pool.cpu().numpy().astype(np.float64)
+        print('Found: {} rois'.format(predictions.shape[0]))
+        return predictions
+    return _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, None)
+
+
+def tiled_pool_device(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5, seam_margin=0.0):
+    """The tiled pipeline with the merge on the device: -> (pool CUDA float32 [M, 6] = x0, y0, x1, y1, score, class in the host
+    merge's order, M, number of classes).  One host read (the count) per image; nothing else leaves the device."""
+    bbox_utils.check_nms_args(nms, nms_sigma)
+    bbox_utils.check_merge_args('gpu', seam_margin, 'none', 0.5, EDGE_EFFECT_RANGE)
+    return _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, float(seam_margin))
+
+
+def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, device_margin):
+    """device_margin None: the host merge -> predictions; a float: the device merge with that seam margin -> tiled_pool_device's tuple."""
     img_size = img.shape
     # the image goes to the GPU once, in its own dtype; cropping, reflect padding, astype(float32) and HWC -> CHW of
     # convert_image_to_tiles (inference_tiled.py:29-100,199-203) happen there, one launch per batch of tiles
@@ -201,6 +233,11 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
     table, xs, ys = tile_table(img_size[0], img_size[1], tile_size)
     table_dev = torch.from_numpy(table).cuda()
     boxes_list, scores_list, class_label_list = [], [], []
+    pool, classes = None, 0
+    if device_margin is not None:
+        # every batch's merge runs on ONE stream, behind that batch's NMS event: the batches append in batch order although their
+        # networks alternate between two streams
+        pool = bbox_utils.TilePool(tile_size, img_size[:2], device_margin, EDGE_EFFECT_RANGE, device=table_dev.device, stream=torch.cuda.Stream())
 
     def merge(collect, b0):
         for k, (boxes, scores, class_label, _) in enumerate(collect()):
@@ -259,19 +296,29 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
                 x = imagereader.zscore_normalize_device(x)               # per TILE statistics (inference_tiled.py:205, Q12)
                 rows = yolo_model(x, training=False, slot=bi % slots) if slots > 1 else yolo_model(x, training=False)
             rows = torch.as_tensor(rows, dtype=torch.float32).cuda().clone()   # the slot's output buffer is reused two batches later
-            queued.append((bbox_utils.detect_async(rows, min_roi_size, method=nms, sigma=nms_sigma), b0))
+            if pool is None:
+                queued.append((bbox_utils.detect_async(rows, min_roi_size, method=nms, sigma=nms_sigma), b0))
+            else:
+                keep = bbox_utils.nms_device(rows, min_roi_size, private_outputs=True, method=nms, sigma=nms_sigma)
+                done = torch.cuda.Event()
+                done.record(torch.cuda.current_stream())
+                bbox_utils.merge_tiles_device(pool, rows, *keep, table_dev[b0:b0 + nb], done)
+                classes = rows.shape[2] - 5
     for item in queued:
         merge(*item)
     for s in streams:
         cur.wait_stream(s)
+    if pool is not None:
+        return pool.finish() + (classes,)
     predictions = finalize_predictions(boxes_list, scores_list, class_label_list, img_size)
     print('Found: {} rois'.format(predictions.shape[0]))
     return predictions
 
 
 def inference_image_folder(image_folder, image_format, saved_model_filepath, output_folder, tile_size, min_roi_size, precision='fp32',
-                           batch_size=None, nms='hard', nms_sigma=0.5):
+                           batch_size=None, nms='hard', nms_sigma=0.5, merge_device='cpu', seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5):
     bbox_utils.check_nms_args(nms, nms_sigma)
+    bbox_utils.check_merge_args(merge_device, seam_margin, merge_nms, merge_nms_sigma, EDGE_EFFECT_RANGE)
     if not os.path.exists(saved_model_filepath):
         raise RuntimeError('Missing saved_model_filepath File')
     if image_format.startswith('.'):
@@ -296,7 +343,8 @@ def inference_image_folder(image_folder, image_format, saved_model_filepath, out
         img = imagereader.imread(img_filepath)
         if len(img.shape) == 2:
             img = np.expand_dims(img, -1)
-        predictions = inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma)
+        predictions = inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, merge_device, seam_margin,
+                                            merge_nms, merge_nms_sigma)
         bbox_utils.write_boxes_from_ltrbpc(predictions, os.path.join(output_folder, file_name.replace(image_format, 'csv')))
 
 
@@ -314,8 +362,19 @@ if __name__ == '__main__':
     parser.add_argument('--nms', choices=list(bbox_utils.NMS_METHODS), default='hard',
                         help='NMS method (extension): hard (the reference\'s greedy NMS, default), diou, soft-linear or soft-gaussian')
     parser.add_argument('--nms-sigma', dest='nms_sigma', type=float, default=0.5, help='sigma of --nms soft-gaussian (> 0)')
+    parser.add_argument('--merge-device', dest='merge_device', choices=['cpu', 'gpu'], default='cpu',
+                        help='where the tiles\' detections are merged (extension): cpu (the reference\'s host loop, default) or gpu')
+    parser.add_argument('--seam-margin', dest='seam_margin', type=float, default=0.0, metavar='PX',
+                        help='with --merge-device gpu: a tile also keeps centres up to PX inside its ghost band (0 <= PX < %d)' % EDGE_EFFECT_RANGE)
+    parser.add_argument('--merge-nms', dest='merge_nms', choices=list(bbox_utils.MERGE_NMS_METHODS), default='none',
+                        help='with --merge-device gpu: class-wise NMS over the merged detections of the whole image')
+    parser.add_argument('--merge-nms-sigma', dest='merge_nms_sigma', type=float, default=0.5, help='sigma of --merge-nms soft-gaussian (> 0)')
     a = parser.parse_args()
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
         parser.error('--nms-sigma must be > 0')
+    try:
+        bbox_utils.check_merge_args(a.merge_device, a.seam_margin, a.merge_nms, a.merge_nms_sigma, EDGE_EFFECT_RANGE)
+    except ValueError as e:
+        parser.error(str(e))
     inference_image_folder(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, [a.tile_height, a.tile_width], a.min_box_size, a.precision, a.batch_size,
-                           a.nms, a.nms_sigma)
+                           a.nms, a.nms_sigma, a.merge_device, a.seam_margin, a.merge_nms, a.merge_nms_sigma)

@@ -112,6 +112,9 @@ SIGNATURES = {
     'y3_nms_single_class': (i32, [fp, i32, f32, ip, ip, fp, vp, sz, vp]),
     'y3_nms_per_class_ex': (i32, [fp, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
     'y3_nms_workspace_bytes_ex': (sz, [i32, i32, i32, i32]),
+    'y3_nms_labelled': (i32, [fp, i32, i32, i32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
+    'y3_tile_merge': (i32, [fp, i32, i32, i32, i32, ip, ip, fp, i32, ip, i32, i32, i32, i32, i32, f32, fp, i32, ip, vp, sz, vp]),
+    'y3_tile_merge_workspace_bytes': (sz, [i32, i32]),
     'y3_filter_small_boxes': (i32, [fp, i32, i32, f32, ip, ip, vp]),
     'y3_compute_iou': (i32, [fp, fp, i32, i32, fp, vp]),
     'y3_comm_unique_id': (i32, [vp]),

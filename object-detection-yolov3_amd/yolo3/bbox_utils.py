@@ -9,7 +9,7 @@ of the candidates.  CSV writers follow bbox_utils.py:47-62 and 284-300.
 import numpy as np
 import torch
 
-from ._hip import lib, check
+from ._hip import lib, check, HipError
 
 
 # opt-in NMS variants (y3_nms_per_class_ex); 'hard' is the reference's greedy NMS and the default everywhere
@@ -122,6 +122,147 @@ def detect_async(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, cli
                 out[i] = (boxes[a:b], sc[a:b], lab[a:b], idx[a:b])
         return out
     return collect
+
+
+# ---- tiled inference: the tiles' detections merged on the device (y3_tile_merge / y3_nms_labelled) ------------
+MERGE_NMS_METHODS = ('none',) + NMS_METHODS
+_MERGE_NMS_CODES = dict(_NMS_CODES, none=4)         # Y3_NMS_NONE
+TILE_POOL_ROWS = 8192                               # first capacity of a pool; an image that needs more is merged again
+
+
+def check_merge_args(merge_device='cpu', seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5, edge=96):
+    """Host-side validation of the merge options of inference_image_tiled / evaluate.py --tiled: ValueError on an unknown
+    device or method, a margin outside [0, edge), Gaussian sigma <= 0, and a margin or a merge NMS without the device merge
+    (the host merge has neither)."""
+    if merge_device not in ('cpu', 'gpu'):
+        raise ValueError("merge_device must be 'cpu' or 'gpu', got {!r}".format(merge_device))
+    if merge_nms not in MERGE_NMS_METHODS:
+        raise ValueError('merge_nms must be one of {}, got {!r}'.format(', '.join(MERGE_NMS_METHODS), merge_nms))
+    if not 0 <= float(seam_margin) < edge:
+        raise ValueError('seam_margin must be in [0, {}), got {}'.format(edge, seam_margin))
+    if merge_nms == 'soft-gaussian' and not float(merge_nms_sigma) > 0:
+        raise ValueError('soft-gaussian needs merge_nms_sigma > 0, got {}'.format(merge_nms_sigma))
+    if merge_device != 'gpu' and (float(seam_margin) != 0 or merge_nms != 'none'):
+        raise ValueError("seam_margin and merge_nms need merge_device='gpu'")
+
+
+class TilePool:
+    """The whole-image detections of one tiled image on the device: rows float32 [cap, 6] = x0, y0, x1, y1, score, class and
+    count int32 [2] = {rows written, rows needed}.  ``merge_tiles_device`` appends a batch of tiles; ``finish`` reads the
+    count (the image's one host read) and merges the retained batches again if the pool was too small.  cap: the first
+    capacity in rows (default TILE_POOL_ROWS).
+    stream: the stream every merge of this pool runs on (default: the current one), so batches append in call order however
+    their networks were scheduled."""
+
+    def __init__(self, tile_size, img_size, margin=0.0, edge=96, cap=None, device=None, stream=None):
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.tile_size = (int(tile_size[0]), int(tile_size[1]))
+        self.img_size = (int(img_size[0]), int(img_size[1]))
+        self.margin, self.edge = float(margin), int(edge)
+        self.stream = torch.cuda.current_stream(self.device) if stream is None else stream
+        self.batches = []             # (rows, keep_idx, keep_cnt, keep_score, table slice): kept for the retry and alive until finish
+        self.ws = None
+        self._alloc(max(1, int(TILE_POOL_ROWS if cap is None else cap)))
+
+    def _alloc(self, cap):
+        self.cap = cap
+        self.rows = torch.empty(cap, 6, dtype=torch.float32, device=self.device)
+        self.count = torch.zeros(2, dtype=torch.int32, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        if self.stream != cur:
+            self.stream.wait_stream(cur)                  # the allocations and the zero fill above
+            self.rows.record_stream(self.stream)
+            self.count.record_stream(self.stream)
+
+    def _launch(self, batch):
+        rows, keep_idx, keep_cnt, keep_score, table = batch
+        n, nb, ld = rows.shape
+        k, max_keep = keep_idx.shape[1], keep_idx.shape[2]
+        ws_bytes = int(lib.y3_tile_merge_workspace_bytes(n, k))
+        if self.ws is None or self.ws.numel() * 4 < ws_bytes:
+            with torch.cuda.stream(self.stream):          # a larger one replaces it behind the launches that use the old one
+                self.ws = torch.empty(ws_bytes // 4 + 1, dtype=torch.int32, device=self.device)
+        check(lib.y3_tile_merge(rows.data_ptr(), n, nb, ld, k, keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(), max_keep,
+                                table.data_ptr(), self.tile_size[0], self.tile_size[1], self.img_size[0], self.img_size[1], self.edge,
+                                self.margin, self.rows.data_ptr(), self.cap, self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 4,
+                                self.stream.cuda_stream), 'y3_tile_merge')
+
+    def finish(self):
+        """-> (rows [M, 6] device view of the pool, M).  Synchronises with the merge stream and reads the count."""
+        cur = torch.cuda.current_stream(self.device)
+        if self.stream != cur:
+            cur.wait_stream(self.stream)
+        need = int(self.count[1].item())
+        if need >= 2 ** 31 - 1:
+            raise HipError('y3_tile_merge: the detections of one image do not fit an int32 count')
+        if need > self.cap:                               # nothing was written past cap; the counts were: merge again, all of it
+            # on the current stream: the batch tensors and the workspace were allocated on the slot streams and the merge stream, so
+            # they are recorded on this one before its launches use them (they may be freed while those are still pending)
+            self.stream = cur
+            for t in [t for batch in self.batches for t in batch] + ([self.ws] if self.ws is not None else []):
+                t.record_stream(cur)
+            self._alloc(need)
+            for batch in self.batches:
+                self._launch(batch)
+        self.batches = []
+        return self.rows[:need], need
+
+
+def merge_tiles_device(pool, rows, keep_idx, keep_cnt, keep_score, table_dev, done=None):
+    """Append one batch of tiles to ``pool`` (y3_tile_merge): rows CUDA float32 [n, Nb, 5+K] and nms_device(...,
+    private_outputs=True)'s outputs for them, table_dev int32 [n, 6] = this batch's rows of the device tile table.
+    done: an event recorded behind the batch's NMS; the pool's stream waits for it.  Nothing is read back."""
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3 and rows.is_contiguous()
+    assert table_dev.dtype == torch.int32 and table_dev.is_contiguous() and table_dev.shape == (rows.shape[0], 6)
+    assert keep_idx.shape[0] == rows.shape[0] and keep_cnt.shape == keep_idx.shape[:2] and keep_score.shape == keep_idx.shape
+    if done is not None:
+        pool.stream.wait_event(done)
+    batch = (rows, keep_idx, keep_cnt, keep_score, table_dev)
+    for t in batch:
+        t.record_stream(pool.stream)
+    pool.batches.append(batch)
+    pool._launch(batch)
+
+
+def nms_labelled_device(pool_rows, num_classes, method='hard', iou_threshold=0.3, score_threshold=0.1, sigma=0.5):
+    """Class-wise NMS over pool rows CUDA float32 [M, 6] = x0, y0, x1, y1, score, class (y3_nms_labelled) on the current
+    stream.  method: 'none' (every row, in keep order: score descending, ties: higher row first) or one of NMS_METHODS;
+    hard / diou / none take every row of a class as a candidate, the soft methods those with score >= score_threshold and
+    return decayed scores.  Returns device (keep_idx [K, max(M, 1)] int32 pool rows, keep_cnt [K], keep_score)."""
+    if method not in _MERGE_NMS_CODES:
+        raise ValueError('merge nms method must be one of {}, got {!r}'.format(', '.join(MERGE_NMS_METHODS), method))
+    if method != 'none':
+        check_nms_args(method, sigma, score_threshold)
+    assert pool_rows.is_cuda and pool_rows.dtype == torch.float32 and pool_rows.dim() == 2 and pool_rows.shape[1] == 6
+    pool_rows = pool_rows.contiguous()
+    m, k, dev = pool_rows.shape[0], int(num_classes), pool_rows.device
+    keep_idx = torch.empty(k, max(m, 1), dtype=torch.int32, device=dev)
+    keep_cnt = torch.zeros(k, dtype=torch.int32, device=dev)
+    keep_score = torch.empty(k, max(m, 1), dtype=torch.float32, device=dev)
+    if m == 0:
+        return keep_idx, keep_cnt, keep_score
+    code = _MERGE_NMS_CODES[method]
+    ws_bytes = int(lib.y3_nms_workspace_bytes_ex(1, m, k, code))
+    ws = torch.empty(ws_bytes // 4 + 4, dtype=torch.float32, device=dev)
+    thr = float(score_threshold) if method.startswith('soft') else -np.inf
+    check(lib.y3_nms_labelled(pool_rows.data_ptr(), m, k, code, thr, float(iou_threshold), float(sigma), keep_idx.data_ptr(),
+                              keep_cnt.data_ptr(), keep_score.data_ptr(), m, ws.data_ptr(), ws_bytes,
+                              torch.cuda.current_stream(dev).cuda_stream), 'y3_nms_labelled')
+    return keep_idx, keep_cnt, keep_score
+
+
+def gather_kept(pool_rows, keep_idx, keep_cnt, keep_score):
+    """The kept rows of nms_labelled_device as a new pool [M', 6] on the device: class-major, keep order inside a class,
+    column 4 = keep_score (the decayed score of the soft methods).  Reads the K keep counts."""
+    cnt = keep_cnt.cpu().numpy().astype(np.int64)
+    k, width = keep_idx.shape
+    if int(cnt.sum()) == 0:
+        return pool_rows[:0].clone()
+    lin = np.concatenate([c * width + np.arange(cnt[c]) for c in range(k)])
+    lin = torch.from_numpy(lin).to(pool_rows.device)
+    out = pool_rows[keep_idx.view(-1)[lin].long()]        # a copy
+    out[:, 4] = keep_score.view(-1)[lin]
+    return out
 
 
 def detect(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5):

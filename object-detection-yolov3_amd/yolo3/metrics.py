@@ -148,6 +148,29 @@ class DetectionEvaluator:
         self._match(torch.from_numpy(rows).to(dev), n, mb, 4, -1.0, -1.0, torch.from_numpy(keep_idx).to(dev),
                     torch.from_numpy(keep_cnt).to(dev), torch.from_numpy(keep_score).to(dev), mb, gtb)
 
+    def add_pool(self, pool, count, gt_xywhc, nms='none', iou_threshold=0.3, score_threshold=0.1, nms_sigma=0.5):
+        """One whole image from the tiled pipeline: pool CUDA float32 [>= count, 6] = x0, y0, x1, y1, score, class
+        (inference_tiled.tiled_pool_device), its first ``count`` rows valid; gt_xywhc [G,5] X,Y,W,H,C.  nms: 'none' or a
+        method of bbox_utils.NMS_METHODS run class-wise over the pool first (bbox_utils.nms_labelled_device; the soft methods
+        replace the scores by the decayed ones), as inference_image_tiled(..., merge_nms=nms) does.  The detections are then
+        put in keep order on the device (y3_nms_labelled with Y3_NMS_NONE: score descending, ties: higher row first) and
+        matched; no detection leaves the GPU.  The state afterwards is, bit for bit, that of ``add_detections`` on the array
+        inference_image_tiled returns for the same settings.  Rows whose class is outside 0..K-1 are ignored."""
+        if nms != 'none':
+            bbox_utils.check_nms_args(nms, nms_sigma, score_threshold)
+        assert pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 2 and pool.shape[1] == 6 and 0 <= int(count) <= pool.shape[0]
+        K = self.num_classes
+        gt = self._gt_batch([gt_xywhc], 1)
+        pool = pool[:int(count)].contiguous()
+        if nms != 'none' and pool.shape[0]:
+            kept = bbox_utils.nms_labelled_device(pool, K, nms, iou_threshold, score_threshold, nms_sigma)
+            pool = bbox_utils.gather_kept(pool, *kept)
+        m = pool.shape[0]
+        keep_idx, keep_cnt, keep_score = bbox_utils.nms_labelled_device(pool, K, 'none')
+        if m == 0:
+            pool = torch.zeros(1, 6, dtype=torch.float32, device=self.device)
+        self._match(pool, 1, max(m, 1), 6, -1.0, -1.0, keep_idx, keep_cnt, keep_score, max(m, 1), gt)
+
     # ---- device plumbing ------------------------------------------------------------------------------------------
     def _gt_batch(self, gt_list, n):
         if len(gt_list) != n:
