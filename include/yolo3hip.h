@@ -377,6 +377,39 @@ int y3_loss_fwd_bwd_ex(const y3_tensor* fm, const float* gt, const float* anchor
                        int num_classes, int img_h, int img_w, float global_batch, int box_loss, float box_weight,
                        float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream);
 
+/* ---- opt-in ignore mask against each image's ground-truth boxes (not in the reference) ---------------
+ * The reference's mask is model.py:250-282.  It quotes the paper next to it (model.py:282: a prediction that is not the best but overlaps a ground-truth
+ * object by more than 0.5 is ignored), but the code above that line (model.py:250-275, Q7) compares with origin-centred
+ * anchor-sized boxes gathered over the whole replica batch.  y3_loss_fwd_bwd and y3_loss_fwd_bwd_ex reproduce that; the two
+ * entry points below state the paper's rule.
+ *
+ * y3_truth_boxes: the per-image box lists of one dense label tensor gt [n][cells_anchors][d], d = 5 + K.  For image i the
+ * rows with gt[..., 4] != 0 have their first four floats (centre x, centre y, w, h in pixels) copied to boxes[i][0..] in
+ * index order (row, column, anchor); boxes is [n][cap][4].  counts[i] is the TRUE number of such rows, also when it exceeds
+ * cap; rows from cap on are not written, and slots past min(count, cap) are left untouched (nothing needs zeroing).  One
+ * workgroup per image, ordered append by ballot prefix: no atomics, the same bits on every run.
+ *
+ * y3_loss_fwd_bwd_truth: y3_loss_fwd_bwd_ex with the truth mask.  Per (cell, anchor) with gm = g[4] and the predicted box
+ * (bx, by, bw, bh) as above (Q6 included): best = max over j < min(truth_counts[image], truth_cap) of the IoU with
+ * truth_boxes[image][j], in fp32 from corners c -+ s/2, inter / (bw bh + tw th - inter), combined with fmaxf from -INFINITY
+ * (an empty list leaves every negative valid, a NaN IoU is dropped); ignore = best < ignore_thresh ? 1 : 0 and
+ * valid = gm + (1 - gm) ignore feed the objectness term, a constant of the backward pass.  Only the objectness term
+ * departs from y3_loss_fwd_bwd_ex: dfm[..., 0:4] and dfm[..., 5:] keep their bits for every box_loss; loss4[0], loss4[1] and
+ * loss4[3] are the same terms added up over another block partition.  *ignored (may be NULL) is increased by the number of predictions with gm == 0 and ignore == 0 of this call
+ * (a float, exact at these counts), through the block partials and a fixed-order finalize like loss4: no atomics.
+ * A workgroup works on one image, whose list it stages in LDS Y3_TRUTH_CHUNK boxes at a time.
+ * ignore_thresh not finite or outside (0, 1], truth_cap < 1, truth_boxes or truth_counts NULL, or box_loss / box_weight
+ * against the rules of y3_loss_fwd_bwd_ex: Y3_EINVAL + message, nothing launched.
+ * workspace: y3_loss_truth_workspace_bytes(n) for a batch of n images (0 for n < 1). */
+#define Y3_TRUTH_CHUNK 256   /* boxes staged in LDS at a time (16 bytes each) */
+int y3_truth_boxes(const float* gt, int n, long long cells_anchors, int d, float* boxes, int* counts, int cap,
+                   y3_stream_t stream);
+size_t y3_loss_truth_workspace_bytes(int n);
+int y3_loss_fwd_bwd_truth(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors,
+                          int num_classes, int img_h, int img_w, float global_batch, int box_loss, float box_weight,
+                          const float* truth_boxes, const int* truth_counts, int truth_cap, float ignore_thresh,
+                          float* loss4, float* ignored, const y3_tensor* dfm, void* workspace, y3_stream_t stream);
+
 /* ---- tf.keras.optimizers.Adam.apply_gradients (model.py:451,500) ----------
  * m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= lr_t*m/(sqrt(v)+eps), with
  * lr_t read from DEVICE memory (*lr_t_dev) so the launch is graph-replayable. */

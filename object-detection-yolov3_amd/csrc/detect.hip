@@ -105,7 +105,12 @@ struct LossArgs {
     float inv_b, gscale;  // 1/local batch, 1/(local batch * global batch)
     float box_weight;     // factor of the box term of the IoU kinds (y3_loss_fwd_bwd_ex); the mse kernel does not read it
     int* present;         // [A] flags: anchor a has at least one GT cell in this batch
-    float* partials;      // [blocks][4]
+    float* partials;      // [blocks][4]; truth variant: [N][blocks per image][5]
+    // truth variant only (y3_loss_fwd_bwd_truth).  Behind every field of the reference's kernel: its loads keep their offsets
+    const float* truth_boxes;  // [N][truth_cap][4] centre x, centre y, w, h in pixels
+    const int* truth_counts;   // [N] boxes found per image; may exceed truth_cap
+    int truth_cap;
+    float ignore_thresh;
 };
 
 __global__ void loss_present_kernel(const float* __restrict__ gt, long long ncell_anchor, int A, int D, int* present) {
@@ -182,15 +187,41 @@ __device__ __forceinline__ float iou_box_loss(float bx, float by, float bw, floa
     return 1.0f - X;
 }
 
-// BOX == Y3_BOX_LOSS_MSE is the reference's loss; the other kinds replace its xy and wh terms by iou_box_loss and leave the rest alone
-template <int BOX>
+// BOX == Y3_BOX_LOSS_MSE is the reference's loss; the other kinds replace its xy and wh terms by iou_box_loss and leave the rest alone.
+// TRUTH == false is the reference's ignore mask (Q7) on a 1-D grid over the whole batch.  TRUTH == true masks against the
+// ground-truth boxes of the prediction's own image: grid (blocks per image, N), the image's box list staged in LDS Y3_TRUTH_CHUNK boxes
+// at a time, a fifth partial sum (the ignored negatives).  Everything TRUTH adds is behind `if (TRUTH)`, a compile-time constant: the
+// TRUTH == false instantiations keep the instructions they had.
+template <int BOX, bool TRUTH>
 __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
-    __shared__ float sm[4][256];
+    constexpr int NP = TRUTH ? 5 : 4;
+    __shared__ float sm[NP][256];
+    __shared__ float4 tb[TRUTH ? Y3_TRUTH_CHUNK : 1];
     const int D = 5 + p.K;
-    const long long total = (long long)p.N * p.G_h * p.G_w * p.A;
+    // TRUTH: one image per workgroup row; j runs over the image's (cell, anchor) slots, i = first + j over the batch's
+    const long long total = TRUTH ? (long long)p.G_h * p.G_w * p.A : (long long)p.N * p.G_h * p.G_w * p.A;
+    const long long first = TRUTH ? (long long)blockIdx.y * total : 0;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    float l_xy = 0.f, l_wh = 0.f, l_obj = 0.f, l_cls = 0.f;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    float l_xy = 0.f, l_wh = 0.f, l_obj = 0.f, l_cls = 0.f, l_ign = 0.f;
+    int cnt = 0;
+    const float* tbox = nullptr;
+    if (TRUTH) {
+        cnt = p.truth_counts[blockIdx.y];
+        cnt = cnt < 0 ? 0 : (cnt > p.truth_cap ? p.truth_cap : cnt);
+        tbox = p.truth_boxes + (long long)blockIdx.y * p.truth_cap * 4;
+        if (cnt <= Y3_TRUTH_CHUNK) {  // the whole list fits: staged once, outside the prediction loop
+            if ((int)threadIdx.x < cnt) {
+                const float* b = tbox + (long long)threadIdx.x * 4;
+                tb[threadIdx.x] = make_float4(b[0], b[1], b[2], b[3]);
+            }
+            __syncthreads();
+        }
+    }
+    // TRUTH: the loop holds barriers when the list is longer than one chunk, so its bound is the workgroup's first slot (uniform); a
+    // thread past the end of the image decodes the image's last slot, takes part in the staging and leaves before anything is written
+    for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; TRUTH ? j - threadIdx.x < total : j < total; j += stride) {
+        const bool active = !TRUTH || j < total;
+        const long long i = TRUTH ? first + (active ? j : total - 1) : j;
         const int a = (int)(i % p.A);
         const long long cell = i / p.A;  // n*G*G + gy*G + gx
         const int gx = (int)(cell % p.G_w);
@@ -206,18 +237,45 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
         const float bw = ew * aw, bh = eh * ah;
         const float gm = g[4];
 
-        // ignore mask (Q7): best IoU against origin-centred anchor-sized boxes of the anchors present in the batch
         float best = -INFINITY;
-        for (int q = 0; q < p.A; ++q) {
-            if (!p.present[q]) continue;
-            const float tw = p.aw[q], th = p.ah[q];
-            const float ix = fmaxf(fminf(bx + bw / 2.0f, tw / 2.0f) - fmaxf(bx - bw / 2.0f, -tw / 2.0f), 0.f);
-            const float iy = fmaxf(fminf(by + bh / 2.0f, th / 2.0f) - fmaxf(by - bh / 2.0f, -th / 2.0f), 0.f);
-            const float inter = ix * iy;
-            const float iou = inter / (bw * bh + tw * th - inter);
-            best = fmaxf(best, iou);
+        if (!TRUTH) {
+            // ignore mask (Q7): best IoU against origin-centred anchor-sized boxes of the anchors present in the batch
+            for (int q = 0; q < p.A; ++q) {
+                if (!p.present[q]) continue;
+                const float tw = p.aw[q], th = p.ah[q];
+                const float ix = fmaxf(fminf(bx + bw / 2.0f, tw / 2.0f) - fmaxf(bx - bw / 2.0f, -tw / 2.0f), 0.f);
+                const float iy = fmaxf(fminf(by + bh / 2.0f, th / 2.0f) - fmaxf(by - bh / 2.0f, -th / 2.0f), 0.f);
+                const float inter = ix * iy;
+                const float iou = inter / (bw * bh + tw * th - inter);
+                best = fmaxf(best, iou);
+            }
+        } else {
+            // ignore mask of the paper: best IoU against the ground-truth boxes of this image.  tb[q] is one broadcast ds_read_b128
+            const float px0 = bx - bw / 2.0f, px1 = bx + bw / 2.0f, py0 = by - bh / 2.0f, py1 = by + bh / 2.0f;
+            const float parea = bw * bh;
+            for (int c0 = 0; c0 < cnt; c0 += Y3_TRUTH_CHUNK) {
+                const int m = cnt - c0 < Y3_TRUTH_CHUNK ? cnt - c0 : Y3_TRUTH_CHUNK;
+                if (cnt > Y3_TRUTH_CHUNK) {  // uniform: cnt is the workgroup's
+                    __syncthreads();         // every reader of the chunk before is done
+                    if ((int)threadIdx.x < m) {
+                        const float* b = tbox + (long long)(c0 + threadIdx.x) * 4;
+                        tb[threadIdx.x] = make_float4(b[0], b[1], b[2], b[3]);
+                    }
+                    __syncthreads();
+                }
+                for (int q = 0; q < m; ++q) {
+                    const float4 b = tb[q];
+                    const float ix = fmaxf(fminf(px1, b.x + b.z / 2.0f) - fmaxf(px0, b.x - b.z / 2.0f), 0.f);
+                    const float iy = fmaxf(fminf(py1, b.y + b.w / 2.0f) - fmaxf(py0, b.y - b.w / 2.0f), 0.f);
+                    const float inter = ix * iy;
+                    const float iou = inter / (parea + b.z * b.w - inter);
+                    best = fmaxf(best, iou);
+                }
+            }
+            if (!active) continue;  // behind the last barrier of this pass
         }
-        const float ignore = best < 0.5f ? 1.f : 0.f;
+        const float ignore = best < (TRUTH ? p.ignore_thresh : 0.5f) ? 1.f : 0.f;
+        if (TRUTH) l_ign += (gm == 0.f && ignore == 0.f) ? 1.f : 0.f;
         const float valid = gm + (1.f - gm) * ignore;
 
         // objectness
@@ -287,14 +345,19 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
     sm[1][threadIdx.x] = l_wh;
     sm[2][threadIdx.x] = l_obj;
     sm[3][threadIdx.x] = l_cls;
+    if (TRUTH) sm[NP - 1][threadIdx.x] = l_ign;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (threadIdx.x < o)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) sm[j][threadIdx.x] += sm[j][threadIdx.x + o];
+            for (int j = 0; j < NP; ++j) sm[j][threadIdx.x] += sm[j][threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x < 4) p.partials[blockIdx.x * 4 + threadIdx.x] = sm[threadIdx.x][0] * p.inv_b;
+    if (!TRUTH) {
+        if (threadIdx.x < 4) p.partials[blockIdx.x * 4 + threadIdx.x] = sm[threadIdx.x][0] * p.inv_b;
+    } else if (threadIdx.x < NP) {  // the count is not a loss term: unscaled
+        p.partials[((long long)blockIdx.y * gridDim.x + blockIdx.x) * NP + threadIdx.x] = sm[threadIdx.x][0] * (threadIdx.x < 4 ? p.inv_b : 1.f);
+    }
 }
 
 __global__ void loss_clear_kernel(int* present) {
@@ -308,12 +371,66 @@ __global__ void loss_finalize_kernel(const float* partials, int nblocks, float* 
     }
 }
 
+// Truth variant: partials [N][bpi][5] -> loss4[0..3] and *ignored, in a fixed order.  Thread (slot, j) adds up, image after image and
+// block after block, the j-th partial of the images slot, slot + 32, ...; thread j then adds the 32 slots in order.
+__global__ __launch_bounds__(256) void loss_finalize_truth_kernel(const float* partials, int n, int bpi, float* loss4, float* ignored) {
+    __shared__ float slots[32][8];
+    const int j = threadIdx.x & 7, slot = threadIdx.x >> 3;
+    float s = 0.f;
+    if (j < 5)
+        for (int img = slot; img < n; img += 32)
+            for (int b = 0; b < bpi; ++b) s += partials[((long long)img * bpi + b) * 5 + j];
+    slots[slot][j] = s;
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        float t = 0.f;
+        for (int q = 0; q < 32; ++q) t += slots[q][threadIdx.x];
+        if (threadIdx.x < 4)
+            loss4[threadIdx.x] += t;
+        else if (ignored)
+            *ignored += t;
+    }
+}
+
 #define Y3_LOSS_BLOCKS 64
 extern "C" size_t y3_loss_workspace_bytes(void) { return (Y3_MAX_ANCHORS + Y3_LOSS_BLOCKS * 4) * sizeof(float); }
 
+#define Y3_LOSS_TRUTH_BLOCKS 16  // workgroups per image of the truth variant, at most
+extern "C" size_t y3_loss_truth_workspace_bytes(int n) {
+    if (n < 1) return 0;
+    return (size_t)n * Y3_LOSS_TRUTH_BLOCKS * 5 * sizeof(float);
+}
+
+// What y3_loss_fwd_bwd_truth adds to the arguments of y3_loss_fwd_bwd_ex
+struct LossTruth {
+    const float* boxes;
+    const int* counts;
+    int cap;
+    float thresh;
+    float* ignored;
+};
+
+template <bool TRUTH>
+static void loss_kernel_launch(int box_loss, dim3 grid, hipStream_t st, const LossArgs& p) {
+    if (box_loss == Y3_BOX_LOSS_MSE)
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_MSE, TRUTH>), grid, dim3(256), 0, st, p);
+    else if (box_loss == Y3_BOX_LOSS_GIOU)
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_GIOU, TRUTH>), grid, dim3(256), 0, st, p);
+    else if (box_loss == Y3_BOX_LOSS_DIOU)
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_DIOU, TRUTH>), grid, dim3(256), 0, st, p);
+    else
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_CIOU, TRUTH>), grid, dim3(256), 0, st, p);
+}
+
 static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h, int img_w,
-                       float global_batch, int box_loss, float box_weight, float* loss4, const y3_tensor* dfm, void* workspace,
-                       y3_stream_t stream) {
+                       float global_batch, int box_loss, float box_weight, const LossTruth* truth, float* loss4, const y3_tensor* dfm,
+                       void* workspace, y3_stream_t stream) {
+    if (truth) {
+        Y3_CHECK_ARG(truth->thresh > 0.f && truth->thresh <= 1.f, "loss_fwd_bwd_truth: ignore_thresh must be finite and in (0, 1] (got %g)",
+                     (double)truth->thresh);
+        Y3_CHECK_ARG(truth->cap >= 1, "loss_fwd_bwd_truth: truth_cap %d (at least 1)", truth->cap);
+        Y3_CHECK_ARG(truth->boxes && truth->counts, "loss_fwd_bwd_truth: null pointer (truth_boxes, truth_counts)");
+    }
     Y3_CHECK_ARG(box_loss >= Y3_BOX_LOSS_MSE && box_loss <= Y3_BOX_LOSS_CIOU, "loss_fwd_bwd: unknown box_loss %d", box_loss);
     Y3_CHECK_ARG(box_weight > 0.f && box_weight <= FLT_MAX, "loss_fwd_bwd: box_weight must be finite and > 0 (got %g)", (double)box_weight);
     Y3_CHECK_ARG(box_loss != Y3_BOX_LOSS_MSE || box_weight == 1.f, "loss_fwd_bwd: box_weight %g needs an IoU box_loss (mse takes 1)",
@@ -343,6 +460,23 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
     p.inv_b = 1.f / (float)fm->n;
     p.gscale = 1.f / ((float)fm->n * global_batch);
     p.box_weight = box_weight;
+    if (truth) {
+        // one image per workgroup row; the anchor-present pass is not needed
+        Y3_CHECK_ARG(fm->n <= 65535, "loss_fwd_bwd_truth: batch %d (at most 65535 images per call)", fm->n);
+        const long long per_image = (long long)p.G_h * p.G_w * p.A;
+        int bpi = (int)((per_image + 255) / 256);
+        if (bpi > Y3_LOSS_TRUTH_BLOCKS) bpi = Y3_LOSS_TRUTH_BLOCKS;
+        p.partials = (float*)workspace;
+        p.truth_boxes = truth->boxes;
+        p.truth_counts = truth->counts;
+        p.truth_cap = truth->cap;
+        p.ignore_thresh = truth->thresh;
+        loss_kernel_launch<true>(box_loss, dim3(bpi, p.N), st, p);
+        Y3_CHECK_LAUNCH("loss (truth mask)");
+        hipLaunchKernelGGL(loss_finalize_truth_kernel, dim3(1), dim3(256), 0, st, (const float*)p.partials, p.N, bpi, loss4, truth->ignored);
+        Y3_CHECK_LAUNCH("loss_finalize (truth mask)");
+        return Y3_OK;
+    }
     p.present = (int*)workspace;
     p.partials = (float*)workspace + Y3_MAX_ANCHORS;
     // (a kernel, not hipMemsetAsync: as a memset NODE of a captured graph the clear was not reliably ordered against the loss kernels of
@@ -356,14 +490,7 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
     Y3_CHECK_LAUNCH("loss_present");
     int blocks = (int)((total + 255) / 256);
     if (blocks > Y3_LOSS_BLOCKS) blocks = Y3_LOSS_BLOCKS;
-    if (box_loss == Y3_BOX_LOSS_MSE)
-        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_MSE>, dim3(blocks), dim3(256), 0, st, p);
-    else if (box_loss == Y3_BOX_LOSS_GIOU)
-        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_GIOU>, dim3(blocks), dim3(256), 0, st, p);
-    else if (box_loss == Y3_BOX_LOSS_DIOU)
-        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_DIOU>, dim3(blocks), dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL(loss_kernel<Y3_BOX_LOSS_CIOU>, dim3(blocks), dim3(256), 0, st, p);
+    loss_kernel_launch<false>(box_loss, dim3(blocks), st, p);
     Y3_CHECK_LAUNCH("loss");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)p.partials, blocks, loss4);
     Y3_CHECK_LAUNCH("loss_finalize");
@@ -372,15 +499,68 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
 
 extern "C" int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
                                int img_w, float global_batch, float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
-    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, Y3_BOX_LOSS_MSE, 1.f, loss4, dfm, workspace,
-                       stream);
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, Y3_BOX_LOSS_MSE, 1.f, nullptr, loss4, dfm,
+                       workspace, stream);
 }
 
 extern "C" int y3_loss_fwd_bwd_ex(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
                                   int img_w, float global_batch, int box_loss, float box_weight, float* loss4, const y3_tensor* dfm,
                                   void* workspace, y3_stream_t stream) {
-    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, loss4, dfm, workspace,
-                       stream);
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, nullptr, loss4, dfm,
+                       workspace, stream);
+}
+
+extern "C" int y3_loss_fwd_bwd_truth(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes,
+                                     int img_h, int img_w, float global_batch, int box_loss, float box_weight, const float* truth_boxes,
+                                     const int* truth_counts, int truth_cap, float ignore_thresh, float* loss4, float* ignored,
+                                     const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
+    const LossTruth truth = {truth_boxes, truth_counts, truth_cap, ignore_thresh, ignored};
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, &truth, loss4, dfm,
+                       workspace, stream);
+}
+
+// ---------------------------------------------------------------------------
+// per-image ground-truth box lists from a dense label tensor (the truth ignore mask)
+// ---------------------------------------------------------------------------
+// One 256-thread workgroup per image.  The rows with gt[..., 4] != 0 go out in index order: ballot prefix inside a wave, the four
+// waves' counts in LDS (as tile_merge_kernel).  No atomics; the loop bound is the kernel argument, the same in every thread.
+__global__ __launch_bounds__(256) void truth_boxes_kernel(const float* __restrict__ gt, int ca, int d, float* __restrict__ boxes,
+                                                         int* __restrict__ counts, int cap) {
+    __shared__ int wave_cnt[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* g = gt + (long long)blockIdx.x * ca * d;
+    float* out = boxes + (long long)blockIdx.x * cap * 4;
+    int base = 0;
+    for (int r0 = 0; r0 < ca; r0 += 256) {
+        const int r = r0 + tid;
+        const float* row = g + (long long)(r < ca ? r : 0) * d;
+        const bool keep = r < ca && row[4] != 0.f;
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wave_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int off = base;
+        for (int w = 0; w < wave; ++w) off += wave_cnt[w];
+        const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && pos < cap) {
+            float* dst = out + (long long)pos * 4;
+            dst[0] = row[0];
+            dst[1] = row[1];
+            dst[2] = row[2];
+            dst[3] = row[3];
+        }
+        base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+    if (tid == 0) counts[blockIdx.x] = base;
+}
+
+extern "C" int y3_truth_boxes(const float* gt, int n, long long cells_anchors, int d, float* boxes, int* counts, int cap, y3_stream_t stream) {
+    Y3_CHECK_ARG(gt && boxes && counts, "truth_boxes: null pointer");
+    Y3_CHECK_ARG(n >= 1 && cells_anchors >= 1 && cells_anchors < (1LL << 31) - 256 && d >= 5 && cap >= 1,
+                 "truth_boxes: bad sizes (n %d, cells_anchors %lld, d %d, cap %d)", n, cells_anchors, d, cap);
+    hipLaunchKernelGGL(truth_boxes_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, gt, (int)cells_anchors, d, boxes, counts, cap);
+    Y3_CHECK_LAUNCH("truth_boxes");
+    return Y3_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -28,6 +28,10 @@ mAP pass, model selection, the checkpoint and the export stay at the size the im
 and three other images of its batch, composed on the device after the augmentation; the draws are a pure function
 of --mosaic_seed, the rank and the batch count, and a box stays when at least --mosaic_min_visible of its area is still visible.
 Composes with the --multiscale_* flags; the test reader, the mAP pass, the checkpoint and the export are untouched.
+--ignore_mask truth (with --ignore_thresh T, default 0.5, and --ignore_max_boxes N, default 1024) leaves a prediction without an
+object out of the objectness loss when it overlaps a ground-truth box of its own image with IoU >= T, the rule of the paper, in
+place of the reference's mask; training and test loss use the same mask.  <scalars>/ignored.csv gets one row per
+optimiser step: the predictions left out in that batch and the longest per-image box list (a warning once if it exceeds N).
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -88,6 +92,7 @@ MODEL_SELECTIONS = ('loss', 'map50', 'map50_95')
 TEST_MAP_NMS_METHODS = ('hard', 'diou', 'soft-linear', 'soft-gaussian')
 # yolo3.model.BOX_LOSSES, restated so that --help needs no device library
 BOX_LOSSES = ('mse', 'giou', 'diou', 'ciou')
+IGNORE_MASKS = ('reference', 'truth')
 
 
 def effective_test_map(test_map, model_selection):
@@ -170,7 +175,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, multiscale_min=None, multiscale_max=None,
-                multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25):
+                multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25,
+                ignore_mask='reference', ignore_thresh=0.5, ignore_max_boxes=1024):
     test_map = effective_test_map(test_map, model_selection)
     mosaic_prob = check_mosaic_args(mosaic_prob, mosaic_min_visible)
     if mosaic_prob and augmentation_device != 'gpu':
@@ -180,8 +186,10 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         raise ValueError('multi-scale training needs augmentation_device gpu: the batches are resampled and labelled on the device')
     if train_sizes is not None and int(multiscale_period) < 1:
         raise ValueError('multiscale_period must be >= 1, got {!r}'.format(multiscale_period))
-    from yolo3.model import check_box_loss_args, check_grad_args
+    from yolo3.model import check_box_loss_args, check_grad_args, check_ignore_mask_args
     check_box_loss_args(box_loss, box_loss_weight)
+    check_ignore_mask_args(ignore_mask, ignore_thresh, ignore_max_boxes)
+    mask_args = dict(ignore_mask=ignore_mask, ignore_thresh=ignore_thresh, max_truth_boxes=ignore_max_boxes) if ignore_mask != 'reference' else {}
     check_grad_args(accumulate_steps, grad_clip_norm)
     if test_map:
         from yolo3 import bbox_utils
@@ -259,7 +267,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         number_classes = train_reader.get_number_classes()
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
-                            grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}))
+                            grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args)
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
@@ -274,6 +282,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             print('Effective batch size {} = batch_size {} x {} replicas x {} accumulated steps; gradient norm {}'.format(
                 batch_size * world * accumulate_steps, batch_size, world, accumulate_steps,
                 'clipped at {}'.format(grad_clip_norm) if grad_clip_norm is not None else 'not clipped'))
+
+        log_ignored = ignore_mask == 'truth'
+        warned_truth_cap = False
+        if log_ignored:
+            print('Ignore mask: predictions without an object that overlap a ground-truth box of their image with IoU >= {:g} are left out '
+                  'of the objectness loss (training and test loss; at most {} boxes per image)'.format(ignore_thresh, ignore_max_boxes))
 
         def averaged():
             """The model the loop judges and keeps: the EMA copy when there is one (each replica's own EMA moving statistics,
@@ -302,6 +316,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             if train_sizes is not None:
                 with open(os.path.join(log_dir, 'train_size.csv'), 'w') as fh:
                     fh.write('step,height,width\n')
+            if log_ignored:
+                with open(os.path.join(log_dir, 'ignored.csv'), 'w') as fh:
+                    fh.write('step,ignored,truth_max\n')
 
         def log_scalars(split, step, metrics):
             if rank == 0:
@@ -336,6 +353,14 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                     with open(os.path.join(log_dir, 'grad_norm.csv'), 'a') as fh:
                         fh.write('{},{!r},{!r}\n'.format(int(epoch * train_epoch_size + step), float(yolo.last_grad_norm),
                                                         float(yolo.grad_scale_dev)))
+                if log_ignored and rank == 0 and yolo.micro_step == 0:       # (of the batch that completed the optimiser step)
+                    truth_max = int(yolo.last_truth_max)
+                    with open(os.path.join(log_dir, 'ignored.csv'), 'a') as fh:
+                        fh.write('{},{},{}\n'.format(int(epoch * train_epoch_size + step), int(yolo.last_ignored), truth_max))
+                    if truth_max > ignore_max_boxes and not warned_truth_cap:
+                        warned_truth_cap = True
+                        print('WARNING: an image has {} ground-truth boxes, --ignore_max_boxes is {}: the ignore mask sees only the first '
+                              '{} of them (warned once)'.format(truth_max, ignore_max_boxes, ignore_max_boxes))
                 for m in train_metrics:
                     m.reset_states()
 
@@ -422,7 +447,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Converting checkpoint into Saved_Model')
         from yolo3 import model
         best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate,
-                            box_loss=box_loss, box_loss_weight=box_loss_weight)
+                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args)
         best.load_weights(training_checkpoint_filepath)
         os.makedirs(os.path.join(output_folder, 'saved_model'), exist_ok=True)
         best.save_weights(os.path.join(output_folder, 'saved_model', 'yolov3.npz'))
@@ -450,6 +475,26 @@ def _grad_clip_norm_arg(text):
     if not (c > 0.0 and c != float('inf')):
         raise argparse.ArgumentTypeError('a finite number > 0, got {!r}'.format(text))
     return c
+
+
+def _ignore_thresh_arg(text):
+    try:
+        t = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a number in (0, 1], got {!r}'.format(text))
+    if not (0.0 < t <= 1.0):
+        raise argparse.ArgumentTypeError('a number in (0, 1], got {!r}'.format(text))
+    return t
+
+
+def _ignore_max_boxes_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    if v < 1 or v >= 2 ** 31:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    return v
 
 
 def _multiscale_side_arg(text):
@@ -489,6 +534,9 @@ class _Parser(argparse.ArgumentParser):
             self.error(str(e))
         if prob and a.augmentation_device != 'gpu':
             self.error('--mosaic_prob needs --augmentation_device gpu')
+        # (yolo3.model.check_ignore_mask_args, which train_model calls, restated: parsing loads no device library)
+        if a.ignore_mask == 'reference' and (a.ignore_thresh != 0.5 or a.ignore_max_boxes != 1024):
+            self.error("--ignore_thresh / --ignore_max_boxes need --ignore_mask truth: the reference's mask has no such parameters")
         return a
 
 
@@ -550,6 +598,13 @@ def build_parser():
                         help='(addition) seed of the mosaic draws: a pure function of (seed, rank, batch count, image)')
     parser.add_argument('--mosaic_min_visible', dest='mosaic_min_visible', type=float, default=0.25,
                         help='(addition) a box of a mosaic stays when at least this share of its area lies in the window taken from its image (default 0.25)')
+    parser.add_argument('--ignore_mask', dest='ignore_mask', choices=IGNORE_MASKS, default='reference',
+                        help='(addition) ignore mask of the objectness loss: reference (default) = the reference\'s; truth = a prediction '
+                             'without an object is left out when it overlaps a ground-truth box of its own image with IoU >= --ignore_thresh')
+    parser.add_argument('--ignore_thresh', dest='ignore_thresh', type=_ignore_thresh_arg, default=0.5,
+                        help='(addition) IoU threshold of --ignore_mask truth, in (0, 1] (default 0.5, the paper\'s; reference takes no other)')
+    parser.add_argument('--ignore_max_boxes', dest='ignore_max_boxes', type=_ignore_max_boxes_arg, default=1024,
+                        help='(addition) ground-truth boxes per image that --ignore_mask truth keeps (default 1024; reference takes no other)')
     return parser
 
 
@@ -562,4 +617,5 @@ if __name__ == "__main__":
                 a.terminate_after_num_epochs_without_test_loss_improvement, a.learning_rate, bool(a.use_augmentation), a.max_epochs, a.reader_count, a.backend,
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
                 a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm, a.multiscale_min, a.multiscale_max,
-                a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible)
+                a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible, a.ignore_mask, a.ignore_thresh,
+                a.ignore_max_boxes)

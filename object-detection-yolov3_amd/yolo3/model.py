@@ -58,6 +58,31 @@ def check_box_loss_args(box_loss, box_loss_weight=1.0):
                          .format(box_loss_weight))
 
 
+IGNORE_MASKS = ('reference', 'truth')
+DEFAULT_IGNORE_THRESH = 0.5
+DEFAULT_MAX_TRUTH_BOXES = 1024
+
+
+def check_ignore_mask_args(ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES):
+    """Host-side validation of the ignore mask of the objectness loss (the library checks the numbers again):
+    ValueError on an unknown mask, a threshold that is not a finite number in (0, 1], a capacity that is not an integer >= 1, or
+    a threshold / capacity other than the defaults with 'reference' (the reference's mask has no such parameters)."""
+    if ignore_mask not in IGNORE_MASKS:
+        raise ValueError('ignore_mask must be one of {}, got {!r}'.format(', '.join(IGNORE_MASKS), ignore_mask))
+    try:
+        t = float(ignore_thresh)
+    except (TypeError, ValueError):
+        raise ValueError('ignore_thresh must be a number, got {!r}'.format(ignore_thresh))
+    if isinstance(ignore_thresh, bool) or not (0.0 < t <= 1.0):
+        raise ValueError('ignore_thresh must be finite and in (0, 1], got {!r}'.format(ignore_thresh))
+    cap = max_truth_boxes
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 1 or cap >= 2 ** 31:
+        raise ValueError('max_truth_boxes must be an integer >= 1, got {!r}'.format(max_truth_boxes))
+    if ignore_mask == 'reference' and (t != DEFAULT_IGNORE_THRESH or cap != DEFAULT_MAX_TRUTH_BOXES):
+        raise ValueError("ignore_thresh {!r} / max_truth_boxes {!r} need ignore_mask 'truth': the reference's mask has no such parameters"
+                         .format(ignore_thresh, max_truth_boxes))
+
+
 def check_grad_args(accumulate_steps=1, grad_clip_norm=None):
     """Host-side validation of the gradient accumulation count and the global-norm clip (the library checks them
     again): ValueError unless accumulate_steps is an integer >= 1 and grad_clip_norm is None (off) or a finite number > 0."""
@@ -494,10 +519,30 @@ class _Plan:
         ws_floats = (int(lib.y3_loss_workspace_bytes()) // 4 + 4 + 63) // 64 * 64
         self.loss_ws = torch.zeros(3 * ws_floats, dtype=torch.float32, device=dev)
         self.loss_calls = []
+        self.truth_call = self.truth_boxes = self.truth_counts = self.ignored = None
+        if mdl.ignore_mask == 'truth':
+            # the paper's ignore mask: per-image box lists gathered from the finest label tensor -- format_boxes
+            # writes every box at all three scales (Q5) and the finest has the fewest cell collisions -- then the truth variant of
+            # the loss at every scale.  All pointers are static: a captured step replays the gather with each step's labels.
+            cap = mdl.max_truth_boxes
+            self.truth_boxes = torch.zeros(N, cap, 4, dtype=torch.float32, device=dev)
+            self.truth_counts = torch.zeros(N, dtype=torch.int32, device=dev)
+            self.ignored = torch.zeros(1, dtype=torch.float32, device=dev)
+            fine, gfine = self.fms[-1], self.gt[-1]
+            self.truth_call = (lib.y3_truth_boxes, (gfine.data_ptr(), N, fine.h * fine.w * A, 5 + K, self.truth_boxes.data_ptr(),
+                                                    self.truth_counts.data_ptr(), cap))
+            ws_floats = (int(lib.y3_loss_truth_workspace_bytes(N)) // 4 + 63) // 64 * 64
+            self.loss_ws = torch.zeros(3 * ws_floats, dtype=torch.float32, device=dev)
         for si, (f, g) in enumerate(zip(self.fms, self.gt)):
             f.grad = self._new(N, f.h, f.w, D, Dld, zero=True)
             ws = self._at(self.loss_ws, si * ws_floats)
-            if mdl.box_loss == 'mse':    # the reference's loss: the call list of a model built without box-loss arguments
+            if mdl.ignore_mask == 'truth':
+                self.loss_calls.append((lib.y3_loss_fwd_bwd_truth, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                                                                    BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
+                                                                    self.truth_boxes.data_ptr(), self.truth_counts.data_ptr(), cap,
+                                                                    mdl.ignore_thresh, self.loss4.data_ptr(), self.ignored.data_ptr(),
+                                                                    f.grad.v, ws)))
+            elif mdl.box_loss == 'mse':    # the reference's loss: the call list of a model built without box-loss arguments
                 self.loss_calls.append((lib.y3_loss_fwd_bwd, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
                                                               self.loss4.data_ptr(), f.grad.v, ws)))
             else:                        # IoU box term in loss4[0], loss4[1] stays 0
@@ -723,8 +768,12 @@ class _Plan:
     def run_loss(self, stream):
         # (a kernel launch, not tensor.zero_(): inside a captured step nothing may turn into a memset node -- DESIGN 9)
         check(lib.y3_fill(self.loss4.data_ptr(), 4, 0.0, stream), 'y3_fill')
+        if self.truth_call is not None:
+            check(lib.y3_fill(self.ignored.data_ptr(), 1, 0.0, stream), 'y3_fill')
+            fn, args = self.truth_call
+            check(fn(*args, stream), 'y3_truth_boxes')
         for fn, args in self.loss_calls:
-            check(fn(*args, stream), 'y3_loss_fwd_bwd')
+            check(fn(*args, stream), fn.__name__)
 
     def run_backward(self, stream, dist=None):
         """dist: the model's DataParallel (all-reduces each gradient bucket as its last layer completes), or None."""
@@ -765,7 +814,8 @@ class YoloV3:
 
     def __init__(self, global_batch_size, img_size, number_classes, anchors=None, learning_rate=1e-4, device=None, seed=None,
                  use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
-                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None):
+                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None,
+                 ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES):
         # input sizes train_step / test_step accept: None = img_size only; checked before the device is needed
         self.train_sizes = check_train_sizes(img_size, train_sizes)
         # gradient accumulation and global-norm clipping: 1 / None = off; checked before the device is needed
@@ -777,6 +827,13 @@ class YoloV3:
         check_box_loss_args(box_loss, box_loss_weight)
         self.box_loss = box_loss
         self.box_loss_weight = float(box_loss_weight)
+        # ignore mask of the objectness loss: 'reference' = the reference's (Q7), 'truth' = the paper's, against each
+        # image's own ground-truth boxes; checked before the device is needed
+        check_ignore_mask_args(ignore_mask, ignore_thresh, max_truth_boxes)
+        self.ignore_mask = ignore_mask
+        self.ignore_thresh = float(ignore_thresh)
+        self.max_truth_boxes = int(max_truth_boxes)
+        self._loss_plan = None                    # the plan whose loss ran last: what last_ignored / last_truth_max read
         # exponential moving average of the weights: None / 0 = off; checked before the device is needed
         if ema_decay is not None and ema_decay != 0 and not 0.0 < float(ema_decay) < 1.0:
             raise ValueError('ema_decay must be None (off) or in (0, 1), got %r' % (ema_decay,))
@@ -1266,9 +1323,25 @@ class YoloV3:
         check(fn(*args, st), fn.__name__)
         self._refresh_transposed()
 
+    @property
+    def last_ignored(self):
+        """ignore_mask='truth': the number of predictions without an object that the last train_step / test_step left out of the
+        objectness loss, summed over the three scales (0-d device tensor, read when used); None before the first step and with
+        'reference'."""
+        plan = self._loss_plan
+        return plan.ignored[0] if plan is not None and plan.ignored is not None else None
+
+    @property
+    def last_truth_max(self):
+        """ignore_mask='truth': the longest per-image ground-truth list of the last train_step / test_step, before the cut at
+        max_truth_boxes (0-d device tensor, computed when asked for); None before the first step and with 'reference'."""
+        plan = self._loss_plan
+        return plan.truth_counts.max() if plan is not None and plan.truth_counts is not None else None
+
     def _loss_out(self, plan, metrics):
         """plan.loss4 of the step just enqueued -> the loss the step returns (0-d device tensor), fed with its four parts to the
         metrics (loss, xy, wh, obj, class; fewer or None = not wanted)."""
+        self._loss_plan = plan
         parts = plan.loss4.clone()
         loss_value = parts.sum() / float(self.global_batch_size)
         for mtr, val in zip(metrics, [loss_value, parts[0], parts[1], parts[2], parts[3]]):
