@@ -571,6 +571,63 @@ int y3_nms_labelled(const float* pool, int m, int num_classes, int method, float
                     int* keep_idx, int* keep_cnt, float* keep_score, int max_keep, void* workspace, size_t workspace_bytes,
                     y3_stream_t stream);
 
+/* ---- test-time augmentation: flipped / transposed views, boxes mapped back, box voting (not in the reference) ----
+ * A view is a 3-bit code: Y3_TTA_TRANSPOSE (applied first), then Y3_TTA_FLIP_X and Y3_TTA_FLIP_Y; 0 is the identity.  With
+ * T = transpose ? S^T : S, view[y][x] = T[flip_y ? H-1-y : y][flip_x ? W-1-x : x].  A view list is a HOST array of
+ * 1 <= k <= Y3_TTA_MAX_VIEWS distinct codes; a code with Y3_TTA_TRANSPOSE needs H == W.  A bad list is Y3_EINVAL + message and
+ * nothing is launched.
+ *
+ * y3_tta_views_nhwc: src fp32 [n][c][h][w] (z-scored already: the statistics of an image are those of its views) -> dst, the
+ * network's NHWC input of n * k images, image-major and view-minor: image i * k + v is view views[v] of source image i.
+ * dst->n == n * k, dst->h == h, dst->w == w, dst->c >= c and a multiple of 4 (channels c .. dst->c - 1 are written as zero, as
+ * y3_nchw_to_nhwc writes them), dst->ld >= dst->c and a multiple of 4 (the floats of a pixel beyond dst->c are not touched),
+ * dst->ptr 16-byte aligned.  Each 32 x 32 source tile is read once, four channel planes at a time, staged in LDS (row pitch 33
+ * dwords) and stored to all k views as 16-byte pixels along the destination row, for transposed and straight views alike.  A
+ * copy: bit-exact, NaN payloads included.
+ *
+ * y3_tta_unmap: rows [n_views][nb][ld] decode rows (corners x0, y0, x1, y1 first), n_views a multiple of k, image j being view
+ * views[j % k].  In place, the inverse map (un-flip, then transpose), W = (float)img_w, H = (float)img_h:
+ *   flip x:    (x0, x1) <- (W - x1, W - x0)
+ *   flip y:    (y0, y1) <- (H - y1, H - y0)
+ *   transpose: (x0, y0, x1, y1) <- (y0, x0, y1, x1)
+ * one fp32 subtraction per value, as written.  Columns 4 .. ld-1 are not touched; rows of view 0 are not touched at all.
+ * img_h, img_w <= 2^24. */
+#define Y3_TTA_FLIP_X 1
+#define Y3_TTA_FLIP_Y 2
+#define Y3_TTA_TRANSPOSE 4
+#define Y3_TTA_MAX_VIEWS 8
+int y3_tta_views_nhwc(const float* src, int n, int c, int h, int w, const int* views, int k, const y3_tensor* dst,
+                      y3_stream_t stream);
+int y3_tta_unmap(float* rows, int n_views, int nb, int ld, const int* views, int k, int img_h, int img_w, y3_stream_t stream);
+
+/* y3_box_vote (Gidaris & Komodakis 2015): every box the NMS kept becomes the score-weighted mean of the candidates that overlap
+ * it.  rows [n][nb][5+K] with nb = views * rows_per_view: the unmapped rows of all views of an image, view v in rows
+ * v * rows_per_view .. (v+1) * rows_per_view - 1.  keep_idx / keep_cnt / keep_score / max_keep: the outputs of
+ * y3_nms_per_class(_ex) over those rows; min_box, score_thr, clip_w, clip_h: what that call got.  For keep j < keep_cnt[i][c]
+ * with row r:
+ *   candidates: the rows of image i that the NMS takes as candidates of class c (its device function: optional clip, strict >
+ *     small-box filter, s = sqrtf(cls_c * obj) >= score_thr), boxes clipped as the NMS clips them;
+ *   members: the candidates q with iou(r, q) >= vote_iou, iou being y3_nms_per_class_ex's fp32 expression in its order, no
+ *     contraction; a NaN iou is no member (r itself has iou 1 unless its area is 0);
+ *   box = sum s_q b_q / sum s_q over the members, products and sums in fp64, rounded to fp32 once.  Candidate p of the row-ordered
+ *     candidate list goes to lane p % 64, a lane adds its members in increasing p, the 64 lanes are combined by an xor butterfly
+ *     (32, 16, .. 1): no atomics, the same bits on every run, and within one fp32 unit in the last place of any other fp64
+ *     summation order.  No member, or members whose scores sum to 0: the keep's own clipped box;
+ *   score = Y3_VOTE_SCORE_KEEP: keep_score[i][c][j] unchanged;
+ *           Y3_VOTE_SCORE_CONSENSUS: (sum over v < views of max{s_q : q member, q / rows_per_view == v}) / (float)views, a view
+ *           without a member contributing 0; fp32, added in increasing v, divided once.
+ * out [n][K][max_keep][6] = x0, y0, x1, y1, score, (float)c, written for j < keep_cnt[i][c] only.  A row kept under two classes
+ * gets two independent results.  0 < vote_iou <= 1; n * num_classes <= 65535.  Two launches: the candidates of every
+ * (image, class) compacted in row order, then one wave per keep.  workspace: y3_box_vote_workspace_bytes(n, nb, num_classes),
+ * 4-byte aligned. */
+#define Y3_VOTE_SCORE_KEEP 0
+#define Y3_VOTE_SCORE_CONSENSUS 1
+int y3_box_vote(const float* rows, int n, int nb, int num_classes, const int* keep_idx, const int* keep_cnt,
+                const float* keep_score, int max_keep, float min_box, float score_thr, float clip_w, float clip_h,
+                float vote_iou, int views, int rows_per_view, int score_mode, float* out, void* workspace,
+                size_t workspace_bytes, y3_stream_t stream);
+size_t y3_box_vote_workspace_bytes(int n, int nb, int num_classes);
+
 /* bbox_utils.filter_small_boxes (bbox_utils.py:274-281): keep_idx[0..*keep_cnt) = indices, in row order, of the rows
  * [x0,y0,x1,y1,...] (pitch ld floats) with (x1-x0) > min_size and (y1-y0) > min_size (strict, Q19).  keep_idx holds m ints. */
 int y3_filter_small_boxes(const float* rows, int m, int ld, float min_size, int* keep_idx, int* keep_cnt, y3_stream_t stream);

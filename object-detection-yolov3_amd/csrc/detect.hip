@@ -1133,6 +1133,196 @@ extern "C" int y3_nms_labelled(const float* pool, int m, int num_classes, int me
 }
 
 // ---------------------------------------------------------------------------
+// box voting over the pooled views of test-time augmentation (y3_box_vote, yolo3hip.h)
+// ---------------------------------------------------------------------------
+#define Y3_VOTE_CHUNK 256  // candidates staged in LDS per pass = threads per workgroup
+#define Y3_VOTE_WAVES 4    // keeps of one (image, class) a workgroup votes at a time, one wave each
+#define Y3_VOTE_GRID_X 32  // workgroups per (image, class) at most; each strides over the keeps
+
+struct VoteArgs {
+    NmsArgs nms;  // rows, sizes, the candidate test's parameters and the keep lists (read only here)
+    float vote_iou;
+    int views, rows_per_view;
+    float* out;     // [n][K][max_keep][6]
+    float* cand;    // [n * K][6][nb]: x0, y0, x1, y1, score, row (as int bits) of the candidates, row order
+    int* cand_cnt;  // [n * K]
+};
+
+// Pass 1, one 256-thread workgroup per (image, class): the candidates nms_candidate accepts, compacted in row order (ballot
+// prefix inside a wave, the four waves' counts in LDS, as truth_boxes_kernel).  No atomics.
+__global__ __launch_bounds__(256) void vote_compact_kernel(const VoteArgs a) {
+    __shared__ int wave_cnt[4];
+    const NmsArgs& p = a.nms;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seg = blockIdx.x, img = seg / p.K, cls = seg - img * p.K;
+    const float* rows = p.rows + (long long)img * p.nb * p.D;
+    float* out = a.cand + (long long)seg * 6 * p.nb;
+    int base = 0;
+    for (int r0 = 0; r0 < p.nb; r0 += 256) {
+        const int r = r0 + tid;
+        float x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f, score = 0.f;
+        const bool keep = r < p.nb && nms_candidate(p, rows + (long long)r * p.D, cls, x0, y0, x1, y1, score);
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) wave_cnt[wave] = __popcll(bal);
+        __syncthreads();
+        int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+        for (int w = 0; w < wave; ++w) pos += wave_cnt[w];
+        if (keep) {
+            out[pos] = x0;
+            out[p.nb + pos] = y0;
+            out[2 * p.nb + pos] = x1;
+            out[3 * p.nb + pos] = y1;
+            out[4 * p.nb + pos] = score;
+            out[5 * p.nb + pos] = __int_as_float(r);
+        }
+        base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
+        __syncthreads();
+    }
+    if (tid == 0) a.cand_cnt[seg] = base;
+}
+
+// Pass 2, one wave per keep, Y3_VOTE_WAVES keeps of one (image, class) per workgroup: they share the candidate list, staged through
+// LDS Y3_VOTE_CHUNK entries at a time.  Candidate p of the list always goes to lane p % 64, a lane adds its members in increasing p,
+// and the lanes are combined by the xor butterfly of y3_wave_sum_d: the same bits on every run.  The keep loop and the chunk loop
+// are uniform over the workgroup (both bounds come from memory every thread reads alike), so every thread meets every barrier.
+template <bool CONSENSUS>
+__global__ __launch_bounds__(256) void vote_kernel(const VoteArgs a) {
+    __shared__ float s_c[6][Y3_VOTE_CHUNK];
+    const NmsArgs& p = a.nms;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seg = blockIdx.y, img = seg / p.K, cls = seg - img * p.K;
+    int cnt = p.keep_cnt[seg];
+    cnt = cnt < 0 ? 0 : (cnt > p.max_keep ? p.max_keep : cnt);
+    int ncand = a.cand_cnt[seg];
+    ncand = ncand > p.nb ? p.nb : ncand;
+    const float* cand = a.cand + (long long)seg * 6 * p.nb;
+    const float* rows = p.rows + (long long)img * p.nb * p.D;
+    for (int j0 = blockIdx.x * Y3_VOTE_WAVES; j0 < cnt; j0 += gridDim.x * Y3_VOTE_WAVES) {
+        const int j = j0 + wave;
+        const long long e = (long long)seg * p.max_keep + j;
+        const int row = j < cnt ? p.keep_idx[e] : -1;
+        const bool active = row >= 0 && row < p.nb;  // anything else is never produced by the NMS kernels; nothing outside `rows` is read
+        float kx0 = 0.f, ky0 = 0.f, kx1 = 0.f, ky1 = 0.f;
+        if (active) nms_load_box(p, rows + (long long)row * p.D, kx0, ky0, kx1, ky1);
+        const float karea = (kx1 - kx0) * (ky1 - ky0);
+        double ax0 = 0., ay0 = 0., ax1 = 0., ay1 = 0., as = 0.;
+        int members = 0;
+        float vmax[Y3_TTA_MAX_VIEWS];
+#pragma unroll
+        for (int v = 0; v < Y3_TTA_MAX_VIEWS; ++v) vmax[v] = 0.f;
+        for (int c0 = 0; c0 < ncand; c0 += Y3_VOTE_CHUNK) {
+            __syncthreads();  // the chunk before this one has been read by every wave
+            if (c0 + tid < ncand) {
+#pragma unroll
+                for (int f = 0; f < 6; ++f) s_c[f][tid] = cand[(long long)f * p.nb + c0 + tid];
+            }
+            __syncthreads();
+            const int m = ncand - c0 < Y3_VOTE_CHUNK ? ncand - c0 : Y3_VOTE_CHUNK;
+            if (active) {
+                for (int t = lane; t < m; t += 64) {
+                    const float x0 = s_c[0][t], y0 = s_c[1][t], x1 = s_c[2][t], y1 = s_c[3][t], s = s_c[4][t];
+                    const float iou = nms_iou(kx0, ky0, kx1, ky1, karea, x0, y0, x1, y1, (x1 - x0) * (y1 - y0));
+                    if (iou >= a.vote_iou) {  // NaN: no member
+                        const double w = (double)s;
+                        ax0 += w * (double)x0;
+                        ay0 += w * (double)y0;
+                        ax1 += w * (double)x1;
+                        ay1 += w * (double)y1;
+                        as += w;
+                        ++members;
+                        if (CONSENSUS) {
+                            const int view = __float_as_int(s_c[5][t]) / a.rows_per_view;
+#pragma unroll
+                            for (int v = 0; v < Y3_TTA_MAX_VIEWS; ++v)
+                                if (v == view) vmax[v] = fmaxf(vmax[v], s);
+                        }
+                    }
+                }
+            }
+        }
+        ax0 = y3_wave_sum_d(ax0);
+        ay0 = y3_wave_sum_d(ay0);
+        ax1 = y3_wave_sum_d(ax1);
+        ay1 = y3_wave_sum_d(ay1);
+        as = y3_wave_sum_d(as);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) members += __shfl_xor(members, o);
+        float score = active ? p.keep_score[e] : 0.f;
+        if (CONSENSUS) {
+            score = 0.f;
+#pragma unroll
+            for (int v = 0; v < Y3_TTA_MAX_VIEWS; ++v) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) vmax[v] = fmaxf(vmax[v], __shfl_xor(vmax[v], o));
+                if (v < a.views) score += vmax[v];  // fp32, increasing view
+            }
+            score = score / (float)a.views;
+        }
+        if (active && lane == 0) {
+            float* o = a.out + e * 6;
+            const bool own = members == 0 || !(as > 0.);  // a degenerate own box (0 / 0 IoU), or members whose scores are all zero
+            o[0] = own ? kx0 : (float)(ax0 / as);
+            o[1] = own ? ky0 : (float)(ay0 / as);
+            o[2] = own ? kx1 : (float)(ax1 / as);
+            o[3] = own ? ky1 : (float)(ay1 / as);
+            o[4] = score;
+            o[5] = (float)cls;
+        }
+    }
+}
+
+extern "C" size_t y3_box_vote_workspace_bytes(int n, int nb, int num_classes) {
+    if (n < 1 || nb < 1 || num_classes < 1) return 0;
+    return (size_t)n * (size_t)num_classes * ((size_t)nb * 24 + 4);
+}
+
+extern "C" int y3_box_vote(const float* rows, int n, int nb, int num_classes, const int* keep_idx, const int* keep_cnt, const float* keep_score,
+                           int max_keep, float min_box, float score_thr, float clip_w, float clip_h, float vote_iou, int views,
+                           int rows_per_view, int score_mode, float* out, void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    Y3_CHECK_ARG(rows && keep_idx && keep_cnt && keep_score && out && workspace, "box_vote: null pointer");
+    Y3_CHECK_ARG(n >= 1 && nb >= 1 && num_classes >= 1 && max_keep >= 1, "box_vote: bad sizes (n %d, nb %d, classes %d, max_keep %d)", n, nb,
+                 num_classes, max_keep);
+    Y3_CHECK_ARG((long long)n * num_classes <= 65535, "box_vote: n * classes = %lld (at most 65535 per call)", (long long)n * num_classes);
+    Y3_CHECK_ARG((long long)n * num_classes * max_keep * 6 < (1LL << 31), "box_vote: n * classes * max_keep * 6 overflows");
+    Y3_CHECK_ARG(views >= 1 && views <= Y3_TTA_MAX_VIEWS && rows_per_view >= 1 && (long long)views * rows_per_view == nb,
+                 "box_vote: %d views of %d rows are not the %d rows of an image (1 .. %d views)", views, rows_per_view, nb, Y3_TTA_MAX_VIEWS);
+    Y3_CHECK_ARG(vote_iou > 0.f && vote_iou <= 1.f, "box_vote: vote_iou %g outside (0, 1]", (double)vote_iou);
+    Y3_CHECK_ARG(score_mode == Y3_VOTE_SCORE_KEEP || score_mode == Y3_VOTE_SCORE_CONSENSUS, "box_vote: unknown score mode %d", score_mode);
+    Y3_CHECK_ARG(workspace_bytes >= y3_box_vote_workspace_bytes(n, nb, num_classes), "box_vote: workspace too small");
+    VoteArgs a = {};
+    a.nms.rows = rows;
+    a.nms.nb = nb;
+    a.nms.D = 5 + num_classes;
+    a.nms.K = num_classes;
+    a.nms.min_box = min_box;
+    a.nms.score_thr = score_thr;
+    a.nms.clip_w = clip_w;
+    a.nms.clip_h = clip_h;
+    a.nms.keep_idx = const_cast<int*>(keep_idx);
+    a.nms.keep_cnt = const_cast<int*>(keep_cnt);
+    a.nms.keep_score = const_cast<float*>(keep_score);
+    a.nms.max_keep = max_keep;
+    a.vote_iou = vote_iou;
+    a.views = views;
+    a.rows_per_view = rows_per_view;
+    a.out = out;
+    a.cand = (float*)workspace;
+    a.cand_cnt = (int*)((float*)workspace + (size_t)n * num_classes * 6 * nb);
+    hipStream_t st = (hipStream_t)stream;
+    const int segs = n * num_classes;
+    hipLaunchKernelGGL(vote_compact_kernel, dim3(segs), dim3(256), 0, st, a);
+    Y3_CHECK_LAUNCH("box_vote (candidates)");
+    const int per = y3_cdiv(max_keep, Y3_VOTE_WAVES);
+    const dim3 grid(per < Y3_VOTE_GRID_X ? per : Y3_VOTE_GRID_X, segs);
+    if (score_mode == Y3_VOTE_SCORE_CONSENSUS)
+        hipLaunchKernelGGL(vote_kernel<true>, grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(vote_kernel<false>, grid, dim3(256), 0, st, a);
+    Y3_CHECK_LAUNCH("box_vote");
+    return Y3_OK;
+}
+
+// ---------------------------------------------------------------------------
 // ground-truth label tensors (ImageReader.__format_boxes, imagereader.py:252-324)
 // ---------------------------------------------------------------------------
 // One launch writes the three label tensors [N, G, G, A, 5+K] completely.  The flat tensor of a scale is cut into runs of whole

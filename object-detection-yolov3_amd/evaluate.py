@@ -43,17 +43,19 @@ def folder_examples(image_folder, csv_folder, image_format, num_shards=1, shard_
 
 
 def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
-             max_detections=None, distributed=False, nms='hard', nms_sigma=0.5):
+             max_detections=None, distributed=False, nms='hard', nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep'):
     """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds).
     distributed: a collective over the default process group; every rank passes its keys[rank::world] share of the
     examples and gets the result over all of them.  nms / nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its
-    Gaussian parameter."""
+    Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time augmentation (metrics.evaluate_examples)."""
     bbox_utils.check_nms_args(nms, nms_sigma)
+    bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision
     ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
     t0 = time.perf_counter()
-    metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size, nms=nms, nms_sigma=nms_sigma)
+    metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size, nms=nms, nms_sigma=nms_sigma, tta=tta, tta_vote_iou=tta_vote_iou,
+                              tta_score=tta_score)
     if distributed:
         ev = metrics.all_gather_evaluator(ev)
     res = ev.result()
@@ -147,6 +149,13 @@ if __name__ == '__main__':
     parser.add_argument('--merge-nms', dest='merge_nms', choices=list(bbox_utils.MERGE_NMS_METHODS), default='none',
                         help='--tiled: class-wise NMS over the merged detections of the whole image')
     parser.add_argument('--merge-nms-sigma', dest='merge_nms_sigma', type=float, default=0.5, help='sigma of --merge-nms soft-gaussian (> 0)')
+    parser.add_argument('--tta', choices=list(bbox_utils.TTA_VIEWS), default='none',
+                        help='test-time augmentation (not with --tiled): also run the flipped (hflip, flips) and transposed (d4: square '
+                        'inputs) views of every image and pool their detections before --nms; none (default) runs each image once')
+    parser.add_argument('--tta-vote-iou', dest='tta_vote_iou', type=float, default=None, metavar='T',
+                        help='--tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
+    parser.add_argument('--tta-score', dest='tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
+                        help='--tta with --tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
     parser.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend under torch.distributed.run: nccl (= RCCL, '
                         'one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
     a = parser.parse_args()
@@ -165,6 +174,14 @@ if __name__ == '__main__':
             parser.error(str(e))
     elif a.tile_height is not None or a.tile_width is not None or a.seam_margin != 0 or a.merge_nms != 'none':
         parser.error('--tile-height, --tile-width, --seam-margin and --merge-nms go with --tiled')
+    try:
+        bbox_utils.check_tta_args(a.tta, a.tta_vote_iou, a.tta_score)
+    except ValueError as e:
+        parser.error(str(e))
+    if a.tta == 'none' and a.tta_vote_iou is not None:
+        parser.error('--tta-vote-iou and --tta-score go with --tta')
+    if a.tiled and a.tta != 'none':
+        parser.error('--tta does not go with --tiled')
     if a.batch_size is None and not a.tiled:
         a.batch_size = 8
     if a.batch_size is not None and a.batch_size < 1:
@@ -199,10 +216,14 @@ if __name__ == '__main__':
                                           seam_margin=a.seam_margin, merge_nms=a.merge_nms, merge_nms_sigma=a.merge_nms_sigma)
     else:
         res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
-                                    distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma)
+                                    distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma, tta=a.tta, tta_vote_iou=a.tta_vote_iou,
+                                    tta_score=a.tta_score)
     if rank == 0:
         print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
         print('NMS: {}'.format(a.nms + (' (sigma {:g})'.format(a.nms_sigma) if a.nms == 'soft-gaussian' else '')))
+        if a.tta != 'none':
+            print('TTA: {} ({} views), {}'.format(a.tta, len(bbox_utils.TTA_VIEWS[a.tta]), 'no voting' if a.tta_vote_iou is None else
+                                                  'vote IoU {:g}, score {}'.format(a.tta_vote_iou, a.tta_score)))
         if a.tiled:
             print('Tiled: {} x {} tiles, seam margin {:g}, merge NMS {}'.format(a.tile_height, a.tile_width, a.seam_margin, a.merge_nms))
         print_table(res)

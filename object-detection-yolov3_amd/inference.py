@@ -20,8 +20,12 @@ def load_model(path):
 
 
 def inference(image_folder, image_format, saved_model_filepath, output_folder, min_box_size, precision='fp32', batch_size=8, nms='hard',
-              nms_sigma=0.5):
+              nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep'):
+    """tta: a view set of bbox_utils.TTA_VIEWS; every image also goes through the network flipped / transposed and the views'
+    detections are pooled before the NMS.  tta_vote_iou: box voting over the pool at this IoU (None: the NMS
+    alone); tta_score: 'keep' or 'consensus'.  'none' is the path without any of it."""
     bbox_utils.check_nms_args(nms, nms_sigma)
+    views = bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
     os.makedirs(output_folder, exist_ok=True)
     if image_format.startswith('.'):
         image_format = image_format[1:]
@@ -49,9 +53,18 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
             raise RuntimeError('images of one folder must share one size (the model input is fixed, Q18): {}'.format({im.shape for im in imgs}))
         x = torch.from_numpy(np.stack([np.ascontiguousarray(im.astype(np.float32).transpose((2, 0, 1))) for im in imgs])).cuda()
         x = imagereader.zscore_normalize_device(x)                       # per-image statistics (inference.py:49)
-        rows = yolo_model(x, training=False)                              # [B, Nb, 5+K]
-        # clip to the image (the intent of inference.py:62-65, Q11), small-box filter (:72), class-wise NMS (:79)
-        dets = bbox_utils.detect(rows, min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma)   # --nms: extension
+        if tta == 'none':
+            rows = yolo_model(x, training=False)                              # [B, Nb, 5+K]
+            # clip to the image (the intent of inference.py:62-65, Q11), small-box filter (:72), class-wise NMS (:79)
+            dets = bbox_utils.detect(rows, min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma)   # --nms: extension
+        else:
+            # --tta (extension): the views of a few images per network call, pooled per image, then the same clip / filter / NMS
+            bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score, (height, width))
+            dets, step = [], bbox_utils.tta_group_size(views)
+            for s0 in range(0, len(group), step):
+                rows = yolo.predict_tta(x[s0:s0 + step], views)              # [b, k * Nb, 5+K], boxes in the image's frame
+                dets += bbox_utils.detect_tta(rows, len(views), min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma,
+                                              vote_iou=tta_vote_iou, score=tta_score)
         for img_filepath, (boxes, scores, class_label, _) in zip(group, dets):
             file_name = os.path.split(img_filepath)[1]
             if boxes is None:                                             # the reference would crash here (Q11); write an empty csv
@@ -76,10 +89,24 @@ if __name__ == '__main__':
     parser.add_argument('--nms', choices=list(bbox_utils.NMS_METHODS), default='hard',
                         help='NMS method (extension): hard (the reference\'s greedy NMS, default), diou, soft-linear or soft-gaussian')
     parser.add_argument('--nms-sigma', dest='nms_sigma', type=float, default=0.5, help='sigma of --nms soft-gaussian (> 0)')
+    parser.add_argument('--tta', choices=list(bbox_utils.TTA_VIEWS), default='none',
+                        help='test-time augmentation (extension): also run the flipped (hflip, flips) and transposed (d4: square inputs) '
+                        'views of every image and pool their detections before --nms; none (default) runs each image once')
+    parser.add_argument('--tta-vote-iou', dest='tta_vote_iou', type=float, default=None, metavar='T',
+                        help='--tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
+    parser.add_argument('--tta-score', dest='tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
+                        help='--tta with --tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
     a = parser.parse_args()
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
         parser.error('--nms-sigma must be > 0')
+    try:
+        bbox_utils.check_tta_args(a.tta, a.tta_vote_iou, a.tta_score)
+    except ValueError as e:
+        parser.error(str(e))
+    if a.tta == 'none' and a.tta_vote_iou is not None:
+        parser.error('--tta-vote-iou and --tta-score go with --tta')
     print('Arguments:')
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
-    inference(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, a.min_box_size, a.precision, a.batch_size, a.nms, a.nms_sigma)
+    inference(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, a.min_box_size, a.precision, a.batch_size, a.nms, a.nms_sigma,
+              a.tta, a.tta_vote_iou, a.tta_score)

@@ -118,6 +118,10 @@ SIGNATURES = {
     'y3_nms_labelled': (i32, [fp, i32, i32, i32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
     'y3_tile_merge': (i32, [fp, i32, i32, i32, i32, ip, ip, fp, i32, ip, i32, i32, i32, i32, i32, f32, fp, i32, ip, vp, sz, vp]),
     'y3_tile_merge_workspace_bytes': (sz, [i32, i32]),
+    'y3_tta_views_nhwc': (i32, [fp, i32, i32, i32, i32, C.POINTER(C.c_int), i32, TP, vp]),     # views: HOST array
+    'y3_tta_unmap': (i32, [fp, i32, i32, i32, C.POINTER(C.c_int), i32, i32, i32, vp]),
+    'y3_box_vote': (i32, [fp, i32, i32, i32, ip, ip, fp, i32, f32, f32, f32, f32, f32, i32, i32, i32, fp, vp, sz, vp]),
+    'y3_box_vote_workspace_bytes': (sz, [i32, i32, i32]),
     'y3_filter_small_boxes': (i32, [fp, i32, i32, f32, ip, ip, vp]),
     'y3_compute_iou': (i32, [fp, fp, i32, i32, fp, vp]),
     'y3_comm_unique_id': (i32, [vp]),
@@ -168,3 +172,7 @@ def view(t, n, h, w, c, ld=None, offset=0):
 def float_array(vals):
     arr = (C.c_float * len(vals))(*[float(v) for v in vals])
     return arr
+
+
+def int_array(vals):
+    return (C.c_int * len(vals))(*[int(v) for v in vals])

@@ -271,6 +271,135 @@ def detect(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=N
     return detect_async(rows, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma)()
 
 
+# ---- test-time augmentation: pooled views, box voting (y3_box_vote) -------------------------------------------
+# a view is a 3-bit code: 4 = transpose (applied first), 1 = flip x, 2 = flip y (Y3_TTA_*, yolo3hip.h); 0 is the identity
+TTA_VIEWS = {'none': (0,), 'hflip': (0, 1), 'flips': (0, 1, 2, 3), 'd4': (0, 1, 2, 3, 4, 5, 6, 7)}
+TTA_SCORES = ('keep', 'consensus')
+_VOTE_SCORE_CODES = {'keep': 0, 'consensus': 1}      # Y3_VOTE_SCORE_*
+TTA_MAX_BATCH = 16                                   # images x views per network call (YoloV3.TTA_MAX_BATCH)
+
+
+def check_tta_args(tta='none', vote_iou=None, score='keep', img_size=None):
+    """Host-side validation of the test-time augmentation options: ValueError on an unknown view set, a transposing set
+    ('d4') on a non-square input (img_size = (H, W), when known), vote_iou outside (0, 1] (None: no voting) and a consensus
+    score without voting (there would be no member sets to count).  Returns the set's view codes."""
+    if tta not in TTA_VIEWS:
+        raise ValueError('tta must be one of {}, got {!r}'.format(', '.join(TTA_VIEWS), tta))
+    if score not in TTA_SCORES:
+        raise ValueError('tta score must be one of {}, got {!r}'.format(', '.join(TTA_SCORES), score))
+    views = TTA_VIEWS[tta]
+    if img_size is not None and int(img_size[0]) != int(img_size[1]) and any(v & 4 for v in views):
+        raise ValueError('tta {!r} transposes the image, which needs a square input, got {} x {}'.format(tta, int(img_size[0]), int(img_size[1])))
+    if vote_iou is not None and not 0 < float(vote_iou) <= 1:
+        raise ValueError('tta vote_iou must be in (0, 1], got {}'.format(vote_iou))
+    if score == 'consensus' and vote_iou is None:
+        raise ValueError('a consensus score needs box voting (give a vote_iou)')
+    return views
+
+
+def tta_group_size(views):
+    """Images per network call under test-time augmentation: as many as keep images x views within TTA_MAX_BATCH."""
+    return max(1, TTA_MAX_BATCH // len(views))
+
+
+_vote_cache = {}
+
+
+def vote_device(rows, keep_idx, keep_cnt, keep_score, views, vote_iou, min_box_size=0.0, score_threshold=0.1, clip_wh=None, score='keep',
+                private_output=False):
+    """Box voting (y3_box_vote) on the current stream.  rows: CUDA float32 [N, k * Nb, 5+K], the unmapped rows of k = ``views``
+    views per image (YoloV3.predict_tta); keep_idx / keep_cnt / keep_score: nms_device's outputs for them; min_box_size,
+    score_threshold, clip_wh: what nms_device got.  Returns out [N, K, max_keep, 6] = x0, y0, x1, y1, score, class on the
+    device, valid for j < keep_cnt; the rest is uninitialised.  Like nms_device's outputs, out and the workspace are buffers
+    cached per shape and stream: the next call of that shape overwrites out unless private_output is set."""
+    if score not in _VOTE_SCORE_CODES:
+        raise ValueError('tta score must be one of {}, got {!r}'.format(', '.join(TTA_SCORES), score))
+    if not 0 < float(vote_iou) <= 1:
+        raise ValueError('tta vote_iou must be in (0, 1], got {}'.format(vote_iou))
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3 and rows.is_contiguous()
+    n, nb, d = rows.shape
+    k, max_keep, views = d - 5, keep_idx.shape[2], int(views)
+    assert keep_idx.shape[:2] == (n, k) and keep_cnt.shape == (n, k) and keep_score.shape == keep_idx.shape
+    assert keep_idx.is_contiguous() and keep_cnt.is_contiguous() and keep_score.is_contiguous()
+    if views < 1 or nb % views:
+        raise ValueError('{} rows per image are not {} views of equal length'.format(nb, views))
+    st_obj = torch.cuda.current_stream(rows.device)
+    key = (n, nb, k, max_keep, str(rows.device), st_obj.cuda_stream)      # one workspace per stream: launches on a stream run in order
+    buf = _vote_cache.get(key)
+    if buf is None:
+        ws_bytes = int(lib.y3_box_vote_workspace_bytes(n, nb, k))
+        buf = _vote_cache[key] = (torch.empty(n, k, max_keep, 6, dtype=torch.float32, device=rows.device), ws_bytes,
+                                  torch.empty(ws_bytes // 4 + 1, dtype=torch.float32, device=rows.device))
+    out, ws_bytes, ws = buf
+    if private_output:
+        out = torch.empty_like(out)
+    cw, chh = (float(clip_wh[0]), float(clip_wh[1])) if clip_wh is not None else (-1.0, -1.0)
+    check(lib.y3_box_vote(rows.data_ptr(), n, nb, k, keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(), max_keep,
+                          float(min_box_size), float(score_threshold), cw, chh, float(vote_iou), views, nb // views, _VOTE_SCORE_CODES[score],
+                          out.data_ptr(), ws.data_ptr(), ws_bytes, st_obj.cuda_stream), 'y3_box_vote')
+    return out
+
+
+def detect_tta_pools(rows, views, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5,
+                     vote_iou=None, score='keep', with_rows=False):
+    """The detections of the pooled views, left on the device.  rows: CUDA float32 [N, k * Nb, 5+K] from YoloV3.predict_tta
+    with k = ``views`` views.  The pooled rows of an image go through the chosen NMS (nms_device) as one image's rows; with
+    vote_iou every kept box is then replaced by the vote of its members (vote_device) and, with score='consensus', its score
+    by the mean over the views of the best member score.  Returns one (pool [M, 6] = x0, y0, x1, y1, score, class, M) per
+    image, class-major and in keep order inside a class (DetectionEvaluator.add_pool's input); with_rows: also the [M] kept row
+    indices.  Without vote_iou the pool holds what ``detect`` returns for the same rows.  Reads the keep counts: one
+    synchronisation; the gathers that follow are indexed by positions computed from them on the host."""
+    rows = rows.contiguous()
+    n, nb, d = rows.shape
+    k = d - 5
+    keep_idx, keep_cnt, keep_score = nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh, private_outputs=True,
+                                                method=method, sigma=sigma)
+    if vote_iou is not None:
+        out = vote_device(rows, keep_idx, keep_cnt, keep_score, views, vote_iou, min_box_size, score_threshold, clip_wh, score)
+    else:
+        if score != 'keep':
+            raise ValueError('a consensus score needs box voting (give a vote_iou)')
+        out = None
+    cnt = keep_cnt.cpu().numpy().astype(np.int64)                       # the one host read: everything below is sized from it
+    per_image = cnt.sum(1)
+    max_keep = keep_idx.shape[2]
+    # flat (image, class, slot) positions of every kept entry, class-major inside an image, as detect_async's collect builds them
+    ii = np.repeat(np.arange(n), per_image)
+    cc = np.concatenate([np.repeat(np.arange(k), cnt[i]) for i in range(n)])
+    jj = np.concatenate([np.arange(c) for c in cnt.reshape(-1)])
+    lin = torch.from_numpy((ii * k + cc) * max_keep + jj).to(rows.device)
+    kept = keep_idx.view(-1)[lin].long()
+    if out is not None:
+        flat = out.view(-1, 6)[lin]                                     # a copy: the cached out may be overwritten after this
+    else:
+        boxes = rows[torch.from_numpy(ii).to(rows.device), kept, 0:4]
+        if clip_wh is not None:
+            boxes[:, 0::2] = boxes[:, 0::2].clamp(0, float(clip_wh[0]))
+            boxes[:, 1::2] = boxes[:, 1::2].clamp(0, float(clip_wh[1]))
+        flat = torch.cat([boxes, keep_score.view(-1)[lin][:, None], torch.from_numpy(cc.astype(np.float32)).to(rows.device)[:, None]], dim=1)
+    ends = np.cumsum(per_image)
+    pools = []
+    for i in range(n):
+        a, b = int(ends[i] - per_image[i]), int(ends[i])
+        pools.append((flat[a:b], b - a, kept[a:b]) if with_rows else (flat[a:b], b - a))
+    return pools
+
+
+def detect_tta(rows, views, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5, vote_iou=None,
+               score='keep'):
+    """``detect`` for the pooled views of YoloV3.predict_tta (see detect_tta_pools): per image (boxes [M,4], score [M],
+    label [M] int32, keep [M] row indices into the image's k * Nb rows) as NumPy arrays, or (None,)*4."""
+    out = []
+    for pool, m, kept in detect_tta_pools(rows, views, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma, vote_iou, score,
+                                          with_rows=True):
+        if m == 0:
+            out.append((None, None, None, None))
+            continue
+        p = pool.cpu().numpy()
+        out.append((np.ascontiguousarray(p[:, 0:4]), np.ascontiguousarray(p[:, 4]), p[:, 5].astype(np.int32), kept.cpu().numpy().astype(np.int32)))
+    return out
+
+
 def per_class_nms(boxes, objectness, class_probs, iou_threshold=0.3, score_threshold=0.1):
     """bbox_utils.py:240-271 (same signature and (None, None, None) convention)."""
     boxes = np.asarray(boxes, np.float32)

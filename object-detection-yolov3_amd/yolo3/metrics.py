@@ -440,14 +440,19 @@ def database_examples(path, num_shards=1, shard_index=0):
         env.close()
 
 
-def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, precision=None, nms='hard', nms_sigma=0.5):
+def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, precision=None, nms='hard', nms_sigma=0.5, tta='none',
+                      tta_vote_iou=None, tta_score='keep'):
     """Feeds (name, HWC image, [G,5] X,Y,W,H,C) examples through ``yolo`` (a YoloV3: per-image z-score -> predict ->
     clip -> small-box filter -> NMS, inference.py's path) into ``evaluator``, ``batch_size`` images per call, the short
     tail as one smaller call.  precision: predict()'s ('fp32' / 'bf16'; default yolo.inference_precision).  nms /
-    nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its Gaussian parameter.  Returns the number of images added."""
+    nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time
+    augmentation (bbox_utils.check_tta_args; DESIGN §3.15): the views of max(1, 16 // k) images per network call, each image's
+    pooled and optionally voted detections matched as a device pool (add_pool with nms='none'); 'none' is the path above.
+    Returns the number of images added."""
     if batch_size < 1:
         raise ValueError('batch_size must be >= 1')
     bbox_utils.check_nms_args(nms, nms_sigma)
+    views = bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
     batch, count = [], 0
 
     def flush():
@@ -456,8 +461,19 @@ def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, preci
             raise RuntimeError('images must share one size (the model input is fixed): {}'.format({im.shape for im in imgs}))
         height, width = imgs[0].shape[:2]
         x = torch.from_numpy(np.stack([np.ascontiguousarray(im.astype(np.float32).transpose((2, 0, 1))) for im in imgs])).to(yolo.device)
-        rows = yolo.predict(imagereader.zscore_normalize_device(x), precision=precision)
-        evaluator.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height), nms=nms, nms_sigma=nms_sigma)
+        x = imagereader.zscore_normalize_device(x)
+        if tta == 'none':
+            rows = yolo.predict(x, precision=precision)
+            evaluator.add_batch(rows, [b[2] for b in batch], min_box_size, clip_wh=(width, height), nms=nms, nms_sigma=nms_sigma)
+        else:
+            bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score, (height, width))
+            step = bbox_utils.tta_group_size(views)
+            for s0 in range(0, len(batch), step):
+                rows = yolo.predict_tta(x[s0:s0 + step], views, precision=precision)
+                pools = bbox_utils.detect_tta_pools(rows, len(views), min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma,
+                                                    vote_iou=tta_vote_iou, score=tta_score)
+                for (pool, m), ex in zip(pools, batch[s0:s0 + step]):
+                    evaluator.add_pool(pool, m, ex[2], nms='none')        # re-establishes keep order under the final scores
         batch.clear()
 
     for ex in examples:

@@ -22,7 +22,7 @@ import torch
 
 from . import _hip
 from . import streams
-from ._hip import lib, check, view, EPI_LRELU, EPI_ACCUM, CONV_X3, BF16_NO_PATCH
+from ._hip import lib, check, view, int_array, EPI_LRELU, EPI_ACCUM, CONV_X3, BF16_NO_PATCH
 
 BN_EPS = 1e-3          # Keras BatchNormalization defaults
 BN_MOMENTUM = 0.99
@@ -1257,6 +1257,35 @@ class YoloV3:
         else:
             plan.run_inference(st, skip_input=True)
         return plan.boxes
+
+    TTA_MAX_BATCH = 16     # images x views per network call: the conv routes are tested for batches 1..16
+
+    def predict_tta(self, images, views, precision=None, slot=0):
+        """Test-time augmentation: images CUDA float32 [N, C, H, W], z-scored already; views: distinct 3-bit
+        codes (bbox_utils.TTA_VIEWS).  The N * k views are written straight into the plan's NHWC input (y3_tta_views_nhwc,
+        image-major and view-minor), go through the network as one batch of N * k, and every view's decode rows are mapped
+        back to the image's frame in place (y3_tta_unmap).  Returns [N, k * Nb, 5+K]: view v of an image in rows v * Nb ..
+        (v + 1) * Nb - 1.  N * k <= TTA_MAX_BATCH."""
+        if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.float32):
+            raise ValueError('predict_tta: images must be a CUDA float32 tensor')
+        h, w = self._input_size(images)
+        views = [int(v) for v in views]
+        n, k = int(images.shape[0]), len(views)
+        if k < 1 or n * k > self.TTA_MAX_BATCH:
+            raise ValueError('predict_tta: {} images x {} views = {} network inputs (1 .. {} per call)'.format(n, k, n * k, self.TTA_MAX_BATCH))
+        images = images.contiguous()
+        plan = self._plan(n * k, False, (precision or self.inference_precision) == 'bf16', slot)
+        st = self._stream()
+        codes = int_array(views)
+        check(lib.y3_tta_views_nhwc(images.data_ptr(), n, int(images.shape[1]), h, w, codes, k, plan.x0.v, st), 'y3_tta_views_nhwc')
+        if self.use_graph:
+            if plan.infer_graph_tiles is None:      # forward without the input transpose: the launch above wrote x0
+                plan.infer_graph_tiles = self._graph_of(functools.partial(plan.run_inference, skip_input=True))
+            plan.infer_graph_tiles.replay()
+        else:
+            plan.run_inference(st, skip_input=True)
+        check(lib.y3_tta_unmap(plan.boxes.data_ptr(), n * k, plan.nb, plan.boxes.shape[2], codes, k, h, w, st), 'y3_tta_unmap')
+        return plan.boxes.view(n, k * plan.nb, plan.boxes.shape[2])
 
     def feature_maps(self, images, training=False, precision=None):
         """The 'yolov3_fm' model (model.py:462): three NCHW feature maps (fp32 unless precision='bf16' is asked for)."""
