@@ -772,6 +772,34 @@ int y3_eval_ap(const long long* keys, const unsigned* tp, long long m, int num_c
                void* workspace, size_t workspace_bytes, float* ap, float* recall, int* tp_count, int* fp_count, y3_stream_t stream);
 size_t y3_eval_ap_workspace_bytes(long long m, int num_thr);
 
+/* ---- AP by area range, best-F1 score cuts and PR curves (opt-in: DetectionEvaluator(area_ranges=..., curves=...)) ----
+ * y3_eval_match_ranges: y3_eval_match over num_ranges (1..8) closed area ranges [area_lo_host[a], area_hi_host[a]] (HOST
+ * arrays of fp32, lo < hi, +-inf allowed, NaN refused).  A box's area is the fp32 product (x1 - x0) * (y1 - y0) of its corners (the
+ * detection's after the clip).  Per segment, range a and threshold t, in keep order, among the unmatched GT boxes of the class
+ * with IoU >= t: the detection takes the in-range box of largest IoU (ties: highest GT index) and is a TP; else the
+ * out-of-range box of largest IoU (same tie rule), which is consumed, and is IGNORED; with no such box it is ignored if its own
+ * area is out of range, else an FP.  pool_tp / pool_ign are entry-major [pool_capacity][num_ranges] words: bit t of word
+ * [offsets[s] + j][a]; pool_key as y3_eval_match.  Same launch shape, LDS cap (4096 GT per (image, class)) and refusals as
+ * y3_eval_match; the waves walk the num_ranges * num_thr pairs. */
+int y3_eval_match_ranges(const float* rows, int n, int nb, int ld, int num_classes, float clip_w, float clip_h, const int* keep_idx,
+                         const int* keep_cnt, const float* keep_score, int max_keep, int max_det, const float* gt, const int* gt_cnt,
+                         int max_gt, int max_gt_per_class, const float* iou_thr_host, int num_thr, const float* area_lo_host,
+                         const float* area_hi_host, int num_ranges, const int* offsets, long long* pool_key, unsigned* pool_tp,
+                         unsigned* pool_ign, long long pool_capacity, y3_stream_t stream);
+/* y3_eval_ap_ranges: keys [m], tp / ign [m][A] = the pool stably sorted by key, npos [K][A] = in-range GT boxes.  Per (class c,
+ * range a, threshold t) over the entries whose ignore bit is clear, ranked as y3_eval_ap ranks them: ap, recall, tp_count,
+ * fp_count as y3_eval_ap, ign_count = ignored entries; the best-F1 cut: among the cuts k (first k ranked entries kept) that do not
+ * split a run of equal scores, the one of largest F1 = 2 TP(k) / (k + npos) (fp64; ties: smallest k): best_n = k, best_tp =
+ * TP(k), best_score = score of entry k (0, 0, NaN without entries or without GT).  Optional (null: skipped) pr_precision /
+ * pr_score [K][A][T][101]: the envelope precision at recall j / 100 (the 101 terms of the AP) and the score of the entry at
+ * which that recall is first reached (NaN where it never is; both NaN where npos == 0).  All other outputs [K][A][T].
+ * workspace: y3_eval_ap_ranges_workspace_bytes(m, num_ranges, num_thr). */
+int y3_eval_ap_ranges(const long long* keys, const unsigned* tp, const unsigned* ign, long long m, int num_classes, int num_ranges,
+                      int num_thr, const int* npos, void* workspace, size_t workspace_bytes, float* ap, float* recall, int* tp_count,
+                      int* fp_count, int* ign_count, int* best_n, int* best_tp, float* best_score, float* pr_precision, float* pr_score,
+                      y3_stream_t stream);
+size_t y3_eval_ap_ranges_workspace_bytes(long long m, int num_ranges, int num_thr);
+
 /* ---- gradient exchange: tf.distribute.MirroredStrategy's all-reduce (train.py:38-39, model.py:500,510-515) -------
  * One process per GPU; SUM over the replicas (the loss is already divided by the global batch, model.py:492).  RCCL over
  * xGMI underneath (librccl.so is opened on first use).  Rank 0 calls y3_comm_unique_id and hands the 128 bytes to the

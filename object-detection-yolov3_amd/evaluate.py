@@ -8,6 +8,9 @@ filter -> class-wise NMS, same defaults) and the NMS keep lists are matched agai
   --image-folder + --csv-folder   images and X,Y,W,H,C csv files of the same basename (build_lmdb.py's input).
 Under `python -m torch.distributed.run --nproc-per-node N` every rank evaluates every N-th example (keys[rank::N]) and
 the ranks' evaluators are merged (yolo3.metrics.all_gather_evaluator, a collective); rank 0 prints and writes the csv.
+--area-ranges scores every class once per range of box area (COCO's AP small / medium / large with its ignore rule),
+--operating-points and --pr-curves write the best-F1 score threshold and the PR curve per class, range and IoU threshold
+(DESIGN §3.16); they go with every other flag.
 """
 import argparse
 import math
@@ -43,16 +46,19 @@ def folder_examples(image_folder, csv_folder, image_format, num_shards=1, shard_
 
 
 def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
-             max_detections=None, distributed=False, nms='hard', nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep'):
+             max_detections=None, distributed=False, nms='hard', nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep',
+             area_ranges=None, area_names=None, curves=False):
     """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds).
     distributed: a collective over the default process group; every rank passes its keys[rank::world] share of the
     examples and gets the result over all of them.  nms / nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its
-    Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time augmentation (metrics.evaluate_examples)."""
+    Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time augmentation (metrics.evaluate_examples).  area_ranges /
+    area_names / curves: DetectionEvaluator's."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision
-    ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
+    ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections, area_ranges=area_ranges, area_names=area_names,
+                                    curves=curves)
     t0 = time.perf_counter()
     metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size, nms=nms, nms_sigma=nms_sigma, tta=tta, tta_vote_iou=tta_vote_iou,
                               tta_score=tta_score)
@@ -65,11 +71,12 @@ def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', bat
 
 def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, precision='fp32', batch_size=None,
                    iou_thresholds=metrics.COCO_IOU_THRESHOLDS, max_detections=None, distributed=False, nms='hard', nms_sigma=0.5,
-                   seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5):
+                   seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5, area_ranges=None, area_names=None, curves=False):
     """``evaluate`` for the tiled pipeline (inference_tiled.py with --merge-device gpu): every image, of any size, is cut
     into tiles, the tiles' detections are merged on the device (seam_margin) and the pool is matched against the
     whole-image ground truth there (DetectionEvaluator.add_pool with nms=merge_nms).  batch_size: tiles per network launch
-    (None: inference_tiled's default).  Returns (result dict, number of images, seconds)."""
+    (None: inference_tiled's default).  area_ranges / area_names / curves: DetectionEvaluator's.  Returns (result dict, number
+    of images, seconds)."""
     import inference_tiled
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args('gpu', seam_margin, merge_nms, merge_nms_sigma, inference_tiled.EDGE_EFFECT_RANGE)
@@ -78,7 +85,8 @@ def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, prec
     if list(tile_size) != list(yolo.img_size[:2]):
         raise RuntimeError('tile size {} must equal the size the model was trained at {} (Q18)'.format(list(tile_size), yolo.img_size[:2]))
     model = yolo.get_keras_model()
-    ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections)
+    ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections, area_ranges=area_ranges, area_names=area_names,
+                                    curves=curves)
     t0 = time.perf_counter()
     for _, img, gt in examples:
         pool, count, _ = inference_tiled.tiled_pool_device(model, img, tile_size, min_box_size, batch_size, nms, nms_sigma, seam_margin)
@@ -94,18 +102,63 @@ def _fmt(v):
     return '' if isinstance(v, float) and math.isnan(v) else repr(float(v))
 
 
-def write_csv(res, path):
-    """One row per class, then a 'mean' row (mean over the classes with ground truth; NaN cells are empty)."""
-    thr = res['iou_thresholds']
+def parse_area_ranges(values):
+    """--area-ranges: ['coco'], or LO:HI strings and 'all' (every area: a leading '-inf' would read as an option) ->
+    (area_ranges, area_names) of DetectionEvaluator; a range is named by its text (raises ValueError)."""
+    if len(values) == 1 and values[0] == 'coco':
+        return metrics.check_area_ranges('coco')
+    out = []
+    for v in values:
+        lo, sep, hi = ('-inf', ':', 'inf') if v == 'all' else v.partition(':')
+        if not sep:
+            raise ValueError("--area-ranges: 'coco', or 'all' and LO:HI pairs, got {!r}".format(v))
+        out.append((float(lo), float(hi)))
+    return metrics.check_area_ranges(out, values)
+
+
+def write_operating_points(res, path):
+    """One row per class, range and IoU threshold: the best-F1 score cut (keep score >= score_threshold) and what it yields."""
     with open(path, 'w') as fh:
-        fh.write(','.join(['class', 'npos', 'tp', 'fp', 'precision', 'recall', 'f1', 'ap'] + ['ap@%.2f' % t for t in thr]) + '\n')
+        fh.write('class,range,iou_threshold,score_threshold,precision,recall,f1,tp,fp,npos\n')
+        for c in range(res['ap'].shape[0]):
+            for a, name in enumerate(res['area_names']):
+                for t, thr in enumerate(res['iou_thresholds']):
+                    fh.write(','.join([str(c), name, repr(float(thr)), _fmt(float(res['best_score'][a, c, t])),
+                                       _fmt(float(res['best_precision'][a, c, t])), _fmt(float(res['best_recall'][a, c, t])),
+                                       _fmt(float(res['best_f1'][a, c, t])), str(int(res['best_tp'][a, c, t])),
+                                       str(int(res['best_fp'][a, c, t])), str(int(res['npos_area'][c, a]))]) + '\n')
+
+
+def write_pr_curves(res, path):
+    """One row per class, range, IoU threshold and recall point j / 100: the envelope precision there and the score at which
+    that recall is first reached (empty where it never is)."""
+    with open(path, 'w') as fh:
+        fh.write('class,range,iou_threshold,recall,precision,score\n')
+        for c in range(res['ap'].shape[0]):
+            for a, name in enumerate(res['area_names']):
+                for t, thr in enumerate(res['iou_thresholds']):
+                    for j in range(101):
+                        fh.write(','.join([str(c), name, repr(float(thr)), repr(j / 100), _fmt(float(res['pr_precision'][a, c, t, j])),
+                                           _fmt(float(res['pr_score'][a, c, t, j]))]) + '\n')
+
+
+def write_csv(res, path, area_columns=False):
+    """One row per class, then a 'mean' row (mean over the classes with ground truth; NaN cells are empty).  area_columns:
+    append one ap_<range name> column per area range (the class's mean AP over the thresholds in that range)."""
+    thr = res['iou_thresholds']
+    names = res['area_names'] if area_columns else []
+    with open(path, 'w') as fh:
+        fh.write(','.join(['class', 'npos', 'tp', 'fp', 'precision', 'recall', 'f1', 'ap'] + ['ap@%.2f' % t for t in thr] +
+                          ['ap_' + n for n in names]) + '\n')
         valid = res['npos'] > 0
         for c in range(res['ap'].shape[0]):
             ap_mean = float(res['ap'][c].mean()) if valid[c] else float('nan')
             cells = [str(c), str(int(res['npos'][c])), str(int(res['tp50'][c])), str(int(res['fp50'][c])), _fmt(res['precision50'][c]),
                      _fmt(res['recall50'][c]), _fmt(res['f1_50'][c]), _fmt(ap_mean)] + [_fmt(v) for v in res['ap'][c]]
+            cells += [_fmt(float(res['ap_area'][a, c].mean())) for a in range(len(names))]         # NaN where the range holds no GT of c
             fh.write(','.join(cells) + '\n')
-        fh.write(','.join(['mean', str(int(res['npos'].sum())), '', '', '', '', '', _fmt(res['map_all'])] + [_fmt(v) for v in res['map']]) + '\n')
+        fh.write(','.join(['mean', str(int(res['npos'].sum())), '', '', '', '', '', _fmt(res['map_all'])] + [_fmt(v) for v in res['map']] +
+                          [_fmt(float(np.mean(res['map_area'][a]))) for a in range(len(names))]) + '\n')
 
 
 def print_table(res):
@@ -120,6 +173,10 @@ def print_table(res):
             res['ap'][c, col], float(np.mean(res['ap'][c]))))
     print('tp / fp / precision / recall / f1 at IoU {:.2f}; AP = mean over IoU {}'.format(op, ', '.join('%.2f' % t for t in thr)))
     print('mAP50 = {:.4f}  mAP50:95 = {:.4f}  mAP (all thresholds) = {:.4f}'.format(res['map50'], res['map50_95'], res['map_all']))
+    for a, name in enumerate(res.get('area_names', [])):
+        lo, hi = res['area_ranges'][a]
+        print('area {:>8} [{:g}, {:g}]: npos {:d}  AP = {:.4f}  AP50 = {:.4f}  AR = {:.4f}'.format(
+            name, lo, hi, int(res['npos_area'][:, a].sum()), float(np.mean(res['map_area'][a])), res['map50_area'][a], res['ar_area'][a]))
 
 
 if __name__ == '__main__':
@@ -156,6 +213,13 @@ if __name__ == '__main__':
                         help='--tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
     parser.add_argument('--tta-score', dest='tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
                         help='--tta with --tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
+    parser.add_argument('--area-ranges', dest='area_ranges', type=str, nargs='+', default=None, metavar='LO:HI',
+                        help="also score per range of box area in px^2, both ends closed: 'coco' (all, small <= 32^2, medium, large > 96^2) "
+                        "or up to 8 of LO:HI (inf allowed) and 'all'; detections and ground truth outside a range are ignored there, not counted")
+    parser.add_argument('--operating-points', dest='operating_points', type=str, default=None, metavar='FILE',
+                        help='csv of the score threshold of best F1 per class, area range and IoU threshold')
+    parser.add_argument('--pr-curves', dest='pr_curves', type=str, default=None, metavar='FILE',
+                        help='csv of the 101-point precision/recall curve per class, area range and IoU threshold')
     parser.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend under torch.distributed.run: nccl (= RCCL, '
                         'one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
     a = parser.parse_args()
@@ -193,6 +257,13 @@ if __name__ == '__main__':
     thresholds = metrics.COCO_IOU_THRESHOLDS if a.iou_thresholds is None else a.iou_thresholds
     if not 1 <= len(thresholds) <= 32 or not all(0 < t <= 1 for t in thresholds):
         parser.error('--iou-thresholds: 1..32 values in (0, 1]')
+    area_ranges = area_names = None
+    if a.area_ranges is not None:
+        try:
+            area_ranges, area_names = parse_area_ranges(a.area_ranges)
+        except ValueError as e:
+            parser.error(str(e))
+    curves = a.operating_points is not None or a.pr_curves is not None
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
         import torch.distributed as dist
@@ -213,11 +284,12 @@ if __name__ == '__main__':
     if a.tiled:
         res, count, secs = evaluate_tiled(examples, a.saved_model_filepath, [a.tile_height, a.tile_width], a.min_box_size, a.precision,
                                           a.batch_size, thresholds, a.max_detections, distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma,
-                                          seam_margin=a.seam_margin, merge_nms=a.merge_nms, merge_nms_sigma=a.merge_nms_sigma)
+                                          seam_margin=a.seam_margin, merge_nms=a.merge_nms, merge_nms_sigma=a.merge_nms_sigma,
+                                          area_ranges=area_ranges, area_names=area_names, curves=curves)
     else:
         res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
                                     distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma, tta=a.tta, tta_vote_iou=a.tta_vote_iou,
-                                    tta_score=a.tta_score)
+                                    tta_score=a.tta_score, area_ranges=area_ranges, area_names=area_names, curves=curves)
     if rank == 0:
         print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
         print('NMS: {}'.format(a.nms + (' (sigma {:g})'.format(a.nms_sigma) if a.nms == 'soft-gaussian' else '')))
@@ -228,7 +300,11 @@ if __name__ == '__main__':
             print('Tiled: {} x {} tiles, seam margin {:g}, merge NMS {}'.format(a.tile_height, a.tile_width, a.seam_margin, a.merge_nms))
         print_table(res)
         if a.output_file:
-            write_csv(res, a.output_file)
+            write_csv(res, a.output_file, area_columns=area_ranges is not None)
+        if a.operating_points:
+            write_operating_points(res, a.operating_points)
+        if a.pr_curves:
+            write_pr_curves(res, a.pr_curves)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

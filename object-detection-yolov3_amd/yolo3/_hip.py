@@ -145,6 +145,10 @@ SIGNATURES = {
                             vp, vp, C.c_longlong, vp]),     # iou_thr: HOST array
     'y3_eval_ap': (i32, [vp, vp, C.c_longlong, i32, i32, ip, vp, sz, fp, fp, ip, ip, vp]),
     'y3_eval_ap_workspace_bytes': (sz, [C.c_longlong, i32]),
+    'y3_eval_match_ranges': (i32, [fp, i32, i32, i32, i32, f32, f32, ip, ip, fp, i32, i32, fp, ip, i32, i32, C.POINTER(C.c_float), i32,
+                                   C.POINTER(C.c_float), C.POINTER(C.c_float), i32, ip, vp, vp, vp, C.c_longlong, vp]),   # thr, lo, hi: HOST
+    'y3_eval_ap_ranges': (i32, [vp, vp, vp, C.c_longlong, i32, i32, i32, ip, vp, sz, fp, fp, ip, ip, ip, ip, ip, fp, fp, fp, vp]),
+    'y3_eval_ap_ranges_workspace_bytes': (sz, [C.c_longlong, i32, i32]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -19,6 +19,10 @@ Across processes: ``state()`` exports the pools with the number o
 concatenates several states' per-image blocks in global image order (the single-process pool order, so the merged
 result is bit-identical to one evaluator that saw every image), and ``all_gather_evaluator`` does that over a
 torch.distributed group.  ``evaluate_examples`` is the batching loop evaluate.py and train.py --test_map share.
+
+Opt-in: ``area_ranges`` scores every class once per closed range of box area with COCO's ignore rule
+(``y3_eval_match_ranges``), ``curves`` adds the best-F1 score cut and the 101-point PR curve per (class, range, threshold)
+(``y3_eval_ap_ranges``).  Without them the three kernels above run exactly as before.
 """
 import numpy as np
 import torch
@@ -29,6 +33,35 @@ from .isg_ai_pb import ImageYoloBoxesPair
 
 COCO_IOU_THRESHOLDS = tuple(float(np.float32(0.5) + np.float32(0.05) * np.float32(k)) for k in range(10))
 MAX_GT_PER_CLASS = 4096     # Y3_EVAL_MAX_GT: the GT boxes of one (image, class) are staged in LDS
+MAX_AREA_RANGES = 8         # Y3_EVAL_MAX_RANGES
+COCO_AREA_RANGES = (('all', -np.inf, np.inf), ('small', 0.0, 32.0 ** 2), ('medium', 32.0 ** 2, 96.0 ** 2), ('large', 96.0 ** 2, 1e10))
+
+
+def check_area_ranges(area_ranges, area_names=None):
+    """'coco' or a sequence of (lo, hi) -> (float32 [A,2], names [A]).  1..8 ranges, lo < hi, +-inf allowed, NaN refused;
+    area_names: one name per range (default: the preset's, else 'LO:HI')."""
+    if isinstance(area_ranges, str):
+        if area_ranges != 'coco':
+            raise ValueError("area_ranges: 'coco' or a sequence of (lo, hi), got {!r}".format(area_ranges))
+        names = [r[0] for r in COCO_AREA_RANGES]
+        area_ranges = [r[1:] for r in COCO_AREA_RANGES]
+    else:
+        names = None
+    try:
+        rng = np.asarray(area_ranges, np.float32)
+    except (TypeError, ValueError):
+        raise ValueError('area_ranges: a sequence of (lo, hi) pairs, got {!r}'.format(area_ranges))
+    if rng.ndim != 2 or rng.shape[1] != 2 or not 1 <= rng.shape[0] <= MAX_AREA_RANGES:
+        raise ValueError('area_ranges: 1..{} (lo, hi) pairs, got shape {}'.format(MAX_AREA_RANGES, rng.shape))
+    if not np.all(rng[:, 0] < rng[:, 1]):                          # a NaN bound fails the comparison too
+        raise ValueError('area_ranges: every range needs lo < hi (no NaN), got {}'.format(rng.tolist()))
+    if area_names is not None:
+        names = [str(v) for v in area_names]
+        if len(names) != rng.shape[0]:
+            raise ValueError('{} area_names for {} ranges'.format(len(names), rng.shape[0]))
+    elif names is None:
+        names = ['{:g}:{:g}'.format(lo, hi) for lo, hi in rng]
+    return rng, names
 
 
 def gt_corners(boxes_xywhc):
@@ -56,9 +89,14 @@ class DetectionEvaluator:
     """Accumulates matches over batches of images; ``result()`` gives AP / recall / TP / FP per (class, threshold).
 
     iou_thresholds: 1..32 values in (0, 1], fp32 (default: COCO's 0.50:0.05:0.95).  max_detections: keep at most this
-    many detections per (image, class) in score order (default: every entry NMS kept)."""
+    many detections per (image, class) in score order (default: every entry NMS kept).  area_ranges: 'coco' or 1..8
+    (lo, hi) closed ranges of box area, area_names their names: AP / recall / TP / FP per range with the ignore rule of DESIGN
+    §3.16.  curves: also the best-F1 score cut and the PR curve per (class, range, threshold); without ranges over the one
+    range (-inf, inf).  Either option switches matching and AP to the *_ranges kernels; ``state``, ``matches`` and ``result``
+    then carry one TP and one ignore mask per entry and range."""
 
-    def __init__(self, num_classes, iou_thresholds=COCO_IOU_THRESHOLDS, max_detections=None, device=None):
+    def __init__(self, num_classes, iou_thresholds=COCO_IOU_THRESHOLDS, max_detections=None, device=None, area_ranges=None, area_names=None,
+                 curves=False):
         self.num_classes = int(num_classes)
         if self.num_classes < 1:
             raise ValueError('num_classes must be >= 1')
@@ -71,11 +109,23 @@ class DetectionEvaluator:
         self.max_detections = None if max_detections is None else int(max_detections)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self._thr_host = float_array(thr)
+        self.curves = bool(curves)
+        self._ranged = area_ranges is not None or self.curves
+        self.area_ranges, self.area_names = None, None
+        if area_ranges is None and area_names is not None:
+            raise ValueError('area_names go with area_ranges')
+        if self._ranged:
+            self.area_ranges, self.area_names = check_area_ranges([COCO_AREA_RANGES[0][1:]], ['all']) if area_ranges is None else \
+                check_area_ranges(area_ranges, area_names)
+            self._lo_host = float_array(self.area_ranges[:, 0])
+            self._hi_host = float_array(self.area_ranges[:, 1])
         self.reset()
 
     def reset(self):
         self._keys = torch.empty(0, dtype=torch.int64, device=self.device)
-        self._tp = torch.empty(0, dtype=torch.int32, device=self.device)
+        self._tp = torch.empty(self._mask_shape(0), dtype=torch.int32, device=self.device)
+        self._ign = torch.empty(self._mask_shape(0), dtype=torch.int32, device=self.device) if self._ranged else None
+        self._npos_area = np.zeros((self.num_classes, len(self.area_ranges)), np.int64) if self._ranged else None
         self._used = 0
         self._counts = []         # per batch: int32 device [n] = pool entries each image added (image order)
         self._npos = np.zeros(self.num_classes, np.int64)
@@ -196,6 +246,19 @@ class DetectionEvaluator:
             cnt[i] = g.shape[0]
         return buf, cnt, max_gt, worst, npos
 
+    def _mask_shape(self, entries):
+        return (entries, len(self.area_ranges)) if self._ranged else (entries,)
+
+    def _npos_in_ranges(self, buf, cnt):
+        """int64 [K, A]: the in-range GT boxes per class, by the match kernel's fp32 area arithmetic."""
+        out = np.zeros_like(self._npos_area)
+        for g, c in zip(buf, cnt):
+            g = g[:c]
+            area = (g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1])                     # float32, as gar in the kernel
+            for a, (lo, hi) in enumerate(self.area_ranges):
+                out[:, a] += np.bincount(g[(lo <= area) & (area <= hi), 4].astype(np.int64), minlength=self.num_classes)
+        return out
+
     def _match(self, rows, n, nb, ld, clip_w, clip_h, keep_idx, keep_cnt, keep_score, max_keep, gt):
         buf, cnt, max_gt, worst, npos = gt
         dev = self.device
@@ -209,10 +272,19 @@ class DetectionEvaluator:
         total = int(offsets[n * K].item())                                # the one host read of the batch
         self._reserve(self._used + total)             # only grows capacity: a refused batch below (GT over the LDS cap) adds nothing
         used = self._used
-        check(lib.y3_eval_match(rows.data_ptr(), n, nb, ld, K, clip_w, clip_h, keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(),
-                                max_keep, max_det, gt_dev.data_ptr(), cnt_dev.data_ptr(), max_gt, worst, self._thr_host,
-                                len(self.iou_thresholds), offsets.data_ptr(), self._keys.data_ptr() + 8 * used,
-                                self._tp.data_ptr() + 4 * used, self._keys.numel() - used, st), 'y3_eval_match')
+        if self._ranged:
+            A = len(self.area_ranges)
+            check(lib.y3_eval_match_ranges(rows.data_ptr(), n, nb, ld, K, clip_w, clip_h, keep_idx.data_ptr(), keep_cnt.data_ptr(),
+                                           keep_score.data_ptr(), max_keep, max_det, gt_dev.data_ptr(), cnt_dev.data_ptr(), max_gt, worst,
+                                           self._thr_host, len(self.iou_thresholds), self._lo_host, self._hi_host, A, offsets.data_ptr(),
+                                           self._keys.data_ptr() + 8 * used, self._tp.data_ptr() + 4 * A * used,
+                                           self._ign.data_ptr() + 4 * A * used, self._keys.numel() - used, st), 'y3_eval_match_ranges')
+            self._npos_area += self._npos_in_ranges(buf, cnt)
+        else:
+            check(lib.y3_eval_match(rows.data_ptr(), n, nb, ld, K, clip_w, clip_h, keep_idx.data_ptr(), keep_cnt.data_ptr(),
+                                    keep_score.data_ptr(), max_keep, max_det, gt_dev.data_ptr(), cnt_dev.data_ptr(), max_gt, worst,
+                                    self._thr_host, len(self.iou_thresholds), offsets.data_ptr(), self._keys.data_ptr() + 8 * used,
+                                    self._tp.data_ptr() + 4 * used, self._keys.numel() - used, st), 'y3_eval_match')
         self._used += total
         self._counts.append(torch.diff(offsets[0::K]))               # image i's entries: offsets[(i+1)K] - offsets[iK]
         self._npos += npos
@@ -224,10 +296,14 @@ class DetectionEvaluator:
             return
         cap = max(need, 2 * cap, 1024)
         keys = torch.empty(cap, dtype=torch.int64, device=self.device)
-        tp = torch.empty(cap, dtype=torch.int32, device=self.device)
+        tp = torch.empty(self._mask_shape(cap), dtype=torch.int32, device=self.device)
         keys[:self._used] = self._keys[:self._used]
         tp[:self._used] = self._tp[:self._used]
         self._keys, self._tp = keys, tp
+        if self._ranged:
+            ign = torch.empty(self._mask_shape(cap), dtype=torch.int32, device=self.device)
+            ign[:self._used] = self._ign[:self._used]
+            self._ign = ign
 
     # ---- state across processes -----------------------------------------------------------------------------------
     def image_counts(self):
@@ -239,10 +315,15 @@ class DetectionEvaluator:
     def state(self):
         """What ``merge`` / ``all_gather_evaluator`` combine (device tensors are copies): keys int64 [M], tp int32 [M] = the
         pools in (image, class, keep rank) order, image_counts int32 [num_images], npos int64 [K] (NumPy), num_images,
-        iou_thresholds (float32), num_classes, max_detections."""
-        return {'keys': self._keys[:self._used].clone(), 'tp': self._tp[:self._used].clone(), 'image_counts': self.image_counts().clone(),
-                'npos': self._npos.copy(), 'num_images': self.num_images, 'iou_thresholds': self.iou_thresholds.copy(),
-                'num_classes': self.num_classes, 'max_detections': self.max_detections}
+        iou_thresholds (float32), num_classes, max_detections.  With area ranges or curves: tp is [M, A] and the state also
+        holds ign int32 [M, A], npos_area int64 [K, A], area_ranges float32 [A, 2], area_names, curves."""
+        st = {'keys': self._keys[:self._used].clone(), 'tp': self._tp[:self._used].clone(), 'image_counts': self.image_counts().clone(),
+              'npos': self._npos.copy(), 'num_images': self.num_images, 'iou_thresholds': self.iou_thresholds.copy(),
+              'num_classes': self.num_classes, 'max_detections': self.max_detections}
+        if self._ranged:
+            st.update(ign=self._ign[:self._used].clone(), npos_area=self._npos_area.copy(), area_ranges=self.area_ranges.copy(),
+                      area_names=list(self.area_names), curves=self.curves)
+        return st
 
     @classmethod
     def merge(cls, states, order='strided', device=None):
@@ -250,8 +331,8 @@ class DetectionEvaluator:
         global image g is local image g // W of state g % W, the keys[rank::world] split of ImageReader(num_shards=W) and
         inference.py), or an explicit sequence of (state, local image) pairs naming every image once.  ``result()`` sorts
         stably, so equal scores rank by pool position: rebuilding the single-process order makes the merged result
-        bit-identical to one evaluator fed all images in that order.  States must share thresholds, classes and
-        max_detections."""
+        bit-identical to one evaluator fed all images in that order.  States must share thresholds, classes,
+        max_detections, area ranges and curves."""
         states = list(states)
         if not states:
             raise ValueError('merge needs at least one state')
@@ -262,13 +343,19 @@ class DetectionEvaluator:
             if s['num_classes'] != s0['num_classes'] or s['max_detections'] != s0['max_detections'] or not np.array_equal(thr, thr0):
                 raise ValueError('state {} does not match state 0: classes {} / {}, max_detections {} / {}, iou_thresholds {} / {}'.format(
                     i, s['num_classes'], s0['num_classes'], s['max_detections'], s0['max_detections'], list(thr), list(thr0)))
+            if not _same_ranges(s, s0):
+                raise ValueError('state {} does not match state 0: area_ranges {} / {}, curves {} / {}'.format(
+                    i, _ranges_list(s), _ranges_list(s0), s.get('curves', False), s0.get('curves', False)))
         state_index, local_index = global_image_order([int(s['num_images']) for s in states], order)
-        ev = cls(s0['num_classes'], thr0, s0['max_detections'], device)
+        ranged = s0.get('area_ranges') is not None
+        ev = cls(s0['num_classes'], thr0, s0['max_detections'], device, area_ranges=s0['area_ranges'] if ranged else None,
+                 area_names=s0['area_names'] if ranged else None, curves=bool(s0.get('curves', False)))
         dev = ev.device
         counts = []
         for i, s in enumerate(states):
             c = s['image_counts'].to(dev, torch.int64)
-            if c.numel() != int(s['num_images']) or int(c.sum()) != s['keys'].numel() or s['tp'].numel() != s['keys'].numel():
+            if c.numel() != int(s['num_images']) or int(c.sum()) != s['keys'].numel() or tuple(s['tp'].shape) != ev._mask_shape(s['keys'].numel()) \
+                    or (ranged and tuple(s['ign'].shape) != tuple(s['tp'].shape)):
                 raise ValueError('state {}: {} image counts summing to {} for {} images and {} keys / {} TP masks'.format(
                     i, c.numel(), int(c.sum()), s['num_images'], s['keys'].numel(), s['tp'].numel()))
             counts.append(c)
@@ -278,17 +365,24 @@ class DetectionEvaluator:
         if total:
             ev._keys[:total] = torch.cat([s['keys'].to(dev) for s in states])[idx]
             ev._tp[:total] = torch.cat([s['tp'].to(dev) for s in states])[idx]
+            if ranged:
+                ev._ign[:total] = torch.cat([s['ign'].to(dev) for s in states])[idx]
         ev._used = total
         ev._counts = [cnt.to(torch.int32)]
         ev._npos = np.sum([np.asarray(s['npos'], np.int64) for s in states], axis=0)
+        if ranged:
+            ev._npos_area = np.sum([np.asarray(s['npos_area'], np.int64) for s in states], axis=0)
         ev.num_images = int(state_index.size)
         return ev
 
     # ---- output ---------------------------------------------------------------------------------------------------
     def matches(self):
-        """Pool entries in (image, class, keep rank) order: (class int32 [M], score float32 [M], TP mask uint32 [M])."""
+        """Pool entries in (image, class, keep rank) order: (class int32 [M], score float32 [M], TP mask uint32 [M]); with
+        area ranges or curves (class, score, TP masks uint32 [M, A], ignore masks uint32 [M, A])."""
         keys = self._keys[:self._used].cpu().numpy()
         cls, score = decode_pool_key(keys)
+        if self._ranged:
+            return cls, score, self._tp[:self._used].cpu().numpy().view(np.uint32), self._ign[:self._used].cpu().numpy().view(np.uint32)
         return cls, score, self._tp[:self._used].cpu().numpy().view(np.uint32)
 
     def result(self):
@@ -297,7 +391,14 @@ class DetectionEvaluator:
         with npos > 0), map50 (t = 0.5; NaN if 0.5 is not a threshold), map50_95 (mean over classes and the ten COCO
         thresholds; NaN unless those are the thresholds), map_all (mean over classes and all thresholds), and at the
         operating-point threshold op_threshold (0.5, else the first one): tp50, fp50, precision50 (TP / (TP+FP), 0 without
-        detections), recall50 (TP / npos, NaN without GT), f1_50 (0 when precision + recall is 0)."""
+        detections), recall50 (TP / npos, NaN without GT), f1_50 (0 when precision + recall is 0).
+        With area ranges or curves (A = ranges) the keys above are those of the first range named 'all', else of
+        range 0, and the dict adds area_ranges [A,2], area_names, ap_area, recall_area, tp_area, fp_area, ign_area [A,K,T],
+        npos_area [K,A], map_area [A,T], map50_area, map50_95_area, ar_area [A] (mean final recall over the classes with GT and
+        the thresholds); with curves also best_score, best_precision, best_recall, best_f1, best_tp, best_fp [A,K,T] (the best-F1
+        score cut: keep score >= best_score; NaN / 0 without entries or GT) and pr_precision, pr_score [A,K,T,101]."""
+        if self._ranged:
+            return self._result_ranges()
         dev = self.device
         st = torch.cuda.current_stream(dev).cuda_stream
         K, T, m = self.num_classes, len(self.iou_thresholds), self._used
@@ -315,6 +416,77 @@ class DetectionEvaluator:
                              ws_bytes, ap.data_ptr(), rec.data_ptr(), tpc.data_ptr(), fpc.data_ptr(), st), 'y3_eval_ap')
         return summarize(ap.cpu().numpy().astype(np.float64), rec.cpu().numpy().astype(np.float64), tpc.cpu().numpy().astype(np.int64),
                          fpc.cpu().numpy().astype(np.int64), self._npos.copy(), self.iou_thresholds)
+
+    def _result_ranges(self):
+        dev = self.device
+        st = torch.cuda.current_stream(dev).cuda_stream
+        K, T, A, m = self.num_classes, len(self.iou_thresholds), len(self.area_ranges), self._used
+        keys, order = torch.sort(self._keys[:m], stable=True)
+        tp = self._tp[:m][order].contiguous()
+        ign = self._ign[:m][order].contiguous()
+        keys = keys.contiguous()
+        npos = torch.from_numpy(self._npos_area.astype(np.int32)).to(dev)
+        ws_bytes = int(lib.y3_eval_ap_ranges_workspace_bytes(m, A, T))
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
+        f = {k: torch.empty(K, A, T, dtype=torch.float32, device=dev) for k in ('ap', 'recall', 'best_score')}
+        i = {k: torch.empty(K, A, T, dtype=torch.int32, device=dev) for k in ('tp', 'fp', 'ign', 'best_n', 'best_tp')}
+        pr = [torch.empty(K, A, T, 101, dtype=torch.float32, device=dev) for _ in range(2)] if self.curves else None
+        check(lib.y3_eval_ap_ranges(keys.data_ptr() if m else None, tp.data_ptr() if m else None, ign.data_ptr() if m else None, m, K, A, T,
+                                    npos.data_ptr(), ws.data_ptr(), ws_bytes, f['ap'].data_ptr(), f['recall'].data_ptr(), i['tp'].data_ptr(),
+                                    i['fp'].data_ptr(), i['ign'].data_ptr(), i['best_n'].data_ptr(), i['best_tp'].data_ptr(),
+                                    f['best_score'].data_ptr(), pr[0].data_ptr() if pr else None, pr[1].data_ptr() if pr else None, st),
+              'y3_eval_ap_ranges')
+        out = {k: v.cpu().numpy().transpose(1, 0, 2) for k, v in f.items()}                      # [K,A,T] -> [A,K,T]
+        out.update({k: v.cpu().numpy().astype(np.int64).transpose(1, 0, 2) for k, v in i.items()})
+        if pr:
+            out['pr_precision'], out['pr_score'] = (v.cpu().numpy().transpose(1, 0, 2, 3) for v in pr)
+        return summarize_ranges(out, self._npos_area.copy(), self.iou_thresholds, self.area_ranges, self.area_names, self.curves)
+
+
+def _ranges_list(state):
+    r = state.get('area_ranges')
+    return None if r is None else np.asarray(r, np.float32).tolist()
+
+
+def _same_ranges(s, s0):
+    a, b = s.get('area_ranges'), s0.get('area_ranges')
+    if (a is None) != (b is None) or bool(s.get('curves', False)) != bool(s0.get('curves', False)):
+        return False
+    return a is None or np.array_equal(np.asarray(a, np.float32), np.asarray(b, np.float32))
+
+
+def summarize_ranges(out, npos_area, iou_thresholds, area_ranges, area_names, curves):
+    """The result dict of a DetectionEvaluator with area ranges or curves from the [A,K,T] numbers of y3_eval_ap_ranges."""
+    thr = np.asarray(iou_thresholds, np.float32)
+    A = len(area_names)
+    a0 = area_names.index('all') if 'all' in area_names else 0
+    ap, rec = out['ap'].astype(np.float64), out['recall'].astype(np.float64)
+    res = summarize(ap[a0], rec[a0], out['tp'][a0], out['fp'][a0], npos_area[:, a0].copy(), thr)
+    res.update(area_ranges=np.asarray(area_ranges, np.float32).copy(), area_names=list(area_names), ap_area=ap, recall_area=rec,
+               tp_area=out['tp'], fp_area=out['fp'], ign_area=out['ign'], npos_area=npos_area)
+    hits = np.nonzero(thr == np.float32(0.5))[0]
+    coco = thr.size == 10 and np.array_equal(thr, np.asarray(COCO_IOU_THRESHOLDS, np.float32))
+    res['map_area'] = np.full((A, thr.size), np.nan)
+    res['map50_area'], res['map50_95_area'], res['ar_area'] = (np.full(A, np.nan) for _ in range(3))
+    for a in range(A):
+        valid = npos_area[:, a] > 0
+        if not valid.any():
+            continue
+        res['map_area'][a] = ap[a][valid].mean(axis=0)
+        if hits.size:
+            res['map50_area'][a] = res['map_area'][a, hits[0]]
+        if coco:
+            res['map50_95_area'][a] = ap[a][valid].mean()
+        res['ar_area'][a] = rec[a][valid].mean()
+    if curves:
+        n, t = out['best_n'], out['best_tp']
+        npos = npos_area.T[:, :, None].astype(np.float64)                                         # [A,K,1]
+        with np.errstate(invalid='ignore', divide='ignore'):
+            res.update(best_score=out['best_score'], best_tp=t, best_fp=n - t, best_precision=np.where(n > 0, t / np.maximum(n, 1), np.nan),
+                       best_recall=np.where(npos > 0, t / np.maximum(npos, 1), np.nan),
+                       best_f1=np.where(npos > 0, 2.0 * t / np.maximum(n + npos, 1), np.nan),
+                       pr_precision=out['pr_precision'], pr_score=out['pr_score'])
+    return res
 
 
 def summarize(ap, recall, tp, fp, npos, iou_thresholds):
@@ -402,26 +574,40 @@ def all_gather_evaluator(ev, group=None):
     T = st['iou_thresholds'].size
     thr[:T] = st['iou_thresholds']
     md = -1 if st['max_detections'] is None else st['max_detections']
-    meta = torch.tensor([st['keys'].numel(), st['num_images'], st['num_classes'], md, T] + thr.view(np.int32).tolist(), dtype=torch.int64, device=dev)
+    ranged = 'area_ranges' in st
+    A = st['area_ranges'].shape[0] if ranged else 0
+    rng = np.zeros((2, MAX_AREA_RANGES), np.float32)
+    if ranged:
+        rng[:, :A] = st['area_ranges'].T
+    meta = torch.tensor([st['keys'].numel(), st['num_images'], st['num_classes'], md, T] + thr.view(np.int32).tolist() +
+                        [A, int(st.get('curves', False))] + rng.reshape(-1).view(np.int32).tolist(), dtype=torch.int64, device=dev)
     metas = [m.cpu().numpy() for m in gather(meta)]
     for r, m in enumerate(metas):                    # every rank sees every meta row: all raise together, before shapes diverge
         if not np.array_equal(m[2:], metas[0][2:]):
-            raise ValueError('rank {} evaluates with classes / max_detections / thresholds {} against rank 0\'s {}'.format(r, m[2:5], metas[0][2:5]))
+            raise ValueError('rank {} evaluates with classes / max_detections / thresholds {} and area ranges / curves {} against rank 0\'s {} '
+                             'and {}'.format(r, m[2:5], m[37:39], metas[0][2:5], metas[0][37:39]))
     max_m = max(1, max(int(m[0]) for m in metas))
     max_n = max(1, max(int(m[1]) for m in metas))
 
     def padded(t, size):
         p = torch.zeros(size, dtype=t.dtype, device=dev)
-        p[:t.numel()] = t.to(dev)
+        p[:t.numel()] = t.to(dev).reshape(-1)
         return p
 
     keys = gather(padded(st['keys'], max_m))
-    tp = gather(padded(st['tp'], max_m))
+    W = max(A, 1)                                            # mask words per entry
+    tp = gather(padded(st['tp'], max_m * W))
     counts = gather(padded(st['image_counts'], max_n))
     npos = gather(torch.from_numpy(st['npos']).to(dev))
-    states = [{'keys': keys[r][:int(m[0])], 'tp': tp[r][:int(m[0])], 'image_counts': counts[r][:int(m[1])], 'npos': npos[r].cpu().numpy(),
+    states = [{'keys': keys[r][:int(m[0])], 'tp': tp[r][:int(m[0]) * W], 'image_counts': counts[r][:int(m[1])], 'npos': npos[r].cpu().numpy(),
                'num_images': int(m[1]), 'iou_thresholds': st['iou_thresholds'], 'num_classes': st['num_classes'],
                'max_detections': st['max_detections']} for r, m in enumerate(metas)]
+    if ranged:
+        ign = gather(padded(st['ign'], max_m * W))
+        npos_area = gather(torch.from_numpy(st['npos_area']).to(dev))
+        for r, (s, m) in enumerate(zip(states, metas)):
+            s.update(tp=s['tp'].reshape(-1, A), ign=ign[r][:int(m[0]) * A].reshape(-1, A), npos_area=npos_area[r].cpu().numpy(),
+                     area_ranges=st['area_ranges'], area_names=st['area_names'], curves=st['curves'])
     return DetectionEvaluator.merge(states, 'strided', device=ev.device)
 
 
