@@ -410,6 +410,31 @@ int y3_loss_fwd_bwd_truth(const y3_tensor* fm, const float* gt, const float* anc
                           const float* truth_boxes, const int* truth_counts, int truth_cap, float ignore_thresh,
                           float* loss4, float* ignored, const y3_tensor* dfm, void* workspace, y3_stream_t stream);
 
+/* ---- opt-in focal loss and class-label smoothing (not in the reference) ------------------------------
+ * The reference's objectness term is model.py:286-287 and its class term model.py:293-294, both plain
+ * tf.nn.sigmoid_cross_entropy_with_logits.  y3_loss_fwd_bwd_focal stands beside those lines only: decode, ignore mask
+ * (reference, Q7, or truth), box terms, partial sums and the finalize step are y3_loss_fwd_bwd_ex's / _truth's, so
+ * dfm[..., 0:4], loss4[0], loss4[1] and *ignored keep their bits.  For a label z in [0, 1], a logit x and p = sigmoid(x):
+ *   ce = max(x, 0) - x z + log1p(exp(-|x|))
+ *   m  = z sigmoid(-x) + (1 - z) sigmoid(x)            (1 - p_t of Lin et al. 2017, formed without that subtraction)
+ *   w  = alpha z + (1 - alpha)(1 - z) for alpha != 0, else 1
+ *   FL = w m^gamma ce,   dFL/dx = w [m^gamma (p - z) + gamma m^gamma r (1 - 2z) ce],   r = p (1 - p) / m, r = 0 where m = 0.
+ * r <= 1, and m^(gamma - 1) is never formed: both are finite for every gamma >= 0 and every logit, saturated ones included.
+ * Objectness: loss4[2] += sum(valid FL(gm, t4; gamma_obj, alpha_obj)) / local batch, with valid as in the entry points above.
+ * Class: z' = g (1 - label_smoothing) + label_smoothing / 2 (Keras BinaryCrossentropy(label_smoothing)), and
+ * loss4[3] += sum(gm FL(z', t; gamma_cls, alpha_cls)) / local batch.  dfm[..., 4:] holds the derivatives / (local batch *
+ * global_batch).  A term is neutral when its gamma and alpha are 0 (and, for class, label_smoothing is 0): it takes the
+ * plain expressions and keeps the bits of y3_loss_fwd_bwd_ex / _truth; with both terms neutral the launch is theirs.
+ * truth_boxes == NULL and truth_counts == NULL select the reference mask: truth_cap, ignore_thresh and ignored are not
+ * read and workspace is y3_loss_workspace_bytes().  Otherwise the arguments and the workspace of y3_loss_fwd_bwd_truth.
+ * gamma not finite or < 0, alpha neither 0 nor in (0, 1), label_smoothing outside [0, 1), or any argument against the rules
+ * of y3_loss_fwd_bwd_truth: Y3_EINVAL + message, nothing launched. */
+int y3_loss_fwd_bwd_focal(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors,
+                          int num_classes, int img_h, int img_w, float global_batch, int box_loss, float box_weight,
+                          const float* truth_boxes, const int* truth_counts, int truth_cap, float ignore_thresh,
+                          float* loss4, float* ignored, const y3_tensor* dfm, void* workspace, float gamma_obj,
+                          float alpha_obj, float gamma_cls, float alpha_cls, float label_smoothing, y3_stream_t stream);
+
 /* ---- tf.keras.optimizers.Adam.apply_gradients (model.py:451,500) ----------
  * m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= lr_t*m/(sqrt(v)+eps), with
  * lr_t read from DEVICE memory (*lr_t_dev) so the launch is graph-replayable. */

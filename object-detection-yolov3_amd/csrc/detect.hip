@@ -111,6 +111,10 @@ struct LossArgs {
     const int* truth_counts;   // [N] boxes found per image; may exceed truth_cap
     int truth_cap;
     float ignore_thresh;
+    // focal variant only (y3_loss_fwd_bwd_focal).  Behind the truth fields, for the same reason
+    float gamma_obj, alpha_obj;  // objectness term: focusing exponent >= 0, balancing factor (0 = none)
+    float gamma_cls, alpha_cls;  // class term
+    float label_smoothing;       // class labels g -> g (1 - eps) + eps / 2
 };
 
 __global__ void loss_present_kernel(const float* __restrict__ gt, long long ncell_anchor, int A, int D, int* present) {
@@ -121,6 +125,22 @@ __global__ void loss_present_kernel(const float* __restrict__ gt, long long ncel
 
 __device__ __forceinline__ float sig_ce(float z, float x) {  // labels z, logits x (App. C6)
     return fmaxf(x, 0.f) - x * z + log1pf(expf(-fabsf(x)));
+}
+
+// Focal form of sig_ce (Lin et al. 2017): returns w m^gamma ce and writes its derivative in x to *dx.
+//   m = z sigmoid(-x) + (1 - z) sigmoid(x) is 1 - p_t, formed without that subtraction: at a saturated logit sigmoid(-x) keeps the small
+//   side's digits where 1 - sigmoid(x) is 0.  w = alpha z + (1 - alpha)(1 - z), or 1 for alpha == 0.
+//   d/dx = w [m^gamma (p - z) + gamma m^gamma r (1 - 2z) ce], r = p (1 - p) / m <= 1 (m >= min(p, 1 - p) >= p (1 - p)), r = 0 where m = 0:
+//   m^(gamma - 1) is never formed, so both values are finite for every gamma >= 0 and every logit.  powf(0, 0) = 1.
+__device__ __forceinline__ float focal_ce(float z, float x, float gamma, float alpha, float* dx) {
+    const float ps = sigmoidf_(x), qs = sigmoidf_(-x);
+    const float ce = sig_ce(z, x);
+    const float m = z * qs + (1.f - z) * ps;
+    const float w = alpha != 0.f ? alpha * z + (1.f - alpha) * (1.f - z) : 1.f;
+    const float mg = powf(m, gamma);
+    const float r = m > 0.f ? (ps * qs) / m : 0.f;
+    *dx = w * (mg * (ps - z) + gamma * mg * r * (1.f - 2.f * z) * ce);
+    return w * mg * ce;
 }
 
 // The box term of the opt-in IoU losses (Y3_BOX_LOSS_GIOU / DIOU / CIOU) for one positive (cell, anchor): returns 1 - X and
@@ -192,7 +212,10 @@ __device__ __forceinline__ float iou_box_loss(float bx, float by, float bw, floa
 // ground-truth boxes of the prediction's own image: grid (blocks per image, N), the image's box list staged in LDS Y3_TRUTH_CHUNK boxes
 // at a time, a fifth partial sum (the ignored negatives).  Everything TRUTH adds is behind `if (TRUTH)`, a compile-time constant: the
 // TRUTH == false instantiations keep the instructions they had.
-template <int BOX, bool TRUTH>
+// FOCAL == true replaces sig_ce by focal_ce in the objectness and class terms, each with its own (gamma, alpha), the class
+// labels smoothed first.  A neutral term (gamma 0, alpha 0, and for class no smoothing) takes the plain expressions behind a uniform
+// branch: its loss part and gradient channels keep the plain kernel's bits.  Everything FOCAL adds is behind `if (FOCAL)`.
+template <int BOX, bool TRUTH, bool FOCAL>
 __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
     constexpr int NP = TRUTH ? 5 : 4;
     __shared__ float sm[NP][256];
@@ -279,12 +302,27 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs p) {
         const float valid = gm + (1.f - gm) * ignore;
 
         // objectness
-        l_obj += valid * sig_ce(gm, t[4]);
-        d[4] = valid * (sigmoidf_(t[4]) - gm) * p.gscale;
+        if (FOCAL && !(p.gamma_obj == 0.f && p.alpha_obj == 0.f)) {
+            float dx;
+            l_obj += valid * focal_ce(gm, t[4], p.gamma_obj, p.alpha_obj, &dx);
+            d[4] = valid * dx * p.gscale;
+        } else {
+            l_obj += valid * sig_ce(gm, t[4]);
+            d[4] = valid * (sigmoidf_(t[4]) - gm) * p.gscale;
+        }
         // class
-        for (int k = 0; k < p.K; ++k) {
-            l_cls += gm * sig_ce(g[5 + k], t[5 + k]);
-            d[5 + k] = gm * (sigmoidf_(t[5 + k]) - g[5 + k]) * p.gscale;
+        if (FOCAL && !(p.gamma_cls == 0.f && p.alpha_cls == 0.f && p.label_smoothing == 0.f)) {
+            for (int k = 0; k < p.K; ++k) {
+                const float z = g[5 + k] * (1.f - p.label_smoothing) + 0.5f * p.label_smoothing;
+                float dx;
+                l_cls += gm * focal_ce(z, t[5 + k], p.gamma_cls, p.alpha_cls, &dx);
+                d[5 + k] = gm * dx * p.gscale;
+            }
+        } else {
+            for (int k = 0; k < p.K; ++k) {
+                l_cls += gm * sig_ce(g[5 + k], t[5 + k]);
+                d[5 + k] = gm * (sigmoidf_(t[5 + k]) - g[5 + k]) * p.gscale;
+            }
         }
         // xy: squared error in logit space of the clipped in-cell position
         if (BOX == Y3_BOX_LOSS_MSE) {
@@ -410,21 +448,44 @@ struct LossTruth {
     float* ignored;
 };
 
-template <bool TRUTH>
-static void loss_kernel_launch(int box_loss, dim3 grid, hipStream_t st, const LossArgs& p) {
+// What y3_loss_fwd_bwd_focal adds to the arguments of y3_loss_fwd_bwd_truth
+struct LossFocal {
+    float gamma_obj, alpha_obj, gamma_cls, alpha_cls, label_smoothing;
+};
+
+template <bool TRUTH, bool FOCAL>
+static void loss_kernel_launch_kind(int box_loss, dim3 grid, hipStream_t st, const LossArgs& p) {
     if (box_loss == Y3_BOX_LOSS_MSE)
-        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_MSE, TRUTH>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_MSE, TRUTH, FOCAL>), grid, dim3(256), 0, st, p);
     else if (box_loss == Y3_BOX_LOSS_GIOU)
-        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_GIOU, TRUTH>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_GIOU, TRUTH, FOCAL>), grid, dim3(256), 0, st, p);
     else if (box_loss == Y3_BOX_LOSS_DIOU)
-        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_DIOU, TRUTH>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_DIOU, TRUTH, FOCAL>), grid, dim3(256), 0, st, p);
     else
-        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_CIOU, TRUTH>), grid, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((loss_kernel<Y3_BOX_LOSS_CIOU, TRUTH, FOCAL>), grid, dim3(256), 0, st, p);
+}
+
+template <bool TRUTH>
+static void loss_kernel_launch(int box_loss, bool focal, dim3 grid, hipStream_t st, const LossArgs& p) {
+    if (focal)
+        loss_kernel_launch_kind<TRUTH, true>(box_loss, grid, st, p);
+    else
+        loss_kernel_launch_kind<TRUTH, false>(box_loss, grid, st, p);
 }
 
 static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h, int img_w,
-                       float global_batch, int box_loss, float box_weight, const LossTruth* truth, float* loss4, const y3_tensor* dfm,
-                       void* workspace, y3_stream_t stream) {
+                       float global_batch, int box_loss, float box_weight, const LossTruth* truth, const LossFocal* focal, float* loss4,
+                       const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
+    bool use_focal = false;  // both terms neutral: the FOCAL == false kernel, the launch of y3_loss_fwd_bwd_ex / _truth
+    if (focal) {
+        const float go = focal->gamma_obj, ao = focal->alpha_obj, gc = focal->gamma_cls, ac = focal->alpha_cls, ls = focal->label_smoothing;
+        Y3_CHECK_ARG(go >= 0.f && go <= FLT_MAX && gc >= 0.f && gc <= FLT_MAX, "loss_fwd_bwd_focal: gamma must be finite and >= 0 (got %g, %g)",
+                     (double)go, (double)gc);
+        Y3_CHECK_ARG((ao == 0.f || (ao > 0.f && ao < 1.f)) && (ac == 0.f || (ac > 0.f && ac < 1.f)),
+                     "loss_fwd_bwd_focal: alpha must be 0 (no balancing factor) or in (0, 1) (got %g, %g)", (double)ao, (double)ac);
+        Y3_CHECK_ARG(ls >= 0.f && ls < 1.f, "loss_fwd_bwd_focal: label_smoothing must be in [0, 1) (got %g)", (double)ls);
+        use_focal = !(go == 0.f && ao == 0.f && gc == 0.f && ac == 0.f && ls == 0.f);
+    }
     if (truth) {
         Y3_CHECK_ARG(truth->thresh > 0.f && truth->thresh <= 1.f, "loss_fwd_bwd_truth: ignore_thresh must be finite and in (0, 1] (got %g)",
                      (double)truth->thresh);
@@ -460,6 +521,13 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
     p.inv_b = 1.f / (float)fm->n;
     p.gscale = 1.f / ((float)fm->n * global_batch);
     p.box_weight = box_weight;
+    if (use_focal) {
+        p.gamma_obj = focal->gamma_obj;
+        p.alpha_obj = focal->alpha_obj;
+        p.gamma_cls = focal->gamma_cls;
+        p.alpha_cls = focal->alpha_cls;
+        p.label_smoothing = focal->label_smoothing;
+    }
     if (truth) {
         // one image per workgroup row; the anchor-present pass is not needed
         Y3_CHECK_ARG(fm->n <= 65535, "loss_fwd_bwd_truth: batch %d (at most 65535 images per call)", fm->n);
@@ -471,7 +539,7 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
         p.truth_counts = truth->counts;
         p.truth_cap = truth->cap;
         p.ignore_thresh = truth->thresh;
-        loss_kernel_launch<true>(box_loss, dim3(bpi, p.N), st, p);
+        loss_kernel_launch<true>(box_loss, use_focal, dim3(bpi, p.N), st, p);
         Y3_CHECK_LAUNCH("loss (truth mask)");
         hipLaunchKernelGGL(loss_finalize_truth_kernel, dim3(1), dim3(256), 0, st, (const float*)p.partials, p.N, bpi, loss4, truth->ignored);
         Y3_CHECK_LAUNCH("loss_finalize (truth mask)");
@@ -490,7 +558,7 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
     Y3_CHECK_LAUNCH("loss_present");
     int blocks = (int)((total + 255) / 256);
     if (blocks > Y3_LOSS_BLOCKS) blocks = Y3_LOSS_BLOCKS;
-    loss_kernel_launch<false>(box_loss, dim3(blocks), st, p);
+    loss_kernel_launch<false>(box_loss, use_focal, dim3(blocks), st, p);
     Y3_CHECK_LAUNCH("loss");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)p.partials, blocks, loss4);
     Y3_CHECK_LAUNCH("loss_finalize");
@@ -499,15 +567,15 @@ static int loss_launch(const y3_tensor* fm, const float* gt, const float* anchor
 
 extern "C" int y3_loss_fwd_bwd(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
                                int img_w, float global_batch, float* loss4, const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
-    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, Y3_BOX_LOSS_MSE, 1.f, nullptr, loss4, dfm,
-                       workspace, stream);
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, Y3_BOX_LOSS_MSE, 1.f, nullptr, nullptr, loss4,
+                       dfm, workspace, stream);
 }
 
 extern "C" int y3_loss_fwd_bwd_ex(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes, int img_h,
                                   int img_w, float global_batch, int box_loss, float box_weight, float* loss4, const y3_tensor* dfm,
                                   void* workspace, y3_stream_t stream) {
-    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, nullptr, loss4, dfm,
-                       workspace, stream);
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, nullptr, nullptr, loss4,
+                       dfm, workspace, stream);
 }
 
 extern "C" int y3_loss_fwd_bwd_truth(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes,
@@ -515,8 +583,21 @@ extern "C" int y3_loss_fwd_bwd_truth(const y3_tensor* fm, const float* gt, const
                                      const int* truth_counts, int truth_cap, float ignore_thresh, float* loss4, float* ignored,
                                      const y3_tensor* dfm, void* workspace, y3_stream_t stream) {
     const LossTruth truth = {truth_boxes, truth_counts, truth_cap, ignore_thresh, ignored};
-    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, &truth, loss4, dfm,
-                       workspace, stream);
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight, &truth, nullptr, loss4,
+                       dfm, workspace, stream);
+}
+
+extern "C" int y3_loss_fwd_bwd_focal(const y3_tensor* fm, const float* gt, const float* anchors_host, int num_anchors, int num_classes,
+                                     int img_h, int img_w, float global_batch, int box_loss, float box_weight, const float* truth_boxes,
+                                     const int* truth_counts, int truth_cap, float ignore_thresh, float* loss4, float* ignored,
+                                     const y3_tensor* dfm, void* workspace, float gamma_obj, float alpha_obj, float gamma_cls,
+                                     float alpha_cls, float label_smoothing, y3_stream_t stream) {
+    const LossTruth truth = {truth_boxes, truth_counts, truth_cap, ignore_thresh, ignored};
+    const LossFocal focal = {gamma_obj, alpha_obj, gamma_cls, alpha_cls, label_smoothing};
+    // no lists at all: the reference mask (Q7) and its workspace layout; one list without the other is the truth variant's null-pointer error
+    const bool reference_mask = !truth_boxes && !truth_counts;
+    return loss_launch(fm, gt, anchors_host, num_anchors, num_classes, img_h, img_w, global_batch, box_loss, box_weight,
+                       reference_mask ? nullptr : &truth, &focal, loss4, dfm, workspace, stream);
 }
 
 // ---------------------------------------------------------------------------

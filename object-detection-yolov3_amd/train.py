@@ -32,6 +32,10 @@ Composes with the --multiscale_* flags; the test reader, the mAP pass, the check
 object out of the objectness loss when it overlaps a ground-truth box of its own image with IoU >= T, the rule of the paper, in
 place of the reference's mask; training and test loss use the same mask.  <scalars>/ignored.csv gets one row per
 optimiser step: the predictions left out in that batch and the longest per-image box list (a warning once if it exceeds N).
+--focal_gamma G (with --focal_alpha A, default 0 = no balancing factor, and --focal_terms obj / class / both, default both) gives the
+objectness and / or class term the focal form w m^G ce of Lin et al., and --label_smoothing E trains the class term against the
+labels g (1 - E) + E / 2; training and test loss use the same terms, the scalar CSVs keep their columns, and the
+weight files record the setting.  Test losses of runs with different settings are not comparable.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -93,6 +97,7 @@ TEST_MAP_NMS_METHODS = ('hard', 'diou', 'soft-linear', 'soft-gaussian')
 # yolo3.model.BOX_LOSSES, restated so that --help needs no device library
 BOX_LOSSES = ('mse', 'giou', 'diou', 'ciou')
 IGNORE_MASKS = ('reference', 'truth')
+FOCAL_TERMS = ('obj', 'class', 'both')
 
 
 def effective_test_map(test_map, model_selection):
@@ -176,7 +181,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, multiscale_min=None, multiscale_max=None,
                 multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25,
-                ignore_mask='reference', ignore_thresh=0.5, ignore_max_boxes=1024):
+                ignore_mask='reference', ignore_thresh=0.5, ignore_max_boxes=1024, focal_gamma=0.0, focal_alpha=0.0, focal_terms=None,
+                label_smoothing=0.0):
     test_map = effective_test_map(test_map, model_selection)
     mosaic_prob = check_mosaic_args(mosaic_prob, mosaic_min_visible)
     if mosaic_prob and augmentation_device != 'gpu':
@@ -186,8 +192,13 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         raise ValueError('multi-scale training needs augmentation_device gpu: the batches are resampled and labelled on the device')
     if train_sizes is not None and int(multiscale_period) < 1:
         raise ValueError('multiscale_period must be >= 1, got {!r}'.format(multiscale_period))
-    from yolo3.model import check_box_loss_args, check_grad_args, check_ignore_mask_args
+    from yolo3.model import check_box_loss_args, check_focal_args, check_grad_args, check_ignore_mask_args
     check_box_loss_args(box_loss, box_loss_weight)
+    check_focal_flags(focal_gamma, focal_alpha, focal_terms)
+    focal_terms = 'both' if focal_terms is None else focal_terms
+    check_focal_args(focal_gamma, focal_alpha, focal_terms, label_smoothing)
+    focal_on = bool(focal_gamma or focal_alpha or label_smoothing)
+    focal_kw = dict(focal_gamma=focal_gamma, focal_alpha=focal_alpha, focal_terms=focal_terms, label_smoothing=label_smoothing) if focal_on else {}
     check_ignore_mask_args(ignore_mask, ignore_thresh, ignore_max_boxes)
     mask_args = dict(ignore_mask=ignore_mask, ignore_thresh=ignore_thresh, max_truth_boxes=ignore_max_boxes) if ignore_mask != 'reference' else {}
     check_grad_args(accumulate_steps, grad_clip_norm)
@@ -267,7 +278,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         number_classes = train_reader.get_number_classes()
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
-                            grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args)
+                            grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args,
+                            **focal_kw)
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
@@ -282,6 +294,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             print('Effective batch size {} = batch_size {} x {} replicas x {} accumulated steps; gradient norm {}'.format(
                 batch_size * world * accumulate_steps, batch_size, world, accumulate_steps,
                 'clipped at {}'.format(grad_clip_norm) if grad_clip_norm is not None else 'not clipped'))
+
+        if focal_on:
+            print('Focal loss: gamma {:g}, alpha {:g} on the {} term{}; class-label smoothing {:g} (training and test loss){}'.format(
+                focal_gamma, focal_alpha, {'obj': 'objectness', 'class': 'class', 'both': 'objectness and class'}[focal_terms],
+                '' if focal_terms != 'both' else 's', label_smoothing,
+                '; the test loss that selects the model is not comparable with that of another setting' if model_selection == 'loss' else ''))
 
         log_ignored = ignore_mask == 'truth'
         warned_truth_cap = False
@@ -447,7 +465,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Converting checkpoint into Saved_Model')
         from yolo3 import model
         best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate,
-                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args)
+                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw)
         best.load_weights(training_checkpoint_filepath)
         os.makedirs(os.path.join(output_folder, 'saved_model'), exist_ok=True)
         best.save_weights(os.path.join(output_folder, 'saved_model', 'yolov3.npz'))
@@ -485,6 +503,43 @@ def _ignore_thresh_arg(text):
     if not (0.0 < t <= 1.0):
         raise argparse.ArgumentTypeError('a number in (0, 1], got {!r}'.format(text))
     return t
+
+
+def _focal_gamma_arg(text):
+    try:
+        g = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a finite number >= 0, got {!r}'.format(text))
+    if not (g >= 0.0 and g != float('inf')):
+        raise argparse.ArgumentTypeError('a finite number >= 0, got {!r}'.format(text))
+    return g
+
+
+def _focal_alpha_arg(text):
+    try:
+        a = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('0 or a number in (0, 1), got {!r}'.format(text))
+    if not (a == 0.0 or 0.0 < a < 1.0):
+        raise argparse.ArgumentTypeError('0 or a number in (0, 1), got {!r}'.format(text))
+    return a
+
+
+def _label_smoothing_arg(text):
+    try:
+        e = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a number in [0, 1), got {!r}'.format(text))
+    if not (0.0 <= e < 1.0):
+        raise argparse.ArgumentTypeError('a number in [0, 1), got {!r}'.format(text))
+    return e
+
+
+def check_focal_flags(focal_gamma, focal_alpha, focal_terms):
+    """--focal_alpha / --focal_terms say how the focal form is applied: without --focal_gamma > 0 there is none.  focal_terms None =
+    the flag was not given."""
+    if (focal_alpha or focal_terms is not None) and not focal_gamma > 0:
+        raise ValueError('--focal_alpha / --focal_terms need --focal_gamma > 0: without it no term has the focal form')
 
 
 def _ignore_max_boxes_arg(text):
@@ -537,6 +592,10 @@ class _Parser(argparse.ArgumentParser):
         # (yolo3.model.check_ignore_mask_args, which train_model calls, restated: parsing loads no device library)
         if a.ignore_mask == 'reference' and (a.ignore_thresh != 0.5 or a.ignore_max_boxes != 1024):
             self.error("--ignore_thresh / --ignore_max_boxes need --ignore_mask truth: the reference's mask has no such parameters")
+        try:
+            check_focal_flags(a.focal_gamma, a.focal_alpha, a.focal_terms)
+        except ValueError as e:
+            self.error(str(e))
         return a
 
 
@@ -605,6 +664,17 @@ def build_parser():
                         help='(addition) IoU threshold of --ignore_mask truth, in (0, 1] (default 0.5, the paper\'s; reference takes no other)')
     parser.add_argument('--ignore_max_boxes', dest='ignore_max_boxes', type=_ignore_max_boxes_arg, default=1024,
                         help='(addition) ground-truth boxes per image that --ignore_mask truth keeps (default 1024; reference takes no other)')
+    parser.add_argument('--focal_gamma', dest='focal_gamma', type=_focal_gamma_arg, default=0.0,
+                        help='(addition) 0 (default): off; G > 0: the objectness and / or class term (--focal_terms) becomes the focal loss '
+                             'w m^G ce, m = 1 - p_t (training and test loss).  With --model_selection loss: test losses of runs with different '
+                             'focal / label-smoothing settings are not comparable')
+    parser.add_argument('--focal_alpha', dest='focal_alpha', type=_focal_alpha_arg, default=0.0,
+                        help='(addition) balancing factor of --focal_gamma: 0 (default) = none, A in (0, 1) weighs a label z by A z + (1 - A)(1 - z)')
+    parser.add_argument('--focal_terms', dest='focal_terms', choices=FOCAL_TERMS, default=None,
+                        help='(addition) the terms --focal_gamma applies to: obj, class or both (default both)')
+    parser.add_argument('--label_smoothing', dest='label_smoothing', type=_label_smoothing_arg, default=0.0,
+                        help='(addition) 0 (default): off; E in (0, 1): the class term is trained against the labels g (1 - E) + E / 2 '
+                             '(as Keras BinaryCrossentropy(label_smoothing=E))')
     return parser
 
 
@@ -618,4 +688,4 @@ if __name__ == "__main__":
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
                 a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm, a.multiscale_min, a.multiscale_max,
                 a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible, a.ignore_mask, a.ignore_thresh,
-                a.ignore_max_boxes)
+                a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing)

@@ -102,6 +102,8 @@ SIGNATURES = {
     'y3_truth_boxes': (i32, [fp, i32, C.c_longlong, i32, fp, ip, i32, vp]),
     'y3_loss_truth_workspace_bytes': (sz, [i32]),
     'y3_loss_fwd_bwd_truth': (i32, [TP, fp, C.POINTER(C.c_float), i32, i32, i32, i32, f32, i32, f32, fp, ip, i32, f32, fp, fp, TP, vp, vp]),
+    'y3_loss_fwd_bwd_focal': (i32, [TP, fp, C.POINTER(C.c_float), i32, i32, i32, i32, f32, i32, f32, fp, ip, i32, f32, fp, fp, TP, vp, f32, f32, f32,
+                                    f32, f32, vp]),
     'y3_adam_step': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, vp]),
     'y3_adam_step_ema': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, fp, fp, sz, fp, vp]),
     'y3_grad_norm_workspace_bytes': (sz, [sz]),

@@ -16,6 +16,7 @@ import contextlib
 import functools
 import math
 import os
+import warnings
 
 import numpy as np
 import torch
@@ -81,6 +82,42 @@ def check_ignore_mask_args(ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE
     if ignore_mask == 'reference' and (t != DEFAULT_IGNORE_THRESH or cap != DEFAULT_MAX_TRUTH_BOXES):
         raise ValueError("ignore_thresh {!r} / max_truth_boxes {!r} need ignore_mask 'truth': the reference's mask has no such parameters"
                          .format(ignore_thresh, max_truth_boxes))
+
+
+FOCAL_TERMS = ('obj', 'class', 'both')
+
+
+def check_focal_args(focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0):
+    """Host-side validation of the focal form of the objectness / class loss and of class-label smoothing (the
+    library checks the numbers again): ValueError unless focal_gamma is a finite number >= 0, focal_alpha is 0 (no balancing
+    factor) or in (0, 1), focal_terms is one of obj, class, both, and label_smoothing is in [0, 1)."""
+    vals = []
+    for name, v in (('focal_gamma', focal_gamma), ('focal_alpha', focal_alpha), ('label_smoothing', label_smoothing)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError('{} must be a number, got {!r}'.format(name, v))
+        if isinstance(v, bool):
+            raise ValueError('{} must be a number, got {!r}'.format(name, v))
+        vals.append(f)
+    g, a, e = vals
+    if not (g >= 0.0 and math.isfinite(g)):
+        raise ValueError('focal_gamma must be finite and >= 0, got {!r}'.format(focal_gamma))
+    if not (a == 0.0 or 0.0 < a < 1.0):
+        raise ValueError('focal_alpha must be 0 (no balancing factor) or in (0, 1), got {!r}'.format(focal_alpha))
+    if focal_terms not in FOCAL_TERMS:
+        raise ValueError('focal_terms must be one of {}, got {!r}'.format(', '.join(FOCAL_TERMS), focal_terms))
+    if not 0.0 <= e < 1.0:
+        raise ValueError('label_smoothing must be in [0, 1), got {!r}'.format(label_smoothing))
+
+
+def focal_term_args(focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0):
+    """(gamma_obj, alpha_obj, gamma_cls, alpha_cls, label_smoothing) as y3_loss_fwd_bwd_focal takes them: the term that
+    focal_terms leaves out gets gamma = alpha = 0; label smoothing belongs to the class term whatever focal_terms says."""
+    g, a = float(focal_gamma), float(focal_alpha)
+    obj = (g, a) if focal_terms in ('obj', 'both') else (0.0, 0.0)
+    cls = (g, a) if focal_terms in ('class', 'both') else (0.0, 0.0)
+    return obj + cls + (float(label_smoothing),)
 
 
 def check_grad_args(accumulate_steps=1, grad_clip_norm=None):
@@ -533,10 +570,20 @@ class _Plan:
                                                     self.truth_counts.data_ptr(), cap))
             ws_floats = (int(lib.y3_loss_truth_workspace_bytes(N)) // 4 + 63) // 64 * 64
             self.loss_ws = torch.zeros(3 * ws_floats, dtype=torch.float32, device=dev)
+        focal = mdl.focal_args()                 # None: no focal setting, the call list of a model built without one
         for si, (f, g) in enumerate(zip(self.fms, self.gt)):
             f.grad = self._new(N, f.h, f.w, D, Dld, zero=True)
             ws = self._at(self.loss_ws, si * ws_floats)
-            if mdl.ignore_mask == 'truth':
+            if focal is not None:
+                # focal objectness / class terms and label smoothing over either mask: null lists select the reference's
+                truth = mdl.ignore_mask == 'truth'
+                self.loss_calls.append((lib.y3_loss_fwd_bwd_focal, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                                                                    BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
+                                                                    self.truth_boxes.data_ptr() if truth else None,
+                                                                    self.truth_counts.data_ptr() if truth else None,
+                                                                    cap if truth else 1, mdl.ignore_thresh, self.loss4.data_ptr(),
+                                                                    self.ignored.data_ptr() if truth else None, f.grad.v, ws) + focal))
+            elif mdl.ignore_mask == 'truth':
                 self.loss_calls.append((lib.y3_loss_fwd_bwd_truth, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
                                                                     BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
                                                                     self.truth_boxes.data_ptr(), self.truth_counts.data_ptr(), cap,
@@ -815,7 +862,8 @@ class YoloV3:
     def __init__(self, global_batch_size, img_size, number_classes, anchors=None, learning_rate=1e-4, device=None, seed=None,
                  use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
                  box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None,
-                 ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES):
+                 ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES,
+                 focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0):
         # input sizes train_step / test_step accept: None = img_size only; checked before the device is needed
         self.train_sizes = check_train_sizes(img_size, train_sizes)
         # gradient accumulation and global-norm clipping: 1 / None = off; checked before the device is needed
@@ -833,6 +881,13 @@ class YoloV3:
         self.ignore_mask = ignore_mask
         self.ignore_thresh = float(ignore_thresh)
         self.max_truth_boxes = int(max_truth_boxes)
+        # focal form of the objectness / class terms and class-label smoothing: all 0 = the reference's plain sigmoid
+        # cross-entropy and its launches; checked before the device is needed
+        check_focal_args(focal_gamma, focal_alpha, focal_terms, label_smoothing)
+        self.focal_gamma = float(focal_gamma)
+        self.focal_alpha = float(focal_alpha)
+        self.focal_terms = focal_terms
+        self.label_smoothing = float(label_smoothing)
         self._loss_plan = None                    # the plan whose loss ran last: what last_ignored / last_truth_max read
         # exponential moving average of the weights: None / 0 = off; checked before the device is needed
         if ema_decay is not None and ema_decay != 0 and not 0.0 < float(ema_decay) < 1.0:
@@ -1074,6 +1129,13 @@ class YoloV3:
             out += [d['W'], d['b']] + ([d['gamma'], d['beta']] if sp.bn else [])
         return out
 
+    def focal_args(self):
+        """The five trailing arguments of y3_loss_fwd_bwd_focal, or None when no focal setting is on (gamma, alpha and label
+        smoothing all 0): the plans then emit the launches they emitted before the setting existed."""
+        if self.focal_gamma == 0.0 and self.focal_alpha == 0.0 and self.label_smoothing == 0.0:
+            return None
+        return focal_term_args(self.focal_gamma, self.focal_alpha, self.focal_terms, self.label_smoothing)
+
     def save_weights(self, path, moving=None):
         """Own weight file (the reference's TF checkpoint / SavedModel formats need TF)."""
         flat = {}
@@ -1085,6 +1147,9 @@ class YoloV3:
         flat['meta_anchors'] = np.asarray(self.anchors, np.float32)
         flat['meta_global_batch_size'] = np.asarray(self.global_batch_size, np.int64)
         flat['meta_learning_rate'] = np.asarray(self.learning_rate, np.float64)
+        if self.focal_args() is not None:         # a file written without a focal setting keeps the entries it had
+            flat['meta_focal'] = np.asarray([self.focal_gamma, self.focal_alpha, self.label_smoothing], np.float64)
+            flat['meta_focal_terms'] = np.asarray(self.focal_terms)
         flat['opt_iterations'] = np.asarray(self.iterations, np.int64)
         flat['opt_m'] = self.adam_m.detach().cpu().numpy()
         flat['opt_v'] = self.adam_v.detach().cpu().numpy()
@@ -1092,6 +1157,11 @@ class YoloV3:
 
     def load_weights(self, path, load_optimizer=False):
         z = np.load(path, allow_pickle=False)
+        mine = dict(focal_gamma=self.focal_gamma, focal_alpha=self.focal_alpha, focal_terms=self.focal_terms,
+                    label_smoothing=self.label_smoothing) if self.focal_args() is not None else {}
+        if YoloV3._focal_meta(z) != mine:          # the weights load all the same; the losses of the two settings are not comparable
+            warnings.warn('load_weights: {} was written with focal setting {}, this model has {}'.format(path, YoloV3._focal_meta(z) or 'none',
+                                                                                                         mine or 'none'))
         layers = []
         for i, sp in enumerate(self.specs):
             d = {k: z['l%03d_%s' % (i, k)] for k in (['W', 'b', 'gamma', 'beta', 'mean', 'var'] if sp.bn else ['W', 'b'])}
@@ -1103,10 +1173,18 @@ class YoloV3:
             self.iterations = int(z['opt_iterations'])
 
     @staticmethod
+    def _focal_meta(z):
+        """The focal settings a weight file carries (save_weights), as constructor arguments; none for a file without them."""
+        if 'meta_focal' not in z:
+            return {}
+        g, a, e = (float(v) for v in z['meta_focal'])
+        return dict(focal_gamma=g, focal_alpha=a, focal_terms=str(z['meta_focal_terms']), label_smoothing=e)
+
+    @staticmethod
     def from_file(path, device=None):
         z = np.load(path, allow_pickle=False)
         y = YoloV3(int(z['meta_global_batch_size']), [int(v) for v in z['meta_img_size']], int(z['meta_number_classes']),
-                   [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device)
+                   [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device, **YoloV3._focal_meta(z))
         y.load_weights(path)
         return y
 
