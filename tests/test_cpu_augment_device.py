@@ -153,6 +153,29 @@ def test_augment_batch_rejects_bad_records_without_device():
         _hip.check(call(_valid_record(), dtype=-1), 'y3_augment_batch')
 
 
+def test_augment_batch_rejects_the_first_width_and_sigma_past_its_limits_without_device():
+    """One pixel past the widest row the LDS stage takes (float32, C = 3: 2560 pixels = 30720 bytes) and the first sigma of
+    radius 9 (int(4 * 2.125 + 0.5)): Y3_EINVAL and a message; the last accepted values are run by tests/test_gpu_augment_edges.py."""
+    from yolo3 import _hip
+    lib = _hip.lib
+    fake = 1 << 20
+
+    def call(rec, dtype, c, h_in, w_in, h_out, w_out):
+        rec = np.ascontiguousarray(rec)
+        return lib.y3_augment_batch(fake, dtype, 1, h_in, w_in, c, rec.ctypes.data, h_out, w_out, fake, fake, None)
+
+    rec = np.zeros(1, augment.AUG_RECORD)
+    rec[0] = (3, 2561, 3, 2561, 0, 0, 0, 0, 0, 0.5, 0, 0, 0)
+    assert call(rec, 2, 3, 3, 2561, 3, 300) == -1 and b'exceed the LDS row stage' in lib.y3_last_error()
+    rec[0] = (3, 5121, 3, 5121, 0, 0, 0, 0, 0, 0.5, 0, 0, 0)                # uint16, C = 3: 5120 pixels are the same 30720 bytes
+    assert call(rec, 1, 3, 3, 5121, 3, 300) == -1 and b'exceed the LDS row stage' in lib.y3_last_error()
+    rec = _valid_record()
+    rec[0]['blur_sigma'] = 2.125
+    assert call(rec, 0, 3, 32, 40, 32, 40) == -1 and b'blur sigma 2.125' in lib.y3_last_error()
+    rec[0]['blur_sigma'] = np.nextafter(np.float32(2.125), np.float32(3))
+    assert call(rec, 0, 3, 32, 40, 32, 40) == -1 and b'blur' in lib.y3_last_error()
+
+
 def test_reader_gpu_mode_hands_out_raw_pixels_and_records(tmp_path):
     """augmentation_device='gpu' workers: stored pixels (HWC, stored dtype), labels of the draw's boxes, one record."""
     import build_lmdb

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import scipy.ndimage
 
+from augment_edges import philox_normals as _philox_normals
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -138,26 +140,6 @@ def test_blur_matches_scipy_gaussian_filter(C):
     if C == 3:
         per_channel = scipy.ndimage.gaussian_filter(_host_crop(img, recs[5], crop), (1.99, 1.99, 0), mode='reflect')
         assert np.abs(out[5] - _chw(per_channel)).max() > 1.0
-
-
-def _philox_normals(seed, n):
-    """Host twin of the device stream (yolo3hip.h): Philox4x32-10, key = seed halves, counter (e, 0, 0, 0); Box-Muller."""
-    M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
-    c0 = np.arange(n, dtype=np.uint32)
-    c1 = np.zeros(n, np.uint32)
-    c2 = np.zeros(n, np.uint32)
-    c3 = np.zeros(n, np.uint32)
-    k0, k1 = seed & 0xffffffff, seed >> 32
-    for _ in range(10):
-        p0 = c0.astype(np.uint64) * M0
-        p1 = c2.astype(np.uint64) * M1
-        hi0, lo0 = (p0 >> np.uint64(32)).astype(np.uint32), p0.astype(np.uint32)
-        hi1, lo1 = (p1 >> np.uint64(32)).astype(np.uint32), p1.astype(np.uint32)
-        c0, c1, c2, c3 = hi1 ^ c1 ^ np.uint32(k0), lo1, hi0 ^ c3 ^ np.uint32(k1), lo0
-        k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
-    u1 = ((c0 >> 8).astype(np.float64) + 1) * 2.0**-24
-    u2 = (c1 >> 8).astype(np.float64) * 2.0**-24
-    return np.sqrt(-2 * np.log(u1)) * np.cos(2 * np.pi * u2)
 
 
 def test_noise_statistics_and_stream():
