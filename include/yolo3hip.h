@@ -261,6 +261,27 @@ int y3_upsample_sum2x_fwd(const y3_tensor* in, const y3_tensor* out, y3_stream_t
 /* din[n,i,j,ci] = sum_{a,b,co} dout[n,2i+a,2j+b,co] for every ci */
 int y3_upsample_sum2x_bwd(const y3_tensor* dout, const y3_tensor* din, y3_stream_t stream);
 
+/* ---- spatial pyramid pooling of YOLOv3-SPP (no call site in the reference: an opt-in variant) ----
+ * dst[n,i,j, b*C + c] = max of src[n,i',j',c] over the (2r+1)^2 window around (i,j) clipped to the image, r = 2, 4, 6 for the
+ * channel blocks b = 0, 1, 2: [pool5 | pool9 | pool13], stride 1, padding SAME, padded positions never win.  One launch reads src
+ * once and writes all three blocks.  src is N x H x W x C, dst N x H x W x 3C, both NHWC with any ld; C and both ld multiples of 4,
+ * pointers 16-byte aligned (bf16: 8-byte).  src and dst may be disjoint channel ranges of ONE allocation (the model: slice 0 and
+ * slice [C, 4C) of the concat buffer the next convolution reads).  Exact: max does not round; -0 / +0 may come out as either;
+ * +-inf are ordinary values; a NaN in a window gives NaN for that window.
+ * H * W <= Y3_SPP_MAX_PLANE (any H, W up to 64 x 64; every grid of the model is at most 19 x 19): the plane of a channel group is
+ * staged in LDS, a larger one is refused with Y3_EINVAL.  Planes of more than 2048 pixels raise the kernel's dynamic LDS limit
+ * (a host call on the current device) before the launch: keep those out of a stream capture. */
+#define Y3_SPP_MAX_PLANE 4096
+int y3_spp_fwd(const y3_tensor* src, const y3_tensor* dst, y3_stream_t stream);      /* fp32 */
+int y3_spp_fwd_bf16(const y3_tensor* src, const y3_tensor* dst, y3_stream_t stream); /* bf16 storage, as y3_upsample_sum2x_fwd_bf16 */
+/* dsrc[p] (+)= sum over the three pools k and the pixels q whose k x k window has its FIRST maximum in row-major order at p of
+ * ddst[q, block k]: the subgradient torch.nn.functional.max_pool2d(x, k, 1, k // 2) takes.  src is the forward input, ddst the
+ * gradient of dst (N x H x W x 3C), dsrc N x H x W x C, fp32, same layout rules and plane limit; ddst and dsrc may be disjoint
+ * channel ranges of one allocation.  accumulate != 0 adds to what dsrc holds (the identity branch's gradient), 0 overwrites.  A
+ * gather per input pixel in a fixed order, no atomics: two runs give the same bits.  NaN in src: some in-bounds pixel wins.
+ * (Two instantiations by plane size, 512 pixels and below or above: the same arithmetic in the same order.) */
+int y3_spp_bwd(const y3_tensor* src, const y3_tensor* ddst, const y3_tensor* dsrc, int accumulate, y3_stream_t stream);
+
 /* ---- bf16 inference path (BASELINE config 5: tiled inference with a bf16 conv path) ----------------
  * Tensors are NHWC with `ld` counted in ELEMENTS; `ptr` addresses bf16 (2-byte) elements unless noted.
  * Replaces the same Conv2D -> LeakyReLU -> BatchNorm(training=False) chain as y3_conv2d_fwd

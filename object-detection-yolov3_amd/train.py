@@ -36,6 +36,9 @@ optimiser step: the predictions left out in that batch and the longest per-image
 objectness and / or class term the focal form w m^G ce of Lin et al., and --label_smoothing E trains the class term against the
 labels g (1 - E) + E / 2; training and test loss use the same terms, the scalar CSVs keep their columns, and the
 weight files record the setting.  Test losses of runs with different settings are not comparable.
+--spp 1 trains the YOLOv3-SPP variant of the network: a 5 / 9 / 13 max-pool pyramid and one more 1x1 layer in the block of the
+coarsest scale.  Checkpoint, EMA export and model selection carry it; the weight files record it, and inference.py,
+inference_tiled.py and evaluate.py take it from there.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -182,7 +185,8 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, multiscale_min=None, multiscale_max=None,
                 multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25,
                 ignore_mask='reference', ignore_thresh=0.5, ignore_max_boxes=1024, focal_gamma=0.0, focal_alpha=0.0, focal_terms=None,
-                label_smoothing=0.0):
+                label_smoothing=0.0, spp=False):
+    spp_kw = dict(spp=True) if spp else {}
     test_map = effective_test_map(test_map, model_selection)
     mosaic_prob = check_mosaic_args(mosaic_prob, mosaic_min_visible)
     if mosaic_prob and augmentation_device != 'gpu':
@@ -279,7 +283,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
                             grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args,
-                            **focal_kw)
+                            **focal_kw, **spp_kw)
+        if spp:
+            print('Network: YOLOv3-SPP (5 / 9 / 13 max-pool pyramid in the block of the coarsest scale, {} conv layers)'.format(len(yolo.specs)))
         if strategy is not None:
             strategy.attach(yolo)
             strategy.broadcast_parameters(yolo.params, yolo.moving)
@@ -465,7 +471,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Converting checkpoint into Saved_Model')
         from yolo3 import model
         best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate,
-                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw)
+                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw, **spp_kw)
         best.load_weights(training_checkpoint_filepath)
         os.makedirs(os.path.join(output_folder, 'saved_model'), exist_ok=True)
         best.save_weights(os.path.join(output_folder, 'saved_model', 'yolov3.npz'))
@@ -675,6 +681,9 @@ def build_parser():
     parser.add_argument('--label_smoothing', dest='label_smoothing', type=_label_smoothing_arg, default=0.0,
                         help='(addition) 0 (default): off; E in (0, 1): the class term is trained against the labels g (1 - E) + E / 2 '
                              '(as Keras BinaryCrossentropy(label_smoothing=E))')
+    parser.add_argument('--spp', dest='spp', type=int, choices=(0, 1), default=0,
+                        help='(addition) 0 (default): the reference\'s network; 1: YOLOv3-SPP, a 5 / 9 / 13 max-pool pyramid and one more 1x1 '
+                             'layer in the block of the coarsest scale (the weight files record it)')
     return parser
 
 
@@ -688,4 +697,4 @@ if __name__ == "__main__":
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
                 a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm, a.multiscale_min, a.multiscale_max,
                 a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible, a.ignore_mask, a.ignore_thresh,
-                a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing)
+                a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing, bool(a.spp))

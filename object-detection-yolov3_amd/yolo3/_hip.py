@@ -80,6 +80,9 @@ SIGNATURES = {
     'y3_bn_bwd_finalize_tiles': (i32, [fp, i32, i32, i32, fp, fp, fp, f32, fp, fp, fp, fp, vp]),
     'y3_upsample_sum2x_fwd': (i32, [TP, TP, vp]),
     'y3_upsample_sum2x_bwd': (i32, [TP, TP, vp]),
+    'y3_spp_fwd': (i32, [TP, TP, vp]),
+    'y3_spp_fwd_bf16': (i32, [TP, TP, vp]),
+    'y3_spp_bwd': (i32, [TP, TP, TP, i32, vp]),
     'y3_copy': (i32, [TP, TP, vp]),
     'y3_conv2d_fwd_bf16': (i32, [TP, vp, fp, i32, i32, TP, i32, u32, f32, fp, fp, TP, vp]),
     'y3_conv2d_fwd_bf16_ws': (i32, [TP, vp, fp, i32, i32, TP, i32, u32, f32, fp, fp, TP, vp, sz, vp]),

@@ -175,9 +175,11 @@ class LayerSpec:
     __slots__ = ('cin', 'cin_pad', 'cout', 'k', 's', 'bn', 'w_off', 'b_off', 'g_off', 'be_off', 'end_off', 'bn_idx', 'ch_off', 'mv_off')
 
 
-def build_layer_specs(in_channels, num_anchors, num_classes):
+def build_layer_specs(in_channels, num_anchors, num_classes, spp=False):
     """Conv layers in Keras creation order (model.py:356-421); see the walk in
-    ``_Plan._build`` which consumes them in the same order."""
+    ``_Plan._build`` which consumes them in the same order.  spp: the YOLOv3-SPP variant, one more 1x1 layer
+    (4 * 512 -> 512) behind the third layer of the coarsest scale's block; everything else, and with spp off every offset, is
+    the reference's network."""
     L = []
 
     def conv(cin, cout, k, s=1, bn=True):
@@ -207,12 +209,14 @@ def build_layer_specs(in_channels, num_anchors, num_classes):
     c = feature_block(c, YoloV3.BLOCK_COUNT // 2)
     D = num_anchors * (5 + num_classes)
 
-    def yolo_block(cin, fc):
+    def yolo_block(cin, fc, spp=False):
         for i in range(3):
             conv(cin if i == 0 else fc, fc // 2, 1)
+            if spp and i == 1:
+                conv(4 * (fc // 2), fc // 2, 1)      # reads concat [x, pool5, pool9, pool13]
             conv(fc // 2, fc, 3)
 
-    yolo_block(FC, FC)
+    yolo_block(FC, FC, spp)
     conv(FC, D, 1, 1, bn=False)
     conv(FC // 2, FC // 2, 1)
     yolo_block(FC, FC // 2)
@@ -247,6 +251,16 @@ def build_layer_specs(in_channels, num_anchors, num_classes):
             sp.ch_off = sp.mv_off = -1
         sp.end_off = off
     return L, off, ch, mv
+
+
+def spp_transfer_map(specs):
+    """For the spec list of an SPP model: per layer the index of the plain network's layer with the same role, None for the
+    layer only the SPP network has (the 1x1 layer whose input is 4x the width of the 1x1 conv_layer before it)."""
+    fresh = [i for i in range(1, len(specs))
+             if specs[i].k == 1 and specs[i - 1].k == 1 and specs[i - 1].bn and specs[i].cin == 4 * specs[i - 1].cout]
+    if len(fresh) != 1:
+        raise ValueError('spp_transfer_map: not the spec list of an SPP model')
+    return [None if i == fresh[0] else i - (i > fresh[0]) for i in range(len(specs))]
 
 
 class _T:
@@ -487,8 +501,22 @@ class _Plan:
                 layer = conv_layer(layer, out=out_last if r == reps - 1 else None, resid=inp)
             return layer
 
-        def yolo_block(inp):
-            for _ in range(5):
+        def spp_block(inp):
+            """YOLOv3-SPP: the block's third layer writes channel slice 0 of a 4x wide buffer, one launch fills the
+            other three slices with its 5 / 9 / 13 max pools, and the 1x1 layer that follows reads the whole buffer."""
+            inp = conv_layer(conv_layer(inp))
+            c = specs[li[0]].cout
+            cat = self._new(N, inp.h, inp.w, 4 * c, dtype=act)      # concat([x, pool5(x), pool9(x), pool13(x)])
+            x = conv_layer(inp, out=cat.slice(0, c))
+            pools = cat.slice(c, 3 * c)
+            self._emit(self.fwd, lib.y3_spp_fwd_bf16 if bf else lib.y3_spp_fwd, x.v, pools.v)
+            self.ops.append(('spp', x, cat, pools))
+            return conv_layer(cat)
+
+        def yolo_block(inp, spp=False):
+            if spp:
+                inp = spp_block(inp)
+            for _ in range(2 if spp else 5):
                 inp = conv_layer(inp)
             return inp, conv_layer(inp)
 
@@ -529,7 +557,7 @@ class _Plan:
         x = conv_layer(x)
         route3 = feature_block(x, YoloV3.BLOCK_COUNT // 2)
 
-        route, x = yolo_block(route3)
+        route, x = yolo_block(route3, mdl.spp)
         fm1 = head(x, 0)
         x = conv_layer(route)
         upsample_into(x, cat2_up)
@@ -661,7 +689,7 @@ class _Plan:
                 reads = [op[2]] + ([op[5]] if op[5] is not None else [])
             elif op[0] == 'head':
                 reads = [op[2]]
-            elif op[0] == 'upsample':
+            elif op[0] in ('upsample', 'spp'):
                 reads = [op[1]]
             for t in reads:
                 first_consumer.setdefault(id(t), op)
@@ -714,6 +742,12 @@ class _Plan:
                 ds = self._grad_of(src)
                 self._emit(self.bwd, lib.y3_upsample_sum2x_bwd, dst.grad.v, ds.v)
                 src.mark_written()
+            elif kind == 'spp':
+                # the data gradient of the layer behind the pools has written the whole concat gradient, slice 0 (the identity
+                # branch) included: the pools' share is added to it, on the main stream, before the producer's BatchNorm backward
+                _, src, cat, pools = op
+                assert cat.gw and src.gw
+                self._emit(self.bwd, lib.y3_spp_bwd, src.v, pools.grad.v, src.grad.v, 1)
             else:
                 _, i, src, a, y, resid, x3 = op
                 smean, srstd, coef = x3.bn
@@ -863,7 +897,11 @@ class YoloV3:
                  use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
                  box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None,
                  ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES,
-                 focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0):
+                 focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0, spp=False):
+        # the YOLOv3-SPP variant of the network: False = the reference's Darknet-53 with three plain heads
+        if not (isinstance(spp, (bool, np.bool_)) or (isinstance(spp, (int, np.integer)) and spp in (0, 1))):
+            raise ValueError('spp must be False or True, got {!r}'.format(spp))
+        self.spp = bool(spp)
         # input sizes train_step / test_step accept: None = img_size only; checked before the device is needed
         self.train_sizes = check_train_sizes(img_size, train_sizes)
         # gradient accumulation and global-norm clipping: 1 / None = off; checked before the device is needed
@@ -916,7 +954,7 @@ class YoloV3:
         self.number_output_boxes = self.number_anchors * (self.box_count_fm1 + self.box_count_fm2 + self.box_count_fm3)
         self.output_shape = [self.number_output_boxes, 5 + self.number_classes]
 
-        self.specs, self.arena_floats, chan_floats, self.moving_stride = build_layer_specs(C, self.number_anchors, self.number_classes)
+        self.specs, self.arena_floats, chan_floats, self.moving_stride = build_layer_specs(C, self.number_anchors, self.number_classes, self.spp)
         dev = self.device
         z = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
         self.params = z(self.arena_floats)        # trainable arena: [W | b | gamma | beta] per layer
@@ -1150,21 +1188,43 @@ class YoloV3:
         if self.focal_args() is not None:         # a file written without a focal setting keeps the entries it had
             flat['meta_focal'] = np.asarray([self.focal_gamma, self.focal_alpha, self.label_smoothing], np.float64)
             flat['meta_focal_terms'] = np.asarray(self.focal_terms)
+        if self.spp:                              # likewise: a file of the reference's network has no such entry
+            flat['meta_spp'] = np.asarray(1, np.int64)
         flat['opt_iterations'] = np.asarray(self.iterations, np.int64)
         flat['opt_m'] = self.adam_m.detach().cpu().numpy()
         flat['opt_v'] = self.adam_v.detach().cpu().numpy()
         np.savez(path, **flat)
 
-    def load_weights(self, path, load_optimizer=False):
+    def load_weights(self, path, load_optimizer=False, transfer=False):
+        """transfer=True: a file of the plain network into an SPP model -- every layer by role, the 4 * 512 -> 512 layer behind
+        the pools keeps its initialisation, no optimiser state (spp_transfer_map)."""
         z = np.load(path, allow_pickle=False)
+        theirs = YoloV3._spp_meta(z)
+        if transfer:
+            if load_optimizer:
+                raise ValueError('load_weights: transfer=True loads no optimiser state')
+            if theirs or not self.spp:
+                raise ValueError('load_weights: transfer=True loads a file written with spp=False into a model with spp=True; {} has spp={}, '
+                                 'this model has spp={}'.format(path, theirs, self.spp))
+            mapping = spp_transfer_map(self.specs)
+        elif theirs != self.spp:
+            raise ValueError('load_weights: {} was written with spp={}, this model has spp={} (the two networks differ by one layer; '
+                             'transfer=True loads a plain file into an SPP model)'.format(path, theirs, self.spp))
+        else:
+            mapping = list(range(len(self.specs)))
         mine = dict(focal_gamma=self.focal_gamma, focal_alpha=self.focal_alpha, focal_terms=self.focal_terms,
                     label_smoothing=self.label_smoothing) if self.focal_args() is not None else {}
         if YoloV3._focal_meta(z) != mine:          # the weights load all the same; the losses of the two settings are not comparable
             warnings.warn('load_weights: {} was written with focal setting {}, this model has {}'.format(path, YoloV3._focal_meta(z) or 'none',
                                                                                                          mine or 'none'))
         layers = []
-        for i, sp in enumerate(self.specs):
-            d = {k: z['l%03d_%s' % (i, k)] for k in (['W', 'b', 'gamma', 'beta', 'mean', 'var'] if sp.bn else ['W', 'b'])}
+        own = self.get_weights() if transfer else None
+        for (i, sp), j in zip(enumerate(self.specs), mapping):
+            if j is None:
+                print('load_weights: layer %d (1x1 %d -> %d behind the pools) is not in %s and keeps its initialisation' % (i, sp.cin, sp.cout, path))
+                layers.append(own[i])
+                continue
+            d = {k: z['l%03d_%s' % (j, k)] for k in (['W', 'b', 'gamma', 'beta', 'mean', 'var'] if sp.bn else ['W', 'b'])}
             layers.append(d)
         self.set_weights(layers)
         if load_optimizer and 'opt_m' in z:
@@ -1181,10 +1241,15 @@ class YoloV3:
         return dict(focal_gamma=g, focal_alpha=a, focal_terms=str(z['meta_focal_terms']), label_smoothing=e)
 
     @staticmethod
+    def _spp_meta(z):
+        """Whether a weight file holds the SPP network (save_weights); a file without the entry holds the plain one."""
+        return bool(int(z['meta_spp'])) if 'meta_spp' in z else False
+
+    @staticmethod
     def from_file(path, device=None):
         z = np.load(path, allow_pickle=False)
         y = YoloV3(int(z['meta_global_batch_size']), [int(v) for v in z['meta_img_size']], int(z['meta_number_classes']),
-                   [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device, **YoloV3._focal_meta(z))
+                   [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device, spp=YoloV3._spp_meta(z), **YoloV3._focal_meta(z))
         y.load_weights(path)
         return y
 
