@@ -510,6 +510,57 @@ int y3_adam_step_ema_scaled(float* param, const float* grad, float* m, float* v,
                             float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
                             const float* omd_dev, const float* scale_dev, y3_stream_t stream);
 
+/* ---- SGD with momentum and AdamW, with weight decay on some segments of the
+ * arena (torch.optim.SGD(momentum, nesterov, weight_decay) and
+ * AdamW as Keras and PyTorch apply it; the reference trains with plain Adam,
+ * model.py:451, and declares a WEIGHT_DECAY it never applies).  One launch
+ * over one flat arena, described by a HOST struct.  Each line one fp32
+ * expression as written; D = element i lies in a decay range; g' = g, or
+ * g * *scale_dev with scale_dev given (as y3_adam_step_scaled):
+ *   Y3_OPT_SGD / Y3_OPT_SGD_NESTEROV   lr = hyper_dev[0]
+ *     if D: g' = g' + weight_decay * p          (coupled L2)
+ *     m = momentum * m + g'
+ *     p = p - lr * m                            (p - lr * (g' + momentum * m) with Nesterov)
+ *   Y3_OPT_ADAMW                       lr_t = hyper_dev[0], lw = hyper_dev[1] (lr * weight decay)
+ *     if D: p = p - lw * p                      (decoupled, before the step)
+ *     then y3_adam_step's update; with n_ranges == 0 its bits
+ * With the EMA pointers given, y3_adam_step_ema's average of param and moving
+ * follows in the same pass.  hyper_dev, omd_dev, scale_dev are DEVICE memory,
+ * so a replayed graph picks up each step's values.  decay_ranges_host: HOST
+ * array of n_ranges pairs [begin, end) in floats, copied into the kernel
+ * arguments: sorted, disjoint (touching allowed), begin < end <= count,
+ * begin % 4 == 0, end % 4 == 0 or end == count.  No per-element mask: 5 fp32
+ * streams per element for SGD, 7 for AdamW, 2 more with the EMA.
+ * Y3_EINVAL + message, nothing launched: null or 16-byte-misaligned arenas,
+ * unknown kind, v null with Y3_OPT_ADAMW, momentum outside [0, 1),
+ * weight_decay < 0, n_ranges outside 0..Y3_OPT_MAX_RANGES, a broken range
+ * rule, a partial set of EMA pointers, count of 2^34 floats or more.
+ * count == 0: Y3_OK, nothing launched.  Counts need not be multiples of 4. */
+#define Y3_OPT_SGD 0
+#define Y3_OPT_SGD_NESTEROV 1
+#define Y3_OPT_ADAMW 2
+#define Y3_OPT_MAX_RANGES 128
+typedef struct y3_optim_desc {
+    int kind;                            /* Y3_OPT_* */
+    float* param;
+    const float* grad;
+    float* m;                            /* momentum buffer (SGD) / first moment (ADAMW) */
+    float* v;                            /* second moment: ADAMW only, NULL otherwise */
+    size_t count;
+    const float* hyper_dev;              /* DEVICE float[2]: {lr (SGD) or lr_t (ADAMW), lr * weight decay (ADAMW; unused by SGD)} */
+    float momentum, weight_decay;        /* SGD */
+    float beta1, beta2, eps;             /* ADAMW */
+    const long long* decay_ranges_host;  /* HOST: n_ranges pairs [begin, end) in floats */
+    int n_ranges;                        /* 0 .. Y3_OPT_MAX_RANGES */
+    float* ema_param;                    /* the five EMA members: all NULL / 0 = no EMA */
+    const float* moving;
+    float* ema_moving;
+    size_t moving_count;
+    const float* omd_dev;
+    const float* scale_dev;              /* NULL = unscaled */
+} y3_optim_desc;
+int y3_optim_step(const y3_optim_desc* d, y3_stream_t stream);
+
 /* ---- class-wise NMS (bbox_utils.py:200-281; inference.py:72-79) ------------
  * rows [N,Nb,5+K].  A row is a candidate of class c if w > min_box and
  * h > min_box (strict) and sqrt(cls_c*obj) >= score_thr; greedy suppression

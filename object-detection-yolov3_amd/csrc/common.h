@@ -15,6 +15,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
         }                                                                  \
     } while (0)
 
+// grid of a streaming kernel with a grid-stride loop (pointwise.hip, optim.hip): one thread per item, capped at ~8 blocks/CU
+static inline int stream_blocks(long long items, int threads) {
+    long long b = (items + threads - 1) / threads;
+    if (b > 2048) b = 2048;
+    if (b < 1) b = 1;
+    return (int)b;
+}
+
 // Blocks are dealt round-robin over the 8 XCDs (each with a private L2): remap so
 // that every XCD works on one contiguous run of tile ids (bijective for any grid).
 __device__ __forceinline__ int y3_xcd_remap(int orig, int nwg) {

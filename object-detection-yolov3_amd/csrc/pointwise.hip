@@ -3,13 +3,7 @@
 // layout changes, Adam, z-score.  All are streaming kernels: 16-byte accesses
 // along the contiguous channel axis, grid-stride loops capped at ~8 blocks/CU.
 #include "common.h"
-
-static inline int stream_blocks(long long items, int threads) {
-    long long b = (items + threads - 1) / threads;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+#include "adam_update.h"
 
 static int check_view(const y3_tensor* t, const char* name) {
     Y3_CHECK_ARG(t && t->ptr, "%s: null tensor", name);
@@ -769,11 +763,8 @@ extern "C" int y3_colsum(const y3_tensor* src, float* out, y3_stream_t stream) {
 // ---------------------------------------------------------------------------
 // Keras Adam (App. C5), fused over the whole parameter arena
 // ---------------------------------------------------------------------------
-// one element of one float4 lane f: the update of adam_kernel, adam_ema_kernel and their scaled forms (one text, so all give the same bits)
-#define Y3_ADAM1(f)                              \
-    mm.f += (gg.f - mm.f) * o1;                  \
-    vv.f += (gg.f * gg.f - vv.f) * o2;           \
-    pp.f -= (mm.f * lr_t) / (sqrtf(vv.f) + eps);
+// Y3_ADAM1(f), one element of one float4 lane f: the update of adam_kernel, adam_ema_kernel and their scaled forms, and of the AdamW
+// kernels of optim.hip (one text in adam_update.h, so all give the same bits)
 // The kernel bodies are macro text shared by the plain and the scaled kernel of each pair (gradient accumulation and global-norm
 // clipping): S_LOAD / S4 / S1 are empty in adam_kernel and adam_ema_kernel, which therefore compile to the instructions
 // they always had, and in the scaled kernels read s = *scale_dev and multiply the gradient operand by it, one fp32 multiply in

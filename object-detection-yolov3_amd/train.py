@@ -39,6 +39,11 @@ weight files record the setting.  Test losses of runs with different settings ar
 --spp 1 trains the YOLOv3-SPP variant of the network: a 5 / 9 / 13 max-pool pyramid and one more 1x1 layer in the block of the
 coarsest scale.  Checkpoint, EMA export and model selection carry it; the weight files record it, and inference.py,
 inference_tiled.py and evaluate.py take it from there.
+--optimizer sgd (with --momentum M, default 0.9, and --nesterov 1) or adamw trains with SGD-momentum or AdamW in place of the
+reference's Adam, and --weight_decay WD decays the convolution kernels only: coupled L2 for sgd, decoupled for adamw (DESIGN
+§3.19).  --lr_schedule constant / cosine / step (with --lr_warmup_steps W, --lr_warmup_start_factor S, --lr_total_steps T,
+--lr_final_factor F, --lr_milestones A B ..., --lr_gamma G) replaces the epoch-0 rule by learning_rate x a factor of the optimiser
+step: epoch 0 then has the full size, and <scalars>/lr.csv gets one row per optimiser step.  The weight files record the optimiser.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -101,6 +106,8 @@ TEST_MAP_NMS_METHODS = ('hard', 'diou', 'soft-linear', 'soft-gaussian')
 BOX_LOSSES = ('mse', 'giou', 'diou', 'ciou')
 IGNORE_MASKS = ('reference', 'truth')
 FOCAL_TERMS = ('obj', 'class', 'both')
+OPTIMIZERS = ('adam', 'adamw', 'sgd')
+LR_SCHEDULES = ('reference', 'constant', 'cosine', 'step')      # 'reference' = the epoch-0 rule of the reference's loop
 
 
 def effective_test_map(test_map, model_selection):
@@ -179,14 +186,34 @@ def check_mosaic_args(mosaic_prob, mosaic_min_visible):
     return p
 
 
+def build_lr_schedule(lr_schedule='reference', warmup_steps=0, warmup_start_factor=0.0, total_steps=None, final_factor=0.01, milestones=(),
+                      gamma=0.1):
+    """--lr_schedule and its flags -> a yolo3.schedule.LrSchedule, or None for 'reference' (the loop's own epoch-0 rule, which
+    takes none of the other flags).  ValueError on a bad combination."""
+    if lr_schedule not in LR_SCHEDULES:
+        raise ValueError('lr_schedule must be one of {}, got {!r}'.format(', '.join(LR_SCHEDULES), lr_schedule))
+    if lr_schedule == 'reference':
+        if warmup_steps or warmup_start_factor or total_steps is not None or final_factor != 0.01 or tuple(milestones) or gamma != 0.1:
+            raise ValueError('--lr_warmup_* / --lr_total_steps / --lr_final_factor / --lr_milestones / --lr_gamma need --lr_schedule '
+                             "constant, cosine or step: 'reference' is the reference's rule, learning_rate / 10 during epoch 0")
+        return None
+    from yolo3.schedule import LrSchedule
+    return LrSchedule(lr_schedule, warmup_steps, warmup_start_factor, total_steps, final_factor, tuple(milestones), gamma)
+
+
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
                 box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, multiscale_min=None, multiscale_max=None,
                 multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25,
                 ignore_mask='reference', ignore_thresh=0.5, ignore_max_boxes=1024, focal_gamma=0.0, focal_alpha=0.0, focal_terms=None,
-                label_smoothing=0.0, spp=False):
+                label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9, nesterov=False, weight_decay=0.0, lr_schedule='reference',
+                lr_warmup_steps=0, lr_warmup_start_factor=0.0, lr_total_steps=None, lr_final_factor=0.01, lr_milestones=(), lr_gamma=0.1):
     spp_kw = dict(spp=True) if spp else {}
+    schedule = build_lr_schedule(lr_schedule, lr_warmup_steps, lr_warmup_start_factor, lr_total_steps, lr_final_factor, lr_milestones, lr_gamma)
+    from yolo3.model import check_optimizer_args
+    check_optimizer_args(optimizer, momentum, nesterov, weight_decay, schedule)
+    optim_kw = dict(optimizer=optimizer, momentum=momentum, nesterov=bool(nesterov), weight_decay=weight_decay) if optimizer != 'adam' else {}
     test_map = effective_test_map(test_map, model_selection)
     mosaic_prob = check_mosaic_args(mosaic_prob, mosaic_min_visible)
     if mosaic_prob and augmentation_device != 'gpu':
@@ -283,7 +310,11 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
                             grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args,
-                            **focal_kw, **spp_kw)
+                            **focal_kw, **spp_kw, **optim_kw, **(dict(lr_schedule=schedule) if schedule is not None else {}))
+        if optimizer != 'adam' or schedule is not None:
+            print('Optimizer: {}{}, weight decay {:g} on the convolution kernels; learning-rate schedule: {}'.format(
+                optimizer, ' (momentum {:g}{})'.format(momentum, ', Nesterov' if nesterov else '') if optimizer == 'sgd' else '', weight_decay,
+                lr_schedule))
         if spp:
             print('Network: YOLOv3-SPP (5 / 9 / 13 max-pool pyramid in the block of the coarsest scale, {} conv layers)'.format(len(yolo.specs)))
         if strategy is not None:
@@ -343,6 +374,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             if log_ignored:
                 with open(os.path.join(log_dir, 'ignored.csv'), 'w') as fh:
                     fh.write('step,ignored,truth_max\n')
+            if schedule is not None:
+                with open(os.path.join(log_dir, 'lr.csv'), 'w') as fh:
+                    fh.write('step,lr\n')
 
         def log_scalars(split, step, metrics):
             if rank == 0:
@@ -353,7 +387,10 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Running Network')
         while True:  # loop until early stopping
             print('---- Epoch: {} ----'.format(epoch))
-            if epoch == 0:
+            if schedule is not None:
+                # the schedule owns the rate: the full epoch size from epoch 0 on, no per-epoch set_learning_rate
+                cur_train_epoch_size = train_epoch_size
+            elif epoch == 0:
                 cur_train_epoch_size = min(1000, train_epoch_size)
                 print('Performing Adam Optimizer learning rate warmup for {} steps'.format(cur_train_epoch_size))
                 yolo.set_learning_rate(learning_rate / 10)
@@ -377,6 +414,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                     with open(os.path.join(log_dir, 'grad_norm.csv'), 'a') as fh:
                         fh.write('{},{!r},{!r}\n'.format(int(epoch * train_epoch_size + step), float(yolo.last_grad_norm),
                                                         float(yolo.grad_scale_dev)))
+                if schedule is not None and rank == 0 and yolo.micro_step == 0:      # one row per optimiser step: its number and rate
+                    with open(os.path.join(log_dir, 'lr.csv'), 'a') as fh:
+                        fh.write('{},{!r}\n'.format(yolo.iterations, yolo.current_learning_rate()))
                 if log_ignored and rank == 0 and yolo.micro_step == 0:       # (of the batch that completed the optimiser step)
                     truth_max = int(yolo.last_truth_max)
                     with open(os.path.join(log_dir, 'ignored.csv'), 'a') as fh:
@@ -471,7 +511,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Converting checkpoint into Saved_Model')
         from yolo3 import model
         best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate,
-                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw, **spp_kw)
+                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw, **spp_kw, **optim_kw)
         best.load_weights(training_checkpoint_filepath)
         os.makedirs(os.path.join(output_folder, 'saved_model'), exist_ok=True)
         best.save_weights(os.path.join(output_folder, 'saved_model', 'yolov3.npz'))
@@ -541,6 +581,66 @@ def _label_smoothing_arg(text):
     return e
 
 
+def _momentum_arg(text):
+    try:
+        m = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a number in [0, 1), got {!r}'.format(text))
+    if not (0.0 <= m < 1.0):
+        raise argparse.ArgumentTypeError('a number in [0, 1), got {!r}'.format(text))
+    return m
+
+
+def _weight_decay_arg(text):
+    try:
+        w = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a finite number >= 0, got {!r}'.format(text))
+    if not (w >= 0.0 and w != float('inf')):
+        raise argparse.ArgumentTypeError('a finite number >= 0, got {!r}'.format(text))
+    return w
+
+
+def _unit_factor_arg(text):
+    try:
+        f = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a number in [0, 1], got {!r}'.format(text))
+    if not (0.0 <= f <= 1.0):
+        raise argparse.ArgumentTypeError('a number in [0, 1], got {!r}'.format(text))
+    return f
+
+
+def _lr_gamma_arg(text):
+    try:
+        g = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('a finite number > 0, got {!r}'.format(text))
+    if not (g > 0.0 and g != float('inf')):
+        raise argparse.ArgumentTypeError('a finite number > 0, got {!r}'.format(text))
+    return g
+
+
+def _step_count_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('an integer >= 0, got {!r}'.format(text))
+    if v < 0:
+        raise argparse.ArgumentTypeError('an integer >= 0, got {!r}'.format(text))
+    return v
+
+
+def _step_number_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    if v < 1:
+        raise argparse.ArgumentTypeError('an integer >= 1, got {!r}'.format(text))
+    return v
+
+
 def check_focal_flags(focal_gamma, focal_alpha, focal_terms):
     """--focal_alpha / --focal_terms say how the focal form is applied: without --focal_gamma > 0 there is none.  focal_terms None =
     the flag was not given."""
@@ -600,6 +700,14 @@ class _Parser(argparse.ArgumentParser):
             self.error("--ignore_thresh / --ignore_max_boxes need --ignore_mask truth: the reference's mask has no such parameters")
         try:
             check_focal_flags(a.focal_gamma, a.focal_alpha, a.focal_terms)
+        except ValueError as e:
+            self.error(str(e))
+        # (yolo3.model.check_optimizer_args restated, as above)
+        if a.optimizer == 'adam' and a.weight_decay > 0:
+            self.error("--weight_decay needs --optimizer adamw or sgd: adam is the reference's Keras Adam, which has none")
+        try:
+            build_lr_schedule(a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor, a.lr_milestones,
+                              a.lr_gamma)
         except ValueError as e:
             self.error(str(e))
         return a
@@ -684,6 +792,31 @@ def build_parser():
     parser.add_argument('--spp', dest='spp', type=int, choices=(0, 1), default=0,
                         help='(addition) 0 (default): the reference\'s network; 1: YOLOv3-SPP, a 5 / 9 / 13 max-pool pyramid and one more 1x1 '
                              'layer in the block of the coarsest scale (the weight files record it)')
+    parser.add_argument('--optimizer', dest='optimizer', choices=OPTIMIZERS, default='adam',
+                        help='(addition) adam (default) = the reference\'s Keras Adam; adamw = the same step with decoupled weight decay; '
+                             'sgd = SGD with momentum and L2 decay (the weight files record it)')
+    parser.add_argument('--momentum', dest='momentum', type=_momentum_arg, default=0.9,
+                        help='(addition) momentum of --optimizer sgd, in [0, 1) (default 0.9)')
+    parser.add_argument('--nesterov', dest='nesterov', type=int, choices=(0, 1), default=0,
+                        help='(addition) 1: Nesterov form of --optimizer sgd')
+    parser.add_argument('--weight_decay', dest='weight_decay', type=_weight_decay_arg, default=0.0,
+                        help='(addition) 0 (default): none; WD > 0: weight decay on the convolution kernels only, never on biases, gamma or '
+                             'beta (needs --optimizer adamw or sgd)')
+    parser.add_argument('--lr_schedule', dest='lr_schedule', choices=LR_SCHEDULES, default='reference',
+                        help='(addition) reference (default) = learning_rate / 10 during the shortened epoch 0, as the reference; constant, '
+                             'cosine or step = learning_rate x a factor of the optimiser step, after a linear warm-up (<scalars>/lr.csv)')
+    parser.add_argument('--lr_warmup_steps', dest='lr_warmup_steps', type=_step_count_arg, default=0,
+                        help='(addition) optimiser steps of the linear warm-up from --lr_warmup_start_factor to 1 (default 0)')
+    parser.add_argument('--lr_warmup_start_factor', dest='lr_warmup_start_factor', type=_unit_factor_arg, default=0.0,
+                        help='(addition) factor the warm-up starts from, in [0, 1] (default 0)')
+    parser.add_argument('--lr_total_steps', dest='lr_total_steps', type=_step_number_arg, default=None,
+                        help='(addition) optimiser step at which --lr_schedule cosine reaches --lr_final_factor (required for cosine, > warm-up)')
+    parser.add_argument('--lr_final_factor', dest='lr_final_factor', type=_unit_factor_arg, default=0.01,
+                        help='(addition) factor --lr_schedule cosine ends at and holds, in [0, 1] (default 0.01)')
+    parser.add_argument('--lr_milestones', dest='lr_milestones', type=_step_number_arg, nargs='*', default=[],
+                        help='(addition) optimiser steps, strictly increasing, at each of which --lr_schedule step multiplies the rate by --lr_gamma')
+    parser.add_argument('--lr_gamma', dest='lr_gamma', type=_lr_gamma_arg, default=0.1,
+                        help='(addition) factor of --lr_schedule step per milestone (default 0.1)')
     return parser
 
 
@@ -697,4 +830,6 @@ if __name__ == "__main__":
                 a.augmentation_device, bool(a.test_map), a.model_selection, a.test_map_min_box_size, a.ema_decay, a.test_map_nms,
                 a.test_map_nms_sigma, a.box_loss, a.box_loss_weight, a.accumulate_steps, a.grad_clip_norm, a.multiscale_min, a.multiscale_max,
                 a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible, a.ignore_mask, a.ignore_thresh,
-                a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing, bool(a.spp))
+                a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing, bool(a.spp), a.optimizer, a.momentum, bool(a.nesterov),
+                a.weight_decay, a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor,
+                tuple(a.lr_milestones), a.lr_gamma)

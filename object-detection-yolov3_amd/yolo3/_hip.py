@@ -37,6 +37,16 @@ class Tensor(C.Structure):
     _fields_ = [('ptr', C.c_void_p), ('n', C.c_int), ('h', C.c_int), ('w', C.c_int), ('c', C.c_int), ('ld', C.c_int)]
 
 
+class OptimDesc(C.Structure):
+    """y3_optim_desc: one SGD-momentum / AdamW step over a flat arena (y3_optim_step).  decay_ranges_host is a HOST array of
+    n_ranges [begin, end) pairs; the holder keeps it alive."""
+    _fields_ = [('kind', C.c_int), ('param', C.c_void_p), ('grad', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('count', C.c_size_t),
+                ('hyper_dev', C.c_void_p), ('momentum', C.c_float), ('weight_decay', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float),
+                ('eps', C.c_float), ('decay_ranges_host', C.POINTER(C.c_longlong)), ('n_ranges', C.c_int), ('ema_param', C.c_void_p),
+                ('moving', C.c_void_p), ('ema_moving', C.c_void_p), ('moving_count', C.c_size_t), ('omd_dev', C.c_void_p),
+                ('scale_dev', C.c_void_p)]
+
+
 TP = C.POINTER(Tensor)
 vp, fp, ip = C.c_void_p, C.c_void_p, C.c_void_p     # device pointers travel as integers
 i32, u32, f32, sz = C.c_int, C.c_uint, C.c_float, C.c_size_t
@@ -115,6 +125,7 @@ SIGNATURES = {
     'y3_grad_clip_scale': (i32, [vp, sz, i32, C.c_double, fp, fp, vp]),
     'y3_adam_step_scaled': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, vp]),
     'y3_adam_step_ema_scaled': (i32, [fp, fp, fp, fp, sz, fp, f32, f32, f32, fp, fp, fp, sz, fp, fp, vp]),
+    'y3_optim_step': (i32, [C.POINTER(OptimDesc), vp]),
     'y3_nms_per_class': (i32, [fp, i32, i32, i32, f32, f32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
     'y3_nms_workspace_bytes': (sz, [i32, i32, i32]),
     'y3_nms_single_class': (i32, [fp, i32, f32, ip, ip, fp, vp, sz, vp]),
@@ -165,6 +176,7 @@ EPI_LRELU = 1
 EPI_ACCUM = 2
 BF16_ROUTE_PP, BF16_ROUTE_C32, BF16_ROUTE_C64, BF16_ROUTE_RING = 1, 2, 3, 4   # Y3_BF16_ROUTE_*: out12[0] of y3_conv2d_fwd_bf16_plan
 BF16_NO_PATCH = 8   # Y3_BF16_NO_PATCH: keep a y3_conv2d_fwd_bf16 launch off the patch kernels (small batches, yolo3hip.h)
+OPT_SGD, OPT_SGD_NESTEROV, OPT_ADAMW, OPT_MAX_RANGES = 0, 1, 2, 128   # Y3_OPT_*: y3_optim_desc.kind, and the longest range table
 CONV_X3 = 4      # Y3_CONV_X3: fp32 arithmetic as three bf16 pieces per operand (conv_x3.hip); the weight operand changes layout
 
 

@@ -13,6 +13,7 @@ only; there is no torch.nn / autograd / CPU fallback on this path.
 """
 import collections
 import contextlib
+import ctypes
 import functools
 import math
 import os
@@ -144,6 +145,45 @@ def clip_scale(norm, clip, k):
     if clip is not None:
         s = s * (float(clip) / max(float(norm), float(clip)))
     return np.float32(s)
+
+
+OPTIMIZERS = ('adam', 'adamw', 'sgd')
+
+
+def check_optimizer_args(optimizer='adam', momentum=0.9, nesterov=False, weight_decay=0.0, lr_schedule=None):
+    """Host-side validation of the optimiser setting (the library checks the numbers again): ValueError on an
+    unknown optimiser, a momentum outside [0, 1), a nesterov that is not a boolean, a weight decay that is not a finite number
+    >= 0, a weight decay with 'adam' (Keras Adam has none: 'adamw' is the decayed form), or a schedule without factor(t)."""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError('optimizer must be one of {}, got {!r}'.format(', '.join(OPTIMIZERS), optimizer))
+    vals = []
+    for name, v in (('momentum', momentum), ('weight_decay', weight_decay)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError('{} must be a number, got {!r}'.format(name, v))
+        if isinstance(v, bool):
+            raise ValueError('{} must be a number, got {!r}'.format(name, v))
+        vals.append(f)
+    mu, wd = vals
+    if not 0.0 <= mu < 1.0:
+        raise ValueError('momentum must be in [0, 1), got {!r}'.format(momentum))
+    if not (isinstance(nesterov, (bool, np.bool_)) or (isinstance(nesterov, (int, np.integer)) and nesterov in (0, 1))):
+        raise ValueError('nesterov must be False or True, got {!r}'.format(nesterov))
+    if not (wd >= 0.0 and math.isfinite(wd)):
+        raise ValueError('weight_decay must be finite and >= 0, got {!r}'.format(weight_decay))
+    if optimizer == 'adam' and wd > 0.0:
+        raise ValueError("weight_decay {!r} needs optimizer 'adamw' (decoupled decay) or 'sgd': 'adam' is the reference's Keras Adam, "
+                         'which has none'.format(weight_decay))
+    if lr_schedule is not None and not callable(getattr(lr_schedule, 'factor', None)):
+        raise ValueError('lr_schedule must be None or have a factor(t) method (yolo3.schedule.LrSchedule), got {!r}'.format(lr_schedule))
+
+
+def decay_ranges(specs):
+    """The segments of the parameter arena that weight decay applies to: the kernel W of every layer,
+    [w_off, w_off + k*k*cin_pad*cout) in floats, in arena order.  Biases, gamma and beta are never decayed.  Segments start on
+    multiples of 64 floats and cin_pad is a multiple of 4, so every begin and end is a multiple of 4 (y3_optim_step's rule)."""
+    return [(sp.w_off, sp.w_off + sp.k * sp.k * sp.cin_pad * sp.cout) for sp in specs]
 
 
 def check_train_sizes(img_size, train_sizes):
@@ -897,7 +937,16 @@ class YoloV3:
                  use_graph=False, inference_precision='fp32', conv_arithmetic=None, ema_decay=None, ema_warmup=2000,
                  box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None,
                  ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES,
-                 focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0, spp=False):
+                 focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9,
+                 nesterov=False, weight_decay=0.0, lr_schedule=None):
+        # the optimiser: 'adam' without decay = the reference's Keras Adam and its launches; 'adamw' / 'sgd' run
+        # y3_optim_step; lr_schedule: None or an object with factor(t) (schedule.LrSchedule); checked before the device is needed
+        check_optimizer_args(optimizer, momentum, nesterov, weight_decay, lr_schedule)
+        self.optimizer_kind = optimizer
+        self.momentum = float(momentum)
+        self.nesterov = bool(nesterov)
+        self.weight_decay = float(weight_decay)
+        self.lr_schedule = lr_schedule
         # the YOLOv3-SPP variant of the network: False = the reference's Darknet-53 with three plain heads
         if not (isinstance(spp, (bool, np.bool_)) or (isinstance(spp, (int, np.integer)) and spp in (0, 1))):
             raise ValueError('spp must be False or True, got {!r}'.format(spp))
@@ -960,11 +1009,13 @@ class YoloV3:
         self.params = z(self.arena_floats)        # trainable arena: [W | b | gamma | beta] per layer
         self.params_t = z(self.arena_floats)      # kernels with channel axes swapped (dgrad operand)
         self.grads = z(self.arena_floats)
-        self.adam_m = z(self.arena_floats)
-        self.adam_v = z(self.arena_floats)
+        self.adam_m = z(self.arena_floats)        # first moment; the momentum buffer of 'sgd'
+        self.adam_v = z(self.arena_floats) if self.optimizer_kind != 'sgd' else None      # 'sgd' has no second moment
         self.moving = z(2 * self.moving_stride)   # [moving_mean | moving_var]
         self.chan = z(chan_floats)                # per BN layer: scale | shift | save_mean | save_rstd | k1 | k2 | k3
-        self.lr_t_dev = z(1)
+        # what the optimiser kernel reads per step: lr_t for 'adam'; {lr, 0} for 'sgd', {lr_t, lr * weight_decay} for 'adamw'
+        self.hyper_dev = z(2)
+        self.lr_t_dev = self.hyper_dev[0:1]
         self.beta1, self.beta2, self.adam_eps = 0.9, 0.999, 1e-7   # Keras Adam defaults (App. C5)
         self.iterations = 0
         # the average (ema_params, ema_moving) and the stash ema_weights() parks the live arenas in; None when off
@@ -1190,10 +1241,22 @@ class YoloV3:
             flat['meta_focal_terms'] = np.asarray(self.focal_terms)
         if self.spp:                              # likewise: a file of the reference's network has no such entry
             flat['meta_spp'] = np.asarray(1, np.int64)
+        if getattr(self, 'optimizer_kind', 'adam') != 'adam':       # likewise: a file of the reference's Adam has no such entry
+            flat['meta_optimizer'] = np.asarray(self.optimizer_kind)
+            flat['meta_optimizer_args'] = np.asarray([self.momentum, float(self.nesterov), self.weight_decay], np.float64)
         flat['opt_iterations'] = np.asarray(self.iterations, np.int64)
         flat['opt_m'] = self.adam_m.detach().cpu().numpy()
-        flat['opt_v'] = self.adam_v.detach().cpu().numpy()
+        if self.adam_v is not None:               # 'sgd' has no second moment
+            flat['opt_v'] = self.adam_v.detach().cpu().numpy()
         np.savez(path, **flat)
+
+    @staticmethod
+    def _optimizer_meta(z):
+        """The optimiser setting a weight file carries (save_weights), as constructor arguments; none for a file without it."""
+        if 'meta_optimizer' not in z:
+            return {}
+        mu, nes, wd = (float(v) for v in z['meta_optimizer_args'])
+        return dict(optimizer=str(z['meta_optimizer']), momentum=mu, nesterov=bool(nes), weight_decay=wd)
 
     def load_weights(self, path, load_optimizer=False, transfer=False):
         """transfer=True: a file of the plain network into an SPP model -- every layer by role, the 4 * 512 -> 512 layer behind
@@ -1217,6 +1280,12 @@ class YoloV3:
         if YoloV3._focal_meta(z) != mine:          # the weights load all the same; the losses of the two settings are not comparable
             warnings.warn('load_weights: {} was written with focal setting {}, this model has {}'.format(path, YoloV3._focal_meta(z) or 'none',
                                                                                                          mine or 'none'))
+        if load_optimizer and 'opt_m' in z:
+            # the moments of one optimiser mean nothing to another (the momentum buffer of 'sgd' is no first moment)
+            theirs_opt = YoloV3._optimizer_meta(z).get('optimizer', 'adam')
+            if theirs_opt != self.optimizer_kind:
+                raise ValueError("load_weights: load_optimizer=True, but {} holds the state of optimizer '{}' and this model has '{}'"
+                                 .format(path, theirs_opt, self.optimizer_kind))
         layers = []
         own = self.get_weights() if transfer else None
         for (i, sp), j in zip(enumerate(self.specs), mapping):
@@ -1229,7 +1298,8 @@ class YoloV3:
         self.set_weights(layers)
         if load_optimizer and 'opt_m' in z:
             self.adam_m.copy_(torch.from_numpy(z['opt_m']))
-            self.adam_v.copy_(torch.from_numpy(z['opt_v']))
+            if self.adam_v is not None:
+                self.adam_v.copy_(torch.from_numpy(z['opt_v']))
             self.iterations = int(z['opt_iterations'])
 
     @staticmethod
@@ -1246,10 +1316,13 @@ class YoloV3:
         return bool(int(z['meta_spp'])) if 'meta_spp' in z else False
 
     @staticmethod
-    def from_file(path, device=None):
+    def from_file(path, device=None, lr_schedule=None):
+        """The model a weight file describes, with its weights.  The file records the network, the focal setting and the optimiser;
+        the learning-rate schedule is the caller's to pass, like box_loss to the constructor."""
         z = np.load(path, allow_pickle=False)
         y = YoloV3(int(z['meta_global_batch_size']), [int(v) for v in z['meta_img_size']], int(z['meta_number_classes']),
-                   [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device, spp=YoloV3._spp_meta(z), **YoloV3._focal_meta(z))
+                   [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device, spp=YoloV3._spp_meta(z), **YoloV3._focal_meta(z),
+                   **YoloV3._optimizer_meta(z), lr_schedule=lr_schedule)
         y.load_weights(path)
         return y
 
@@ -1324,6 +1397,14 @@ class YoloV3:
 
     def get_learning_rate(self):
         return self.learning_rate
+
+    def _lr(self, t):
+        """lr(t) of optimiser step t = 1, 2, ...: the base rate times the schedule's factor (fp64)."""
+        return self.learning_rate * float(self.lr_schedule.factor(t)) if self.lr_schedule is not None else self.learning_rate
+
+    def current_learning_rate(self):
+        """The rate the last optimiser step ran with, lr(iterations); the base rate before the first step."""
+        return self._lr(self.iterations) if self.iterations >= 1 else self.learning_rate
 
     # ---- execution -------------------------------------------------------------------------
     def _plan(self, n, training, bf16=False, slot=0, size=None):
@@ -1449,7 +1530,17 @@ class YoloV3:
 
     def _lr_t(self):
         t = self.iterations
-        return self.learning_rate * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
+        return self._lr(t) * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
+
+    def _fill_hyper(self):
+        """The device scalars of optimiser step `iterations`, computed in fp64 and rounded once to fp32: lr_t for 'adam' and
+        'adamw', lr for 'sgd'; 'adamw' also lr * weight_decay."""
+        if self.optimizer_kind == 'sgd':
+            self.lr_t_dev.fill_(float(np.float32(self._lr(self.iterations))))
+            return
+        self.lr_t_dev.fill_(self._lr_t())
+        if self.optimizer_kind == 'adamw':
+            self.hyper_dev[1:2].fill_(float(np.float32(self._lr(self.iterations) * self.weight_decay)))
 
     def _fwd_bwd(self, plan, st):
         plan.run_forward(st)
@@ -1473,10 +1564,30 @@ class YoloV3:
                                          self.grad_scale_dev.data_ptr(), st), 'y3_grad_clip_scale')
 
     def _adam_launch(self):
-        """(entry point, arguments up to the stream) of the optimiser step.  Every buffer it names is allocated by the constructor
-        and only ever written in place, so the constructor calls this once; what changes per step (lr_t, the EMA factor, the
+        """(entry point, arguments up to the stream) of the optimiser step: y3_adam_step* for the default 'adam', y3_optim_step for
+        'adamw' / 'sgd' (the one place that chooses).  Every buffer it names is allocated by the constructor and only ever written
+        in place, so the constructor calls this once; what changes per step (lr or lr_t, lr * weight decay, the EMA factor, the
         gradient scale) is read from device memory."""
         g = self.grad_acc if self.grad_acc is not None else self.grads
+        if self.optimizer_kind != 'adam':
+            # SGD with momentum / AdamW, decay on the kernels only (DESIGN §3.19): one descriptor, built once like the tuple below.
+            # The range table is host memory the descriptor points into; both live as long as the model.
+            ranges = self.decay_ranges = decay_ranges(self.specs)
+            self._decay_table = (ctypes.c_longlong * (2 * len(ranges)))(*[v for r in ranges for v in r])
+            d = self._optim_desc = _hip.OptimDesc()
+            d.kind = _hip.OPT_ADAMW if self.optimizer_kind == 'adamw' else _hip.OPT_SGD_NESTEROV if self.nesterov else _hip.OPT_SGD
+            d.param, d.grad, d.m, d.count = self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.arena_floats
+            d.v = self.adam_v.data_ptr() if self.adam_v is not None else None
+            d.hyper_dev = self.hyper_dev.data_ptr()
+            d.momentum, d.weight_decay = self.momentum, self.weight_decay
+            d.beta1, d.beta2, d.eps = self.beta1, self.beta2, self.adam_eps
+            d.decay_ranges_host, d.n_ranges = self._decay_table, len(ranges)
+            if self.ema_decay is not None:
+                d.ema_param, d.moving, d.ema_moving = self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr()
+                d.moving_count, d.omd_dev = self.moving.numel(), self.ema_omd_dev.data_ptr()
+            if self._grad_ws is not None:
+                d.scale_dev = self.grad_scale_dev.data_ptr()
+            return lib.y3_optim_step, (ctypes.byref(d),)
         name = 'y3_adam_step'
         args = [self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.arena_floats,
                 self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps]
@@ -1538,7 +1649,7 @@ class YoloV3:
         if last:
             self.iterations += 1
             self._bf16_stale = True
-            self.lr_t_dev.fill_(self._lr_t())
+            self._fill_hyper()
             if self.ema_decay is not None:
                 self.ema_omd_dev.fill_(float(self._ema_omd()))
         if self.grad_acc is not None:
