@@ -823,6 +823,38 @@ typedef struct y3_mosaic_record {   /* 64 bytes, one per OUTPUT image */
 int y3_mosaic_batch(const float* src, int n, int c, int h, int w, const y3_mosaic_record* records_host, float* out,
                     y3_stream_t stream);
 
+/* ---- affine warp (not in the reference; yolo3/augment.py draw_affine / affine_boxes / affine_reference) -------
+ * Every output image is its own input image resampled through an affine map: rotation, shear, gain, translation.  The record
+ * holds the INVERSE map, output pixel (x, y) -> source coordinate, pixel centres at the integers:
+ *   coordinates    sx = (m0*x + m1*y) + m2, sy = (m3*x + m4*y) + m5 in fp32, x and y converted to fp32, every operation rounded on
+ *                  its own in exactly this order (no fused multiply-add).  x0 = floor(sx), fx = sx - x0 in fp32; y alike.  NumPy
+ *                  float32 arithmetic reproduces sx, sy, the floors and the fractions bit for bit (augment.affine_coords).
+ *   interpolation  bilinear over the taps (y0 + {0,1}, x0 + {0,1}) of the pixel's own image and channel; a tap outside
+ *                  [0,h) x [0,w) has the value `fill` -- scipy.ndimage.affine_transform(order=1, mode='grid-constant', cval=fill).
+ *   weight zero    a tap whose weight is exactly zero (fx == 0: the right column; fx == 1, which fp32 gives for a tiny negative sx:
+ *                  the left column; rows alike) contributes nothing and is not read: NaN or Inf there never reaches the output.
+ *                  With fx == 0 and fy == 0 the output is the bits of the one tap, NaN payload and -0.0 included, so the identity
+ *                  {1,0,0, 0,1,0}, integer translations, the flips {-1,0,w-1, 0,1,0} / {1,0,0, 0,-1,h-1} and the quarter turns
+ *                  (square images: {0,-1,w-1, 1,0,0} and its powers) are exact copies / permutations (with `fill` where the
+ *                  source lies outside).
+ *   arithmetic     lerp(a, b, f) = f == 0 ? a : 1 - f == 0 ? b : (1 - f) * a + f * b, along x for both rows, then along y: at most
+ *                  6 fp32 roundings on a tap's path, |out - exact| <= 6 * 2^-24 * sum |weight_i * tap_i| to first order.
+ * src, out: DEVICE float32 [n][c][h][w], c = 1 or 3, any h, w >= 1 (h * w < 2^31 - 8, at most 2^23 tiles of 32 x 32), 4-byte
+ * aligned; the ranges must not overlap (the pass cannot run in place).  records: HOST array of n records, validated before any
+ * launch (Y3_EINVAL + message: null pointer; bad c, n, h, w; misaligned or overlapping src / out; non-zero reserved; a
+ * non-finite coefficient or fill; |m0| (w-1) + |m1| (h-1) + |m2| > 2^30 or the same of m3..m5 with (w-1), (h-1) -- this sum bounds
+ * the source coordinate at every corner of the output and every intermediate, so the float -> int conversion of the floor is
+ * defined) and handed to the kernel as kernel arguments, 32 images per launch.  One thread per output pixel and all its
+ * channels, 32 x 32 pixels per workgroup; every output element is written by exactly one thread: no atomics, no workspace, the
+ * same bits on every launch. */
+typedef struct y3_affine_record {   /* 32 bytes, one per image */
+    float m[6];                     /* INVERSE map, output pixel -> source coordinate: sx = m0*x + m1*y + m2, sy = m3*x + m4*y + m5 */
+    float fill;                     /* value of every tap outside the source */
+    int32_t reserved;               /* 0 */
+} y3_affine_record;
+int y3_affine_batch(const float* src, int n, int c, int h, int w, const y3_affine_record* records_host, float* out,
+                    y3_stream_t stream);
+
 /* ---- ground-truth label tensors: ImageReader.__format_boxes (imagereader.py:252-324) on the device ------------------------
  * For ImageReader(..., label_device='gpu') and multi-scale training: the boxes of a batch cross PCIe, the three
  * label tensors are built where the loss reads them.  boxes: DEVICE int32 [n][max_boxes][5] = x, y, w, h, class with (x, y) the

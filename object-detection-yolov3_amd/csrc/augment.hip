@@ -18,6 +18,12 @@
 //                 lies inside one span (one row, one side of the seam column) is one 16-byte load at 4-byte alignment -- the
 //                 source is shifted against the destination by ox - qx, any residue mod 4 -- and one aligned 16-byte store; the
 //                 at most three groups a row has at its seam and its ends copy their floats one by one.
+//
+// Affine warp (not in the reference; y3_affine_batch, semantics in yolo3hip.h): a third, separate pass that resamples
+// every image of the batch through its own inverse affine map.
+//   affine        one thread per output pixel and all its channels, 32 x 32 pixels per workgroup: fp32 coordinates in a stated
+//                 unfused order, four taps gathered straight from global memory (the two of a row as one 8-byte load in the
+//                 interior), `fill` outside the image, taps of weight zero never read.
 #include "common.h"
 #include <math.h>
 #include <algorithm>
@@ -467,6 +473,126 @@ extern "C" int y3_mosaic_batch(const float* src, int n, int c, int h, int w, con
         }
         hipLaunchKernelGGL(mosaic_kernel, dim3(y3_cdiv(groups, 256), c, nb), dim3(256), 0, st, src, out + (size_t)base * image, tab, c, h, w, div_mul, div_shift);
         Y3_CHECK_LAUNCH("mosaic_batch");
+    }
+    return Y3_OK;
+}
+
+// ---- affine warp: every output pixel gathers four taps of its own image (not in the reference) -----------------------------
+#define Y3_AFF_TILE 32             // a 256-thread workgroup covers 32 x 32 output pixels: 32 columns x 8 rows of threads, 4 rows each
+#define Y3_AFF_MAX_COORD 1073741824.0      // 2^30: bound on |m0| (w-1) + |m1| (h-1) + |m2| (y alike), so (int)floorf(s) is defined
+
+struct AffImg {                    // 32 bytes
+    float m[6];
+    float fill;
+    int pad0;
+};
+struct AffTable {
+    AffImg img[Y3_AUG_CHUNK];
+};
+typedef float aff_f2u __attribute__((ext_vector_type(2), aligned(4)));      // 8 bytes at 4-byte alignment: one global_load_dwordx2
+
+// aug_lerp's form with the second weight-zero case: f == 1 happens (sx = -1e-9 has floor -1 and the fp32 fraction 1), and then `a`
+// must not be touched either.  Roundings: g (1), g * a (1), f * b (1), the sum (1): a's term carries 3, b's term 2, and a lerp of
+// two lerps twice that, so the worst tap of a bilinear value carries 6 fp32 roundings (the bound of tests/affine_reference.py).
+__device__ __forceinline__ float aff_lerp(float a, float b, float f) {
+    const float g = 1.f - f;
+    return f == 0.f ? a : g == 0.f ? b : g * a + f * b;
+}
+
+// grid (tiles of a plane, 1, images of the chunk); `src` and `out` are the chunk's first image.  Thread t owns column
+// tile_x + (t & 31) of rows tile_y + (t >> 5) + {0, 8, 16, 24}: a wave stores two 128-byte row pieces per channel plane and its
+// taps lie in two short source segments.  A tap that is outside the image or has weight zero is not read: it takes `fill`, which
+// aff_lerp then uses (outside) or drops (weight zero).  Where all four taps are inside and live -- every pixel of a rotated or
+// scaled image but those at its border -- the two taps of a row are one global_load_dwordx2 at 4-byte alignment: six loads per
+// pixel of three channels instead of twelve (profiles/affine_cost.txt has both forms).
+template <int C>
+__global__ __launch_bounds__(256) void affine_kernel(const float* __restrict__ src, float* __restrict__ out, AffTable tab, int H, int W, int tilesx) {
+    const AffImg& a = tab.img[blockIdx.z];
+    const int ty = (int)blockIdx.x / tilesx, tx = (int)blockIdx.x - ty * tilesx;
+    const int x = tx * Y3_AFF_TILE + (int)(threadIdx.x & 31);
+    if (x >= W) return;
+    const size_t plane = (size_t)H * W;
+    const float* s = src + (size_t)blockIdx.z * C * plane;
+    float* o = out + (size_t)blockIdx.z * C * plane;
+    const float xf = (float)x, fill = a.fill;
+    const float ax = a.m[0] * xf, bx = a.m[3] * xf;
+#pragma unroll
+    for (int k = 0; k < Y3_AFF_TILE / 8; ++k) {
+        const int y = ty * Y3_AFF_TILE + (int)(threadIdx.x >> 5) + 8 * k;
+        if (y >= H) break;
+        const float yf = (float)y;
+        const float sx = (ax + a.m[1] * yf) + a.m[2];      // unfused, in this order (-ffp-contract=off): augment.affine_coords
+        const float sy = (bx + a.m[4] * yf) + a.m[5];
+        const float flx = floorf(sx), fly = floorf(sy);
+        const float fx = sx - flx, fy = sy - fly;
+        const int x0 = (int)flx, y0 = (int)fly;             // |s| <= 2^30 (1 + 2^-22): checked on the host
+        const bool cl = fx != 1.f, cr = fx != 0.f, rt = fy != 1.f, rb = fy != 0.f;      // the column / row has a non-zero weight
+        const bool inl = (unsigned)x0 < (unsigned)W, inr = (unsigned)(x0 + 1) < (unsigned)W;
+        const bool int_ = (unsigned)y0 < (unsigned)H, inb = (unsigned)(y0 + 1) < (unsigned)H;
+        const unsigned e = (unsigned)y0 * (unsigned)W + (unsigned)x0;      // mod 2^32; a tap inside the image has 0 <= index < H * W < 2^31
+        const bool r00 = cl && rt && inl && int_, r01 = cr && rt && inr && int_, r10 = cl && rb && inl && inb, r11 = cr && rb && inr && inb;
+        float v[C][4];
+        if (r00 && r01 && r10 && r11) {                      // the interior: the two taps of a row are one 8-byte load at 4-byte alignment
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {                 // all loads of the pixel issued before the first use
+                const float* p = s + ch * plane + e;
+                const aff_f2u top = *(const aff_f2u*)p, bot = *(const aff_f2u*)(p + W);
+                v[ch][0] = top.x;
+                v[ch][1] = top.y;
+                v[ch][2] = bot.x;
+                v[ch][3] = bot.y;
+            }
+        } else {                                             // an edge of the image or a weight of zero
+#pragma unroll
+            for (int ch = 0; ch < C; ++ch) {
+                const float* p = s + ch * plane;
+                v[ch][0] = r00 ? p[e] : fill;
+                v[ch][1] = r01 ? p[e + 1] : fill;
+                v[ch][2] = r10 ? p[e + W] : fill;
+                v[ch][3] = r11 ? p[e + W + 1] : fill;
+            }
+        }
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch)
+            o[ch * plane + (size_t)y * W + x] = aff_lerp(aff_lerp(v[ch][0], v[ch][1], fx), aff_lerp(v[ch][2], v[ch][3], fx), fy);
+    }
+}
+
+extern "C" int y3_affine_batch(const float* src, int n, int c, int h, int w, const y3_affine_record* records, float* out, y3_stream_t stream) {
+    Y3_CHECK_ARG(src && records && out, "affine_batch: null pointer");
+    Y3_CHECK_ARG(c == 1 || c == 3, "affine_batch: channels %d (1 or 3)", c);
+    Y3_CHECK_ARG(n > 0 && h > 0 && w > 0, "affine_batch: bad dims n %d, %dx%d", n, h, w);
+    Y3_CHECK_ARG((long long)h * w < (1LL << 31) - 8, "affine_batch: plane %dx%d too large", h, w);
+    const size_t plane = (size_t)h * w, image = plane * c, bytes = (size_t)n * image * sizeof(float);
+    Y3_CHECK_ARG((((size_t)src | (size_t)out) & 3) == 0, "affine_batch: src / out not 4-byte aligned");
+    Y3_CHECK_ARG((size_t)src + bytes <= (size_t)out || (size_t)out + bytes <= (size_t)src, "affine_batch: src and out overlap (the pass cannot run in place)");
+    for (int i = 0; i < n; ++i) {
+        const y3_affine_record& r = records[i];
+        Y3_CHECK_ARG(r.reserved == 0, "affine_batch: record %d: reserved word %d", i, r.reserved);
+        bool finite = isfinite(r.fill);
+        for (int k = 0; k < 6; ++k) finite = finite && isfinite(r.m[k]);
+        Y3_CHECK_ARG(finite, "affine_batch: record %d: non-finite coefficient or fill", i);
+        for (int k = 0; k < 6; k += 3) {
+            const double reach = fabs((double)r.m[k]) * (w - 1) + fabs((double)r.m[k + 1]) * (h - 1) + fabs((double)r.m[k + 2]);
+            Y3_CHECK_ARG(reach <= Y3_AFF_MAX_COORD, "affine_batch: record %d: source %s coordinate reaches %g at a corner of the output (limit 2^30)", i,
+                         k ? "y" : "x", reach);
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int tilesx = y3_cdiv(w, Y3_AFF_TILE), tilesy = y3_cdiv(h, Y3_AFF_TILE);
+    Y3_CHECK_ARG((long long)tilesx * tilesy <= (1LL << 23), "affine_batch: %dx%d needs more than 2^23 tiles of %d x %d", h, w, Y3_AFF_TILE, Y3_AFF_TILE);
+    for (int base = 0; base < n; base += Y3_AUG_CHUNK) {
+        const int nb = std::min(Y3_AUG_CHUNK, n - base);
+        AffTable tab = {};
+        for (int i = 0; i < nb; ++i) {
+            const y3_affine_record& r = records[base + i];
+            for (int k = 0; k < 6; ++k) tab.img[i].m[k] = r.m[k];
+            tab.img[i].fill = r.fill;
+        }
+        const dim3 grid((unsigned)((long long)tilesx * tilesy), 1, nb);
+        if (c == 1) hipLaunchKernelGGL(affine_kernel<1>, grid, dim3(256), 0, st, src + (size_t)base * image, out + (size_t)base * image, tab, h, w, tilesx);
+        else hipLaunchKernelGGL(affine_kernel<3>, grid, dim3(256), 0, st, src + (size_t)base * image, out + (size_t)base * image, tab, h, w, tilesx);
+        Y3_CHECK_LAUNCH("affine_batch");
     }
     return Y3_OK;
 }

@@ -28,6 +28,11 @@ mAP pass, model selection, the checkpoint and the export stay at the size the im
 and three other images of its batch, composed on the device after the augmentation; the draws are a pure function
 of --mosaic_seed, the rank and the batch count, and a box stays when at least --mosaic_min_visible of its area is still visible.
 Composes with the --multiscale_* flags; the test reader, the mAP pass, the checkpoint and the export are untouched.
+--affine_prob P (with --augmentation_device gpu; 0 = off) warps each training image, with probability P, through a random rotation
+(+-affine_degrees), shear (+-affine_shear degrees per axis), gain (1 +- affine_scale) and translation (+-affine_translate of the
+side) on the device, after the augmentation and the mosaic; pixels from outside the image get --affine_fill, the
+draws are a pure function of --affine_seed, the rank, the batch count and the image, and a box stays when at least
+--affine_min_visible of its transformed area is inside the image.  Composes with --multiscale_* and --mosaic_prob.
 --ignore_mask truth (with --ignore_thresh T, default 0.5, and --ignore_max_boxes N, default 1024) leaves a prediction without an
 object out of the objectness loss when it overlaps a ground-truth box of its own image with IoU >= T, the rule of the paper, in
 place of the reference's mask; training and test loss use the same mask.  <scalars>/ignored.csv gets one row per
@@ -186,6 +191,29 @@ def check_mosaic_args(mosaic_prob, mosaic_min_visible):
     return p
 
 
+def check_affine_args(affine_prob, affine_degrees=10.0, affine_shear=2.0, affine_scale=0.1, affine_translate=0.1, affine_fill=0.0,
+                      affine_min_visible=0.25):
+    """--affine_prob and its magnitudes -> the probability as a float (0.0 = off).  ValueError outside the ranges of
+    Dataset.affine: prob in [0, 1], degrees in [0, 180], shear in [0, 45), scale in [0, 1), translate in [0, 1], a finite fill,
+    min_visible in [0, 1]."""
+    p = float(affine_prob or 0.0)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('--affine_prob must be in [0, 1], got {!r}'.format(affine_prob))
+    if not 0.0 <= float(affine_degrees) <= 180.0:
+        raise ValueError('--affine_degrees must be in [0, 180], got {!r}'.format(affine_degrees))
+    if not 0.0 <= float(affine_shear) < 45.0:
+        raise ValueError('--affine_shear must be in [0, 45), got {!r}'.format(affine_shear))
+    if not 0.0 <= float(affine_scale) < 1.0:
+        raise ValueError('--affine_scale must be in [0, 1), got {!r}'.format(affine_scale))
+    if not 0.0 <= float(affine_translate) <= 1.0:
+        raise ValueError('--affine_translate must be in [0, 1], got {!r}'.format(affine_translate))
+    if not abs(float(affine_fill)) < float('inf'):
+        raise ValueError('--affine_fill must be finite, got {!r}'.format(affine_fill))
+    if not 0.0 <= float(affine_min_visible) <= 1.0:
+        raise ValueError('--affine_min_visible must be in [0, 1], got {!r}'.format(affine_min_visible))
+    return p
+
+
 def build_lr_schedule(lr_schedule='reference', warmup_steps=0, warmup_start_factor=0.0, total_steps=None, final_factor=0.01, milestones=(),
                       gamma=0.1):
     """--lr_schedule and its flags -> a yolo3.schedule.LrSchedule, or None for 'reference' (the loop's own epoch-0 rule, which
@@ -208,7 +236,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 multiscale_period=10, multiscale_seed=0, mosaic_prob=0.0, mosaic_seed=0, mosaic_min_visible=0.25,
                 ignore_mask='reference', ignore_thresh=0.5, ignore_max_boxes=1024, focal_gamma=0.0, focal_alpha=0.0, focal_terms=None,
                 label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9, nesterov=False, weight_decay=0.0, lr_schedule='reference',
-                lr_warmup_steps=0, lr_warmup_start_factor=0.0, lr_total_steps=None, lr_final_factor=0.01, lr_milestones=(), lr_gamma=0.1):
+                lr_warmup_steps=0, lr_warmup_start_factor=0.0, lr_total_steps=None, lr_final_factor=0.01, lr_milestones=(), lr_gamma=0.1,
+                affine_prob=0.0, affine_degrees=10.0, affine_shear=2.0, affine_scale=0.1, affine_translate=0.1, affine_fill=0.0, affine_seed=0,
+                affine_min_visible=0.25):
     spp_kw = dict(spp=True) if spp else {}
     schedule = build_lr_schedule(lr_schedule, lr_warmup_steps, lr_warmup_start_factor, lr_total_steps, lr_final_factor, lr_milestones, lr_gamma)
     from yolo3.model import check_optimizer_args
@@ -218,6 +248,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     mosaic_prob = check_mosaic_args(mosaic_prob, mosaic_min_visible)
     if mosaic_prob and augmentation_device != 'gpu':
         raise ValueError('mosaic augmentation needs augmentation_device gpu: the batches are composed and labelled on the device')
+    affine_prob = check_affine_args(affine_prob, affine_degrees, affine_shear, affine_scale, affine_translate, affine_fill, affine_min_visible)
+    if affine_prob and augmentation_device != 'gpu':
+        raise ValueError('affine augmentation needs augmentation_device gpu: the batches are warped and labelled on the device')
     train_sizes = multiscale_sizes(multiscale_min, multiscale_max)
     if train_sizes is not None and augmentation_device != 'gpu':
         raise ValueError('multi-scale training needs augmentation_device gpu: the batches are resampled and labelled on the device')
@@ -261,9 +294,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     print('Setting up training image reader')
     train_reader = imagereader.ImageReader(train_database_filepath, anchors, use_augmentation=use_augmentation, shuffle=True,
                                            num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device,
-                                           **(dict(label_device='gpu') if train_sizes is not None or mosaic_prob else {}),
-                                           # (a shuffled reader ignores its shard when it picks keys; the mosaic draws are keyed by it)
-                                           **(dict(num_shards=world, shard_index=rank) if mosaic_prob else {}))
+                                           **(dict(label_device='gpu') if train_sizes is not None or mosaic_prob or affine_prob else {}),
+                                           # (a shuffled reader ignores its shard when it picks keys; the mosaic and affine draws are keyed by it)
+                                           **(dict(num_shards=world, shard_index=rank) if mosaic_prob or affine_prob else {}))
     print('Train Reader has {} images'.format(train_reader.get_image_count()))
     training_checkpoint_filepath = None
     try:
@@ -304,6 +337,13 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
             train_dataset = train_dataset.mosaic(mosaic_prob, mosaic_seed, mosaic_min_visible)
             print('Mosaic augmentation: probability {:g} per image, four images of the batch per mosaic (seed {}); boxes with less than '
                   '{:g} of their area visible are dropped; the test reader is untouched'.format(mosaic_prob, mosaic_seed, mosaic_min_visible))
+        if affine_prob:
+            train_dataset = train_dataset.affine(affine_prob, affine_degrees, affine_shear, affine_scale, affine_translate, affine_fill, affine_seed,
+                                                 affine_min_visible)
+            print('Affine augmentation: probability {:g} per image, rotation +-{:g} deg, shear +-{:g} deg, gain 1 +- {:g}, translation +-{:g} of '
+                  'the side, fill {:g} (seed {}); boxes with less than {:g} of their area inside the image are dropped; the test reader is '
+                  'untouched'.format(affine_prob, affine_degrees, affine_shear, affine_scale, affine_translate, affine_fill, affine_seed,
+                                     affine_min_visible))
 
         print('Creating model')
         number_classes = train_reader.get_number_classes()
@@ -695,6 +735,13 @@ class _Parser(argparse.ArgumentParser):
             self.error(str(e))
         if prob and a.augmentation_device != 'gpu':
             self.error('--mosaic_prob needs --augmentation_device gpu')
+        try:
+            prob = check_affine_args(a.affine_prob, a.affine_degrees, a.affine_shear, a.affine_scale, a.affine_translate, a.affine_fill,
+                                     a.affine_min_visible)
+        except ValueError as e:
+            self.error(str(e))
+        if prob and a.augmentation_device != 'gpu':
+            self.error('--affine_prob needs --augmentation_device gpu')
         # (yolo3.model.check_ignore_mask_args, which train_model calls, restated: parsing loads no device library)
         if a.ignore_mask == 'reference' and (a.ignore_thresh != 0.5 or a.ignore_max_boxes != 1024):
             self.error("--ignore_thresh / --ignore_max_boxes need --ignore_mask truth: the reference's mask has no such parameters")
@@ -771,6 +818,24 @@ def build_parser():
                         help='(addition) seed of the mosaic draws: a pure function of (seed, rank, batch count, image)')
     parser.add_argument('--mosaic_min_visible', dest='mosaic_min_visible', type=float, default=0.25,
                         help='(addition) a box of a mosaic stays when at least this share of its area lies in the window taken from its image (default 0.25)')
+    parser.add_argument('--affine_prob', dest='affine_prob', type=float, default=0.0,
+                        help='(addition) off by default; P in (0, 1]: each training image is warped, with probability P, through a random '
+                             'rotation, shear, gain and translation on the device (needs --augmentation_device gpu; composes with '
+                             '--multiscale_* and --mosaic_prob; the test reader is untouched)')
+    parser.add_argument('--affine_degrees', dest='affine_degrees', type=float, default=10.0,
+                        help='(addition) the rotation is drawn in +- this many degrees, in [0, 180] (default 10)')
+    parser.add_argument('--affine_shear', dest='affine_shear', type=float, default=2.0,
+                        help='(addition) the x and y shear angles are each drawn in +- this many degrees, in [0, 45) (default 2)')
+    parser.add_argument('--affine_scale', dest='affine_scale', type=float, default=0.1,
+                        help='(addition) the isotropic gain is drawn in 1 +- this, in [0, 1) (default 0.1)')
+    parser.add_argument('--affine_translate', dest='affine_translate', type=float, default=0.1,
+                        help='(addition) the translation is drawn in +- this share of the image side per axis, in [0, 1] (default 0.1)')
+    parser.add_argument('--affine_fill', dest='affine_fill', type=float, default=0.0,
+                        help='(addition) value of the pixels a warp brings in from outside the image, in stored-pixel units (default 0)')
+    parser.add_argument('--affine_seed', dest='affine_seed', type=int, default=0,
+                        help='(addition) seed of the affine draws: a pure function of (seed, rank, batch count, image)')
+    parser.add_argument('--affine_min_visible', dest='affine_min_visible', type=float, default=0.25,
+                        help='(addition) a warped box stays when at least this share of its transformed area lies inside the image (default 0.25)')
     parser.add_argument('--ignore_mask', dest='ignore_mask', choices=IGNORE_MASKS, default='reference',
                         help='(addition) ignore mask of the objectness loss: reference (default) = the reference\'s; truth = a prediction '
                              'without an object is left out when it overlaps a ground-truth box of its own image with IoU >= --ignore_thresh')
@@ -832,4 +897,5 @@ if __name__ == "__main__":
                 a.multiscale_period, a.multiscale_seed, a.mosaic_prob, a.mosaic_seed, a.mosaic_min_visible, a.ignore_mask, a.ignore_thresh,
                 a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing, bool(a.spp), a.optimizer, a.momentum, bool(a.nesterov),
                 a.weight_decay, a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor,
-                tuple(a.lr_milestones), a.lr_gamma)
+                tuple(a.lr_milestones), a.lr_gamma, a.affine_prob, a.affine_degrees, a.affine_shear, a.affine_scale, a.affine_translate,
+                a.affine_fill, a.affine_seed, a.affine_min_visible)

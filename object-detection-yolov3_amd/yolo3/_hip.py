@@ -155,6 +155,7 @@ SIGNATURES = {
     'y3_augment_batch': (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, fp, vp, vp]),     # records: HOST pointer (augment.AUG_RECORD)
     'y3_augment_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'y3_mosaic_batch': (i32, [fp, i32, i32, i32, i32, vp, fp, vp]),     # records: HOST pointer (augment.MOSAIC_RECORD)
+    'y3_affine_batch': (i32, [fp, i32, i32, i32, i32, vp, fp, vp]),     # records: HOST pointer (augment.AFFINE_RECORD)
     'y3_format_labels': (i32, [ip, ip, i32, i32, C.POINTER(C.c_float), i32, i32, i32, i32, fp, fp, fp, vp]),
     'y3_eval_offsets':(i32, [ip, i32, i32, i32, ip, vp]),
     'y3_eval_match': (i32, [fp, i32, i32, i32, i32, f32, f32, ip, ip, fp, i32, i32, fp, ip, i32, i32, C.POINTER(C.c_float), i32, ip,

@@ -10,6 +10,9 @@ offsets identical, pixels to 1e-4 of the 8-bit range.  Boxes are [n,5] = x, y, w
 
 draw_augmentation is the device path's half of augment_image_box_pair: the same random decisions, boxes transformed here,
 the pixels left to y3_augment_batch (csrc/augment.hip) through one AUG_RECORD per image.
+
+Not in the reference, device path only: draw_mosaic / mosaic_boxes / mosaic_reference and draw_affine / affine_boxes /
+affine_reference (the rotation the reference's rotation_flag names and asserts away, with shear, gain and translation).
 """
 import numpy as np
 import scipy.ndimage
@@ -374,3 +377,187 @@ def mosaic_reference(batch, records):
             oy, ox = int(r['oy'][q]), int(r['ox'][q])
             out[i, :, qy:qy + qh, qx:qx + qw] = batch[int(r['src'][q]), :, oy:oy + qh, ox:ox + qw]
     return out
+
+
+# ---- random affine warp (not in the reference): rotation, shear, isotropic gain and translation ---------------
+# y3_affine_record (include/yolo3hip.h), one per image of a y3_affine_batch call
+AFFINE_RECORD = np.dtype([('m', '<f4', (6,)), ('fill', '<f4'), ('reserved', '<i4')])
+assert AFFINE_RECORD.itemsize == 32
+AFFINE_MAX_COORD = 2.0 ** 30      # y3_affine_batch refuses |m0| (w-1) + |m1| (h-1) + |m2| (and the y row alike) above this
+_AFFINE_STREAM = 0xAFF1E          # folded into the key after (seed, shard, batch, image): not the mosaic's stream of the same seed
+
+
+def affine_identity_records(n, fill=0.0):
+    """n records of the identity map (an exact copy of the image)."""
+    rec = np.zeros(int(n), AFFINE_RECORD)
+    rec['m'] = (1, 0, 0, 0, 1, 0)
+    rec['fill'] = fill
+    return rec
+
+
+def affine_record(forward, fill=0.0):
+    """One AFFINE_RECORD from a FORWARD 3 x 3 matrix (source pixel -> output pixel, last row 0 0 1): inverted in float64, the six
+    coefficients rounded once to float32."""
+    inv = np.linalg.inv(np.asarray(forward, np.float64))
+    rec = np.zeros(1, AFFINE_RECORD)
+    rec['m'][0] = inv[:2].reshape(6).astype(np.float32)
+    rec['fill'] = fill
+    return rec
+
+
+def draw_affine_parameters(seed, shard, batch_index, image, prob, degrees=0.0, shear=0.0, scale=0.0, translate=0.0):
+    """The draw of one image (draw_affine's docstring has the stream and the order): None when the image is not warped, else
+    (rotation degrees, x shear degrees, y shear degrees, gain, x translation, y translation as shares of the side)."""
+    key = 0
+    for v in (seed, shard, batch_index, image, _AFFINE_STREAM):
+        key = _mix64((key ^ (int(v) & _M64)) + _GOLDEN)
+    u = lambda j: (_mix64(key + (j + 1) * _GOLDEN) >> 11) * 2.0 ** -53
+    if not u(0) < prob:
+        return None
+    between = lambda j, mag: -float(mag) + 2.0 * float(mag) * u(j)
+    return (between(1, degrees), between(2, shear), between(3, shear), 1.0 + between(4, scale), between(5, translate), between(6, translate))
+
+
+def draw_affine(seed, shard, batch_index, n, size, prob, degrees=0.0, shear=0.0, scale=0.0, translate=0.0, fill=0.0):
+    """(AFFINE_RECORD [n], forward matrices float64 [n, 3, 3]) for the batch_index-th batch of n images of size = (h, w) on reader
+    shard `shard`: a pure function of its arguments, counter based exactly as draw_mosaic is (no global np.random).  Image i owns
+    the key folded over (seed, shard, batch_index, i, 0xAFF1E) -- k = 0; for v in those five: k = mix((k ^ v) + 0x9E3779B97F4A7C15)
+    -- so its draw does not depend on n; its j-th word is u_j = mix(key + (j + 1) * 0x9E3779B97F4A7C15), the uniform U_j =
+    (u_j >> 11) * 2^-53 in [0, 1), and a value in [lo, hi] is lo + (hi - lo) * U_j.  Draw order per image:
+      U_0       the image is warped when U_0 < prob; otherwise it gets the identity record and matrix, the other words unused
+      U_1       rotation angle a in [-degrees, degrees]: Rot = [[cos a, -sin a], [sin a, cos a]] on (x, y), x to the right, y down
+      U_2, U_3  x and y shear angles in [-shear, shear] degrees: Shear = [[1, tan sx], [tan sy, 1]]
+      U_4       gain in [1 - scale, 1 + scale]
+      U_5, U_6  translation in [-translate, translate] * w along x, * h along y
+    forward = T . Shear . (gain Rot) . C in float64, C moving the image centre ((w-1)/2, (h-1)/2) to the origin and T moving it back
+    plus the drawn translation; the record holds its float64 inverse rounded once to float32.  A draw with every magnitude zero is
+    the identity record exactly."""
+    h, w = int(size[0]), int(size[1])
+    n = int(n)
+    if n < 1 or h < 1 or w < 1:
+        raise ValueError('draw_affine: n, h, w must be >= 1, got {} {} {}'.format(n, h, w))
+    rec = affine_identity_records(n, fill)
+    mats = np.tile(np.eye(3), (n, 1, 1))
+    cx, cy = (w - 1) / 2.0, (h - 1) / 2.0
+    for i in range(n):
+        par = draw_affine_parameters(seed, shard, batch_index, i, prob, degrees, shear, scale, translate)
+        if par is None or par == (0.0, 0.0, 0.0, 1.0, 0.0, 0.0):
+            continue
+        rot, shx, shy = np.deg2rad(par[0]), np.deg2rad(par[1]), np.deg2rad(par[2])
+        gain, tx, ty = par[3], par[4] * w, par[5] * h
+        c = np.array([[1, 0, -cx], [0, 1, -cy], [0, 0, 1]], np.float64)
+        r = np.array([[gain * np.cos(rot), -gain * np.sin(rot), 0], [gain * np.sin(rot), gain * np.cos(rot), 0], [0, 0, 1]], np.float64)
+        s = np.array([[1, np.tan(shx), 0], [np.tan(shy), 1, 0], [0, 0, 1]], np.float64)
+        t = np.array([[1, 0, cx + tx], [0, 1, cy + ty], [0, 0, 1]], np.float64)
+        mats[i] = t @ s @ r @ c
+        rec[i] = affine_record(mats[i], fill)[0]
+    return rec, mats
+
+
+def affine_boxes(box_lists, matrices, size, min_visible=0.25):
+    """The boxes of the output images of y3_affine_batch from the boxes of its input images and the FORWARD matrices (float64
+    [n, 3, 3], source pixel -> output pixel; draw_affine's second result).  box_lists: one int32 [k, 5] array per image (x, y, w, h,
+    class; top-left corner; the box covers the pixel centres x .. x+w-1, y .. y+h-1), None or empty = no boxes.  Returns one int32
+    [k', 5] array per image ([0, 5] when empty), order kept.
+
+    Per box: its four pixel-centre corners (x, y), (x+w-1, y), (x, y+h-1), (x+w-1, y+h-1) go through the matrix in float64; the
+    axis-aligned bounds of the four are rounded to the nearest pixel centre, halves up (floor(v + 0.5)), which gives the
+    unclipped box x0..x1, y0..y1 (inclusive) of area (x1-x0+1)(y1-y0+1); it is clipped to [0, w-1] x [0, h-1]; dropped when a
+    clipped side is below 2 px; dropped when the clipped area < min_visible * the unclipped area (exact integer products compared
+    in float64: a share of exactly min_visible stays).  The class is unchanged.  An image whose matrix is exactly the identity
+    keeps its boxes as they came (no clipping, no 2 px rule).  Integer matrices (flips, quarter turns, integer shifts) move the
+    corners exactly, so the boxes are the permuted boxes of the permuted pixels: a flip sends x to w-1-x -- one pixel left of
+    transform_boxes' reflection, which is the reference's w - x.  Under a rotation the bounds are those of the rotated rectangle,
+    so they grow; the min_visible share is taken of that grown box.  min_visible = 0.25 is a default, not a tuned value."""
+    h, w = int(size[0]), int(size[1])
+    empty = np.zeros((0, 5), np.int32)
+    src = [empty if b is None or len(b) == 0 else np.asarray(b, np.int32).reshape(-1, 5) for b in box_lists]
+    matrices = np.asarray(matrices, np.float64)
+    assert matrices.shape == (len(src), 3, 3), (matrices.shape, len(src))
+    out = []
+    for b, m in zip(src, matrices):
+        if np.array_equal(m, np.eye(3)) or len(b) == 0:
+            out.append(b.copy())
+            continue
+        bx = b.astype(np.float64)
+        xa, ya, xb, yb = bx[:, 0], bx[:, 1], bx[:, 0] + bx[:, 2] - 1, bx[:, 1] + bx[:, 3] - 1
+        px = np.stack([xa, xb, xa, xb], 1)
+        py = np.stack([ya, ya, yb, yb], 1)
+        qx = (m[0, 0] * px + m[0, 1] * py) + m[0, 2]
+        qy = (m[1, 0] * px + m[1, 1] * py) + m[1, 2]
+        x0, x1 = np.floor(qx.min(1) + 0.5).astype(np.int64), np.floor(qx.max(1) + 0.5).astype(np.int64)
+        y0, y1 = np.floor(qy.min(1) + 0.5).astype(np.int64), np.floor(qy.max(1) + 0.5).astype(np.int64)
+        full = (x1 - x0 + 1) * (y1 - y0 + 1)
+        cx0, cy0, cx1, cy1 = np.maximum(x0, 0), np.maximum(y0, 0), np.minimum(x1, w - 1), np.minimum(y1, h - 1)
+        cw, ch = cx1 - cx0 + 1, cy1 - cy0 + 1
+        keep = (cw >= 2) & (ch >= 2)
+        keep &= ~((cw * ch).astype(np.float64) < np.float64(min_visible) * full.astype(np.float64))
+        out.append(np.stack([cx0, cy0, cw, ch, b[:, 4].astype(np.int64)], 1)[keep].astype(np.int32).reshape(-1, 5))
+    return out
+
+
+def affine_coords(records, size, dtype=np.float32):
+    """The source coordinates y3_affine_batch evaluates, restated: (sx, sy) of shape [n, h, w] each, in `dtype` arithmetic with the
+    kernel's order of unfused operations, sx = (m0 * x + m1 * y) + m2 and sy = (m3 * x + m4 * y) + m5, x and y the output pixel's
+    column and row converted to `dtype`.  dtype float32 reproduces the kernel bit for bit; float64 (the float32 coefficients
+    widened) is the exact-coordinate mode the comparison with scipy uses."""
+    h, w = int(size[0]), int(size[1])
+    m = np.asarray(records['m']).astype(dtype).reshape(-1, 6)
+    x = np.arange(w).astype(dtype)[None, None, :]
+    y = np.arange(h).astype(dtype)[None, :, None]
+    c = lambda k: m[:, k][:, None, None]
+    sx = (c(0) * x + c(1) * y) + c(2)
+    sy = (c(3) * x + c(4) * y) + c(5)
+    assert sx.dtype == dtype and sy.dtype == dtype
+    return sx, sy
+
+
+def affine_reference(batch, records, coords=np.float32, detail=False):
+    """y3_affine_batch restated in NumPy (the oracle of the tests): batch [n, c, h, w] float32 -> float64 [n, c, h, w].
+
+    Coordinates as affine_coords(records, (h, w), coords); x0 = floor(sx), fx = sx - x0 in that dtype (y alike).  The four taps
+    (y0 + {0, 1}, x0 + {0, 1}) carry the weights (1 - fy | fy) * (1 - fx | fx), formed in float64; a tap outside the image has the
+    value `fill`; a tap whose weight is exactly zero contributes nothing, whatever it holds (NaN and Inf included).  A pixel with
+    exactly one non-zero weight is that tap itself.  detail=True returns (values, magnitude, single, bits): magnitude = the
+    float64 sum of |weight * tap| the error bound of the tests scales with, single = the pixels with one non-zero weight, and
+    bits = uint32, for those pixels the tap's own bit pattern (NaN payload and -0.0 kept), elsewhere the float32 rounding of the
+    value."""
+    batch = np.ascontiguousarray(batch, dtype=np.float32)
+    n, ch, h, w = batch.shape
+    records = np.asarray(records, dtype=AFFINE_RECORD)
+    assert records.shape == (n,)
+    sx, sy = affine_coords(records, (h, w), coords)
+    x0f, y0f = np.floor(sx), np.floor(sy)
+    fx, fy = (sx - x0f).astype(np.float64), (sy - y0f).astype(np.float64)
+    x0, y0 = x0f.astype(np.int64), y0f.astype(np.int64)
+    val = np.zeros((n, ch, h, w), np.float64)
+    mag = np.zeros((n, ch, h, w), np.float64)
+    bits = np.zeros((n, ch, h, w), np.uint32)
+    count = np.zeros((n, h, w), np.int64)
+    words = batch.view(np.uint32)
+    img = np.arange(n)[:, None, None]
+    for dy, wy in ((0, 1.0 - fy), (1, fy)):
+        for dx, wx in ((0, 1.0 - fx), (1, fx)):
+            wgt = wy * wx
+            live = wgt != 0
+            yy, xx = y0 + dy, x0 + dx
+            inside = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+            yc, xc = np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)
+            count += live
+            for k in range(ch):
+                fill = np.broadcast_to(records['fill'][:, None, None], (n, h, w))
+                tap32 = np.where(inside, batch[img, k, yc, xc], fill).astype(np.float32)
+                with np.errstate(invalid='ignore', over='ignore'):
+                    tap = tap32.astype(np.float64)              # (a signalling NaN raises 'invalid' when it is widened)
+                    term = np.where(live, wgt * np.where(live, tap, 0.0), 0.0)
+                val[:, k] += term
+                mag[:, k] += np.abs(term)
+                tapbits = np.where(inside, words[img, k, yc, xc], np.ascontiguousarray(fill.astype(np.float32)).view(np.uint32))
+                bits[:, k] = np.where(live, tapbits, bits[:, k])
+    single = np.broadcast_to((count == 1)[:, None], val.shape)
+    with np.errstate(invalid='ignore', over='ignore'):
+        rounded = val.astype(np.float32).view(np.uint32)
+    bits = np.where(single, bits, rounded)
+    if detail:
+        return val, mag, single, bits
+    return val

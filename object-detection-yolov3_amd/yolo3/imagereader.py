@@ -10,6 +10,8 @@ format_boxes      ImageReader.__format_boxes, imagereader.py:252-324 (host NumPy
                   as in the reference: it runs in the reader processes)
 mosaic_device     y3_mosaic_batch (csrc/augment.hip): the augmented batch recombined, four windows per output image, for
                   Dataset.mosaic() (not in the reference)
+affine_device     y3_affine_batch (csrc/augment.hip): every image of the batch warped through an affine map, bilinear, for
+                  Dataset.affine() (not in the reference)
 format_labels_device  the same three label tensors built on the device from the boxes of a batch (y3_format_labels,
                   csrc/detect.hip) for ImageReader(..., label_device='gpu') and Dataset.multiscale()
 """
@@ -85,6 +87,21 @@ def mosaic_device(x, records):
     out = torch.empty_like(x)
     st = torch.cuda.current_stream(x.device).cuda_stream
     check(lib.y3_mosaic_batch(x.data_ptr(), b, c, h, w, records.ctypes.data, out.data_ptr(), st), 'y3_mosaic_batch')
+    return out
+
+
+def affine_device(x, records):
+    """y3_affine_batch: x CUDA float32 [B, C, H, W] (C = 1 or 3), records AFFINE_RECORD [B] (host; see augment.draw_affine) -> a new
+    tensor of the same shape, every image warped through its record's inverse map (bilinear, `fill` outside).  Enqueued on the
+    current stream."""
+    assert x.is_cuda and x.dim() == 4 and x.dtype == torch.float32, (x.dtype, tuple(x.shape))
+    x = x.contiguous()
+    records = np.ascontiguousarray(records, dtype=augment.AFFINE_RECORD)
+    b, c, h, w = x.shape
+    assert records.shape == (b,)
+    out = torch.empty_like(x)
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    check(lib.y3_affine_batch(x.data_ptr(), b, c, h, w, records.ctypes.data, out.data_ptr(), st), 'y3_affine_batch')
     return out
 
 
@@ -212,19 +229,25 @@ class Dataset:
     (seed, i // period): the batch is augmented straight to that size and its labels are built at it.
     ``mosaic(prob, seed, min_visible)`` (such a reader only) turns each image of a batch, with probability prob, into a
     mosaic of itself and three other images of the same batch: drawn as a pure function of (seed, the reader's shard, i), composed
-    on the device after the augmentation at the batch's size, the boxes remapped on the host before they are uploaded."""
+    on the device after the augmentation at the batch's size, the boxes remapped on the host before they are uploaded.
+    ``affine(prob, degrees, shear, scale, translate, fill, seed, min_visible)`` (such a reader only) warps each image
+    of a batch, with probability prob, through a random rotation, shear, gain and translation: drawn as a pure function of (seed,
+    the reader's shard, i, image), applied on the device after the augmentation and the mosaic and before the z-score, at the
+    batch's own size; the boxes are remapped on the host (augment.affine_boxes) after the mosaic's."""
 
-    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None, mosaic=None):
+    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None, mosaic=None, affine=None):
         self.reader, self.batch_size, self.device, self.prefetch_depth = reader, batch_size, device, prefetch_depth
         self.multiscale_cfg = multiscale       # None or (sizes [(h, w)], period, seed)
         self.mosaic_cfg = mosaic               # None or (prob, seed, min_visible)
+        self.affine_cfg = affine               # None or (prob, degrees, shear, scale, translate, fill, seed, min_visible)
         self.batches = 0                       # batches handed out so far, over every iteration of this object
 
     def batch(self, n):
-        return Dataset(self.reader, int(n), self.device, self.prefetch_depth, self.multiscale_cfg, self.mosaic_cfg)
+        return Dataset(self.reader, int(n), self.device, self.prefetch_depth, self.multiscale_cfg, self.mosaic_cfg, self.affine_cfg)
 
     def prefetch(self, n):
-        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)), self.multiscale_cfg, self.mosaic_cfg)     # batches, not examples: 4 is plenty
+        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)), self.multiscale_cfg, self.mosaic_cfg,     # batches, not examples: 4 is plenty
+                       self.affine_cfg)
 
     def multiscale(self, sizes, period, seed=0):
         """Multi-scale training: see the class docstring.  sizes: (h, w) pairs, multiples of 32; period: batches per draw."""
@@ -235,7 +258,7 @@ class Dataset:
             raise ValueError('multiscale sizes must be (h, w) multiples of {}, got {!r}'.format(NETWORK_DOWNSAMPLE_FACTOR, sizes))
         if isinstance(period, bool) or int(period) != period or int(period) < 1:
             raise ValueError('multiscale period must be an integer >= 1, got {!r}'.format(period))
-        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, (sizes, int(period), int(seed)), self.mosaic_cfg)
+        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, (sizes, int(period), int(seed)), self.mosaic_cfg, self.affine_cfg)
 
     def mosaic(self, prob, seed=0, min_visible=0.25):
         """Mosaic augmentation: see the class docstring.  prob: share of mosaic images, 0 < prob <= 1; min_visible: a box stays when
@@ -246,7 +269,26 @@ class Dataset:
             raise ValueError('mosaic prob must be in (0, 1], got {!r}'.format(prob))
         if isinstance(min_visible, bool) or not 0 <= float(min_visible) <= 1:
             raise ValueError('mosaic min_visible must be in [0, 1], got {!r}'.format(min_visible))
-        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, self.multiscale_cfg, (float(prob), int(seed), float(min_visible)))
+        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, self.multiscale_cfg, (float(prob), int(seed), float(min_visible)),
+                       self.affine_cfg)
+
+    def affine(self, prob, degrees=10.0, shear=2.0, scale=0.1, translate=0.1, fill=0.0, seed=0, min_visible=0.25):
+        """Random affine warp: see the class docstring.  prob: share of warped images, 0 < prob <= 1; degrees in [0, 180]: rotation
+        drawn in +-degrees; shear in [0, 45): x and y shear angles in +-shear degrees; scale in [0, 1): gain in 1 +- scale;
+        translate in [0, 1]: shift in +-translate of the image side; fill: finite value of the pixels from outside the image (in
+        the units of the stored pixels, before the z-score); min_visible: a box stays when at least this share of its transformed
+        area lies inside the image (augment.affine_boxes).  The magnitudes are defaults, not tuned values."""
+        if getattr(self.reader, 'label_device', 'cpu') != 'gpu':
+            raise ValueError("affine() needs a reader with label_device='gpu': label tensors built in the workers cannot be remapped")
+        if isinstance(prob, bool) or not 0 < float(prob) <= 1:
+            raise ValueError('affine prob must be in (0, 1], got {!r}'.format(prob))
+        for name, v, ok in (('degrees', degrees, lambda v: 0 <= v <= 180), ('shear', shear, lambda v: 0 <= v < 45),
+                            ('scale', scale, lambda v: 0 <= v < 1), ('translate', translate, lambda v: 0 <= v <= 1),
+                            ('fill', fill, np.isfinite), ('min_visible', min_visible, lambda v: 0 <= v <= 1)):
+            if isinstance(v, bool) or not ok(float(v)):
+                raise ValueError('affine {} out of range, got {!r}'.format(name, v))
+        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, self.multiscale_cfg, self.mosaic_cfg,
+                       (float(prob), float(degrees), float(shear), float(scale), float(translate), float(fill), int(seed), float(min_visible)))
 
     def size_of_batch(self, i):
         """(h, w) of batch i of this dataset: the reader's stored size unless multiscale() is on."""
@@ -259,7 +301,8 @@ class Dataset:
         """A label_device='gpu' batch on the device: imgs the raw pixels (already there), records host AUG_RECORD [B], boxes /
         counts host int32 (NumPy arrays or pinned tensors).  Augments to this batch's size, z-scores, builds the labels; with
         mosaic() on, the records of this batch are drawn here, the boxes remapped on the host and the augmented images recombined
-        before the z-score."""
+        before the z-score; with affine() on, its records are drawn here too, the boxes go through affine_boxes after mosaic_boxes
+        and the images through y3_affine_batch after the mosaic.  Without affine() no call is added."""
         crop = tuple(self.reader.image_size[:2])
         index = self.batches
         size = self.size_of_batch(index)
@@ -275,12 +318,20 @@ class Dataset:
             b, c = (x.numpy() if torch.is_tensor(x) else x for x in (boxes, counts))
             # an output image can hold the boxes of four inputs: collated afresh (never into the pinned prefetch buffer)
             boxes, counts = collate_boxes(augment.mosaic_boxes([b[i, :c[i]] for i in range(len(c))], mosaic, size, min_visible))
-        as_t = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True)
+        affine = None
+        if self.affine_cfg is not None:
+            prob, degrees, shear, scale, translate, fill, seed, min_visible = self.affine_cfg
+            affine, forward = augment.draw_affine(seed, self.reader.shard_index, index, len(records), size, prob, degrees, shear, scale, translate, fill)
+            b, c = (x.numpy() if torch.is_tensor(x) else x for x in (boxes, counts))
+            boxes, counts = collate_boxes(augment.affine_boxes([b[i, :c[i]] for i in range(len(c))], forward, size, min_visible))
+        as_t =lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True)
         labels = format_labels_device(as_t(boxes), as_t(counts), (size[0], size[1], self.reader.image_size[2]), self.reader.anchors,
                                       self.reader.number_classes)
         imgs = augment_device(imgs, records, size)
         if mosaic is not None:
             imgs = mosaic_device(imgs, mosaic)
+        if affine is not None:
+            imgs = affine_device(imgs, affine)
         return (zscore_normalize_device(imgs), *labels)
 
     def shard(self, num_shards, index):
@@ -307,6 +358,8 @@ class Dataset:
         if self.batch_size is None:
             if self.mosaic_cfg is not None:
                 raise ValueError('mosaic() combines the images of a batch: call batch(n) before iterating')
+            if self.affine_cfg is not None:
+                raise ValueError('affine() warps the images of a batch on the device: call batch(n) before iterating')
             yield from self.reader.generator()           # z-scored examples, as the reference's unbatched dataset yields them
             return
         dev = self.device or torch.device('cuda', torch.cuda.current_device())
