@@ -855,6 +855,67 @@ typedef struct y3_affine_record {   /* 32 bytes, one per image */
 int y3_affine_batch(const float* src, int n, int c, int h, int w, const y3_affine_record* records_host, float* out,
                     y3_stream_t stream);
 
+/* ---- letterbox front end of inference: images of any size into the network frame and the boxes back (opt-in, not in the
+ * reference: inference.py / evaluate.py --letterbox, YoloV3.predict_letterbox) --------------------------------------
+ * A ragged batch of 1 <= n <= Y3_LETTERBOX_MAX_IMAGES images lies in ONE device buffer src (16-byte aligned), image i densely
+ * packed [src_h][src_w][c] at byte src_offset (a multiple of 16), dtype 0 = uint8, 1 = uint16, 2 = float32 (as y3_tile_gather),
+ * c = 1 or 3.  records: HOST array, validated before any launch and handed to the kernels as kernel arguments.  Image i is
+ * resampled to new_h x new_w (yolo3/letterbox.py letterbox_record: aspect ratio kept, rounded, at least 1, enlarged when smaller
+ * than the frame) and placed at rows pad_y .., columns pad_x .. of the H x W frame.
+ *
+ * Resampling: separable, triangle filtered -- the function of torch's interpolate(mode='bilinear', antialias=True,
+ * align_corners=False).  One axis, in -> out, in / out = a / b in lowest terms, D = 2 max(a, b); for output o:
+ *   taps      j = lo .. hi-1, lo = max(0, floor((a (2o+1) - D + b) / (2b))), hi = min(in, floor((a (2o+1) + D + b) / (2b)))
+ *             (= int(ctr - u + 0.5), int(ctr + u + 0.5) for ctr = (in / out)(o + 0.5), u = max(in / out, 1)), exact integers
+ *   weight    wn_j = max(0, D - |(2j+1) b - (2o+1) a|), an integer <= 65536: D times the triangle max(0, 1 - |(j - ctr + 0.5) / u|)
+ *   value     (sum over j ascending, wn_j > 0, of fl(fl(wn_j) * fl(v_j))) / fl(sum wn_j)          -- fp32, -ffp-contract=off
+ * first along x for every source row (the taps of a row, ascending, for each channel), then along y over the reduced rows,
+ * ascending.  fl(wn_j) and fl(sum wn_j) are exact (the sum is < 2^24 inside the limits below); the first product starts the sum
+ * (nothing is added to zero).  A tap of weight zero is never read.  Hence in == out is an exact copy (uint8 / uint16 -> float32
+ * exactly; a float NaN reaches only its own pixel) and a reduction by exactly 2 weighs 1, 3, 3, 1 over 8.  With Tx, Ty non-zero
+ * taps on the two axes, |out - exact| <= (Tx + Ty + 3) 2^-24 sum |wy wx tap|.
+ * Limits: source and frame sides 1 .. 32768; src / new <= 64 on each axis.  Refused with Y3_EINVAL + message, nothing launched:
+ * those, a null pointer, bad dtype / c / n, new_* < 1, negative padding, pad + new beyond the frame, a misaligned src or offset.
+ *
+ * The resample kernel: one 256-thread workgroup per band of 8 output rows and group of 256 output elements (column x channel) of
+ * one image, one element per thread.  A source row is read from memory once per workgroup whose filter reaches it: once per band
+ * and per element group (neighbouring bands, and the groups of a band, share the filter support only).  It is read as 16-byte
+ * slots from the 16-byte boundary below its first needed byte, whatever the row's own alignment; the last slot of an image is
+ * read byte-wise up to the image's end.  The slots go through double-buffered LDS stages of 16 KiB that hold as many whole rows
+ * as fit (their loads are in flight together) or one chunk of a longer row, so a row of any length works.  Each thread reduces
+ * the taps of its output element from LDS, carries the partial sum across the chunks of a long row, and keeps the band's 8
+ * partial sums in registers.  No [src_h][new_w] intermediate, no atomics, each output element written by one thread: the same
+ * bits on every launch.
+ *
+ * y3_letterbox_batch: out float32 [n][c][H][W] = the un-normalised frame: the content at [pad_y, pad_y + new_h) x [pad_x,
+ * pad_x + new_w), `fill` (any bits, NaN included) everywhere else.
+ * y3_letterbox_zscore_nhwc: the network's NHWC input directly.  dst->n == n, H = dst->h, W = dst->w; dst->c >= c and a multiple
+ * of 4, dst->ld >= dst->c and a multiple of 4, dst->ptr 16-byte aligned (refused as y3_tta_views_nhwc refuses them).  The content
+ * values are those of y3_letterbox_batch bit for bit (staged in the workspace), z-scored per image over the CONTENT only: sum and
+ * sum of squares in fp64 over the content as a [c][new_h][new_w] tensor in y3_zscore's partition (128 x 256 strided partials, the
+ * same tree), then mean = s / count, var = max(0, q / count - mean^2), mu = (float)mean, sd = (float)sqrt(var),
+ * out = sd <= 1 ? x - mu : (x - mu) / sd -- the expressions of y3_zscore.  Padding pixels are 0 (the content mean); channels
+ * c .. dst->c - 1 are 0, as y3_nchw_to_nhwc writes them; the floats of a pixel beyond dst->c are not touched.  Pixels are stored
+ * 16 bytes at a time.  workspace: y3_letterbox_workspace_bytes(n, H, W, c) bytes, 16-byte aligned.
+ * y3_letterbox_unmap: rows [n][nb][ld] decode rows (corners x0, y0, x1, y1 first) of frame i -> image i's own pixels, in place:
+ *   x <- (x - (float)pad_x) * sx,  y <- (y - (float)pad_y) * sy,   sx = (float)((double)src_w / new_w), sy likewise
+ * one fp32 subtraction, then one fp32 multiplication (no contraction); with clip = 1 then v < 0 ? 0 : v > lim ? lim : v for
+ * lim = (float)src_w or (float)src_h (a NaN stays).  Columns 4 .. ld-1 are not touched.  Needs no frame: the records' offsets and
+ * the scale limit are not looked at. */
+#define Y3_LETTERBOX_MAX_IMAGES 16
+typedef struct y3_letterbox_record {
+    uint64_t src_offset;      /* byte offset of this image in src; a multiple of 16 */
+    int32_t  src_h, src_w;    /* its size; the image is [src_h][src_w][c], densely packed */
+    int32_t  new_h, new_w;    /* content size in the frame */
+    int32_t  pad_y, pad_x;    /* top / left padding */
+} y3_letterbox_record;        /* 32 bytes */
+int y3_letterbox_batch(const void* src, int dtype, int c, int n, const y3_letterbox_record* records, int H, int W,
+                       float fill, float* out /* [n][c][H][W] */, y3_stream_t stream);
+int y3_letterbox_zscore_nhwc(const void* src, int dtype, int c, int n, const y3_letterbox_record* records,
+                             const y3_tensor* dst /* the network's NHWC input */, void* workspace, y3_stream_t stream);
+size_t y3_letterbox_workspace_bytes(int n, int H, int W, int c);
+int y3_letterbox_unmap(float* rows, int n, int nb, int ld, const y3_letterbox_record* records, int clip, y3_stream_t stream);
+
 /* ---- ground-truth label tensors: ImageReader.__format_boxes (imagereader.py:252-324) on the device ------------------------
  * For ImageReader(..., label_device='gpu') and multi-scale training: the boxes of a batch cross PCIe, the three
  * label tensors are built where the loss reads them.  boxes: DEVICE int32 [n][max_boxes][5] = x, y, w, h, class with (x, y) the

@@ -47,12 +47,13 @@ def folder_examples(image_folder, csv_folder, image_format, num_shards=1, shard_
 
 def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
              max_detections=None, distributed=False, nms='hard', nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep',
-             area_ranges=None, area_names=None, curves=False):
+             area_ranges=None, area_names=None, curves=False, letterbox=False):
     """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds).
     distributed: a collective over the default process group; every rank passes its keys[rank::world] share of the
     examples and gets the result over all of them.  nms / nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its
     Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time augmentation (metrics.evaluate_examples).  area_ranges /
-    area_names / curves: DetectionEvaluator's."""
+    area_names / curves: DetectionEvaluator's.  letterbox: images of any size, each letterboxed into the model input (not with
+    tta; metrics.evaluate_examples)."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
     yolo = load_model(saved_model_filepath)
@@ -61,7 +62,7 @@ def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', bat
                                     curves=curves)
     t0 = time.perf_counter()
     metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size, nms=nms, nms_sigma=nms_sigma, tta=tta, tta_vote_iou=tta_vote_iou,
-                              tta_score=tta_score)
+                              tta_score=tta_score, letterbox=letterbox)
     if distributed:
         ev = metrics.all_gather_evaluator(ev)
     res = ev.result()
@@ -213,6 +214,9 @@ if __name__ == '__main__':
                         help='--tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
     parser.add_argument('--tta-score', dest='tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
                         help='--tta with --tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
+    parser.add_argument('--letterbox', action='store_true',
+                        help='images of any size (not with --tta or --tiled): rescale each with its aspect ratio kept and pad it to the model '
+                        'input on the device; detections are matched in the image\'s own pixels')
     parser.add_argument('--area-ranges', dest='area_ranges', type=str, nargs='+', default=None, metavar='LO:HI',
                         help="also score per range of box area in px^2, both ends closed: 'coco' (all, small <= 32^2, medium, large > 96^2) "
                         "or up to 8 of LO:HI (inf allowed) and 'all'; detections and ground truth outside a range are ignored there, not counted")
@@ -246,6 +250,8 @@ if __name__ == '__main__':
         parser.error('--tta-vote-iou and --tta-score go with --tta')
     if a.tiled and a.tta != 'none':
         parser.error('--tta does not go with --tiled')
+    if a.letterbox and (a.tiled or a.tta != 'none'):
+        parser.error('--letterbox does not go with --tta or --tiled')
     if a.batch_size is None and not a.tiled:
         a.batch_size = 8
     if a.batch_size is not None and a.batch_size < 1:
@@ -289,13 +295,16 @@ if __name__ == '__main__':
     else:
         res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
                                     distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma, tta=a.tta, tta_vote_iou=a.tta_vote_iou,
-                                    tta_score=a.tta_score, area_ranges=area_ranges, area_names=area_names, curves=curves)
+                                    tta_score=a.tta_score, area_ranges=area_ranges, area_names=area_names, curves=curves,
+                                    letterbox=a.letterbox)
     if rank == 0:
         print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
         print('NMS: {}'.format(a.nms + (' (sigma {:g})'.format(a.nms_sigma) if a.nms == 'soft-gaussian' else '')))
         if a.tta != 'none':
             print('TTA: {} ({} views), {}'.format(a.tta, len(bbox_utils.TTA_VIEWS[a.tta]), 'no voting' if a.tta_vote_iou is None else
                                                   'vote IoU {:g}, score {}'.format(a.tta_vote_iou, a.tta_score)))
+        if a.letterbox:
+            print('Letterbox: images of any size into the model input, boxes in their own pixels')
         if a.tiled:
             print('Tiled: {} x {} tiles, seam margin {:g}, merge NMS {}'.format(a.tile_height, a.tile_width, a.seam_margin, a.merge_nms))
         print_table(res)

@@ -19,13 +19,31 @@ def load_model(path):
     return YoloV3.from_file(path)
 
 
+def write_detections(group, dets, output_folder, image_format):
+    """One X,Y,W,H,C csv per image of the group."""
+    for img_filepath, (boxes, scores, class_label, _) in zip(group, dets):
+        file_name = os.path.split(img_filepath)[1]
+        if boxes is None:                                             # the reference would crash here (Q11); write an empty csv
+            out = np.zeros((0, 5), np.int32)
+        else:
+            boxes[:, 2] = boxes[:, 2] - boxes[:, 0]
+            boxes[:, 3] = boxes[:, 3] - boxes[:, 1]
+            out = np.concatenate((boxes, class_label.reshape(-1, 1)), axis=-1).astype(np.int32)    # truncation (Q20)
+        print('Found: {} rois'.format(out.shape[0]))
+        bbox_utils.write_boxes_from_xywhc(out, os.path.join(output_folder, file_name.replace(image_format, 'csv')))
+
+
 def inference(image_folder, image_format, saved_model_filepath, output_folder, min_box_size, precision='fp32', batch_size=8, nms='hard',
-              nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep'):
-    """tta: a view set of bbox_utils.TTA_VIEWS; every image also goes through the network flipped / transposed and the views'
+              nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep', letterbox=False):
+    """letterbox: the images of the folder may differ in size; each is rescaled with its aspect ratio kept and padded to the model's
+    input on the device, and its boxes come back in its own pixels (YoloV3.predict_letterbox); not with tta.
+    tta: a view set of bbox_utils.TTA_VIEWS; every image also goes through the network flipped / transposed and the views'
     detections are pooled before the NMS.  tta_vote_iou: box voting over the pool at this IoU (None: the NMS
     alone); tta_score: 'keep' or 'consensus'.  'none' is the path without any of it."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     views = bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
+    if letterbox and tta != 'none':
+        raise ValueError('letterbox does not go with tta')
     os.makedirs(output_folder, exist_ok=True)
     if image_format.startswith('.'):
         image_format = image_format[1:]
@@ -48,6 +66,14 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
             print('{}/{} : {}'.format(g0 + i, len(img_filepath_list), os.path.split(img_filepath)[1]))
             img = imagereader.imread(img_filepath)
             imgs.append(img[:, :, None] if img.ndim == 2 else img)
+        if letterbox:
+            # --letterbox (extension): any sizes; the kernel has clipped the boxes to each image, --min-box-size is in its own pixels
+            dets, step = [], yolo.LETTERBOX_MAX_BATCH
+            for s0 in range(0, len(group), step):
+                rows, _ = yolo.predict_letterbox(imgs[s0:s0 + step])
+                dets += bbox_utils.detect(rows, min_box_size, clip_wh=None, method=nms, sigma=nms_sigma)
+            write_detections(group, dets, output_folder, image_format)
+            continue
         height, width, channels = imgs[0].shape
         if any(im.shape != imgs[0].shape for im in imgs):
             raise RuntimeError('images of one folder must share one size (the model input is fixed, Q18): {}'.format({im.shape for im in imgs}))
@@ -65,16 +91,7 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
                 rows = yolo.predict_tta(x[s0:s0 + step], views)              # [b, k * Nb, 5+K], boxes in the image's frame
                 dets += bbox_utils.detect_tta(rows, len(views), min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma,
                                               vote_iou=tta_vote_iou, score=tta_score)
-        for img_filepath, (boxes, scores, class_label, _) in zip(group, dets):
-            file_name = os.path.split(img_filepath)[1]
-            if boxes is None:                                             # the reference would crash here (Q11); write an empty csv
-                out = np.zeros((0, 5), np.int32)
-            else:
-                boxes[:, 2] = boxes[:, 2] - boxes[:, 0]
-                boxes[:, 3] = boxes[:, 3] - boxes[:, 1]
-                out = np.concatenate((boxes, class_label.reshape(-1, 1)), axis=-1).astype(np.int32)    # truncation (Q20)
-            print('Found: {} rois'.format(out.shape[0]))
-            bbox_utils.write_boxes_from_xywhc(out, os.path.join(output_folder, file_name.replace(image_format, 'csv')))
+        write_detections(group, dets, output_folder, image_format)
 
 
 if __name__ == '__main__':
@@ -96,7 +113,12 @@ if __name__ == '__main__':
                         help='--tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
     parser.add_argument('--tta-score', dest='tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
                         help='--tta with --tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
+    parser.add_argument('--letterbox', action='store_true',
+                        help='images of any size (extension): rescale each with its aspect ratio kept and pad it to the model input on '
+                        'the device; boxes and --min-box-size are in the image\'s own pixels (not with --tta)')
     a = parser.parse_args()
+    if a.letterbox and a.tta != 'none':
+        parser.error('--letterbox does not go with --tta')
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
         parser.error('--nms-sigma must be > 0')
     try:
@@ -109,4 +131,4 @@ if __name__ == '__main__':
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
     inference(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, a.min_box_size, a.precision, a.batch_size, a.nms, a.nms_sigma,
-              a.tta, a.tta_vote_iou, a.tta_score)
+              a.tta, a.tta_vote_iou, a.tta_score, a.letterbox)

@@ -156,6 +156,10 @@ SIGNATURES = {
     'y3_augment_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'y3_mosaic_batch': (i32, [fp, i32, i32, i32, i32, vp, fp, vp]),     # records: HOST pointer (augment.MOSAIC_RECORD)
     'y3_affine_batch': (i32, [fp, i32, i32, i32, i32, vp, fp, vp]),     # records: HOST pointer (augment.AFFINE_RECORD)
+    'y3_letterbox_batch': (i32, [vp, i32, i32, i32, vp, i32, i32, f32, fp, vp]),     # records: HOST pointer (letterbox.LETTERBOX_RECORD)
+    'y3_letterbox_zscore_nhwc': (i32, [vp, i32, i32, i32, vp, TP, vp, vp]),
+    'y3_letterbox_workspace_bytes': (sz, [i32, i32, i32, i32]),
+    'y3_letterbox_unmap': (i32, [fp, i32, i32, i32, vp, i32, vp]),
     'y3_format_labels': (i32, [ip, ip, i32, i32, C.POINTER(C.c_float), i32, i32, i32, i32, fp, fp, fp, vp]),
     'y3_eval_offsets':(i32, [ip, i32, i32, i32, ip, vp]),
     'y3_eval_match': (i32, [fp, i32, i32, i32, i32, f32, f32, ip, ip, fp, i32, i32, fp, ip, i32, i32, C.POINTER(C.c_float), i32, ip,

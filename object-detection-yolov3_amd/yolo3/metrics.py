@@ -627,22 +627,33 @@ def database_examples(path, num_shards=1, shard_index=0):
 
 
 def evaluate_examples(yolo, examples, evaluator, min_box_size, batch_size, precision=None, nms='hard', nms_sigma=0.5, tta='none',
-                      tta_vote_iou=None, tta_score='keep'):
+                      tta_vote_iou=None, tta_score='keep', letterbox=False):
     """Feeds (name, HWC image, [G,5] X,Y,W,H,C) examples through ``yolo`` (a YoloV3: per-image z-score -> predict ->
     clip -> small-box filter -> NMS, inference.py's path) into ``evaluator``, ``batch_size`` images per call, the short
     tail as one smaller call.  precision: predict()'s ('fp32' / 'bf16'; default yolo.inference_precision).  nms /
     nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time
     augmentation (bbox_utils.check_tta_args; DESIGN §3.15): the views of max(1, 16 // k) images per network call, each image's
     pooled and optionally voted detections matched as a device pool (add_pool with nms='none'); 'none' is the path above.
-    Returns the number of images added."""
+    letterbox: the images may differ in size; each is letterboxed into the model input on the device and its rows come back in its
+    own pixels, clipped (YoloV3.predict_letterbox, DESIGN §3.21; at most 16 images per network call), where the ground truth is;
+    not with tta.  Returns the number of images added."""
     if batch_size < 1:
         raise ValueError('batch_size must be >= 1')
     bbox_utils.check_nms_args(nms, nms_sigma)
     views = bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
+    if letterbox and tta != 'none':
+        raise ValueError('letterbox does not go with tta')
     batch, count = [], 0
 
     def flush():
         imgs = [b[1] for b in batch]
+        if letterbox:
+            step = yolo.LETTERBOX_MAX_BATCH
+            for s0 in range(0, len(batch), step):
+                rows, _ = yolo.predict_letterbox(imgs[s0:s0 + step], precision=precision)
+                evaluator.add_batch(rows, [b[2] for b in batch[s0:s0 + step]], min_box_size, clip_wh=None, nms=nms, nms_sigma=nms_sigma)
+            batch.clear()
+            return
         if any(im.shape != imgs[0].shape for im in imgs):
             raise RuntimeError('images must share one size (the model input is fixed): {}'.format({im.shape for im in imgs}))
         height, width = imgs[0].shape[:2]

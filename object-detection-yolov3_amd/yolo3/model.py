@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _hip
+from . import letterbox
 from . import streams
 from ._hip import lib, check, view, int_array, EPI_LRELU, EPI_ACCUM, CONV_X3, BF16_NO_PATCH
 
@@ -397,6 +398,7 @@ class _Plan:
         self.infer_graph = None
         self.infer_graph_tiles = None     # forward (without the input transpose) + decode, for predict_tiles
         self.zs_ws = None
+        self.lb_ws = None            # workspace of y3_letterbox_zscore_nhwc (predict_letterbox)
         self._build()
 
     # -- allocation helpers -------------------------------------------------
@@ -1063,6 +1065,7 @@ class YoloV3:
         self._bf16_stale = True
         self.dist = None                          # set by parallel.DataParallel.attach()
         self._plans = {}
+        self._lb_staging = {}        # slot -> pinned and device byte buffers of predict_letterbox
         self._tr_table = None
         self._fold_table = None
         self._adam_call = self._adam_launch()
@@ -1510,6 +1513,61 @@ class YoloV3:
             plan.run_inference(st, skip_input=True)
         check(lib.y3_tta_unmap(plan.boxes.data_ptr(), n * k, plan.nb, plan.boxes.shape[2], codes, k, h, w, st), 'y3_tta_unmap')
         return plan.boxes.view(n, k * plan.nb, plan.boxes.shape[2])
+
+    LETTERBOX_MAX_BATCH = letterbox.MAX_IMAGES     # images per call: Y3_LETTERBOX_MAX_IMAGES, and the batches the conv routes are tested for
+
+    def _letterbox_upload(self, images, slot):
+        """HWC NumPy images of any sizes, one dtype, the model's channel count -> (device byte buffer, dtype code, records): the images
+        packed at 16-byte aligned offsets into pinned staging and copied in one transfer; both buffers grow and are kept per slot."""
+        images = [np.ascontiguousarray(im[:, :, None] if im.ndim == 2 else im) for im in images]
+        if not 1 <= len(images) <= self.LETTERBOX_MAX_BATCH:
+            raise ValueError('predict_letterbox: {} images (1 .. {} per call)'.format(len(images), self.LETTERBOX_MAX_BATCH))
+        dt = images[0].dtype
+        if dt not in letterbox.DTYPE_CODES or any(im.dtype != dt for im in images):
+            raise ValueError('predict_letterbox: images must share one dtype of uint8, uint16, float32 (got {})'.format({str(im.dtype) for im in images}))
+        if any(im.ndim != 3 or im.shape[2] != self.img_size[2] for im in images):
+            raise ValueError('predict_letterbox: images must be HWC with the model\'s {} channels (got {})'.format(
+                self.img_size[2], [tuple(im.shape) for im in images]))
+        records, total = letterbox.pack_layout([im.shape for im in images], dt.itemsize, self.img_size[0], self.img_size[1])
+        st = self._lb_staging.setdefault(int(slot), {'dev': None, 'pin': None, 'done': None})
+        if st['done'] is not None:
+            st['done'].synchronize()          # the copy of the call before this one has left the pinned staging
+        if st['pin'] is None or st['pin'].numel() < total:
+            cap = max(total, 2 * (st['pin'].numel() if st['pin'] is not None else 0))
+            st['pin'] = torch.empty(cap, dtype=torch.uint8).pin_memory()
+            st['dev'] = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        host = st['pin'].numpy()
+        for im, rec in zip(images, records):
+            off = int(rec['src_offset'])
+            host[off:off + im.nbytes] = im.reshape(-1).view(np.uint8)
+        st['dev'][:total].copy_(st['pin'][:total], non_blocking=True)
+        st['done'] = torch.cuda.Event()
+        st['done'].record(torch.cuda.current_stream(self.device))
+        return st['dev'], letterbox.DTYPE_CODES[dt], records
+
+    def predict_letterbox(self, images, precision=None, slot=0):
+        """Letterbox inference: images: 1 .. 16 HWC NumPy arrays of ANY sizes, one dtype (uint8 / uint16 / float32) and
+        the model's channel count.  They are packed into one device byte buffer, resampled (antialiased, aspect ratio kept), padded
+        and z-scored on their own content straight into the plan's NHWC input (y3_letterbox_zscore_nhwc), go through the network as
+        one batch, and the decode rows are mapped back to each image's own pixels and clipped to it, in place
+        (y3_letterbox_unmap).  Returns (rows [n, Nb, 5+K], records): letterbox.LETTERBOX_RECORD of every image."""
+        src, code, records = self._letterbox_upload(images, slot)
+        n, c = len(records), self.img_size[2]
+        plan = self._plan(n, False, (precision or self.inference_precision) == 'bf16', slot)
+        st = self._stream()
+        if plan.lb_ws is None:
+            plan.lb_ws = torch.empty(int(lib.y3_letterbox_workspace_bytes(n, self.img_size[0], self.img_size[1], c)) // 8 + 2, dtype=torch.float64,
+                                     device=self.device)
+        check(lib.y3_letterbox_zscore_nhwc(src.data_ptr(), code, c, n, records.ctypes.data, plan.x0.v, plan.lb_ws.data_ptr(), st),
+              'y3_letterbox_zscore_nhwc')
+        if self.use_graph:
+            if plan.infer_graph_tiles is None:      # forward without the input transpose: the launches above wrote x0
+                plan.infer_graph_tiles = self._graph_of(functools.partial(plan.run_inference, skip_input=True))
+            plan.infer_graph_tiles.replay()
+        else:
+            plan.run_inference(st, skip_input=True)
+        check(lib.y3_letterbox_unmap(plan.boxes.data_ptr(), n, plan.nb, plan.boxes.shape[2], records.ctypes.data, 1, st), 'y3_letterbox_unmap')
+        return plan.boxes, records
 
     def feature_maps(self, images, training=False, precision=None):
         """The 'yolov3_fm' model (model.py:462): three NCHW feature maps (fp32 unless precision='bf16' is asked for)."""
