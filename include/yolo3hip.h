@@ -254,6 +254,28 @@ int y3_bn_bwd_apply_fanin(const y3_tensor* dy, const y3_tensor* a, const float* 
 int y3_bn_bwd_finalize_tiles(const float* partials, int tiles, int c, int count, const float* gamma,
                              const float* save_mean, const float* save_rstd, float alpha,
                              float* dgamma, float* dbeta, float* dbias, float* coef, y3_stream_t stream);
+/*
+ * The same backward with FROZEN statistics (no call site in the reference: fine-tuning).  Forward was
+ * y = a*scale + shift with scale = gamma / sqrt(moving_var + eps) and shift folded from the moving statistics
+ * (y3_bn_fold_inference*), so nothing of the batch enters the normalisation and ONE pass over dy and a does it all:
+ *   dz   = (dy * scale_c) * (a > 0 ? 1 : alpha)        two fp32 roundings, in this order
+ *   dres = dy (dres_accumulate == 0) or dres += dy      when dres is given: the residual fan-in of model.py:47
+ *   S1 = sum dy, S2 = sum dy*a, S3 = sum dz (the stored fp32 values): every term converted to fp64, summed in fp64 in a fixed order
+ *   dbeta = S1,  dgamma = (S2 - mean_c * S1) / sqrt(var_c + eps) in fp64,  dbias = S3,  each rounded to fp32 once.
+ * The sums are reduced inside the launch as in y3_bn_bwd_stats: fp64 partials in `workspace`, combined by the workgroup that
+ * arrives last, in an order that does not depend on which one that is -- no floating-point atomics, two launches give the same
+ * bits.  `workspace`: y3_bn_frozen_bwd_workspace(m, c) bytes, 16-byte aligned; its first 1 KiB (tickets) must be zero before the
+ * FIRST call and every call leaves it zero again.
+ * dy, a, dz (and dres): NHWC views of one geometry, any ld >= c; channels 4 / 8 / 16 or a multiple of 32 up to 1024.  Views whose
+ * ld is a multiple of 4 and whose base is 16-byte aligned are accessed 16 bytes at a time, otherwise element by element.  dz must
+ * not overlap dy, a or dres.  scale: 16-byte aligned.  Y3_EINVAL before any launch for a null pointer, an unsupported channel
+ * count, mismatched shapes, an overlapping dz, a too small or misaligned workspace, a non-finite eps.
+ */
+int y3_bn_frozen_bwd(const y3_tensor* dy, const y3_tensor* a, const y3_tensor* dres, int dres_accumulate,
+                     const float* scale, const float* moving_mean, const float* moving_var, float eps, float alpha,
+                     const y3_tensor* dz, float* dgamma, float* dbeta, float* dbias,
+                     void* workspace, size_t workspace_bytes, y3_stream_t stream);
+size_t y3_bn_frozen_bwd_workspace(int m, int c); /* 0 if the channel count is unsupported */
 
 /* ---- upsample_2x: frozen all-ones Conv2DTranspose k2 s2 (model.py:94-105) ---- */
 /* out[n,2i+a,2j+b,co] = sum_ci in[n,i,j,ci] for every co */

@@ -577,6 +577,260 @@ extern "C" int y3_bn_bwd_apply_fanin(const y3_tensor* dy, const y3_tensor* a, co
 }
 
 // ---------------------------------------------------------------------------
+// BatchNorm + leaky-relu backward with FROZEN statistics (fine-tuning)
+// ---------------------------------------------------------------------------
+// y = a*scale + shift with scale / shift folded from the moving statistics: nothing of the batch enters the normalisation, so
+// dz = dy*scale*slope(a) needs no reduction first and the two passes of the pair above (stats, then apply, each reading dy and a)
+// become one: dz (and the residual fan-in) are written while the three sums stream by.
+//   S1 = sum dy, S2 = sum dy*a, S3 = sum dz   (fp64; dy*a of two fp32 values is exact in fp64)
+//   dbeta = S1, dgamma = (S2 - mean*S1) / sqrt(var + eps), dbias = S3
+// Same decomposition as bn_bwd_stats_kernel (plan_bnb: channel slices of <= 32, a band of rows per workgroup, fp64 partials,
+// ticket, the last arrival of a slice sums its partials in a fixed order); half the sums, so half the LDS and partial traffic.
+#define Y3_BNZ_SUMS 3
+struct BnzArgs {
+    const float* dy;
+    const float* a;
+    float* dres;
+    float* dz;
+    double* partials;     // [slice][part][3][sw]
+    int* tickets;
+    const float* scale;
+    const float* mean;
+    const float* var;
+    float* dgamma;
+    float* dbeta;
+    float* dbias;
+    long long npix;
+    double eps;
+    int dy_ld, a_ld, dres_ld, dz_ld, dres_acc;
+    int lc, slices, parts;
+    float alpha;
+};
+template <bool VEC>
+__device__ __forceinline__ float4 bnz_load4(const float* q) {
+    if (VEC) return *reinterpret_cast<const float4*>(q);
+    return make_float4(q[0], q[1], q[2], q[3]);
+}
+template <bool VEC>
+__device__ __forceinline__ void bnz_store4(float* q, const float4 v) {
+    if (VEC) {
+        *reinterpret_cast<float4*>(q) = v;
+    } else {
+        q[0] = v.x;
+        q[1] = v.y;
+        q[2] = v.z;
+        q[3] = v.w;
+    }
+}
+// VEC: every view has ld % 4 == 0 and a 16-byte aligned base (16-byte accesses); otherwise element-wise accesses
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const BnzArgs p) {
+    __shared__ double sm[256 * 4 * Y3_BNZ_SUMS];
+    __shared__ int last_flag;
+    const int tid = threadIdx.x;
+    const int lc = p.lc, rgn = 256 / lc, sw = 4 * lc;
+    const int slice = blockIdx.x % p.slices, part = blockIdx.x / p.slices;
+    const int cq = tid % lc, rg = tid / lc;
+    const int c = slice * sw + cq * 4;
+    double acc[Y3_BNZ_SUMS][4];
+#pragma unroll
+    for (int j = 0; j < Y3_BNZ_SUMS; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j][e] = 0.0;
+    const float4 sc4 = *reinterpret_cast<const float4*>(p.scale + c);      // (per-channel arrays: 16-byte aligned, checked by the host)
+    const float scv[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
+    const float alpha = p.alpha;
+    const long long rows_per_block = (p.npix + p.parts - 1) / p.parts;
+    const long long r0 = (long long)part * rows_per_block;
+    long long r1 = r0 + rows_per_block;
+    if (r1 > p.npix) r1 = p.npix;
+    // one row: dz, the fan-in, the three sums.  Rows past the band come in as zeros, are not stored and leave the sums unchanged.
+    auto use_row = [&](long long row, bool in, const float4 d4, const float4 a4) {
+        const float dv[4] = {d4.x, d4.y, d4.z, d4.w}, av[4] = {a4.x, a4.y, a4.z, a4.w};
+        float zv[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float t = dv[e] * scv[e];                        // two roundings, in this order
+            zv[e] = t * (av[e] > 0.f ? 1.f : alpha);
+            const double d = (double)dv[e];
+            acc[0][e] += d;
+            acc[1][e] += d * (double)av[e];
+            acc[2][e] += in ? (double)zv[e] : 0.0;                 // (0 * a non-finite scale is no zero)
+        }
+        if (in) {
+            bnz_store4<VEC>(p.dz + row * p.dz_ld + c, make_float4(zv[0], zv[1], zv[2], zv[3]));
+            if (RES) {
+                float* q = p.dres + row * p.dres_ld + c;
+                float4 o = d4;
+                if (p.dres_acc) {
+                    const float4 t = bnz_load4<VEC>(q);
+                    o = make_float4(t.x + d4.x, t.y + d4.y, t.z + d4.z, t.w + d4.w);
+                }
+                bnz_store4<VEC>(q, o);
+            }
+        }
+    };
+    // four rows per trip, the next trip's loads issued before this trip's rows are used (as bn_bwd_stats_kernel)
+    const long long trip = 4LL * rgn;
+    long long r = r0 + rg;
+    float4 d4[2][4], a4[2][4];
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto load_trip = [&](int b, long long row) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long ru = row + (long long)u * rgn;
+            const bool in = ru < r1;
+            d4[b][u] = in ? bnz_load4<VEC>(p.dy + ru * p.dy_ld + c) : zero4;
+            a4[b][u] = in ? bnz_load4<VEC>(p.a + ru * p.a_ld + c) : zero4;
+        }
+    };
+    auto use_trip = [&](int b, long long row) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long ru = row + (long long)u * rgn;
+            use_row(ru, ru < r1, d4[b][u], a4[b][u]);
+        }
+    };
+    const long long ntrips = r < r1 ? (r1 - r + trip - 1) / trip : 0;
+    if (ntrips > 0) {
+        load_trip(0, r);
+        long long t = 0;
+        for (; t + 2 < ntrips; t += 2) {
+            load_trip(1, r + trip);
+            use_trip(0, r);
+            load_trip(0, r + 2 * trip);
+            use_trip(1, r + trip);
+            r += 2 * trip;
+        }
+        if (t + 1 < ntrips) {
+            load_trip(1, r + trip);
+            use_trip(0, r);
+            use_trip(1, r + trip);
+        } else {
+            use_trip(0, r);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        double* q = sm + tid * (4 * Y3_BNZ_SUMS) + e;
+        q[0] = acc[0][e];
+        q[4] = acc[1][e];
+        q[8] = acc[2][e];
+    }
+    __syncthreads();
+    // sum the row groups in a fixed order: output o = (sum j, channel ch of the slice)
+    double* mine = p.partials + ((long long)slice * p.parts + part) * (Y3_BNZ_SUMS * sw);
+    for (int o = tid; o < Y3_BNZ_SUMS * sw; o += 256) {
+        const int j = o / sw, ch = o - j * sw;
+        const double* q = sm + (ch >> 2) * (4 * Y3_BNZ_SUMS) + j * 4 + (ch & 3);
+        double s = q[0];
+        for (int g = 1; g < rgn; ++g) s += q[(long long)g * lc * (4 * Y3_BNZ_SUMS)];
+        __hip_atomic_store(mine + o, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // sc1: written through to where every XCD sees it
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const int old = __hip_atomic_fetch_add(p.tickets + slice, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = old == p.parts - 1;
+        if (last) __hip_atomic_store(p.tickets + slice, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last_flag = last;
+    }
+    __syncthreads();
+    if (last_flag == 0) return;
+
+    // ---- the slice's last arrival.  Thread = (channel, part lane): lane pl sums parts pl, pl + pln, ... in that order, then the
+    // lanes are added in lane order.  Which workgroup does this has no say in the order: two launches give the same bits.
+    const int ch = tid % sw, pl = tid / sw, pln = 256 / sw;
+    const double* base = p.partials + (long long)slice * p.parts * (Y3_BNZ_SUMS * sw);
+    double t[Y3_BNZ_SUMS] = {0.0, 0.0, 0.0};
+    for (int q = pl; q < p.parts; q += pln)
+#pragma unroll
+        for (int j = 0; j < Y3_BNZ_SUMS; ++j)
+            t[j] += __hip_atomic_load(base + ((long long)q * Y3_BNZ_SUMS + j) * sw + ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (`sm` was last read before the barriers around the ticket)
+#pragma unroll
+    for (int j = 0; j < Y3_BNZ_SUMS; ++j) sm[(pl * Y3_BNZ_SUMS + j) * sw + ch] = t[j];
+    __syncthreads();
+    if (tid < sw) {
+        double s[Y3_BNZ_SUMS];
+#pragma unroll
+        for (int j = 0; j < Y3_BNZ_SUMS; ++j) {
+            s[j] = sm[j * sw + tid];
+            for (int g = 1; g < pln; ++g) s[j] += sm[(g * Y3_BNZ_SUMS + j) * sw + tid];
+        }
+        const int cc = slice * sw + tid;
+        const double mu = (double)p.mean[cc], sd = sqrt((double)p.var[cc] + p.eps);
+        p.dbeta[cc] = (float)s[0];
+        p.dgamma[cc] = (float)((s[1] - mu * s[0]) / sd);
+        p.dbias[cc] = (float)s[2];
+    }
+}
+
+extern "C" size_t y3_bn_frozen_bwd_workspace(int m, int c) {
+    BnbPlan p;
+    if (m < 1 || !plan_bnb(m, c, &p)) return 0;
+    return (size_t)Y3_BNB_TICKETS + (size_t)p.parts * p.slices * Y3_BNZ_SUMS * p.sw * sizeof(double);
+}
+
+// byte range [lo, hi) a view touches
+static inline void view_range(const y3_tensor* t, uintptr_t* lo, uintptr_t* hi) {
+    *lo = (uintptr_t)t->ptr;
+    *hi = *lo + (size_t)((pixels(t) - 1) * t->ld + t->c) * sizeof(float);
+}
+static inline bool views_overlap(const y3_tensor* x, const y3_tensor* y) {
+    uintptr_t xl, xh, yl, yh;
+    view_range(x, &xl, &xh);
+    view_range(y, &yl, &yh);
+    return xl < yh && yl < xh;
+}
+static inline bool view_vec4(const y3_tensor* t) { return (t->ld & 3) == 0 && ((uintptr_t)t->ptr & 15) == 0; }
+
+extern "C" int y3_bn_frozen_bwd(const y3_tensor* dy, const y3_tensor* a, const y3_tensor* dres, int dres_accumulate, const float* scale,
+                                const float* moving_mean, const float* moving_var, float eps, float alpha, const y3_tensor* dz, float* dgamma,
+                                float* dbeta, float* dbias, void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    if (int e = check_view(dy, "bn_frozen_bwd dy")) return e;
+    if (int e = check_view(a, "bn_frozen_bwd a")) return e;
+    if (int e = check_view(dz, "bn_frozen_bwd dz")) return e;
+    Y3_CHECK_ARG(same_geom(dy, a) && same_geom(dy, dz), "bn_frozen_bwd: dy / a / dz geometry");
+    Y3_CHECK_ARG(scale && moving_mean && moving_var && dgamma && dbeta && dbias && workspace, "bn_frozen_bwd: null pointer");
+    Y3_CHECK_ARG(((uintptr_t)scale & 15) == 0, "bn_frozen_bwd: scale must be 16-byte aligned");
+    Y3_CHECK_ARG(eps == eps && eps - eps == 0.f, "bn_frozen_bwd: eps must be finite");
+    if (dres) {
+        if (int e = check_view(dres, "bn_frozen_bwd dres")) return e;
+        Y3_CHECK_ARG(same_geom(dy, dres), "bn_frozen_bwd: dres geometry");
+        Y3_CHECK_ARG(!views_overlap(dz, dres), "bn_frozen_bwd: dz overlaps dres");
+    }
+    Y3_CHECK_ARG(!views_overlap(dz, dy) && !views_overlap(dz, a), "bn_frozen_bwd: dz overlaps dy or a");
+    BnbPlan pl;
+    Y3_CHECK_ARG(plan_bnb(pixels(a), a->c, &pl), "bn_frozen_bwd: channels %d unsupported (4 / 8 / 16, or a multiple of 32 up to 1024)", a->c);
+    const size_t need = (size_t)Y3_BNB_TICKETS + (size_t)pl.parts * pl.slices * Y3_BNZ_SUMS * pl.sw * sizeof(double);
+    Y3_CHECK_ARG(workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0, "bn_frozen_bwd: workspace %zu bytes, %zu needed (16-byte aligned)",
+                 workspace_bytes, need);
+    BnzArgs p;
+    p.dy = dy->ptr; p.a = a->ptr; p.dres = dres ? dres->ptr : nullptr; p.dz = dz->ptr;
+    p.tickets = reinterpret_cast<int*>(workspace);
+    p.partials = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + Y3_BNB_TICKETS);
+    p.scale = scale; p.mean = moving_mean; p.var = moving_var;
+    p.dgamma = dgamma; p.dbeta = dbeta; p.dbias = dbias;
+    p.npix = pixels(a); p.eps = (double)eps;
+    p.dy_ld = dy->ld; p.a_ld = a->ld; p.dres_ld = dres ? dres->ld : 0; p.dz_ld = dz->ld; p.dres_acc = dres_accumulate;
+    p.lc = pl.lc; p.slices = pl.slices; p.parts = pl.parts;
+    p.alpha = alpha;
+    const bool vec = view_vec4(dy) && view_vec4(a) && view_vec4(dz) && (!dres || view_vec4(dres));
+    const dim3 grid(pl.parts * pl.slices), block(256);
+    if (dres && vec)
+        hipLaunchKernelGGL((bn_frozen_bwd_kernel<true, true>), grid, block, 0, (hipStream_t)stream, p);
+    else if (dres)
+        hipLaunchKernelGGL((bn_frozen_bwd_kernel<true, false>), grid, block, 0, (hipStream_t)stream, p);
+    else if (vec)
+        hipLaunchKernelGGL((bn_frozen_bwd_kernel<false, true>), grid, block, 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL((bn_frozen_bwd_kernel<false, false>), grid, block, 0, (hipStream_t)stream, p);
+    Y3_CHECK_LAUNCH("bn_frozen_bwd");
+    return Y3_OK;
+}
+
+// ---------------------------------------------------------------------------
 // upsample_2x = frozen all-ones Conv2DTranspose(k2,s2): a channel sum, broadcast
 // ---------------------------------------------------------------------------
 // one wave per input pixel

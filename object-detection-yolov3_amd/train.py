@@ -229,6 +229,17 @@ def build_lr_schedule(lr_schedule='reference', warmup_steps=0, warmup_start_fact
     return LrSchedule(lr_schedule, warmup_steps, warmup_start_factor, total_steps, final_factor, tuple(milestones), gamma)
 
 
+def describe_freeze(specs, freeze_layers, freeze_bn):
+    """The line train_model prints about a fine-tuning run: how many layers and parameters are frozen and how many train."""
+    count = lambda sp: sp.k * sp.k * sp.cin * sp.cout + sp.cout * (3 if sp.bn else 1)
+    frozen = sum(count(sp) for sp in specs[:freeze_layers])
+    total = sum(count(sp) for sp in specs)
+    return ('Fine-tuning: {} of {} layers frozen ({} parameters, BatchNorm on the stored statistics), {} layers train ({} parameters); '
+            'BatchNorm of the trainable layers uses {}'.format(freeze_layers, len(specs), frozen, len(specs) - freeze_layers, total - frozen,
+                                                                'the stored statistics, which stay (gamma and beta train)' if freeze_bn
+                                                                else 'batch statistics'))
+
+
 def train_model(batch_size, test_every_n_steps, train_database_filepath, test_database_filepath, output_folder, early_stopping_count,
                 learning_rate, use_augmentation, max_epochs=None, reader_count=None, backend='nccl', augmentation_device='cpu',
                 test_map=False, model_selection='loss', test_map_min_box_size=32, ema_decay=0.0, test_map_nms='hard', test_map_nms_sigma=0.5,
@@ -238,8 +249,14 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9, nesterov=False, weight_decay=0.0, lr_schedule='reference',
                 lr_warmup_steps=0, lr_warmup_start_factor=0.0, lr_total_steps=None, lr_final_factor=0.01, lr_milestones=(), lr_gamma=0.1,
                 affine_prob=0.0, affine_degrees=10.0, affine_shear=2.0, affine_scale=0.1, affine_translate=0.1, affine_fill=0.0, affine_seed=0,
-                affine_min_visible=0.25):
+                affine_min_visible=0.25, init_weights=None, init_optimizer=False, freeze_layers=0, freeze_bn=False):
     spp_kw = dict(spp=True) if spp else {}
+    from yolo3.model import check_freeze_args
+    check_freeze_args(freeze_layers, freeze_bn)
+    if init_optimizer and not init_weights:
+        raise ValueError('init_optimizer needs init_weights: there is no file to take the optimiser state from')
+    # fine-tuning: settings of this run, not of the network -- the export below is built without them
+    freeze_kw = dict(freeze_layers=int(freeze_layers), freeze_bn=bool(freeze_bn)) if freeze_layers or freeze_bn else {}
     schedule = build_lr_schedule(lr_schedule, lr_warmup_steps, lr_warmup_start_factor, lr_total_steps, lr_final_factor, lr_milestones, lr_gamma)
     from yolo3.model import check_optimizer_args
     check_optimizer_args(optimizer, momentum, nesterov, weight_decay, schedule)
@@ -350,7 +367,19 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
                             grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args,
-                            **focal_kw, **spp_kw, **optim_kw, **(dict(lr_schedule=schedule) if schedule is not None else {}))
+                            **focal_kw, **spp_kw, **optim_kw, **(dict(lr_schedule=schedule) if schedule is not None else {}), **freeze_kw)
+        if init_weights:
+            # every rank reads the same file, so the replicas start equal (the broadcast below then changes nothing)
+            if init_optimizer:
+                yolo.load_weights(init_weights, load_optimizer=True)      # (refuses another network or optimiser)
+                print('Initial weights, optimiser moments and step count ({}) from {}; the epoch counter, the early-stopping history and '
+                      'the EMA start fresh'.format(yolo.iterations, init_weights))
+            else:
+                kept = yolo.load_pretrained(init_weights)
+                print('Initial weights from {}: {} of {} layers loaded, {} keep their initialisation; optimiser state and step count start '
+                      'fresh'.format(init_weights, len(yolo.specs) - len(kept), len(yolo.specs), kept if kept else 'none'))
+        if freeze_kw:
+            print(describe_freeze(yolo.specs, yolo.freeze_layers, yolo.freeze_bn))
         if optimizer != 'adam' or schedule is not None:
             print('Optimizer: {}{}, weight decay {:g} on the convolution kernels; learning-rate schedule: {}'.format(
                 optimizer, ' (momentum {:g}{})'.format(momentum, ', Nesterov' if nesterov else '') if optimizer == 'sgd' else '', weight_decay,
@@ -718,6 +747,19 @@ def _multiscale_period_arg(text):
     return v
 
 
+def _freeze_layers_arg(text):
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError('an integer >= 0, got {!r}'.format(text))
+    if v < 0:
+        raise argparse.ArgumentTypeError('an integer >= 0, got {!r}'.format(text))
+    return v
+
+
+FREEZE_NAMES = {'backbone': 52}      # yolo3.model.BACKBONE_LAYERS restated: parsing loads no device library
+
+
 class _Parser(argparse.ArgumentParser):
     """The checks that span several flags: an argparse error like any other."""
 
@@ -752,6 +794,12 @@ class _Parser(argparse.ArgumentParser):
         # (yolo3.model.check_optimizer_args restated, as above)
         if a.optimizer == 'adam' and a.weight_decay > 0:
             self.error("--weight_decay needs --optimizer adamw or sgd: adam is the reference's Keras Adam, which has none")
+        if a.freeze is not None:
+            if a.freeze_layers not in (0, FREEZE_NAMES[a.freeze]):
+                self.error('--freeze {} means --freeze_layers {}, got --freeze_layers {}'.format(a.freeze, FREEZE_NAMES[a.freeze], a.freeze_layers))
+            a.freeze_layers = FREEZE_NAMES[a.freeze]
+        if a.init_optimizer and not a.init_weights:
+            self.error('--init_optimizer 1 needs --init_weights')
         try:
             build_lr_schedule(a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor, a.lr_milestones,
                               a.lr_gamma)
@@ -882,6 +930,22 @@ def build_parser():
                         help='(addition) optimiser steps, strictly increasing, at each of which --lr_schedule step multiplies the rate by --lr_gamma')
     parser.add_argument('--lr_gamma', dest='lr_gamma', type=_lr_gamma_arg, default=0.1,
                         help='(addition) factor of --lr_schedule step per milestone (default 0.1)')
+    parser.add_argument('--init_weights', dest='init_weights', type=str, default=None,
+                        help='(addition) start from this weight file (written by a training run or save_weights) instead of random weights: '
+                             'layers are matched by role, the class count, anchors, batch size, learning rate and optimiser may differ, a '
+                             'detection head of another shape keeps its initialisation; every rank reads the file')
+    parser.add_argument('--init_optimizer', dest='init_optimizer', type=int, choices=(0, 1), default=0,
+                        help='(addition) 1: with --init_weights, also restore the optimiser moments and step count, so that a learning-rate '
+                             'schedule continues (the file must hold the same network and optimiser); the epoch counter, the early-stopping '
+                             'history and the EMA start fresh all the same')
+    parser.add_argument('--freeze_layers', dest='freeze_layers', type=_freeze_layers_arg, default=0,
+                        help='(addition) 0 (default): every layer trains; N: the first N conv layers are not trainable, their BatchNorm '
+                             'included (as Keras layer.trainable = False): no gradients, no optimiser step, no weight decay for them')
+    parser.add_argument('--freeze', dest='freeze', choices=tuple(FREEZE_NAMES), default=None,
+                        help='(addition) backbone: the same as --freeze_layers 52, the Darknet-53 layers in front of the first yolo block')
+    parser.add_argument('--freeze_bn', dest='freeze_bn', type=int, choices=(0, 1), default=0,
+                        help='(addition) 1: the BatchNorm of the trainable layers normalises with the stored moving statistics, which are '
+                             'not updated; gamma and beta keep training (for batches too small to estimate statistics from)')
     return parser
 
 
@@ -898,4 +962,4 @@ if __name__ == "__main__":
                 a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing, bool(a.spp), a.optimizer, a.momentum, bool(a.nesterov),
                 a.weight_decay, a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor,
                 tuple(a.lr_milestones), a.lr_gamma, a.affine_prob, a.affine_degrees, a.affine_shear, a.affine_scale, a.affine_translate,
-                a.affine_fill, a.affine_seed, a.affine_min_visible)
+                a.affine_fill, a.affine_seed, a.affine_min_visible, a.init_weights, bool(a.init_optimizer), a.freeze_layers, bool(a.freeze_bn))

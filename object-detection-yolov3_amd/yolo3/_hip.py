@@ -88,6 +88,8 @@ SIGNATURES = {
     'y3_bn_bwd_apply': (i32, [TP, TP, fp, f32, TP, vp]),
     'y3_bn_bwd_apply_fanin': (i32, [TP, TP, fp, f32, TP, TP, i32, vp]),
     'y3_bn_bwd_finalize_tiles': (i32, [fp, i32, i32, i32, fp, fp, fp, f32, fp, fp, fp, fp, vp]),
+    'y3_bn_frozen_bwd': (i32, [TP, TP, TP, i32, fp, fp, fp, f32, f32, TP, fp, fp, fp, vp, sz, vp]),
+    'y3_bn_frozen_bwd_workspace': (sz, [i32, i32]),
     'y3_upsample_sum2x_fwd': (i32, [TP, TP, vp]),
     'y3_upsample_sum2x_bwd': (i32, [TP, TP, vp]),
     'y3_spp_fwd': (i32, [TP, TP, vp]),

@@ -187,6 +187,37 @@ def decay_ranges(specs):
     return [(sp.w_off, sp.w_off + sp.k * sp.k * sp.cin_pad * sp.cout) for sp in specs]
 
 
+BACKBONE_LAYERS = 52      # the conv layers of Darknet-53 in front of the first yolo block: what `--freeze backbone` names
+
+
+def check_freeze_args(freeze_layers=0, freeze_bn=False, n_layers=None):
+    """Host-side validation of the fine-tuning settings: ValueError unless freeze_layers is an integer with
+    0 <= freeze_layers < n_layers (n_layers None: the upper end is not checked) and freeze_bn is a boolean."""
+    n = freeze_layers
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+        raise ValueError('freeze_layers must be an integer, got {!r}'.format(freeze_layers))
+    if n < 0 or (n_layers is not None and n >= n_layers):
+        raise ValueError('freeze_layers must be in [0, {}): at least the last layer trains, got {!r}'.format(
+            n_layers if n_layers is not None else 'number of layers', freeze_layers))
+    if not (isinstance(freeze_bn, (bool, np.bool_)) or (isinstance(freeze_bn, (int, np.integer)) and freeze_bn in (0, 1))):
+        raise ValueError('freeze_bn must be False or True, got {!r}'.format(freeze_bn))
+
+
+def trainable_suffix(specs, arena_floats, freeze_layers=0):
+    """(offset, count) in floats of the part of the parameter arena that trains with layers 0 .. freeze_layers - 1 frozen: the
+    arena is in creation order, so it is the suffix from specs[freeze_layers].w_off on.  Every per-arena pass of a step (the
+    optimiser, accumulation, norm, weight refresh, all-reduce) runs over it; the offset is a multiple of ALIGN floats."""
+    off = specs[freeze_layers].w_off
+    return off, arena_floats - off
+
+
+def suffix_decay_ranges(specs, freeze_layers=0):
+    """decay_ranges of the trainable layers, relative to the start of the trainable suffix (trainable_suffix): the table
+    y3_optim_step gets when its arenas are passed from that offset on.  Frozen kernels are in no range: decay cannot shrink them."""
+    off = specs[freeze_layers].w_off
+    return [(lo - off, hi - off) for lo, hi in decay_ranges(specs[freeze_layers:])]
+
+
 def check_train_sizes(img_size, train_sizes):
     """Host-side validation of the network input sizes train_step / test_step accept (multi-scale training).  None:
     the constructed size only, returned as [(H, W)].  Otherwise a list of (H, W), each a positive multiple of 32; the constructed
@@ -304,6 +335,34 @@ def spp_transfer_map(specs):
     return [None if i == fresh[0] else i - (i > fresh[0]) for i in range(len(specs))]
 
 
+def pretrained_map(specs, spp, file_shapes, file_spp):
+    """How load_pretrained fills a model (spec list `specs`, SPP or not) from a weight file whose layers have the kernel shapes
+    `file_shapes` ((k, k, Cin, Cout) each, creation order) and which holds the SPP network or not.  Returns (mapping, kept):
+    mapping[i] = the file's layer with the role of model layer i, or None where the layer keeps its initialisation; kept = those i.
+    Layers are matched by role: the same index, or spp_transfer_map for a plain file and an SPP model.  A detection head (bn=False)
+    whose shape differs -- another class count or anchor count -- keeps its initialisation; any other difference is refused:
+    ValueError for an SPP file and a plain model, another input channel count, another layer count or body shape."""
+    if file_spp and not spp:
+        raise ValueError('load_pretrained: the file holds the SPP network and this model is plain (spp=False): the layer behind the '
+                         'pools has no place to go')
+    mapping = spp_transfer_map(specs) if spp and not file_spp else list(range(len(specs)))
+    if len(file_shapes) != 1 + max(j for j in mapping if j is not None):
+        raise ValueError('load_pretrained: the file has {} layers, this model needs {}'.format(len(file_shapes), 1 + max(j for j in mapping if j is not None)))
+    if tuple(file_shapes[0])[2] != specs[0].cin:
+        raise ValueError('load_pretrained: the file was trained on {} input channels, this model reads {}'.format(tuple(file_shapes[0])[2], specs[0].cin))
+    kept = []
+    for i, sp in enumerate(specs):
+        j = mapping[i]
+        if j is None:
+            kept.append(i)
+        elif tuple(int(v) for v in file_shapes[j]) != (sp.k, sp.k, sp.cin, sp.cout):
+            if sp.bn:
+                raise ValueError('load_pretrained: layer {} is {} in the file and {} in this model'.format(i, tuple(file_shapes[j]), (sp.k, sp.k, sp.cin, sp.cout)))
+            mapping[i] = None
+            kept.append(i)
+    return mapping, kept
+
+
 class _T:
     """An NHWC activation (or a channel slice of one) plus its gradient twin."""
 
@@ -316,6 +375,12 @@ class _T:
         self.gw = False           # gradient already holds a contribution (next writer accumulates)
         self.children = []
         self.parent = None
+        self.frozen = False       # written by a frozen layer (or the image): it gets no gradient
+
+    @property
+    def no_grad(self):
+        """No gradient is wanted for this activation: its producer is frozen, or it is a concat whose producers all are."""
+        return self.frozen or (bool(self.children) and all(ch.frozen for ch in self.children))
 
     @property
     def m(self):
@@ -460,7 +525,12 @@ class _Plan:
         li = [0]
 
         x0 = self._new(N, H, W, specs[0].cin_pad, zero=True)
+        x0.frozen = True
         self.x0 = x0                      # the network's NHWC input (channels padded to 4): predict_tiles writes it directly
+        # fine-tuning, training plans only: layers 0 .. nfrozen - 1 run as in inference and leave nothing for
+        # backward; fbn: the BatchNorm of the trainable layers normalises with the moving statistics
+        nfrozen = mdl.freeze_layers if tr else 0
+        fbn = tr and mdl.freeze_bn
         self._emit(self.fwd, lib.y3_nchw_to_nhwc, self.in_nchw.data_ptr(), N, C, H, W, x0.v)
 
         # shared workspaces.  The largest M*Cout of the net is conv1's (full resolution, FILTER_COUNT/32
@@ -475,6 +545,13 @@ class _Plan:
             # inference-mode BatchNorm (training=False, model.py:38): moving statistics folded into scale / shift, all layers at once
             self._emit(self.fwd, lib.y3_bn_fold_inference_batched, P.data_ptr(), mdl.moving.data_ptr(), mdl.chan.data_ptr(),
                        mdl.fold_table().data_ptr(), mdl.fold_layers, BN_EPS)
+        if nfrozen or fbn:
+            # scale / shift of the layers that normalise with the moving statistics, folded once per step so that they follow
+            # set_weights / load_pretrained and, with freeze_bn, the gamma / beta of the step before.  The table is in creation
+            # order: the frozen prefix is its first rows, freeze_bn takes all of them.
+            rows = sum(1 for sp in specs if sp.bn) if fbn else sum(1 for sp in specs[:nfrozen] if sp.bn)
+            self._emit(self.fwd, lib.y3_bn_fold_inference_batched, P.data_ptr(), mdl.moving.data_ptr(), mdl.chan.data_ptr(),
+                       mdl.fold_table().data_ptr(), rows, BN_EPS)
         if tr:
             self.dz = torch.empty(max_mc, dtype=torch.float32, device=dev)
             # y3_bn_bwd_workspace(): 1 KiB of tickets (zero before the first launch) + <= 512 x 6 x 64 fp64 partials
@@ -488,7 +565,10 @@ class _Plan:
             sp = specs[i]
             oh, ow = -(-src.h // sp.s), -(-src.w // sp.s)
             y = out if out is not None else self._new(N, oh, ow, sp.cout, dtype=act)
-            a = self._new(N, oh, ow, sp.cout) if tr else None      # the convolution's own output: BatchNorm reads it again in backward
+            frozen = i < nfrozen                                   # runs as in inference: no `a`, no statistics, no record for backward
+            y.frozen = frozen
+            train = tr and not frozen
+            a = self._new(N, oh, ow, sp.cout) if train else None   # the convolution's own output: BatchNorm reads it again in backward
             rv = resid.v if resid is not None else None
             ch = self._at(mdl.chan, sp.ch_off)       # per-layer [scale|shift|mean|rstd|coef(3)] block
             cs = sp.cout * 4
@@ -496,14 +576,20 @@ class _Plan:
             # fp32 arithmetic as three bf16 pieces per operand (conv_x3.hip) for the launches the model's policy names.  The gradients
             # have their activations' geometry, which is all the data-gradient query reads; the first layer has no data gradient.
             x3 = _Layer(CONV_X3 if not bf and mdl.x3_forward(sp, N * oh * ow) else 0,
-                        CONV_X3 if tr and src is not x0 and mdl.x3_dgrad(a.v, sp.k, sp.s, src.v) else 0,
-                        CONV_X3 if tr and mdl.x3_wgrad(sp, N * oh * ow) else 0, (smean, srstd, coef))
+                        CONV_X3 if train and not src.no_grad and mdl.x3_dgrad(a.v, sp.k, sp.s, src.v) else 0,
+                        CONV_X3 if train and mdl.x3_wgrad(sp, N * oh * ow) else 0, (smean, srstd, coef))
             if x3.fwd:
                 self.x3_fwd.append(i)
             # the x3 kernel wants the copy of the weights with K contiguous per output column, i.e. the three bf16 planes of the
             # TRANSPOSED kernel in the forward pass
             wfwd = self._at(mdl.planes_t, sp.w_off) if x3.fwd else ptr(sp.w_off)
-            if tr:
+            if train and fbn:
+                # frozen statistics: the batch's are not collected; scale / shift come from the fold at the head of the list
+                self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, wfwd, ptr(sp.b_off), sp.k, sp.s, a.v, EPI_LRELU | x3.fwd,
+                                LRELU_ALPHA, None, None, None, None)
+                self._emit(self.fwd, lib.y3_bn_apply, a.v, scale, shift, rv, y.v)
+                self.ops.append(('conv_layer', i, src, a, y, resid, x3))
+            elif train:
                 tiles = lib.y3_conv2d_stats_tiles_x(a.m, sp.cin_pad, sp.k, sp.cout, x3.fwd)
                 assert tiles * 2 * sp.cout <= self.stats_ws.numel()
                 self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, wfwd, ptr(sp.b_off), sp.k, sp.s, a.v, EPI_LRELU | x3.fwd,
@@ -552,7 +638,9 @@ class _Plan:
             x = conv_layer(inp, out=cat.slice(0, c))
             pools = cat.slice(c, 3 * c)
             self._emit(self.fwd, lib.y3_spp_fwd_bf16 if bf else lib.y3_spp_fwd, x.v, pools.v)
-            self.ops.append(('spp', x, cat, pools))
+            pools.frozen = x.frozen
+            if not x.frozen:
+                self.ops.append(('spp', x, cat, pools))
             return conv_layer(cat)
 
         def yolo_block(inp, spp=False):
@@ -573,12 +661,15 @@ class _Plan:
                                 None, None, None)
                 return fm
             self._conv_call(self.fwd, lib.y3_conv2d_fwd, src.v, ptr(sp.w_off), ptr(sp.b_off), 1, 1, fm.v, 0, 0.0, None, None, None, None)
-            self.ops.append(('head', i, src, fm, _Layer(0, 0, 0, None)))      # the heads stay on the fp32 kernels
+            if i >= nfrozen:
+                self.ops.append(('head', i, src, fm, _Layer(0, 0, 0, None)))      # the heads stay on the fp32 kernels
             return fm
 
         def upsample_into(src, dst):
             self._emit(self.fwd, lib.y3_upsample_sum2x_fwd_bf16 if bf else lib.y3_upsample_sum2x_fwd, src.v, dst.v)
-            self.ops.append(('upsample', src, dst))
+            dst.frozen = src.no_grad      # (no parameters of its own: frozen with its producer)
+            if not dst.frozen:
+                self.ops.append(('upsample', src, dst))
 
         FC = YoloV3.FILTER_COUNT
         g1h, g1w = H // 32, W // 32
@@ -740,7 +831,7 @@ class _Plan:
                 for ch in t.children:
                     first_consumer.setdefault(id(ch), op)
         for op in self.ops:
-            if op[0] != 'conv_layer':
+            if op[0] != 'conv_layer' or mdl.freeze_bn:      # (frozen statistics need no moments of dy: y3_bn_frozen_bwd, below)
                 continue
             a, y = op[3], op[4]
             cons = first_consumer.get(id(y))
@@ -774,9 +865,10 @@ class _Plan:
                 dfm = fm.grad
                 self._emit(self.bwd, lib.y3_colsum, dfm.v, gptr(sp.b_off))
                 head_wg = self._kernel_grad(lib.y3_conv2d_wgrad, src.v, dfm.v, 1, 1, gptr(sp.w_off))
-                ds = self._grad_of(src)
-                self._conv_call(self.bwd, lib.y3_conv2d_dgrad, dfm.v, self._at(mdl.params_t, sp.w_off), 1, 1, ds.v, EPI_ACCUM if src.gw else 0)
-                src.mark_written()
+                if not src.no_grad:
+                    ds = self._grad_of(src)
+                    self._conv_call(self.bwd, lib.y3_conv2d_dgrad, dfm.v, self._at(mdl.params_t, sp.w_off), 1, 1, ds.v, EPI_ACCUM if src.gw else 0)
+                    src.mark_written()
                 self.bwd.append(('layer_done', i))
             elif kind == 'upsample':
                 _, src, dst = op
@@ -798,7 +890,7 @@ class _Plan:
                 dy = y.grad
                 dr = None
                 dr_acc = 0
-                if resid is not None:                       # out = resid + y  ->  d resid += d out, fused into the pass that reads dy anyway
+                if resid is not None and not resid.no_grad:     # out = resid + y  ->  d resid += d out, fused into the pass that reads dy anyway
                     dr = self._grad_of(resid)
                     dr_acc = 1 if resid.gw else 0
                     resid.mark_written()
@@ -807,7 +899,15 @@ class _Plan:
                 dz = _T(dz_bufs[slot], a.n, a.h, a.w, sp.cout)
                 self.keep.append(dz)
                 epi = epi_for.get(id(op))
-                if epi is not None:
+                if mdl.freeze_bn:
+                    # frozen statistics: dz, the residual fan-in, dgamma / dbeta / dbias in ONE pass over dy and a (it writes dz: the
+                    # kernel gradient of two layers ago must have left the buffer)
+                    assert int(lib.y3_bn_frozen_bwd_workspace(a.m, sp.cout)) <= self.bnb_ws.numel()
+                    self._main_wait(dz_busy[slot])
+                    self._emit(self.bwd, lib.y3_bn_frozen_bwd, dy.v, a.v, dr.v if dr is not None else None, dr_acc,
+                               self._at(mdl.chan, sp.ch_off), self._at(mdl.moving, sp.mv_off), self._at(mdl.moving, mdl.moving_stride + sp.mv_off),
+                               BN_EPS, LRELU_ALPHA, dz.v, gptr(sp.g_off), gptr(sp.be_off), gptr(sp.b_off), self.bnb_ws.data_ptr(), self.bnb_ws.numel())
+                elif epi is not None:
                     # the statistics were summed by the data gradient that completed dy: finalize, then apply (+ residual fan-in)
                     part, tiles = epi
                     self._emit(self.bwd, lib.y3_bn_bwd_finalize_tiles, part.data_ptr(), tiles, sp.cout, a.m, self._at(mdl.params, sp.g_off),
@@ -817,16 +917,17 @@ class _Plan:
                     self._emit(self.bwd, lib.y3_bn_bwd_stats, dy.v, a.v, dr.v if dr is not None else None, dr_acc,
                                self._at(mdl.params, sp.g_off), smean, srstd, LRELU_ALPHA, gptr(sp.g_off), gptr(sp.be_off), gptr(sp.b_off), coef,
                                self.bnb_ws.data_ptr(), self.bnb_ws.numel())
-                self._main_wait(dz_busy[slot])      # the kernel gradient of two layers ago still reads this dz buffer
-                if epi is not None and dr is not None:
-                    self._emit(self.bwd, lib.y3_bn_bwd_apply_fanin, dy.v, a.v, coef, LRELU_ALPHA, dz.v, dr.v, dr_acc)
-                else:
-                    self._emit(self.bwd, lib.y3_bn_bwd_apply, dy.v, a.v, coef, LRELU_ALPHA, dz.v)
+                if not mdl.freeze_bn:
+                    self._main_wait(dz_busy[slot])      # the kernel gradient of two layers ago still reads this dz buffer
+                    if epi is not None and dr is not None:
+                        self._emit(self.bwd, lib.y3_bn_bwd_apply_fanin, dy.v, a.v, coef, LRELU_ALPHA, dz.v, dr.v, dr_acc)
+                    else:
+                        self._emit(self.bwd, lib.y3_bn_bwd_apply, dy.v, a.v, coef, LRELU_ALPHA, dz.v)
                 # (kernel gradient on the x3 arithmetic: both operands are activations, no weight copy involved)
                 dz_busy[slot] = self._kernel_grad(lib.y3_conv2d_wgrad_x, src.v, dz.v, sp.k, sp.s, gptr(sp.w_off), x3.wgrad)
                 if x3.wgrad:
                     self.x3_wgrad.append(i)
-                if src is not self.x0:
+                if not src.no_grad:
                     ds = self._grad_of(src)
                     # x3 data gradient: the kernel wants K (= this layer's output channels) contiguous per column: the planes of the Keras arena
                     wdg = self._at(mdl.planes, sp.w_off) if x3.dgrad else self._at(mdl.params_t, sp.w_off)
@@ -940,7 +1041,9 @@ class YoloV3:
                  box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None,
                  ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES,
                  focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9,
-                 nesterov=False, weight_decay=0.0, lr_schedule=None):
+                 nesterov=False, weight_decay=0.0, lr_schedule=None, freeze_layers=0, freeze_bn=False):
+        """freeze_layers / freeze_bn are settings of a training run, not of the network: save_weights does not
+        record them (inference does not care), from_file builds a model without them, and every run names them again."""
         # the optimiser (DESIGN §3.19): 'adam' without decay = the reference's Keras Adam and its launches; 'adamw' / 'sgd' run
         # y3_optim_step; lr_schedule: None or an object with factor(t) (schedule.LrSchedule); checked before the device is needed
         check_optimizer_args(optimizer, momentum, nesterov, weight_decay, lr_schedule)
@@ -953,6 +1056,13 @@ class YoloV3:
         if not (isinstance(spp, (bool, np.bool_)) or (isinstance(spp, (int, np.integer)) and spp in (0, 1))):
             raise ValueError('spp must be False or True, got {!r}'.format(spp))
         self.spp = bool(spp)
+        # fine-tuning: layers 0 .. freeze_layers - 1 are not trainable (Keras layer.trainable = False, BatchNorm
+        # included: they run as in inference); freeze_bn: the BatchNorm of the trainable layers normalises with the moving
+        # statistics, which then stay.  0 / False = every layer trains, today's launches; checked before the device is needed
+        check_freeze_args(freeze_layers, freeze_bn, len(build_layer_specs(int(img_size[2]), 3 if anchors is None else len(anchors),
+                                                                          int(number_classes), self.spp)[0]))
+        self.freeze_layers = int(freeze_layers)
+        self.freeze_bn = bool(freeze_bn)
         # input sizes train_step / test_step accept: None = img_size only; checked before the device is needed
         self.train_sizes = check_train_sizes(img_size, train_sizes)
         # gradient accumulation and global-norm clipping: 1 / None = off; checked before the device is needed
@@ -1006,6 +1116,8 @@ class YoloV3:
         self.output_shape = [self.number_output_boxes, 5 + self.number_classes]
 
         self.specs, self.arena_floats, chan_floats, self.moving_stride = build_layer_specs(C, self.number_anchors, self.number_classes, self.spp)
+        # the part of the arenas a step touches: everything with no layer frozen (trainable_suffix)
+        self.train_off, self.train_floats = trainable_suffix(self.specs, self.arena_floats, self.freeze_layers)
         dev = self.device
         z = lambda n: torch.zeros(n, dtype=torch.float32, device=dev)
         self.params = z(self.arena_floats)        # trainable arena: [W | b | gamma | beta] per layer
@@ -1067,9 +1179,12 @@ class YoloV3:
         self._plans = {}
         self._lb_staging = {}        # slot -> pinned and device byte buffers of predict_letterbox
         self._tr_table = None
+        self._tr_suffix = None
         self._fold_table = None
         self._adam_call = self._adam_launch()
         self._init_weights(seed)
+        if self.freeze_layers:
+            self._refresh_transposed_from(self.freeze_layers, launch=False)      # the tables of the optimiser step's refresh
         self.model = _CallableModel(self, False)
         self.model_feature_maps = _CallableModel(self, True)
         self.optimizer = self
@@ -1305,6 +1420,31 @@ class YoloV3:
                 self.adam_v.copy_(torch.from_numpy(z['opt_v']))
             self.iterations = int(z['opt_iterations'])
 
+    def load_pretrained(self, path):
+        """Start fine-tuning from a file written by save_weights.  The model may differ from the file's in
+        number_classes, anchors (values or count per scale), global_batch_size, learning rate and optimiser: layers are matched by
+        role (pretrained_map; a plain file into an SPP model goes through spp_transfer_map), heads of equal shape load, and a
+        detection head of another shape keeps its initialisation and is named in a printed line.  No optimiser state is loaded and
+        `iterations` stays as it is (0 in a fresh model); the EMA restarts from the loaded weights (set_weights).  Raises ValueError
+        for an SPP file into a plain model and for another input channel count.  Returns the indices of the layers that kept their
+        initialisation."""
+        z = np.load(path, allow_pickle=False)
+        n_file = 0
+        while 'l%03d_W' % n_file in z:
+            n_file += 1
+        mapping, kept = pretrained_map(self.specs, self.spp, [z['l%03d_W' % j].shape for j in range(n_file)], YoloV3._spp_meta(z))
+        own = self.get_weights()
+        layers = []
+        for (i, sp), j in zip(enumerate(self.specs), mapping):
+            if j is None:
+                print('load_pretrained: layer %d (%s %dx%d %d -> %d) is not in %s with this shape and keeps its initialisation'
+                      % (i, 'conv' if sp.bn else 'detection head', sp.k, sp.k, sp.cin, sp.cout, path))
+                layers.append(own[i])
+                continue
+            layers.append({k: z['l%03d_%s' % (j, k)] for k in (['W', 'b', 'gamma', 'beta', 'mean', 'var'] if sp.bn else ['W', 'b'])})
+        self.set_weights(layers)
+        return kept
+
     @staticmethod
     def _focal_meta(z):
         """The focal settings a weight file carries (save_weights), as constructor arguments; none for a file without them."""
@@ -1332,8 +1472,12 @@ class YoloV3:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _refresh_transposed(self):
-        """params_t <- kernels with the channel axes swapped (operand of the data gradient), all layers in one launch."""
+    def _refresh_transposed(self, first=0):
+        """params_t <- kernels with the channel axes swapped (operand of the data gradient), all layers in one launch.
+        first: refresh layers `first` on only (the optimiser step with a frozen prefix: the copies of the frozen layers are
+        current, and a table of fewer rows is the whole difference); 0: every layer, as set_weights needs."""
+        if first:
+            return self._refresh_transposed_from(first)
         if self._tr_table is None:
             rows, start = [], 0
             for sp in self.specs[1:]:          # the first layer has no data gradient
@@ -1366,6 +1510,40 @@ class YoloV3:
             for (arena, planes), (tab, nl, blocks) in zip(((self.params, self.planes), (self.params_t, self.planes_t)), self._x3_table):
                 check(lib.y3_x3_split_weights_batched(arena.data_ptr(), planes.data_ptr(), tab.data_ptr(), nl, blocks, self._stream()), 'y3_x3_split_weights_batched')
         self._bf16_stale = True
+
+    def _refresh_transposed_from(self, first, launch=True):
+        """_refresh_transposed for layers `first` >= 1 on: the same launches over tables that start at that layer.  The tables
+        are device tensors: the constructor makes them (launch=False), never a captured step."""
+        if self._tr_suffix is None or self._tr_suffix[0] != first:
+            specs = self.specs[first:]
+            rows, start = [], 0
+            for sp in specs:
+                rows.append([sp.w_off, sp.k * sp.k, sp.cin_pad, sp.cout, start])
+                start += sp.k * sp.k * (-(-sp.cin_pad // 32)) * (-(-sp.cout // 32))
+            tabs = []
+            for fwd_copy in (False, True):
+                xrows, xstart = [], 0
+                for sp in specs:
+                    nrows, kpr = (sp.cout, sp.cin_pad) if fwd_copy else (sp.cin_pad, sp.cout)
+                    if kpr % 16:
+                        continue
+                    xrows.append([sp.w_off, sp.k * sp.k, nrows, kpr, xstart])
+                    xstart += -(-(sp.k * sp.k * nrows * kpr) // 1024)
+                tabs.append((torch.tensor(xrows, dtype=torch.int32, device=self.device), len(xrows), xstart))
+            self._tr_suffix = (first, torch.tensor(rows, dtype=torch.int32, device=self.device), len(rows), start, tabs)
+        if not launch:
+            return
+        _, table, nl, tiles, tabs = self._tr_suffix
+        self._bf16_stale = True
+        if self.planes is not None and os.environ.get('Y3_PREP_FUSED', '1') != '0':
+            check(lib.y3_x3_prepare_weights_batched(self.params.data_ptr(), self.params_t.data_ptr(), self.planes.data_ptr(), self.planes_t.data_ptr(),
+                                                    table.data_ptr(), nl, tiles, self._stream()), 'y3_x3_prepare_weights_batched')
+            return
+        check(lib.y3_transpose_weights_batched(self.params.data_ptr(), self.params_t.data_ptr(), table.data_ptr(), nl, tiles, self._stream()),
+              'y3_transpose_weights_batched')
+        if self.planes is not None:
+            for (arena, planes), (tab, xl, blocks) in zip(((self.params, self.planes), (self.params_t, self.planes_t)), tabs):
+                check(lib.y3_x3_split_weights_batched(arena.data_ptr(), planes.data_ptr(), tab.data_ptr(), xl, blocks, self._stream()), 'y3_x3_split_weights_batched')
 
     def fold_table(self):
         """Device table for y3_bn_fold_inference_batched (one row per BatchNorm layer)."""
@@ -1610,49 +1788,56 @@ class YoloV3:
     def _grad_passes(self, st, last):
         """After the backward pass of a micro-step (kernel gradients joined into `st` by run_backward, all-reduce by finish_step):
         fold grads into the accumulator, and on the last micro-step leave the norm and the Adam scale in device memory."""
-        n = self.arena_floats
+        n = self.train_floats                 # the trainable suffix of the arenas: all of them with no layer frozen
         if self.grad_acc is not None:
-            check(lib.y3_grad_accumulate(self.grad_acc.data_ptr(), self.grads.data_ptr(), n, self._acc_first_dev.data_ptr(),
+            check(lib.y3_grad_accumulate(self._tp(self.grad_acc), self._tp(self.grads), n, self._acc_first_dev.data_ptr(),
                                          self._grad_ws.data_ptr(), st), 'y3_grad_accumulate')
         elif last:
-            check(lib.y3_grad_sumsq(self.grads.data_ptr(), n, self._grad_ws.data_ptr(), st), 'y3_grad_sumsq')
+            check(lib.y3_grad_sumsq(self._tp(self.grads), n, self._grad_ws.data_ptr(), st), 'y3_grad_sumsq')
         if last:
             clip = self.grad_clip_norm if self.grad_clip_norm is not None else math.inf        # Y3_GRAD_CLIP_OFF
             check(lib.y3_grad_clip_scale(self._grad_ws.data_ptr(), n, self.accumulate_steps, clip, self.last_grad_norm.data_ptr(),
                                          self.grad_scale_dev.data_ptr(), st), 'y3_grad_clip_scale')
 
+    def _tp(self, arena):
+        """Device address of the trainable suffix of a parameter-shaped arena (its start with no layer frozen)."""
+        return arena.data_ptr() + 4 * self.train_off
+
     def _adam_launch(self):
         """(entry point, arguments up to the stream) of the optimiser step: y3_adam_step* for the default 'adam', y3_optim_step for
         'adamw' / 'sgd' (the one place that chooses).  Every buffer it names is allocated by the constructor and only ever written
         in place, so the constructor calls this once; what changes per step (lr or lr_t, lr * weight decay, the EMA factor, the
-        gradient scale) is read from device memory."""
+        gradient scale) is read from device memory.  With frozen layers every arena is passed from the trainable suffix on
+        (trainable_suffix: a pointer and a count), the decay ranges relative to it: frozen parameters, their moments and their EMA
+        copies are never read or written."""
         g = self.grad_acc if self.grad_acc is not None else self.grads
+        tp = self._tp
         if self.optimizer_kind != 'adam':
             # SGD with momentum / AdamW, decay on the kernels only (DESIGN §3.19): one descriptor, built once like the tuple below.
             # The range table is host memory the descriptor points into; both live as long as the model.
-            ranges = self.decay_ranges = decay_ranges(self.specs)
+            ranges = self.decay_ranges = suffix_decay_ranges(self.specs, self.freeze_layers)
             self._decay_table = (ctypes.c_longlong * (2 * len(ranges)))(*[v for r in ranges for v in r])
             d = self._optim_desc = _hip.OptimDesc()
             d.kind = _hip.OPT_ADAMW if self.optimizer_kind == 'adamw' else _hip.OPT_SGD_NESTEROV if self.nesterov else _hip.OPT_SGD
-            d.param, d.grad, d.m, d.count = self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.arena_floats
-            d.v = self.adam_v.data_ptr() if self.adam_v is not None else None
+            d.param, d.grad, d.m, d.count = tp(self.params), tp(g), tp(self.adam_m), self.train_floats
+            d.v = tp(self.adam_v) if self.adam_v is not None else None
             d.hyper_dev = self.hyper_dev.data_ptr()
             d.momentum, d.weight_decay = self.momentum, self.weight_decay
             d.beta1, d.beta2, d.eps = self.beta1, self.beta2, self.adam_eps
             d.decay_ranges_host, d.n_ranges = self._decay_table, len(ranges)
             if self.ema_decay is not None:
-                d.ema_param, d.moving, d.ema_moving = self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr()
+                d.ema_param, d.moving, d.ema_moving = tp(self.ema_params), self.moving.data_ptr(), self.ema_moving.data_ptr()
                 d.moving_count, d.omd_dev = self.moving.numel(), self.ema_omd_dev.data_ptr()
             if self._grad_ws is not None:
                 d.scale_dev = self.grad_scale_dev.data_ptr()
             return lib.y3_optim_step, (ctypes.byref(d),)
         name = 'y3_adam_step'
-        args = [self.params.data_ptr(), g.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.arena_floats,
+        args = [tp(self.params), tp(g), tp(self.adam_m), tp(self.adam_v), self.train_floats,
                 self.lr_t_dev.data_ptr(), self.beta1, self.beta2, self.adam_eps]
         if self.ema_decay is not None:
             # the same Adam step + the weight / moving-statistics average in the same pass (DESIGN §3.7)
             name += '_ema'
-            args += [self.ema_params.data_ptr(), self.moving.data_ptr(), self.ema_moving.data_ptr(), self.moving.numel(), self.ema_omd_dev.data_ptr()]
+            args += [tp(self.ema_params), self.moving.data_ptr(), self.ema_moving.data_ptr(), self.moving.numel(), self.ema_omd_dev.data_ptr()]
         if self._grad_ws is not None:
             # accumulation / clipping on: the same update on (accumulated gradient) * scale (DESIGN §3.10)
             name += '_scaled'
@@ -1662,7 +1847,7 @@ class YoloV3:
     def _adam(self, st):
         fn, args = self._adam_call
         check(fn(*args, st), fn.__name__)
-        self._refresh_transposed()
+        self._refresh_transposed(self.freeze_layers)
 
     @property
     def last_ignored(self):

@@ -96,8 +96,11 @@ class DataParallel:
     def attach(self, model):
         """model needs ``grads`` (flat tensor) and ``specs`` with w_off / end_off."""
         self.model = model
-        ranges = [(sp.w_off, sp.end_off) for sp in model.specs]
-        self.buckets = make_buckets(ranges, self.bucket_floats)
+        # with a frozen prefix (model.freeze_layers) the ranks exchange only the trainable suffix of the arena: the buckets are
+        # made of the trainable layers, whose backward is all that reports a layer done
+        first = int(getattr(model, 'freeze_layers', 0))
+        ranges = [(sp.w_off, sp.end_off) for sp in model.specs[first:]]
+        self.buckets = [(lo, hi, i + first) for lo, hi, i in make_buckets(ranges, self.bucket_floats)]
         self._by_layer = {b[2]: b for b in self.buckets}
         model.dist = self
         if model.grads.is_cuda:
