@@ -480,7 +480,12 @@ int y3_loss_fwd_bwd_focal(const y3_tensor* fm, const float* gt, const float* anc
 
 /* ---- tf.keras.optimizers.Adam.apply_gradients (model.py:451,500) ----------
  * m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= lr_t*m/(sqrt(v)+eps), with
- * lr_t read from DEVICE memory (*lr_t_dev) so the launch is graph-replayable. */
+ * lr_t read from DEVICE memory (*lr_t_dev, ONE float) so the launch is
+ * graph-replayable.  This entry point and its _ema / _scaled forms below run
+ * the kernel of y3_optim_step with everything that serves weight decay
+ * compiled out; each states its form, so a NULL ema_param, omd_dev or
+ * scale_dev is an error there (moving / ema_moving may be NULL with
+ * moving_count == 0). */
 int y3_adam_step(float* param, const float* grad, float* m, float* v, size_t count,
                  const float* lr_t_dev, float beta1, float beta2, float eps, y3_stream_t stream);
 

@@ -1,9 +1,8 @@
 // HBM-bound kernels around the convolutions: BatchNorm (training statistics,
 // apply, backward), the all-ones upsample, concat copies, gradient fan-in,
-// layout changes, Adam, z-score.  All are streaming kernels: 16-byte accesses
+// layout changes, z-score.  All are streaming kernels: 16-byte accesses
 // along the contiguous channel axis, grid-stride loops capped at ~8 blocks/CU.
 #include "common.h"
-#include "adam_update.h"
 
 static int check_view(const y3_tensor* t, const char* name) {
     Y3_CHECK_ARG(t && t->ptr, "%s: null tensor", name);
@@ -1011,276 +1010,6 @@ extern "C" int y3_colsum(const y3_tensor* src, float* out, y3_stream_t stream) {
     Y3_CHECK_ARG(out && src->c <= 65535, "colsum: bad args");
     hipLaunchKernelGGL(colsum_kernel, dim3(src->c), dim3(1024), 0, (hipStream_t)stream, src->ptr, src->ld, src->c, pixels(src), out);
     Y3_CHECK_LAUNCH("colsum");
-    return Y3_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Keras Adam (App. C5), fused over the whole parameter arena
-// ---------------------------------------------------------------------------
-// Y3_ADAM1(f), one element of one float4 lane f: the update of adam_kernel, adam_ema_kernel and their scaled forms, and of the AdamW
-// kernels of optim.hip (one text in adam_update.h, so all give the same bits)
-// The kernel bodies are macro text shared by the plain and the scaled kernel of each pair (gradient accumulation and global-norm
-// clipping): S_LOAD / S4 / S1 are empty in adam_kernel and adam_ema_kernel, which therefore compile to the instructions
-// they always had, and in the scaled kernels read s = *scale_dev and multiply the gradient operand by it, one fp32 multiply in
-// front of Y3_ADAM1.  With s = 1 the scaled kernels give the plain kernels' bits.
-#define Y3_ADAM_S_LOAD const float s = *scale_dev;
-#define Y3_ADAM_S4 gg.x *= s, gg.y *= s, gg.z *= s, gg.w *= s;
-#define Y3_ADAM_S1 gg.x *= s;
-#define Y3_ADAM_KERNEL_BODY(S_LOAD, S4, G1)                                                      \
-{                                                                                              \
-    const float lr_t = *lr_t_dev;                                                              \
-    S_LOAD                                                                                     \
-    const float o1 = 1.f - b1, o2 = 1.f - b2;                                                  \
-    const size_t stride = (size_t)gridDim.x * blockDim.x;                                      \
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count4; i += stride) {  \
-        float4 pp = reinterpret_cast<float4*>(p)[i];                                           \
-        float4 gg = reinterpret_cast<const float4*>(g)[i];                                     \
-        float4 mm = reinterpret_cast<float4*>(m)[i];                                           \
-        float4 vv = reinterpret_cast<float4*>(v)[i];                                           \
-        S4                                                                                     \
-        Y3_ADAM1(x) Y3_ADAM1(y) Y3_ADAM1(z) Y3_ADAM1(w)                                        \
-        reinterpret_cast<float4*>(p)[i] = pp;                                                  \
-        reinterpret_cast<float4*>(m)[i] = mm;                                                  \
-        reinterpret_cast<float4*>(v)[i] = vv;                                                  \
-    }                                                                                          \
-    /* tail (G1: the gradient operand) */                                                      \
-    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {                                        \
-        const size_t i = (count4 << 2) + threadIdx.x;                                          \
-        float mm = m[i], vv = v[i];                                                            \
-        mm += (G1 - mm) * o1;                                                                  \
-        vv += (G1 * G1 - vv) * o2;                                                             \
-        p[i] -= (mm * lr_t) / (sqrtf(vv) + eps);                                               \
-        m[i] = mm;                                                                             \
-        v[i] = vv;                                                                             \
-    }                                                                                          \
-}
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t count4,
-                            size_t count, const float* __restrict__ lr_t_dev, float b1, float b2, float eps)
-    Y3_ADAM_KERNEL_BODY(, , g[i])
-__global__ void adam_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                   size_t count4, size_t count, const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
-                                   const float* __restrict__ scale_dev)
-    Y3_ADAM_KERNEL_BODY(Y3_ADAM_S_LOAD, Y3_ADAM_S4, (g[i] * s))
-extern "C" int y3_adam_step(float* param, const float* grad, float* m, float* v, size_t count, const float* lr_t_dev, float beta1, float beta2,
-                            float eps, y3_stream_t stream) {
-    Y3_CHECK_ARG(param && grad && m && v && lr_t_dev, "adam_step: null pointer");
-    Y3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_step: arenas must be 16-byte aligned");
-    if (count == 0) return Y3_OK;
-    hipLaunchKernelGGL(adam_kernel, dim3(stream_blocks((long long)(count / 4 + 1), 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v,
-                       count / 4, count, lr_t_dev, beta1, beta2, eps);
-    Y3_CHECK_LAUNCH("adam_step");
-    return Y3_OK;
-}
-extern "C" int y3_adam_step_scaled(float* param, const float* grad, float* m, float* v, size_t count, const float* lr_t_dev, float beta1,
-                                   float beta2, float eps, const float* scale_dev, y3_stream_t stream) {
-    Y3_CHECK_ARG(param && grad && m && v && lr_t_dev && scale_dev, "adam_step_scaled: null pointer");
-    Y3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
-                 "adam_step_scaled: arenas must be 16-byte aligned");
-    if (count == 0) return Y3_OK;
-    hipLaunchKernelGGL(adam_scaled_kernel, dim3(stream_blocks((long long)(count / 4 + 1), 256)), dim3(256), 0, (hipStream_t)stream, param,
-                       grad, m, v, count / 4, count, lr_t_dev, beta1, beta2, eps, scale_dev);
-    Y3_CHECK_LAUNCH("adam_step_scaled");
-    return Y3_OK;
-}
-
-// adam_kernel + the exponential moving average of the weights in the same pass: p, m, v come out with the bits
-// adam_kernel gives; then ema_p += (p_new - ema_p) * omd over the arena, and the same update of ema_mv towards the BatchNorm
-// moving statistics mv (a second, small segment, written by this step's forward pass).  omd = 1 - decay is read from device
-// memory, like lr_t, so a replayed graph picks up each step's value.  Two more fp32 streams than Adam alone: 9 per element.
-#define Y3_ADAM_EMA_KERNEL_BODY(S_LOAD, S4, S1)                        \
-{                                                                      \
-    const float lr_t = *lr_t_dev;                                      \
-    const float omd = *omd_dev;                                        \
-    S_LOAD                                                             \
-    const float o1 = 1.f - b1, o2 = 1.f - b2;                          \
-    const size_t stride = (size_t)gridDim.x * blockDim.x;              \
-    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;  \
-    for (size_t i = tid; i < count4; i += stride) {                    \
-        float4 pp = reinterpret_cast<float4*>(p)[i];                   \
-        float4 gg = reinterpret_cast<const float4*>(g)[i];             \
-        float4 mm = reinterpret_cast<float4*>(m)[i];                   \
-        float4 vv = reinterpret_cast<float4*>(v)[i];                   \
-        float4 ee = reinterpret_cast<float4*>(ema_p)[i];               \
-        S4                                                             \
-        Y3_ADAM1(x) Y3_ADAM1(y) Y3_ADAM1(z) Y3_ADAM1(w)                \
-        ee.x += (pp.x - ee.x) * omd;                                   \
-        ee.y += (pp.y - ee.y) * omd;                                   \
-        ee.z += (pp.z - ee.z) * omd;                                   \
-        ee.w += (pp.w - ee.w) * omd;                                   \
-        reinterpret_cast<float4*>(p)[i] = pp;                          \
-        reinterpret_cast<float4*>(m)[i] = mm;                          \
-        reinterpret_cast<float4*>(v)[i] = vv;                          \
-        reinterpret_cast<float4*>(ema_p)[i] = ee;                      \
-    }                                                                  \
-    for (size_t i = tid; i < mcount4; i += stride) {                   \
-        const float4 s4 = reinterpret_cast<const float4*>(mv)[i];      \
-        float4 ee = reinterpret_cast<float4*>(ema_mv)[i];              \
-        ee.x += (s4.x - ee.x) * omd;                                   \
-        ee.y += (s4.y - ee.y) * omd;                                   \
-        ee.z += (s4.z - ee.z) * omd;                                   \
-        ee.w += (s4.w - ee.w) * omd;                                   \
-        reinterpret_cast<float4*>(ema_mv)[i] = ee;                     \
-    }                                                                  \
-    /* tails: lane x of a float4 through the same update text */       \
-    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {                \
-        const size_t i = (count4 << 2) + threadIdx.x;                  \
-        float4 pp, gg, mm, vv;                                         \
-        pp.x = p[i], gg.x = g[i], mm.x = m[i], vv.x = v[i];            \
-        S1                                                             \
-        Y3_ADAM1(x)                                                    \
-        p[i] = pp.x;                                                   \
-        m[i] = mm.x;                                                   \
-        v[i] = vv.x;                                                   \
-        ema_p[i] += (pp.x - ema_p[i]) * omd;                           \
-    }                                                                  \
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < (mcount & 3)) {   \
-        const size_t i = (mcount4 << 2) + threadIdx.x;                 \
-        ema_mv[i] += (mv[i] - ema_mv[i]) * omd;                        \
-    }                                                                  \
-}
-__global__ void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t count4,
-                                size_t count, const float* __restrict__ lr_t_dev, float b1, float b2, float eps, float* __restrict__ ema_p,
-                                const float* __restrict__ mv, float* __restrict__ ema_mv, size_t mcount4, size_t mcount,
-                                const float* __restrict__ omd_dev)
-    Y3_ADAM_EMA_KERNEL_BODY(, , )
-__global__ void adam_ema_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                       size_t count4, size_t count, const float* __restrict__ lr_t_dev, float b1, float b2, float eps,
-                                       float* __restrict__ ema_p, const float* __restrict__ mv, float* __restrict__ ema_mv, size_t mcount4,
-                                       size_t mcount, const float* __restrict__ omd_dev, const float* __restrict__ scale_dev)
-    Y3_ADAM_EMA_KERNEL_BODY(Y3_ADAM_S_LOAD, Y3_ADAM_S4, Y3_ADAM_S1)
-extern "C" int y3_adam_step_ema(float* param, const float* grad, float* m, float* v, size_t count, const float* lr_t_dev, float beta1,
-                                float beta2, float eps, float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
-                                const float* omd_dev, y3_stream_t stream) {
-    Y3_CHECK_ARG(param && grad && m && v && lr_t_dev && ema_param && omd_dev, "adam_step_ema: null pointer");
-    Y3_CHECK_ARG(moving_count == 0 || (moving && ema_moving), "adam_step_ema: null moving-statistics pointer");
-    Y3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema_param | (uintptr_t)moving |
-                   (uintptr_t)ema_moving) & 15) == 0,
-                 "adam_step_ema: arenas must be 16-byte aligned");
-    if (count == 0 && moving_count == 0) return Y3_OK;
-    const long long items = (long long)((count > moving_count ? count : moving_count) / 4 + 1);
-    hipLaunchKernelGGL(adam_ema_kernel, dim3(stream_blocks(items, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, count / 4, count,
-                       lr_t_dev, beta1, beta2, eps, ema_param, moving, ema_moving, moving_count / 4, moving_count, omd_dev);
-    Y3_CHECK_LAUNCH("adam_step_ema");
-    return Y3_OK;
-}
-extern "C" int y3_adam_step_ema_scaled(float* param, const float* grad, float* m, float* v, size_t count, const float* lr_t_dev, float beta1,
-                                       float beta2, float eps, float* ema_param, const float* moving, float* ema_moving, size_t moving_count,
-                                       const float* omd_dev, const float* scale_dev, y3_stream_t stream) {
-    Y3_CHECK_ARG(param && grad && m && v && lr_t_dev && ema_param && omd_dev && scale_dev, "adam_step_ema_scaled: null pointer");
-    Y3_CHECK_ARG(moving_count == 0 || (moving && ema_moving), "adam_step_ema_scaled: null moving-statistics pointer");
-    Y3_CHECK_ARG((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema_param | (uintptr_t)moving |
-                   (uintptr_t)ema_moving) & 15) == 0,
-                 "adam_step_ema_scaled: arenas must be 16-byte aligned");
-    if (count == 0 && moving_count == 0) return Y3_OK;
-    const long long items = (long long)((count > moving_count ? count : moving_count) / 4 + 1);
-    hipLaunchKernelGGL(adam_ema_scaled_kernel, dim3(stream_blocks(items, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, m, v,
-                       count / 4, count, lr_t_dev, beta1, beta2, eps, ema_param, moving, ema_moving, moving_count / 4, moving_count, omd_dev,
-                       scale_dev);
-    Y3_CHECK_LAUNCH("adam_step_ema_scaled");
-    return Y3_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Gradient accumulation and the global gradient norm, over the whole gradient arena
-// ---------------------------------------------------------------------------
-// ACC: acc = *first_dev ? g : acc + g (plain fp32; the first micro-step does not read acc), and the block's sum of squares of the
-// RESULT.  !ACC: the sum of squares of g alone.  Squares and sums in fp64 (an fp32 x fp32 product is exact there); a thread adds
-// its elements in loop order, the block a fixed LDS tree, and EVERY block writes its partial, so nothing needs zeroing and the
-// bits do not depend on the run.  `first` comes from device memory so a replayed graph serves every micro-step.
-#define Y3_GN_SQ(f) q += (double)aa.f * (double)aa.f;
-template <bool ACC>
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(float* __restrict__ acc, const float* __restrict__ g, size_t count4, size_t count,
-                                                         const int* __restrict__ first_dev, double* __restrict__ partials) {
-    __shared__ double sm[256];
-    bool first = true;
-    if constexpr (ACC) first = *first_dev != 0;
-    double q = 0.0;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count4; i += stride) {
-        float4 aa = reinterpret_cast<const float4*>(g)[i];
-        if constexpr (ACC) {
-            if (!first) {
-                const float4 gg = aa;
-                aa = reinterpret_cast<float4*>(acc)[i];
-                aa.x += gg.x, aa.y += gg.y, aa.z += gg.z, aa.w += gg.w;
-            }
-            reinterpret_cast<float4*>(acc)[i] = aa;
-        }
-        Y3_GN_SQ(x) Y3_GN_SQ(y) Y3_GN_SQ(z) Y3_GN_SQ(w)
-    }
-    // tail: lane x of a float4 through the same text
-    if (blockIdx.x == 0 && threadIdx.x < (count & 3)) {
-        const size_t i = (count4 << 2) + threadIdx.x;
-        float4 aa;
-        aa.x = g[i];
-        if constexpr (ACC) {
-            if (!first) {
-                const float gx = aa.x;
-                aa.x = acc[i];
-                aa.x += gx;
-            }
-            acc[i] = aa.x;
-        }
-        Y3_GN_SQ(x)
-    }
-    sm[threadIdx.x] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sm[threadIdx.x] += sm[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = sm[0];
-}
-// One workgroup: the partials staged in LDS, added by one lane in index order; norm = sqrt(S) / k and
-// s = (1/k) * (clip / max(norm, clip)) (1/k with clipping off) in fp64, each rounded once to fp32.
-#define Y3_GN_MAX_BLOCKS 2048      // the cap of stream_blocks today; y3_grad_clip_scale refuses more partials than this LDS array holds
-__global__ __launch_bounds__(256) void grad_clip_scale_kernel(const double* __restrict__ partials, int nblocks, int k, double clip, int clip_on,
-                                                              float* __restrict__ norm_dev, float* __restrict__ scale_dev) {
-    __shared__ double sm[Y3_GN_MAX_BLOCKS];
-    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) sm[b] = partials[b];
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double S = 0.0;
-    for (int b = 0; b < nblocks; ++b) S += sm[b];
-    const double norm = sqrt(S) / (double)k;
-    double s = 1.0 / (double)k;
-    if (clip_on) s = s * (clip / (norm > clip ? norm : clip));
-    *norm_dev = (float)norm;
-    *scale_dev = (float)s;
-}
-static inline int grad_norm_blocks(size_t count) { return stream_blocks((long long)(count / 4 + 1), 256); }
-extern "C" size_t y3_grad_norm_workspace_bytes(size_t count) { return (size_t)grad_norm_blocks(count) * sizeof(double); }
-extern "C" int y3_grad_accumulate(float* acc, const float* grad, size_t count, const int* first_dev, void* workspace, y3_stream_t stream) {
-    Y3_CHECK_ARG(acc && grad && first_dev && workspace, "grad_accumulate: null pointer");
-    Y3_CHECK_ARG((((uintptr_t)acc | (uintptr_t)grad) & 15) == 0 && ((uintptr_t)workspace & 7) == 0,
-                 "grad_accumulate: arenas must be 16-byte aligned, the workspace 8-byte");
-    hipLaunchKernelGGL(grad_sumsq_kernel<true>, dim3(grad_norm_blocks(count)), dim3(256), 0, (hipStream_t)stream, acc, grad, count / 4, count,
-                       first_dev, (double*)workspace);
-    Y3_CHECK_LAUNCH("grad_accumulate");
-    return Y3_OK;
-}
-extern "C" int y3_grad_sumsq(const float* grad, size_t count, void* workspace, y3_stream_t stream) {
-    Y3_CHECK_ARG(grad && workspace, "grad_sumsq: null pointer");
-    Y3_CHECK_ARG(((uintptr_t)grad & 15) == 0 && ((uintptr_t)workspace & 7) == 0,
-                 "grad_sumsq: the arena must be 16-byte aligned, the workspace 8-byte");
-    hipLaunchKernelGGL(grad_sumsq_kernel<false>, dim3(grad_norm_blocks(count)), dim3(256), 0, (hipStream_t)stream, (float*)nullptr, grad,
-                       count / 4, count, (const int*)nullptr, (double*)workspace);
-    Y3_CHECK_LAUNCH("grad_sumsq");
-    return Y3_OK;
-}
-extern "C" int y3_grad_clip_scale(const void* workspace, size_t count, int accumulate_steps, double clip_norm, float* norm_dev,
-                                  float* scale_dev, y3_stream_t stream) {
-    Y3_CHECK_ARG(workspace && norm_dev && scale_dev, "grad_clip_scale: null pointer");
-    Y3_CHECK_ARG(((uintptr_t)workspace & 7) == 0, "grad_clip_scale: the workspace must be 8-byte aligned");
-    Y3_CHECK_ARG(accumulate_steps >= 1, "grad_clip_scale: accumulate_steps %d (needs >= 1)", accumulate_steps);
-    const bool off = clip_norm == Y3_GRAD_CLIP_OFF;      // +infinity: no bound
-    Y3_CHECK_ARG(off || (clip_norm > 0.0 && clip_norm < Y3_GRAD_CLIP_OFF), "grad_clip_scale: clip_norm %g (needs finite > 0, or Y3_GRAD_CLIP_OFF)",
-                 clip_norm);
-    Y3_CHECK_ARG(grad_norm_blocks(count) <= Y3_GN_MAX_BLOCKS, "grad_clip_scale: %d partial sums (the finalize kernel holds %d)",
-                 grad_norm_blocks(count), Y3_GN_MAX_BLOCKS);
-    hipLaunchKernelGGL(grad_clip_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, grad_norm_blocks(count),
-                       accumulate_steps, off ? 1.0 : clip_norm, off ? 0 : 1, norm_dev, scale_dev);
-    Y3_CHECK_LAUNCH("grad_clip_scale");
     return Y3_OK;
 }
 

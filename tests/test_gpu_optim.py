@@ -209,6 +209,39 @@ def test_adamw_identities_with_the_adam_kernels(count):
                 assert _same(got[k], w[k]), (t, k)
 
 
+ADAM_ENTRIES = {(False, False): 'y3_adam_step', (False, True): 'y3_adam_step_scaled', (True, False): 'y3_adam_step_ema',
+                (True, True): 'y3_adam_step_ema_scaled'}
+# (count, moving_count): a tail alone, a body alone, both, a full grid-stride pass and a tail; with the EMA a grid sized by the moving
+# statistics (their tail is the last block's), none of them (null pointers), them alone, and nothing at all
+ADAM_SIZES = [(3, 37), (4, 37), (1023, 37), (PASS + 4 * 300 + 3, 37)]
+ADAM_EMA_SIZES = [(6, 1027), (1023, 0), (0, 7), (0, 0)]
+
+
+@pytest.mark.parametrize('ema, scaled', sorted(ADAM_ENTRIES))
+def test_the_adam_entry_points_match_the_restatement_bit_for_bit(ema, scaled):
+    """The four y3_adam_step* entry points themselves (the identities above compare them with y3_optim_step) against AdamW's
+    restatement under an all-false decay mask, and the EMA's; lr_t in a tensor of ONE float, as the model passes it."""
+    from yolo3._hip import lib, check
+    name = ADAM_ENTRIES[ema, scaled]
+    lr_t = torch.zeros(1, device='cuda')
+    for count, mcount in ADAM_SIZES + (ADAM_EMA_SIZES if ema else [(0, 37)]):
+        gs = _grads(count, 5)
+        run = Run(R.ADAMW, ema, scaled, count, [], mcount=mcount)
+        assert not run.D.any()
+        d = run.d
+        args = [d['p'].data_ptr(), run.gd.data_ptr(), d['m'].data_ptr(), d['v'].data_ptr(), count, lr_t.data_ptr(), R.B1, R.B2, R.EPS]
+        if ema:
+            args += [d['e'].data_ptr(), d['mv'].data_ptr() if mcount else None, d['emv'].data_ptr() if mcount else None, mcount, run.omd.data_ptr()]
+        if scaled:
+            args.append(run.s.data_ptr())
+        for t in range(3):
+            run.set(gs[t], HYPER[t], OMD[t], SCALE[t])
+            lr_t.fill_(float(F32(HYPER[t][0])))
+            check(getattr(lib, name)(*args, _stream()), name)
+            run.restate()
+            run.check((name, count, mcount, t))        # every arena, the ones this form leaves alone too, and the canaries past each
+
+
 @pytest.mark.parametrize('kind', [R.SGD, R.SGD_NESTEROV])
 def test_sgd_without_decay_or_with_unit_scale_gives_the_plain_bits(kind):
     count = 1023

@@ -1,6 +1,7 @@
 """Cost of the weight EMA: the bench.py training step at batch 8 x 416^2, host-launched, with and without
 ema_decay.  python tools/ema_cost.py [ema_decay (0 = off)] [steps]
-Under `rocprofv3 --kernel-trace --stats -- python tools/ema_cost.py ...` the stats file gives adam_kernel against adam_ema_kernel."""
+Under `rocprofv3 --kernel-trace --stats -- python tools/ema_cost.py ...` the stats file gives y3_adam_step's kernel against y3_adam_step_ema's
+(optim_kernel<3, false, false> against optim_kernel<3, true, false>, csrc/optim.hip)."""
 import os
 import sys
 import time

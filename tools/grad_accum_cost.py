@@ -2,7 +2,8 @@
 host-launched.  python tools/grad_accum_cost.py [accumulate_steps (1 = off)] [grad_clip_norm (0 = off)] [micro-steps] [--plain-too]
 --plain-too also steps a second, default model (no accumulation, no clipping) in the same process, one optimiser step of each in
 turn, so that under `rocprofv3 --kernel-trace --stats -- python tools/grad_accum_cost.py ... --plain-too` the stats file holds
-grad_sumsq_kernel<false / true>, grad_clip_scale_kernel and adam_scaled_kernel NEXT TO adam_kernel of the same run, the yardstick.
+grad_sumsq_kernel<false / true>, grad_clip_scale_kernel and the scaled Adam kernel NEXT TO the plain one of the same run, the yardstick (optim_kernel<3, EMA, SCALED>:
+the Adam kind of the optimiser template of csrc/optim.hip).
 `tools/grad_accum_cost.py --rates STATS.csv ...` prints each of them as bytes / time (bytes counted here from the arena size)."""
 import os
 import sys
@@ -13,7 +14,7 @@ sys.path.insert(0, ROOT + '/object-detection-yolov3_amd')
 
 ARENA_FLOATS = 61790400            # YoloV3(…, [416, 416, 3], 2, bench.ANCHORS).arena_floats (checked below when a model is built)
 # fp32 arena streams per launch: reads + writes
-STREAMS = {'adam_kernel': 7, 'adam_scaled_kernel': 7, 'adam_ema_kernel': 9, 'adam_ema_scaled_kernel': 9,
+STREAMS = {'optim_kernel<3, false, false>': 7, 'optim_kernel<3, false, true>': 7, 'optim_kernel<3, true, false>': 9, 'optim_kernel<3, true, true>': 9,
            'grad_sumsq_kernel<false>': 1, 'grad_sumsq_kernel<true>': 3}
 
 
@@ -29,13 +30,13 @@ def rates(paths):
                 continue
             avg, lo, hi = float(row['AverageNs']) / 1e3, float(row['MinNs']) / 1e3, float(row['MaxNs']) / 1e3
             if key is None:
-                print('  %-26s calls %4s  average %8.1f us  min %8.1f  max %8.1f' % ('grad_clip_scale_kernel', row['Calls'], avg, lo, hi))
+                print('  %-30s calls %4s  average %8.1f us  min %8.1f  max %8.1f' % ('grad_clip_scale_kernel', row['Calls'], avg, lo, hi))
                 continue
             nbytes = STREAMS[key] * ARENA_FLOATS * 4
             note = ''
             if key == 'grad_sumsq_kernel<true>':
                 note = '  (3 streams assumed; the first micro-step of each optimiser step moves 2: the min is that launch)'
-            print('  %-26s calls %4s  average %8.1f us  min %8.1f  max %8.1f  %d x %.1f MB  %.2f TB/s%s'
+            print('  %-30s calls %4s  average %8.1f us  min %8.1f  max %8.1f  %d x %.1f MB  %.2f TB/s%s'
                   % (key, row['Calls'], avg, lo, hi, STREAMS[key], ARENA_FLOATS * 4 / 1e6, nbytes / (avg * 1e-6) / 1e12, note))
 
 

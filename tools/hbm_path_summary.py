@@ -11,7 +11,8 @@ import csv
 import sys
 from collections import defaultdict
 
-KERNELS = ('decode_kernel', 'nms_kernel', 'zscore_partial_kernel', 'zscore_apply_kernel', 'adam_kernel', 'nchw_to_nhwc_kernel')
+ADAM = 'optim_kernel<3, false, false>'          # y3_adam_step: the Adam kind of the optimiser template (csrc/optim.hip), plain form
+KERNELS = ('decode_kernel', 'nms_kernel', 'zscore_partial_kernel', 'zscore_apply_kernel', ADAM, 'nchw_to_nhwc_kernel')
 K, A = 2, 2
 PARAMS = 61789770 + 288          # arena floats incl. the zero-padded RGB channel, alignment excluded
 
@@ -31,7 +32,7 @@ def algorithmic(kern, grid, wg):
         rows = n * nb * (5 + K) * 4
         vals = n * 3 * img * img
         out[n] = {'decode_kernel': 2 * rows, 'nms_kernel': rows, 'zscore_partial_kernel': vals * 4, 'zscore_apply_kernel': vals * 8,
-                  'nchw_to_nhwc_kernel': vals * 4 + n * img * img * 16, 'adam_kernel': 7 * PARAMS * 4}
+                  'nchw_to_nhwc_kernel': vals * 4 + n * img * img * 16, ADAM: 7 * PARAMS * 4}
     return out
 
 
@@ -83,7 +84,7 @@ def main():
         keys = sorted(by_kernel.get(k, []), key=lambda t: t[1])
         for i, key in enumerate(keys):
             n = 8 if (len(keys) == 1 or i < len(keys) / 2) else 25
-            if k == 'adam_kernel':
+            if k == ADAM:
                 n = 8
             cfg = 'bs %d, grid %d x %d' % (n, key[1] // max(key[2], 1), key[2])
             if k == 'nms_kernel' and len(dur[key]) % 3 == 0:

@@ -2,7 +2,9 @@
 
     python tools/optimizer_cost.py kernels [launches]    every y3_optim_step instantiation at the real arena sizes (plain and SPP) with
                                                          the model's 75 / 76 decay ranges, beside y3_adam_step / y3_adam_step_ema on the
-                                                         same arenas; run it under `rocprofv3 --kernel-trace --stats --` for the times
+                                                         same arenas (optim_kernel<3, false, false> and <3, true, false>: Adam is the
+                                                         fourth kind of the same template, with the decay machinery compiled out); run
+                                                         it under `rocprofv3 --kernel-trace --stats --` for the times
     python tools/optimizer_cost.py steps [steps] [rounds]    train_step at 8 x 416^2 for adam, adamw and sgd, alternated in one process
 """
 import ctypes
