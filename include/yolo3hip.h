@@ -959,6 +959,33 @@ int y3_letterbox_unmap(float* rows, int n, int nb, int ld, const y3_letterbox_re
 int y3_format_labels(const int* boxes, const int* counts, int n, int max_boxes, const float* anchors_host, int num_anchors,
                      int num_classes, int img_h, int img_w, float* out1, float* out2, float* out3, y3_stream_t stream);
 
+/* ---- anchor fitting: P candidate anchor sets scored against n box sizes (opt-in, not in the reference: yolo3/anchors.py,
+ * find_anchor_sizes.py --metric iou, train.py --auto_anchors) -------------------------------------------------------
+ * wh_dev: DEVICE int32 [n][2] = (w, h) in pixels, 8-byte aligned (16-byte loads are used at either alignment); cand_dev: DEVICE
+ * float32 [P][k][2] = (w, h), positive and finite.  For every box and every set p: the IoU of the co-centred box and anchor, in
+ * the fp32 arithmetic of y3_format_labels (min / max / product / (sum - inter) / IEEE quotient, no contraction); the best anchor is
+ * the FIRST maximum (np.argmax: the slot y3_format_labels writes); the score is the integer q = rint(iou * 2^24) (to nearest even)
+ * in [0, 2^24].  Every accumulated quantity is an integer, so the sums depend neither on the order nor on the grid: two calls give
+ * the same bytes, and a NumPy restatement (yolo3.anchors.anchor_stats(device='cpu')) gives them too.
+ *   per_anchor != 0: out[P][k][5] = count, sum w, sum h, sum q, count(q >= thr_q) over the boxes whose best anchor it is;
+ *   per_anchor == 0: out[P][2]    = sum q, count(q >= thr_q) over all boxes;
+ * followed in both modes by ONE more int64: the number of skipped boxes.  A box whose w or h lies outside [1, 65535] is skipped and
+ * contributes nothing else.  labels_dev (nullable; P == 1 only): labels[i] = best anchor of box i, 255 for a skipped box.
+ * out_dev (8-byte aligned) need not be zeroed.  workspace: y3_anchor_stats_workspace_bytes(P, k) bytes, 8-byte aligned: one
+ * partial row per workgroup, added up by a second launch (no float atomics, no global atomics).
+ * The grid: a workgroup takes Y3_ANCHOR_BLOCK_BOXES boxes per pass, at most Y3_ANCHOR_MAX_BLOCKS workgroups run, so n above
+ * Y3_ANCHOR_MAX_BLOCKS * Y3_ANCHOR_BLOCK_BOXES makes the workgroups stride.
+ * Y3_EINVAL + message, nothing launched: k outside 1..Y3_ANCHOR_MAX_K (the 16 anchors the loss and decode take), P < 1, P * k > Y3_ANCHOR_MAX_CANDIDATES, n outside
+ * 1..2^31-1, thr_q outside 0..2^24, labels_dev with P != 1, a null or misaligned pointer.  (The workspace query returns 0 for a
+ * refused shape.) */
+#define Y3_ANCHOR_MAX_K 16
+#define Y3_ANCHOR_MAX_CANDIDATES 1024
+#define Y3_ANCHOR_BLOCK_BOXES 512
+#define Y3_ANCHOR_MAX_BLOCKS 512
+size_t y3_anchor_stats_workspace_bytes(int P, int k);
+int y3_anchor_stats(const int* wh_dev, long long n, const float* cand_dev, int P, int k, int thr_q, int per_anchor,
+                    long long* out_dev, unsigned char* labels_dev, void* workspace, y3_stream_t stream);
+
 /* ---- detection accuracy: matching + 101-point AP (not in the reference; yolo3/metrics.py, evaluate.py) ----
  * Detections are the keep lists of y3_nms_per_class: per (image, class) segment s = img * K + c the first
  * min(keep_cnt[s], max_keep, max_det) entries of keep_idx / keep_score, in keep order (descending score, ties: higher row

@@ -49,6 +49,11 @@ reference's Adam, and --weight_decay WD decays the convolution kernels only: cou
 §3.19).  --lr_schedule constant / cosine / step (with --lr_warmup_steps W, --lr_warmup_start_factor S, --lr_total_steps T,
 --lr_final_factor F, --lr_milestones A B ..., --lr_gamma G) replaces the epoch-0 rule by learning_rate x a factor of the optimiser
 step: epoch 0 then has the full size, and <scalars>/lr.csv gets one row per optimiser step.  The weight files record the optimiser.
+--anchors W,H [W,H ...], --anchors_file FILE (written by find_anchor_sizes.py --metric iou --output) or --auto_anchors K replace the
+reference's pair of anchors; at most one of the three.  --auto_anchors K fits K anchors to the boxes of the training
+database before the readers start (yolo3.anchors.fit_anchors; --auto_anchors_evolve, --auto_anchors_seed), on the host or, with
+--auto_anchors_device gpu, in a child process that runs find_anchor_sizes.py --device gpu (this process must not touch the GPU before
+its readers are forked); every rank computes the same anchors, rank 0 writes <out>/anchors.json.  The weight files carry the anchors.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -229,6 +234,63 @@ def build_lr_schedule(lr_schedule='reference', warmup_steps=0, warmup_start_fact
     return LrSchedule(lr_schedule, warmup_steps, warmup_start_factor, total_steps, final_factor, tuple(milestones), gamma)
 
 
+REFERENCE_ANCHORS = [(64, 384), (384, 64)]      # train.py:33
+
+
+def check_anchor_flags(anchors, anchors_file, auto_anchors):
+    """At most one of --anchors, --anchors_file and --auto_anchors; -> the checked --anchors list, or None without that flag."""
+    given = [name for name, v in (('--anchors', anchors), ('--anchors_file', anchors_file), ('--auto_anchors', auto_anchors)) if v is not None]
+    if len(given) > 1:
+        raise ValueError('{} and {} exclude each other: give at most one source of anchors'.format(given[0], given[1]))
+    if auto_anchors is not None and not 1 <= int(auto_anchors) <= 16:
+        raise ValueError('--auto_anchors K: K in 1..16, got {!r}'.format(auto_anchors))
+    if anchors is None:
+        return None
+    from yolo3.anchors import check_anchors, parse_anchor_args
+    if all(isinstance(a, str) for a in anchors):
+        return parse_anchor_args(anchors)
+    check_anchors(anchors)
+    return [tuple(a) for a in anchors]
+
+
+def resolve_anchors(anchors, anchors_file, auto_anchors, train_database_filepath, output_folder, rank=0, evolve=1000, seed=0, device='cpu'):
+    """The anchors of a run: the flag's, a file's, a fit to the boxes of the training database, or the reference's pair.  Runs before
+    the readers are created and never touches the GPU in this process: the device fit is a fresh child process."""
+    parsed = check_anchor_flags(anchors, anchors_file, auto_anchors)
+    if parsed is not None:
+        return parsed
+    if anchors_file is None and auto_anchors is None:
+        return list(REFERENCE_ANCHORS)
+    from yolo3 import anchors as fitting
+    if anchors_file is not None:
+        return [tuple(a) for a in fitting.load_anchors(anchors_file)['anchors']]
+    if device == 'gpu':
+        import subprocess
+        import sys
+        import tempfile
+        here = os.path.dirname(os.path.abspath(__file__))
+        with tempfile.TemporaryDirectory(prefix='anchors-rank{}-'.format(rank)) as tmp:
+            path = os.path.join(tmp, 'anchors.json')
+            env = dict(os.environ, PYTHONPATH=here + os.pathsep + os.environ.get('PYTHONPATH', ''))
+            r = subprocess.run([sys.executable, os.path.join(here, 'find_anchor_sizes.py'), '--metric', 'iou', '--database', train_database_filepath,
+                                '--k', str(int(auto_anchors)), '--evolve', str(int(evolve)), '--seed', str(int(seed)), '--device', 'gpu',
+                                '--output', path], env=env, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError('--auto_anchors_device gpu: find_anchor_sizes.py failed ({}):\n{}'.format(r.returncode, r.stderr[-2000:]))
+            fit = fitting.load_anchors(path)
+    else:
+        wh = fitting.load_sizes_lmdb(train_database_filepath)
+        if wh.shape[0] == 0:
+            raise ValueError('--auto_anchors: {} holds no boxes'.format(train_database_filepath))
+        fit = fitting.fit_anchors(wh, int(auto_anchors), seed=int(seed), evolve=int(evolve), device='cpu')
+    if rank == 0:
+        print('Anchors fitted to the {} boxes of {} (scored on the {}):'.format(fit['n'], train_database_filepath, device))
+        for line in fitting.format_fit(fit):
+            print(line)
+        fitting.save_anchors(os.path.join(output_folder, 'anchors.json'), fit)
+    return [tuple(a) for a in fit['anchors']]
+
+
 def describe_freeze(specs, freeze_layers, freeze_bn):
     """The line train_model prints about a fine-tuning run: how many layers and parameters are frozen and how many train."""
     count = lambda sp: sp.k * sp.k * sp.cin * sp.cout + sp.cout * (3 if sp.bn else 1)
@@ -249,7 +311,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9, nesterov=False, weight_decay=0.0, lr_schedule='reference',
                 lr_warmup_steps=0, lr_warmup_start_factor=0.0, lr_total_steps=None, lr_final_factor=0.01, lr_milestones=(), lr_gamma=0.1,
                 affine_prob=0.0, affine_degrees=10.0, affine_shear=2.0, affine_scale=0.1, affine_translate=0.1, affine_fill=0.0, affine_seed=0,
-                affine_min_visible=0.25, init_weights=None, init_optimizer=False, freeze_layers=0, freeze_bn=False):
+                affine_min_visible=0.25, init_weights=None, init_optimizer=False, freeze_layers=0, freeze_bn=False, anchors=None, anchors_file=None,
+                auto_anchors=None, auto_anchors_evolve=1000, auto_anchors_seed=0, auto_anchors_device='cpu'):
+    check_anchor_flags(anchors, anchors_file, auto_anchors)
     spp_kw = dict(spp=True) if spp else {}
     from yolo3.model import check_freeze_args
     check_freeze_args(freeze_layers, freeze_bn)
@@ -288,10 +352,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         bbox_utils.check_nms_args(test_map_nms, test_map_nms_sigma)
     ema_decay = float(ema_decay) if ema_decay else None
     os.makedirs(output_folder, exist_ok=True)
-    anchors = [(64, 384), (384, 64)]
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
+    # the reference's pair unless a flag says otherwise; before the readers, which take the anchors and fork
+    anchors = resolve_anchors(anchors, anchors_file, auto_anchors, train_database_filepath, output_folder, rank, auto_anchors_evolve,
+                              auto_anchors_seed, auto_anchors_device)
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     global_batch_size = batch_size * world
     local_world = int(os.environ.get('LOCAL_WORLD_SIZE', str(world)))
@@ -801,6 +867,12 @@ class _Parser(argparse.ArgumentParser):
         if a.init_optimizer and not a.init_weights:
             self.error('--init_optimizer 1 needs --init_weights')
         try:
+            check_anchor_flags(a.anchors, a.anchors_file, a.auto_anchors)
+        except ValueError as e:
+            self.error(str(e))
+        if a.auto_anchors is None and (a.auto_anchors_evolve != 1000 or a.auto_anchors_seed != 0 or a.auto_anchors_device != 'cpu'):
+            self.error('--auto_anchors_evolve / --auto_anchors_seed / --auto_anchors_device need --auto_anchors K')
+        try:
             build_lr_schedule(a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor, a.lr_milestones,
                               a.lr_gamma)
         except ValueError as e:
@@ -946,6 +1018,20 @@ def build_parser():
     parser.add_argument('--freeze_bn', dest='freeze_bn', type=int, choices=(0, 1), default=0,
                         help='(addition) 1: the BatchNorm of the trainable layers normalises with the stored moving statistics, which are '
                              'not updated; gamma and beta keep training (for batches too small to estimate statistics from)')
+    parser.add_argument('--anchors', dest='anchors', type=str, nargs='+', default=None, metavar='W,H',
+                        help='(addition) the anchors, as W,H pairs in pixels (at most 16), in place of the reference\'s 64,384 384,64; the '
+                             'weight files carry them, so inference.py, inference_tiled.py and evaluate.py need no flag')
+    parser.add_argument('--anchors_file', dest='anchors_file', type=str, default=None,
+                        help='(addition) take the anchors from this JSON file (find_anchor_sizes.py --metric iou --output)')
+    parser.add_argument('--auto_anchors', dest='auto_anchors', type=int, default=None, metavar='K',
+                        help='(addition) fit K anchors (1..16) to the boxes of the training database before training starts (IoU k-means and a '
+                             'mutation search); <output_dir>/anchors.json records them')
+    parser.add_argument('--auto_anchors_evolve', dest='auto_anchors_evolve', type=_step_count_arg, default=1000,
+                        help='(addition) mutants tried by the search of --auto_anchors (default 1000; 0: IoU k-means alone)')
+    parser.add_argument('--auto_anchors_seed', dest='auto_anchors_seed', type=int, default=0, help='(addition) seed of --auto_anchors')
+    parser.add_argument('--auto_anchors_device', dest='auto_anchors_device', choices=('cpu', 'gpu'), default='cpu',
+                        help='(addition) where --auto_anchors scores its candidates: cpu (in this process) or gpu (a child process running the '
+                             'HIP kernel); the same anchors either way')
     return parser
 
 
@@ -962,4 +1048,5 @@ if __name__ == "__main__":
                 a.ignore_max_boxes, a.focal_gamma, a.focal_alpha, a.focal_terms, a.label_smoothing, bool(a.spp), a.optimizer, a.momentum, bool(a.nesterov),
                 a.weight_decay, a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor,
                 tuple(a.lr_milestones), a.lr_gamma, a.affine_prob, a.affine_degrees, a.affine_shear, a.affine_scale, a.affine_translate,
-                a.affine_fill, a.affine_seed, a.affine_min_visible, a.init_weights, bool(a.init_optimizer), a.freeze_layers, bool(a.freeze_bn))
+                a.affine_fill, a.affine_seed, a.affine_min_visible, a.init_weights, bool(a.init_optimizer), a.freeze_layers, bool(a.freeze_bn),
+                a.anchors, a.anchors_file, a.auto_anchors, a.auto_anchors_evolve, a.auto_anchors_seed, a.auto_anchors_device)

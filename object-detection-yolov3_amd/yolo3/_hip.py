@@ -163,6 +163,8 @@ SIGNATURES = {
     'y3_letterbox_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'y3_letterbox_unmap': (i32, [fp, i32, i32, i32, vp, i32, vp]),
     'y3_format_labels': (i32, [ip, ip, i32, i32, C.POINTER(C.c_float), i32, i32, i32, i32, fp, fp, fp, vp]),
+    'y3_anchor_stats_workspace_bytes': (sz, [i32, i32]),
+    'y3_anchor_stats': (i32, [ip, C.c_longlong, fp, i32, i32, i32, i32, vp, vp, vp, vp]),
     'y3_eval_offsets':(i32, [ip, i32, i32, i32, ip, vp]),
     'y3_eval_match': (i32, [fp, i32, i32, i32, i32, f32, f32, ip, ip, fp, i32, i32, fp, ip, i32, i32, C.POINTER(C.c_float), i32, ip,
                             vp, vp, C.c_longlong, vp]),     # iou_thr: HOST array
