@@ -882,6 +882,49 @@ typedef struct y3_affine_record {   /* 32 bytes, one per image */
 int y3_affine_batch(const float* src, int n, int c, int h, int w, const y3_affine_record* records_host, float* out,
                     y3_stream_t stream);
 
+/* ---- colour / tone jitter and MixUp (not in the reference; yolo3/augment.py draw_photometric / draw_mixup / mixup_boxes /
+ * photometric_reference) ------------------------------------------------------------------------------------------
+ * One elementwise pass over an augmented batch, just before the z-score.  The z-score cancels a uniform gain and offset, so what
+ * this pass offers is cross-channel (the matrix: hue, saturation) or non-linear (clamp, tone curve), and a blend of two images.
+ * P_r(x), the photometric value of the pixel x (all its channels c0, c1, c2) under record r, is evaluated in fp32, every
+ * operation rounded on its own in exactly this order (no fused multiply-add), so NumPy float32 reproduces stages 1, 2 and 4 bit
+ * for bit (augment.photometric_reference):
+ *   1 matrix   v_k = ((m_k0*c0 + m_k1*c1) + m_k2*c2) + bias_k.  A term whose coefficient is exactly 0 is not evaluated and its
+ *              channel is not read for that row; a coefficient of exactly 1 passes its channel unmultiplied; a zero bias is not
+ *              added; a row with no term and no bias is +0.  So a row with one coefficient 1, the others 0 and zero bias copies
+ *              that channel's bits: the identity and the six channel permutations are exact copies, NaN payloads and -0.0
+ *              included, and NaN or Inf in one channel never reaches a row that does not use it.  C == 1 uses m[0], bias[0] only.
+ *   2 clamp    (white > 0)  t = v < 0 ? 0 : (v > white ? white : v): selects, so NaN stays NaN.
+ *   3 curve    (gamma != 1) y = white * pow(t / white, gamma): IEEE division, pow(s, g) = exp2f(g * log2f(s)) with the device
+ *              library's exp2f / log2f (the hardware exponential and logarithm with denormal scaling), pow(0, g) = 0 and
+ *              pow(1, g) = 1 exactly, so t = 0 and t = white are fixed points.  No accuracy of these two functions is documented
+ *              for this target; the one relied on is measured: |y - exact| <= K * (1 + g * |log2(t / white)|) * 2^-24 * |y| with
+ *              K four times the worst ratio seen on an MI355X (tests/photometric_reference.py, profiles/photometric_err.txt).
+ *              Only images whose record (or whose partner's record) has gamma != 1 execute it.
+ *   4 MixUp    out_i = lambda == 1 ? P_i(src_i) : (lambda * P_i(src_i)) + ((1 - lambda) * P_p(src_partner)), 1 - lambda formed
+ *              in fp32, P_p under the PARTNER's own record: a mixed image blends two finished images.  With lambda == 1 the
+ *              partner is not read.  The payload of a NaN that goes through arithmetic (stages 1 with a product or sum, 3, 4) is
+ *              the hardware's; that it is a NaN is guaranteed.
+ * src, out: DEVICE float32 [n][c][h][w], c = 1 or 3, any h, w >= 1 (h * w < 2^31 - 8), 4-byte aligned; the ranges must not
+ * overlap (output i reads images i and partner: the pass cannot run in place).  records: HOST array of n records, validated
+ * before any launch (Y3_EINVAL + message: null pointer; bad c, n, h, w; misaligned or overlapping src / out; a non-finite
+ * coefficient, bias, gamma, white or lambda; gamma <= 0; white < 0; white == 0 with gamma != 1; lambda outside [0, 1]; lambda < 1
+ * with partner outside [0, n)) and handed to the kernel as kernel arguments, 16 output images per launch (each with its
+ * partner's operator beside its own).  One thread per 16-byte-aligned group of four pixels of `out` and all their channel planes
+ * when h * w is a multiple of 4 (16-byte loads at 4-byte alignment, aligned 16-byte stores, the partial first and last group of
+ * a plane float by float), one pixel per thread otherwise; every output element is written by exactly one thread: no atomics,
+ * no workspace, the same bits on every launch. */
+typedef struct y3_photo_record {   /* 64 bytes, one per OUTPUT image */
+    float   m[9];      /* colour matrix, row-major: out channel k = m[3k+0]*c0 + m[3k+1]*c1 + m[3k+2]*c2 (+ bias[k]); C == 1 uses m[0], bias[0] only */
+    float   bias[3];
+    float   gamma;     /* 1 = no tone curve */
+    float   white;     /* > 0: clamp to [0, white] after the matrix and scale the tone curve by it; 0: no clamp, gamma must be 1 */
+    int32_t partner;   /* MixUp source image in [0, n); ignored when lambda == 1 */
+    float   lambda;    /* in [0, 1]; 1 = no MixUp */
+} y3_photo_record;
+int y3_photometric_batch(const float* src, int n, int c, int h, int w, const y3_photo_record* records_host, float* out,
+                         y3_stream_t stream);
+
 /* ---- letterbox front end of inference: images of any size into the network frame and the boxes back (opt-in, not in the
  * reference: inference.py / evaluate.py --letterbox, YoloV3.predict_letterbox) --------------------------------------
  * A ragged batch of 1 <= n <= Y3_LETTERBOX_MAX_IMAGES images lies in ONE device buffer src (16-byte aligned), image i densely

@@ -24,6 +24,14 @@
 //   affine        one thread per output pixel and all its channels, 32 x 32 pixels per workgroup: fp32 coordinates in a stated
 //                 unfused order, four taps gathered straight from global memory (the two of a row as one 8-byte load in the
 //                 interior), `fill` outside the image, taps of weight zero never read.
+//
+// Colour / tone jitter and MixUp (not in the reference; y3_photometric_batch, semantics in yolo3hip.h): a fourth,
+// separate pass, elementwise over the batch.
+//   photometric   one thread per 16-byte-aligned group of four pixels and all their channel planes (planes of a multiple of four
+//                 elements; one pixel per thread otherwise): colour matrix with scalar branches on the record's zeros, clamp,
+//                 tone curve as exp2(gamma * log2(t / white)) only for images whose record asks for it, and the blend with the
+//                 partner image evaluated under the partner's own record.  Streaming: each source element is read once (twice
+//                 for a mixed image) with 16-byte loads at 4-byte alignment, each output element stored once, aligned.
 #include "common.h"
 #include <math.h>
 #include <algorithm>
@@ -593,6 +601,179 @@ extern "C" int y3_affine_batch(const float* src, int n, int c, int h, int w, con
         if (c == 1) hipLaunchKernelGGL(affine_kernel<1>, grid, dim3(256), 0, st, src + (size_t)base * image, out + (size_t)base * image, tab, h, w, tilesx);
         else hipLaunchKernelGGL(affine_kernel<3>, grid, dim3(256), 0, st, src + (size_t)base * image, out + (size_t)base * image, tab, h, w, tilesx);
         Y3_CHECK_LAUNCH("affine_batch");
+    }
+    return Y3_OK;
+}
+
+// ---- colour matrix, clamp, tone curve and MixUp: one elementwise pass (not in the reference) --------------------------------
+#define Y3_PHO_CHUNK 16            // images per launch: 16 x 128 B of table travel as a kernel argument
+
+struct PhoOp {                     // 56 bytes: the photometric part of one y3_photo_record
+    float m[9];
+    float bias[3];
+    float gamma, white;
+};
+struct PhoImg {                    // 128 bytes, one per OUTPUT image
+    PhoOp self, other;             // its own record's and its partner's record's operator (`other` unused when lambda == 1)
+    long long own, partner;        // element offsets of the image and of its partner from `src` (the whole batch)
+};
+struct PhoTable {
+    PhoImg img[Y3_PHO_CHUNK];
+    float lambda[Y3_PHO_CHUNK];
+};
+typedef float pho_f4 __attribute__((ext_vector_type(4)));
+typedef float pho_f4u __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes at 4-byte alignment: one global_load_dwordx4
+
+// P_r of the G pixels e0 .. e0 + G - 1 of the image at `p` (planes of P elements) -> v[channel][pixel].  Only the pixels in
+// [lo, hi) are read (`whole`: all G = 4 of them, as one 16-byte load per plane); the others come out as P_r(0) and are never
+// stored.  Every branch on the record is uniform over the workgroup (the record is per image): scalar branches.  fp32, one
+// rounding per operation in the order of yolo3hip.h (-ffp-contract=off), which augment.photometric_reference restates:
+//   matrix   a term with coefficient 0 is skipped, and a channel no row uses is not loaded; a coefficient of exactly 1 passes its
+//            channel unmultiplied; a zero bias is not added; a row without terms and bias is +0
+//   clamp    selects, not max / min: NaN stays NaN (and -0.0 stays -0.0)
+//   curve    s = t / white (IEEE division), white * exp2f(gamma * log2f(s)); s == 0 gives 0 and s == 1 gives 1 (log2f(1) = 0,
+//            exp2f(0) = 1), so both ends are exact; exp2f / log2f are the device library's (they scale denormals around the
+//            hardware v_exp_f32 / v_log_f32); the accuracy relied on is the measured one of profiles/photometric_err.txt
+template <int C, int G>
+__device__ __forceinline__ void pho_eval(const PhoOp& r, const float* __restrict__ p, int P, int e0, bool whole, int lo, int hi, float (&v)[C][G]) {
+    float c[C][G];
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        bool used = false;
+#pragma unroll
+        for (int k = 0; k < C; ++k) used = used || r.m[3 * k + j] != 0.f;
+#pragma unroll
+        for (int i = 0; i < G; ++i) c[j][i] = 0.f;
+        if (!used) continue;
+        const float* q = p + (size_t)j * (size_t)P;
+        if (G == 4 && whole) {
+            const pho_f4u t = *(const pho_f4u*)(q + e0);
+#pragma unroll
+            for (int i = 0; i < G; ++i) c[j][i] = t[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                if (e0 + i >= lo && e0 + i < hi) c[j][i] = q[e0 + i];
+        }
+    }
+    const bool clamp = r.white > 0.f, curve = r.gamma != 1.f;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const float* mk = r.m + 3 * k;
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            float acc = 0.f;
+            bool started = false;
+#pragma unroll
+            for (int j = 0; j < C; ++j)
+                if (mk[j] != 0.f) {
+                    const float t = mk[j] == 1.f ? c[j][i] : mk[j] * c[j][i];
+                    acc = started ? acc + t : t;
+                    started = true;
+                }
+            if (r.bias[k] != 0.f) acc = started ? acc + r.bias[k] : r.bias[k];
+            if (clamp) acc = acc < 0.f ? 0.f : (acc > r.white ? r.white : acc);
+            if (curve) {
+                const float s = acc / r.white;
+                acc = r.white * (s == 0.f ? 0.f : exp2f(r.gamma * log2f(s)));
+            }
+            v[k][i] = acc;
+        }
+    }
+}
+
+// grid (groups of a plane / 256, 1, images of the chunk).  `out` is the chunk's first output image, `src` the whole batch.  G = 4:
+// thread t of the grid owns the 16-byte-aligned group of four output floats that starts e0 = 4 t - a elements into each plane of
+// its image, a = the plane's offset into a 16-byte group (the same for every plane: P is a multiple of 4); the first and last group
+// of a plane may be partial and go float by float.  G = 1 (P no multiple of 4): one pixel per thread.
+template <int C, int G>
+__global__ __launch_bounds__(256) void photometric_kernel(const float* __restrict__ src, float* __restrict__ out, PhoTable tab, int P) {
+    const PhoImg& r = tab.img[blockIdx.z];
+    const float lambda = tab.lambda[blockIdx.z];
+    float* o = out + (size_t)blockIdx.z * C * (size_t)P;
+    const int a = G == 4 ? (int)(((size_t)o >> 2) & 3) : 0;
+    const int e0 = (int)((blockIdx.x * 256u + threadIdx.x) * (unsigned)G) - a;      // -3 .. P-1
+    if (e0 >= P) return;
+    const int lo = max(e0, 0), hi = min(e0 + G, P);
+    const bool whole = e0 >= 0 && e0 + G <= P;
+    float v[C][G];
+    pho_eval<C, G>(r.self, src + r.own, P, e0, whole, lo, hi, v);
+    if (lambda != 1.f) {                                         // uniform: an image that is not mixed never reads a partner
+        float u[C][G];
+        pho_eval<C, G>(r.other, src + r.partner, P, e0, whole, lo, hi, u);
+        const float rest = 1.f - lambda;
+#pragma unroll
+        for (int k = 0; k < C; ++k)
+#pragma unroll
+            for (int i = 0; i < G; ++i) v[k][i] = (lambda * v[k][i]) + (rest * u[k][i]);
+    }
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        float* q = o + (size_t)k * (size_t)P;
+        if (G == 4 && whole) {
+            pho_f4 t;
+#pragma unroll
+            for (int i = 0; i < G; ++i) t[i] = v[k][i];
+            *(pho_f4*)(q + e0) = t;
+        } else {
+#pragma unroll
+            for (int i = 0; i < G; ++i)
+                if (e0 + i >= lo && e0 + i < hi) q[e0 + i] = v[k][i];
+        }
+    }
+}
+
+extern "C" int y3_photometric_batch(const float* src, int n, int c, int h, int w, const y3_photo_record* records, float* out, y3_stream_t stream) {
+    Y3_CHECK_ARG(src && records && out, "photometric_batch: null pointer");
+    Y3_CHECK_ARG(c == 1 || c == 3, "photometric_batch: channels %d (1 or 3)", c);
+    Y3_CHECK_ARG(n > 0 && h > 0 && w > 0, "photometric_batch: bad dims n %d, %dx%d", n, h, w);
+    Y3_CHECK_ARG((long long)h * w < (1LL << 31) - 8, "photometric_batch: plane %dx%d too large", h, w);
+    const size_t plane = (size_t)h * w, image = plane * c, bytes = (size_t)n * image * sizeof(float);
+    Y3_CHECK_ARG((((size_t)src | (size_t)out) & 3) == 0, "photometric_batch: src / out not 4-byte aligned");
+    Y3_CHECK_ARG((size_t)src + bytes <= (size_t)out || (size_t)out + bytes <= (size_t)src, "photometric_batch: src and out overlap (the pass cannot run in place)");
+    for (int i = 0; i < n; ++i) {
+        const y3_photo_record& r = records[i];
+        bool finite = isfinite(r.gamma) && isfinite(r.white) && isfinite(r.lambda);
+        for (int k = 0; k < 9; ++k) finite = finite && isfinite(r.m[k]);
+        for (int k = 0; k < 3; ++k) finite = finite && isfinite(r.bias[k]);
+        Y3_CHECK_ARG(finite, "photometric_batch: record %d: non-finite coefficient, bias, gamma, white or lambda", i);
+        Y3_CHECK_ARG(r.gamma > 0.f, "photometric_batch: record %d: gamma %g (must be > 0)", i, r.gamma);
+        Y3_CHECK_ARG(r.white >= 0.f, "photometric_batch: record %d: white %g (must be >= 0)", i, r.white);
+        Y3_CHECK_ARG(r.white > 0.f || r.gamma == 1.f, "photometric_batch: record %d: gamma %g needs white > 0 (the tone curve is scaled by it)", i, r.gamma);
+        Y3_CHECK_ARG(r.lambda >= 0.f && r.lambda <= 1.f, "photometric_batch: record %d: lambda %g outside [0, 1]", i, r.lambda);
+        Y3_CHECK_ARG(r.lambda == 1.f || (r.partner >= 0 && r.partner < n), "photometric_batch: record %d: partner image %d of %d", i, r.partner, n);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int g = (plane & 3) == 0 ? 4 : 1;
+    const int groups = g == 4 ? y3_cdiv((long long)plane + 3, 4) : (int)plane;
+    auto op = [](const y3_photo_record& r) {
+        PhoOp p;
+        for (int k = 0; k < 9; ++k) p.m[k] = r.m[k];
+        for (int k = 0; k < 3; ++k) p.bias[k] = r.bias[k];
+        p.gamma = r.gamma;
+        p.white = r.white;
+        return p;
+    };
+    for (int base = 0; base < n; base += Y3_PHO_CHUNK) {
+        const int nb = std::min(Y3_PHO_CHUNK, n - base);
+        PhoTable tab = {};
+        for (int i = 0; i < nb; ++i) {
+            const y3_photo_record& r = records[base + i];
+            const bool mixed = r.lambda != 1.f;
+            tab.img[i].self = op(r);
+            tab.img[i].other = op(mixed ? records[r.partner] : r);
+            tab.img[i].own = (long long)(base + i) * (long long)image;
+            tab.img[i].partner = mixed ? (long long)r.partner * (long long)image : tab.img[i].own;
+            tab.lambda[i] = r.lambda;
+        }
+        for (int i = nb; i < Y3_PHO_CHUNK; ++i) tab.lambda[i] = 1.f;
+        const dim3 grid((unsigned)y3_cdiv(groups, 256), 1, nb);
+        float* o = out + (size_t)base * image;
+        if (c == 1 && g == 4) hipLaunchKernelGGL((photometric_kernel<1, 4>), grid, dim3(256), 0, st, src, o, tab, (int)plane);
+        else if (c == 1) hipLaunchKernelGGL((photometric_kernel<1, 1>), grid, dim3(256), 0, st, src, o, tab, (int)plane);
+        else if (g == 4) hipLaunchKernelGGL((photometric_kernel<3, 4>), grid, dim3(256), 0, st, src, o, tab, (int)plane);
+        else hipLaunchKernelGGL((photometric_kernel<3, 1>), grid, dim3(256), 0, st, src, o, tab, (int)plane);
+        Y3_CHECK_LAUNCH("photometric_batch");
     }
     return Y3_OK;
 }

@@ -33,6 +33,13 @@ Composes with the --multiscale_* flags; the test reader, the mAP pass, the check
 side) on the device, after the augmentation and the mosaic; pixels from outside the image get --affine_fill, the
 draws are a pure function of --affine_seed, the rank, the batch count and the image, and a box stays when at least
 --affine_min_visible of its transformed area is inside the image.  Composes with --multiscale_* and --mosaic_prob.
+--photo_prob P (with --augmentation_device gpu; 0 = off) sends each training image, with probability P, through a random colour
+matrix (hue rotation by +-photo_hue turns and saturation gain 1 +- photo_saturation of the YIQ chroma plane, value gain 1 +-
+photo_value), a clamp to [0, photo_white] and a tone curve with exponent 2^(+-photo_gamma); --mixup_prob P (0 = off) blends each
+image, with probability P, with another image of its batch, lambda uniform in 0.5 +- mixup_spread, and gives it the boxes of both.
+Both are one elementwise pass on the device after the warp, right before the z-score; the draws are pure functions
+of --photo_seed / --mixup_seed, the rank, the batch count and the image.  A brightness gain alone would be cancelled by the
+per-image z-score; that is why there is no such flag.
 --ignore_mask truth (with --ignore_thresh T, default 0.5, and --ignore_max_boxes N, default 1024) leaves a prediction without an
 object out of the objectness loss when it overlaps a ground-truth box of its own image with IoU >= T, the rule of the paper, in
 place of the reference's mask; training and test loss use the same mask.  <scalars>/ignored.csv gets one row per
@@ -219,6 +226,37 @@ def check_affine_args(affine_prob, affine_degrees=10.0, affine_shear=2.0, affine
     return p
 
 
+def check_photo_args(photo_prob, photo_hue=0.015, photo_saturation=0.7, photo_value=0.4, photo_gamma=0.0, photo_white=None):
+    """--photo_prob and its magnitudes -> the probability as a float (0.0 = off).  ValueError outside the ranges of
+    Dataset.photometric: prob in [0, 1], hue in [0, 0.5], saturation and value in [0, 1], gamma in [0, 4], white finite and > 0
+    (or not given: the top of the stored pixel range)."""
+    p = float(photo_prob or 0.0)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('--photo_prob must be in [0, 1], got {!r}'.format(photo_prob))
+    if not 0.0 <= float(photo_hue) <= 0.5:
+        raise ValueError('--photo_hue must be in [0, 0.5], got {!r}'.format(photo_hue))
+    if not 0.0 <= float(photo_saturation) <= 1.0:
+        raise ValueError('--photo_saturation must be in [0, 1], got {!r}'.format(photo_saturation))
+    if not 0.0 <= float(photo_value) <= 1.0:
+        raise ValueError('--photo_value must be in [0, 1], got {!r}'.format(photo_value))
+    if not 0.0 <= float(photo_gamma) <= 4.0:
+        raise ValueError('--photo_gamma must be in [0, 4], got {!r}'.format(photo_gamma))
+    if photo_white is not None and not 0.0 < float(photo_white) < float('inf'):
+        raise ValueError('--photo_white must be finite and > 0, got {!r}'.format(photo_white))
+    return p
+
+
+def check_mixup_args(mixup_prob, mixup_spread=0.1):
+    """--mixup_prob and --mixup_spread -> the probability as a float (0.0 = off).  ValueError outside prob in [0, 1], spread in
+    [0, 0.5]."""
+    p = float(mixup_prob or 0.0)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError('--mixup_prob must be in [0, 1], got {!r}'.format(mixup_prob))
+    if not 0.0 <= float(mixup_spread) <= 0.5:
+        raise ValueError('--mixup_spread must be in [0, 0.5], got {!r}'.format(mixup_spread))
+    return p
+
+
 def build_lr_schedule(lr_schedule='reference', warmup_steps=0, warmup_start_factor=0.0, total_steps=None, final_factor=0.01, milestones=(),
                       gamma=0.1):
     """--lr_schedule and its flags -> a yolo3.schedule.LrSchedule, or None for 'reference' (the loop's own epoch-0 rule, which
@@ -312,7 +350,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 lr_warmup_steps=0, lr_warmup_start_factor=0.0, lr_total_steps=None, lr_final_factor=0.01, lr_milestones=(), lr_gamma=0.1,
                 affine_prob=0.0, affine_degrees=10.0, affine_shear=2.0, affine_scale=0.1, affine_translate=0.1, affine_fill=0.0, affine_seed=0,
                 affine_min_visible=0.25, init_weights=None, init_optimizer=False, freeze_layers=0, freeze_bn=False, anchors=None, anchors_file=None,
-                auto_anchors=None, auto_anchors_evolve=1000, auto_anchors_seed=0, auto_anchors_device='cpu'):
+                auto_anchors=None, auto_anchors_evolve=1000, auto_anchors_seed=0, auto_anchors_device='cpu', photo_prob=0.0, photo_hue=0.015,
+                photo_saturation=0.7, photo_value=0.4, photo_gamma=0.0, photo_white=None, photo_seed=0, mixup_prob=0.0, mixup_spread=0.1,
+                mixup_seed=0):
     check_anchor_flags(anchors, anchors_file, auto_anchors)
     spp_kw = dict(spp=True) if spp else {}
     from yolo3.model import check_freeze_args
@@ -332,6 +372,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     affine_prob = check_affine_args(affine_prob, affine_degrees, affine_shear, affine_scale, affine_translate, affine_fill, affine_min_visible)
     if affine_prob and augmentation_device != 'gpu':
         raise ValueError('affine augmentation needs augmentation_device gpu: the batches are warped and labelled on the device')
+    photo_prob = check_photo_args(photo_prob, photo_hue, photo_saturation, photo_value, photo_gamma, photo_white)
+    if photo_prob and augmentation_device != 'gpu':
+        raise ValueError('photometric augmentation needs augmentation_device gpu: the pass runs on the device, after the augmentation')
+    mixup_prob = check_mixup_args(mixup_prob, mixup_spread)
+    if mixup_prob and augmentation_device != 'gpu':
+        raise ValueError('mixup needs augmentation_device gpu: the batches are blended and labelled on the device')
     train_sizes = multiscale_sizes(multiscale_min, multiscale_max)
     if train_sizes is not None and augmentation_device != 'gpu':
         raise ValueError('multi-scale training needs augmentation_device gpu: the batches are resampled and labelled on the device')
@@ -377,9 +423,10 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     print('Setting up training image reader')
     train_reader = imagereader.ImageReader(train_database_filepath, anchors, use_augmentation=use_augmentation, shuffle=True,
                                            num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device,
-                                           **(dict(label_device='gpu') if train_sizes is not None or mosaic_prob or affine_prob else {}),
-                                           # (a shuffled reader ignores its shard when it picks keys; the mosaic and affine draws are keyed by it)
-                                           **(dict(num_shards=world, shard_index=rank) if mosaic_prob or affine_prob else {}))
+                                           **(dict(label_device='gpu') if train_sizes is not None or mosaic_prob or affine_prob or mixup_prob else {}),
+                                           # (a shuffled reader ignores its shard when it picks keys; the mosaic, affine, photometric and
+                                           # mixup draws are keyed by it)
+                                           **(dict(num_shards=world, shard_index=rank) if mosaic_prob or affine_prob or photo_prob or mixup_prob else {}))
     print('Train Reader has {} images'.format(train_reader.get_image_count()))
     training_checkpoint_filepath = None
     try:
@@ -427,6 +474,15 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                   'the side, fill {:g} (seed {}); boxes with less than {:g} of their area inside the image are dropped; the test reader is '
                   'untouched'.format(affine_prob, affine_degrees, affine_shear, affine_scale, affine_translate, affine_fill, affine_seed,
                                      affine_min_visible))
+        if photo_prob:
+            train_dataset = train_dataset.photometric(photo_prob, photo_hue, photo_saturation, photo_value, photo_gamma, photo_seed, photo_white)
+            print('Photometric augmentation: probability {:g} per image, hue +-{:g} turns, saturation 1 +- {:g}, value 1 +- {:g}, tone exponent '
+                  '2^+-{:g}, white {:g} (seed {}); the test reader is untouched'.format(photo_prob, photo_hue, photo_saturation, photo_value, photo_gamma,
+                                                                                       train_dataset.photo_cfg[6], photo_seed))
+        if mixup_prob:
+            train_dataset = train_dataset.mixup(mixup_prob, mixup_spread, mixup_seed)
+            print('MixUp: probability {:g} per image, lambda uniform in 0.5 +- {:g} (seed {}), partner from the same batch, boxes of both '
+                  'images kept; the test reader is untouched'.format(mixup_prob, mixup_spread, mixup_seed))
 
         print('Creating model')
         number_classes = train_reader.get_number_classes()
@@ -850,6 +906,18 @@ class _Parser(argparse.ArgumentParser):
             self.error(str(e))
         if prob and a.augmentation_device != 'gpu':
             self.error('--affine_prob needs --augmentation_device gpu')
+        try:
+            prob = check_photo_args(a.photo_prob, a.photo_hue, a.photo_saturation, a.photo_value, a.photo_gamma, a.photo_white)
+        except ValueError as e:
+            self.error(str(e))
+        if prob and a.augmentation_device != 'gpu':
+            self.error('--photo_prob needs --augmentation_device gpu')
+        try:
+            prob = check_mixup_args(a.mixup_prob, a.mixup_spread)
+        except ValueError as e:
+            self.error(str(e))
+        if prob and a.augmentation_device != 'gpu':
+            self.error('--mixup_prob needs --augmentation_device gpu')
         # (yolo3.model.check_ignore_mask_args, which train_model calls, restated: parsing loads no device library)
         if a.ignore_mask == 'reference' and (a.ignore_thresh != 0.5 or a.ignore_max_boxes != 1024):
             self.error("--ignore_thresh / --ignore_max_boxes need --ignore_mask truth: the reference's mask has no such parameters")
@@ -956,6 +1024,30 @@ def build_parser():
                         help='(addition) seed of the affine draws: a pure function of (seed, rank, batch count, image)')
     parser.add_argument('--affine_min_visible', dest='affine_min_visible', type=float, default=0.25,
                         help='(addition) a warped box stays when at least this share of its transformed area lies inside the image (default 0.25)')
+    parser.add_argument('--photo_prob', dest='photo_prob', type=float, default=0.0,
+                        help='(addition) off by default; P in (0, 1]: each training image goes, with probability P, through a random colour '
+                             'matrix, clamp and tone curve on the device (needs --augmentation_device gpu; the test reader is untouched)')
+    parser.add_argument('--photo_hue', dest='photo_hue', type=float, default=0.015,
+                        help='(addition) the YIQ chroma plane is rotated by +- this many turns, in [0, 0.5] (default 0.015)')
+    parser.add_argument('--photo_saturation', dest='photo_saturation', type=float, default=0.7,
+                        help='(addition) the chroma gain is drawn in 1 +- this, in [0, 1] (default 0.7)')
+    parser.add_argument('--photo_value', dest='photo_value', type=float, default=0.4,
+                        help='(addition) the value gain is drawn in 1 +- this, in [0, 1] (default 0.4); alone it is cancelled by the z-score '
+                             'up to the clamp at --photo_white')
+    parser.add_argument('--photo_gamma', dest='photo_gamma', type=float, default=0.0,
+                        help='(addition) the tone exponent is 2^e, e drawn in +- this, in [0, 4] (default 0: no tone curve)')
+    parser.add_argument('--photo_white', dest='photo_white', type=float, default=None,
+                        help='(addition) top of the pixel range: the clamp and the scale of the tone curve (default: 255 for a uint8, 65535 '
+                             'for a uint16 database; a float32 database must give it)')
+    parser.add_argument('--photo_seed', dest='photo_seed', type=int, default=0,
+                        help='(addition) seed of the photometric draws: a pure function of (seed, rank, batch count, image)')
+    parser.add_argument('--mixup_prob', dest='mixup_prob', type=float, default=0.0,
+                        help='(addition) off by default; P in (0, 1]: each training image is blended, with probability P, with another image '
+                             'of its batch and gets the boxes of both (needs --augmentation_device gpu; the test reader is untouched)')
+    parser.add_argument('--mixup_spread', dest='mixup_spread', type=float, default=0.1,
+                        help='(addition) lambda is uniform in 0.5 +- this, in [0, 0.5] (default 0.1); a uniform window, not a Beta draw')
+    parser.add_argument('--mixup_seed', dest='mixup_seed', type=int, default=0,
+                        help='(addition) seed of the MixUp draws: a pure function of (seed, rank, batch count, image)')
     parser.add_argument('--ignore_mask', dest='ignore_mask', choices=IGNORE_MASKS, default='reference',
                         help='(addition) ignore mask of the objectness loss: reference (default) = the reference\'s; truth = a prediction '
                              'without an object is left out when it overlaps a ground-truth box of its own image with IoU >= --ignore_thresh')
@@ -1049,4 +1141,7 @@ if __name__ == "__main__":
                 a.weight_decay, a.lr_schedule, a.lr_warmup_steps, a.lr_warmup_start_factor, a.lr_total_steps, a.lr_final_factor,
                 tuple(a.lr_milestones), a.lr_gamma, a.affine_prob, a.affine_degrees, a.affine_shear, a.affine_scale, a.affine_translate,
                 a.affine_fill, a.affine_seed, a.affine_min_visible, a.init_weights, bool(a.init_optimizer), a.freeze_layers, bool(a.freeze_bn),
-                a.anchors, a.anchors_file, a.auto_anchors, a.auto_anchors_evolve, a.auto_anchors_seed, a.auto_anchors_device)
+                a.anchors, a.anchors_file, a.auto_anchors, a.auto_anchors_evolve, a.auto_anchors_seed, a.auto_anchors_device,
+                photo_prob=a.photo_prob, photo_hue=a.photo_hue, photo_saturation=a.photo_saturation, photo_value=a.photo_value,
+                photo_gamma=a.photo_gamma, photo_white=a.photo_white, photo_seed=a.photo_seed, mixup_prob=a.mixup_prob,
+                mixup_spread=a.mixup_spread, mixup_seed=a.mixup_seed)

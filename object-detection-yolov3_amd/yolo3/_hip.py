@@ -162,6 +162,7 @@ SIGNATURES = {
     'y3_letterbox_zscore_nhwc': (i32, [vp, i32, i32, i32, vp, TP, vp, vp]),
     'y3_letterbox_workspace_bytes': (sz, [i32, i32, i32, i32]),
     'y3_letterbox_unmap': (i32, [fp, i32, i32, i32, vp, i32, vp]),
+    'y3_photometric_batch': (i32, [fp, i32, i32, i32, i32, vp, fp, vp]),     # records: HOST pointer (augment.PHOTO_RECORD)
     'y3_format_labels': (i32, [ip, ip, i32, i32, C.POINTER(C.c_float), i32, i32, i32, i32, fp, fp, fp, vp]),
     'y3_anchor_stats_workspace_bytes': (sz, [i32, i32]),
     'y3_anchor_stats': (i32, [ip, C.c_longlong, fp, i32, i32, i32, i32, vp, vp, vp, vp]),

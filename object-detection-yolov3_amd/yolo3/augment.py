@@ -11,8 +11,10 @@ offsets identical, pixels to 1e-4 of the 8-bit range.  Boxes are [n,5] = x, y, w
 draw_augmentation is the device path's half of augment_image_box_pair: the same random decisions, boxes transformed here,
 the pixels left to y3_augment_batch (csrc/augment.hip) through one AUG_RECORD per image.
 
-Not in the reference, device path only: draw_mosaic / mosaic_boxes / mosaic_reference and draw_affine / affine_boxes /
-affine_reference (the rotation the reference's rotation_flag names and asserts away, with shear, gain and translation).
+Not in the reference, device path only: draw_mosaic / mosaic_boxes / mosaic_reference, draw_affine / affine_boxes /
+affine_reference (the rotation the reference's rotation_flag names and asserts away, with shear, gain and translation)
+and colour_matrix / draw_photometric / draw_mixup / mixup_boxes / photometric_reference (colour matrix, clamp, tone
+curve and MixUp, one elementwise pass).
 """
 import numpy as np
 import scipy.ndimage
@@ -561,3 +563,196 @@ def affine_reference(batch, records, coords=np.float32, detail=False):
     if detail:
         return val, mag, single, bits
     return val
+
+
+# ---- colour / tone jitter and MixUp (not in the reference) -----------------------------------------------------
+# y3_photo_record (include/yolo3hip.h), one per OUTPUT image of a y3_photometric_batch call
+PHOTO_RECORD = np.dtype([('m', '<f4', (9,)), ('bias', '<f4', (3,)), ('gamma', '<f4'), ('white', '<f4'), ('partner', '<i4'), ('lambda', '<f4')])
+assert PHOTO_RECORD.itemsize == 64
+_PHOTO_STREAM = 0xC0105           # folded into the key after (seed, shard, batch, image): apart from the mosaic's and the affine's words
+_MIXUP_STREAM = 0x313C5           # MixUp's own stream, so that --photo_seed == --mixup_seed does not couple the two draws
+# RGB -> YIQ (NTSC).  The rows of I and Q sum to zero and the row of Y to one, so grey (r = g = b) has no chroma and its own luma.
+_YIQ = np.array([[0.299, 0.587, 0.114], [0.596, -0.274, -0.322], [0.211, -0.523, 0.312]], np.float64)
+_YIQ_INV = np.linalg.inv(_YIQ)
+
+
+def photo_identity_records(n):
+    """n records that leave their image alone: identity matrix, no bias, gamma 1, white 0 (no clamp), lambda 1, partner = itself."""
+    rec = np.zeros(int(n), PHOTO_RECORD)
+    rec['m'] = np.eye(3, dtype=np.float32).reshape(9)
+    rec['gamma'] = 1
+    rec['lambda'] = 1
+    rec['partner'] = np.arange(int(n))
+    return rec
+
+
+def colour_matrix(hue_turns=0.0, saturation=1.0, value=1.0):
+    """float64 3 x 3 matrix on (r, g, b): the chroma plane (I, Q) of YIQ rotated by 2 pi hue_turns and scaled by `saturation`, the
+    luma Y scaled by `value`, converted back to RGB -- the linear hue-rotate and saturate operators, not a piecewise HSV round trip:
+    continuous in all three arguments, M(h1) M(h2) = M(h1 + h2), grey maps to value * grey, saturation 0 sends a pixel to its luma
+    grey.  hue_turns == 0 and saturation == 1 return value * I exactly (built directly, not as a rounded product)."""
+    hue_turns, saturation, value = float(hue_turns), float(saturation), float(value)
+    if hue_turns == 0.0 and saturation == 1.0:
+        return value * np.eye(3)
+    a = 2.0 * np.pi * hue_turns
+    mid = np.array([[value, 0, 0], [0, saturation * np.cos(a), -saturation * np.sin(a)], [0, saturation * np.sin(a), saturation * np.cos(a)]], np.float64)
+    return _YIQ_INV @ mid @ _YIQ
+
+
+def _stream(seed, shard, batch_index, image, stream):
+    """The counter-based stream of one image (draw_affine's construction): j -> the 64-bit word u_j."""
+    key = 0
+    for v in (seed, shard, batch_index, image, stream):
+        key = _mix64((key ^ (int(v) & _M64)) + _GOLDEN)
+    return lambda j: _mix64(key + (j + 1) * _GOLDEN)
+
+
+def draw_photometric(seed, shard, batch_index, n, channels, prob, hue=0.0, saturation=0.0, value=0.0, gamma=0.0, white=255.0):
+    """PHOTO_RECORD [n] (lambda 1: no MixUp) for the batch_index-th batch of n images on reader shard `shard`: a pure function of
+    its arguments, counter based exactly as draw_affine is.  Image i owns the key folded over (seed, shard, batch_index, i, 0xC0105)
+    -- k = 0; for v in those five: k = mix((k ^ v) + 0x9E3779B97F4A7C15) --, so its draw does not depend on n; its j-th word is
+    u_j = mix(key + (j + 1) * 0x9E3779B97F4A7C15), the uniform U_j = (u_j >> 11) * 2^-53 in [0, 1), and a value in [lo, hi] is
+    lo + (hi - lo) * U_j.  Draw order per image:
+      U_0   the image is changed when U_0 < prob; otherwise it gets the identity record, the other words unused
+      U_1   hue rotation in [-hue, hue] turns           (channels == 3 only; the word is skipped, not reused, when channels == 1)
+      U_2   saturation gain in [1 - saturation, 1 + saturation]     (channels == 3 only, likewise)
+      U_3   value gain in [1 - value, 1 + value]
+      U_4   tone exponent e in [-gamma, gamma]; the record's gamma is 2^e, uniform in the exponent
+    m = colour_matrix(hue, saturation, value) rounded once to float32 (channels == 1: m[0] = the value gain), bias 0, the clamp
+    to [0, white] on.  A changed image whose draw is neutral (every magnitude zero) gets the identity record exactly, clamp off.
+    Note that a value gain alone is cancelled by the z-score that follows, up to the clamp at `white`: it matters through the
+    clamp and in a mixed image only."""
+    n, channels = int(n), int(channels)
+    if n < 1 or channels not in (1, 3):
+        raise ValueError('draw_photometric: n >= 1 and channels 1 or 3, got {} {}'.format(n, channels))
+    if not float(white) > 0:
+        raise ValueError('draw_photometric: white must be > 0, got {!r}'.format(white))
+    rec = photo_identity_records(n)
+    for i in range(n):
+        word = _stream(seed, shard, batch_index, i, _PHOTO_STREAM)
+        u = lambda j: (word(j) >> 11) * 2.0 ** -53
+        if not u(0) < prob:
+            continue
+        between = lambda j, mag: -float(mag) + 2.0 * float(mag) * u(j)
+        h, s = (between(1, hue), 1.0 + between(2, saturation)) if channels == 3 else (0.0, 1.0)
+        v, e = 1.0 + between(3, value), between(4, gamma)
+        if (h, s, v, e) == (0.0, 1.0, 1.0, 0.0):
+            continue
+        m = colour_matrix(h, s, v)
+        rec['m'][i] = m.reshape(9).astype(np.float32) if channels == 3 else np.array([v, 0, 0, 0, 1, 0, 0, 0, 1], np.float32)
+        rec['gamma'][i] = 2.0 ** e
+        rec['white'][i] = white
+    return rec
+
+
+def draw_mixup(records, seed, shard, batch_index, prob, spread=0.1):
+    """A copy of PHOTO_RECORD [n] `records` with `partner` and `lambda` set for MixUp (Zhang et al., "mixup"; as used for detection
+    in "Bag of Freebies for Training Object Detection Neural Networks"): image i owns the key folded over (seed, shard,
+    batch_index, i, 0x313C5), words and uniforms as in draw_photometric.  Draw order per image:
+      U_0   the image is mixed when U_0 < prob and n > 1; otherwise lambda = 1 and partner = i, the other words unused
+      u_1   partner: j = u_1 % (n - 1) over the other n - 1 images in ascending order, partner = j + (j >= i)
+      U_2   lambda = (0.5 - spread) + 2 spread U_2, rounded once to float32: uniform in [0.5 - spread, 0.5 + spread]
+    The papers draw lambda from Beta(a, a) (a = 1.5 for detection; 32 in other recipes): mass around 0.5.  A uniform window
+    around 0.5 stands in for it here because it keeps the draw a closed-form function of one word (no rejection loop, so the
+    number of words per image is fixed); it is not a Beta draw and is not claimed to be one.  out_i = lambda * image_i + (1 -
+    lambda) * image_partner, each image finished under its own record."""
+    rec = np.array(records, dtype=PHOTO_RECORD, copy=True)
+    n = len(rec)
+    if not 0.0 <= float(spread) <= 0.5:
+        raise ValueError('draw_mixup: spread must be in [0, 0.5], got {!r}'.format(spread))
+    for i in range(n):
+        rec['partner'][i], rec['lambda'][i] = i, 1.0
+        if n < 2:
+            continue
+        word = _stream(seed, shard, batch_index, i, _MIXUP_STREAM)
+        if not (word(0) >> 11) * 2.0 ** -53 < prob:
+            continue
+        j = word(1) % (n - 1)
+        rec['partner'][i] = j + (j >= i)
+        rec['lambda'][i] = (0.5 - float(spread)) + 2.0 * float(spread) * ((word(2) >> 11) * 2.0 ** -53)
+    return rec
+
+
+def mixup_boxes(box_lists, records):
+    """The boxes of the output images of y3_photometric_batch: image i keeps its own boxes, followed by its partner's where
+    records['lambda'][i] < 1 (a mixed image shows the objects of both).  box_lists: one int32 [k, 5] array per image, None or empty
+    = no boxes.  Returns one fresh int32 [k', 5] array per image ([0, 5] when empty): order kept, nothing dropped or clipped, no
+    result shares memory with an input."""
+    empty = np.zeros((0, 5), np.int32)
+    src = [empty if b is None or len(b) == 0 else np.asarray(b, np.int32).reshape(-1, 5) for b in box_lists]
+    records = np.asarray(records, dtype=PHOTO_RECORD)
+    assert records.shape == (len(src),), (records.shape, len(src))
+    out = []
+    for i, b in enumerate(src):
+        if records['lambda'][i] < 1:
+            out.append(np.concatenate([b, src[int(records['partner'][i])]]).astype(np.int32).reshape(-1, 5))
+        else:
+            out.append(b.copy())
+    return out
+
+
+def _photo_finish(img, r, dtype):
+    """Stages 1-3 of y3_photometric_batch on one image [c, h, w] float32 under record r -> (the finished image in `dtype`, the
+    float32 value t after the clamp).  Stages 1 and 2 are float32 in the kernel's order whatever `dtype` is."""
+    c = img.shape[0]
+    m = np.asarray(r['m'], np.float32).reshape(3, 3)
+    rows = []
+    with np.errstate(invalid='ignore', over='ignore', divide='ignore'):
+        for k in range(c):
+            acc = None
+            for j in range(c):
+                if m[k, j] == 0:
+                    continue
+                t = img[j] if m[k, j] == 1 else m[k, j] * img[j]
+                acc = t if acc is None else acc + t
+            b = np.float32(r['bias'][k])
+            if b != 0:
+                acc = np.full(img.shape[1:], b, np.float32) if acc is None else acc + b
+            rows.append(np.zeros(img.shape[1:], np.float32) if acc is None else acc)
+        t = np.stack(rows)
+        assert t.dtype == np.float32
+        white, gamma = np.float32(r['white']), np.float32(r['gamma'])
+        if white > 0:
+            t = np.where(t < 0, np.float32(0), np.where(t > white, white, t))
+        if gamma == 1:
+            return t.astype(dtype), t
+        s = t / white                      # float32 in both modes: an IEEE division, the same word as the kernel's
+        assert s.dtype == np.float32
+        if dtype == np.float32:
+            y = white * np.where(s == 0, np.float32(0), np.exp2(gamma * np.log2(s)))
+            assert y.dtype == np.float32
+        else:
+            s = s.astype(np.float64)
+            y = np.float64(white) * np.where(s == 0, 0.0, np.power(np.where(s == 0, 1.0, s), np.float64(gamma)))
+    return y, t
+
+
+def photometric_reference(batch, records, dtype=np.float32, detail=False):
+    """y3_photometric_batch restated in NumPy (the oracle of the tests): batch [n, c, h, w] float32 -> `dtype` [n, c, h, w].
+
+    dtype float32 follows the kernel operation by operation -- the matrix with its skipped zero terms, unmultiplied ones and
+    skipped zero bias, the clamp as selects, the curve as white * exp2(gamma * log2(t / white)), the blend (lambda * a) + ((1 -
+    lambda) * b) -- and is bit-exact for every record without a tone curve (NumPy's exp2 / log2 are not the device's).  dtype
+    float64 is the exact-curve mode of the error bound: stages 1 and 2 and the quotient s = t / white stay float32 (they are
+    exact restatements: the division is IEEE on both sides, so a t below white * 2^-149 gives s = 0 and y = 0 here as there), the
+    power s^gamma and its product with white are evaluated in float64 on that s, and the blend in float64 with the float32 lambda
+    and the float32 1 - lambda.  detail=True returns (out, finished, t): `finished` the images after stage 3 in `dtype` (the blend mixes
+    finished[i] and finished[partner]), t the float32 values after the clamp."""
+    batch = np.ascontiguousarray(batch, dtype=np.float32)
+    n = batch.shape[0]
+    records = np.asarray(records, dtype=PHOTO_RECORD)
+    assert batch.ndim == 4 and batch.shape[1] in (1, 3) and records.shape == (n,)
+    done = [_photo_finish(batch[i], records[i], dtype) for i in range(n)]
+    finished = np.stack([d[0] for d in done])
+    t = np.stack([d[1] for d in done])
+    out = finished.copy()
+    with np.errstate(invalid='ignore', over='ignore'):
+        for i in range(n):
+            lam = np.float32(records['lambda'][i])
+            if lam != 1:
+                rest = np.float32(1) - lam
+                out[i] = (lam.astype(dtype) * finished[i]) + (rest.astype(dtype) * finished[int(records['partner'][i])])
+    assert out.dtype == dtype
+    if detail:
+        return out, finished, t
+    return out

@@ -12,6 +12,8 @@ mosaic_device     y3_mosaic_batch (csrc/augment.hip): the augmented batch recomb
                   Dataset.mosaic() (not in the reference)
 affine_device     y3_affine_batch (csrc/augment.hip): every image of the batch warped through an affine map, bilinear, for
                   Dataset.affine() (not in the reference)
+photometric_device  y3_photometric_batch (csrc/augment.hip): colour matrix, clamp, tone curve and MixUp of the batch in one
+                  elementwise pass, for Dataset.photometric() / Dataset.mixup() (not in the reference)
 format_labels_device  the same three label tensors built on the device from the boxes of a batch (y3_format_labels,
                   csrc/detect.hip) for ImageReader(..., label_device='gpu') and Dataset.multiscale()
 """
@@ -102,6 +104,21 @@ def affine_device(x, records):
     out = torch.empty_like(x)
     st = torch.cuda.current_stream(x.device).cuda_stream
     check(lib.y3_affine_batch(x.data_ptr(), b, c, h, w, records.ctypes.data, out.data_ptr(), st), 'y3_affine_batch')
+    return out
+
+
+def photometric_device(x, records):
+    """y3_photometric_batch: x CUDA float32 [B, C, H, W] (C = 1 or 3), records PHOTO_RECORD [B] (host; see augment.draw_photometric
+    and augment.draw_mixup) -> a new tensor of the same shape: every image through its record's colour matrix, clamp and tone
+    curve, then blended with its partner's finished image where lambda < 1.  Enqueued on the current stream."""
+    assert x.is_cuda and x.dim() == 4 and x.dtype == torch.float32, (x.dtype, tuple(x.shape))
+    x = x.contiguous()
+    records = np.ascontiguousarray(records, dtype=augment.PHOTO_RECORD)
+    b, c, h, w = x.shape
+    assert records.shape == (b,)
+    out = torch.empty_like(x)
+    st = torch.cuda.current_stream(x.device).cuda_stream
+    check(lib.y3_photometric_batch(x.data_ptr(), b, c, h, w, records.ctypes.data, out.data_ptr(), st), 'y3_photometric_batch')
     return out
 
 
@@ -233,21 +250,36 @@ class Dataset:
     ``affine(prob, degrees, shear, scale, translate, fill, seed, min_visible)`` (such a reader only) warps each image
     of a batch, with probability prob, through a random rotation, shear, gain and translation: drawn as a pure function of (seed,
     the reader's shard, i, image), applied on the device after the augmentation and the mosaic and before the z-score, at the
-    batch's own size; the boxes are remapped on the host (augment.affine_boxes) after the mosaic's."""
+    batch's own size; the boxes are remapped on the host (augment.affine_boxes) after the mosaic's.
+    ``photometric(prob, hue, saturation, value, gamma, seed, white)`` (a reader with augmentation_device='gpu') sends
+    each image of a batch, with probability prob, through a random colour matrix (hue rotation and saturation gain of the YIQ
+    chroma plane, value gain), a clamp to [0, white] and a tone curve; ``mixup(prob, spread, seed)`` (label_device='gpu' as well)
+    blends each image, with probability prob, with another finished image of its batch and gives it the boxes of both
+    (augment.mixup_boxes, after the affine's).  Both are one device pass, y3_photometric_batch, after the warp and right before the
+    z-score, at the batch's own size; a fill region left by the warp goes through the colour transform like any other pixel."""
 
-    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None, mosaic=None, affine=None):
+    def __init__(self, reader, batch_size=None, device=None, prefetch_depth=0, multiscale=None, mosaic=None, affine=None, photometric=None,
+                 mixup=None):
         self.reader, self.batch_size, self.device, self.prefetch_depth = reader, batch_size, device, prefetch_depth
         self.multiscale_cfg = multiscale       # None or (sizes [(h, w)], period, seed)
         self.mosaic_cfg = mosaic               # None or (prob, seed, min_visible)
         self.affine_cfg = affine               # None or (prob, degrees, shear, scale, translate, fill, seed, min_visible)
+        self.photo_cfg = photometric           # None or (prob, hue, saturation, value, gamma, seed, white)
+        self.mixup_cfg = mixup                 # None or (prob, spread, seed)
         self.batches = 0                       # batches handed out so far, over every iteration of this object
 
+    def _with(self, **changes):
+        """A Dataset on the same reader with every setting of this one but `changes`."""
+        cfg = dict(batch_size=self.batch_size, device=self.device, prefetch_depth=self.prefetch_depth, multiscale=self.multiscale_cfg,
+                   mosaic=self.mosaic_cfg, affine=self.affine_cfg, photometric=self.photo_cfg, mixup=self.mixup_cfg)
+        cfg.update(changes)
+        return Dataset(self.reader, **cfg)
+
     def batch(self, n):
-        return Dataset(self.reader, int(n), self.device, self.prefetch_depth, self.multiscale_cfg, self.mosaic_cfg, self.affine_cfg)
+        return self._with(batch_size=int(n))
 
     def prefetch(self, n):
-        return Dataset(self.reader, self.batch_size, self.device, max(1, min(int(n), 4)), self.multiscale_cfg, self.mosaic_cfg,     # batches, not examples: 4 is plenty
-                       self.affine_cfg)
+        return self._with(prefetch_depth=max(1, min(int(n), 4)))     # batches, not examples: 4 is plenty
 
     def multiscale(self, sizes, period, seed=0):
         """Multi-scale training: see the class docstring.  sizes: (h, w) pairs, multiples of 32; period: batches per draw."""
@@ -258,7 +290,7 @@ class Dataset:
             raise ValueError('multiscale sizes must be (h, w) multiples of {}, got {!r}'.format(NETWORK_DOWNSAMPLE_FACTOR, sizes))
         if isinstance(period, bool) or int(period) != period or int(period) < 1:
             raise ValueError('multiscale period must be an integer >= 1, got {!r}'.format(period))
-        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, (sizes, int(period), int(seed)), self.mosaic_cfg, self.affine_cfg)
+        return self._with(multiscale=(sizes, int(period), int(seed)))
 
     def mosaic(self, prob, seed=0, min_visible=0.25):
         """Mosaic augmentation: see the class docstring.  prob: share of mosaic images, 0 < prob <= 1; min_visible: a box stays when
@@ -269,8 +301,7 @@ class Dataset:
             raise ValueError('mosaic prob must be in (0, 1], got {!r}'.format(prob))
         if isinstance(min_visible, bool) or not 0 <= float(min_visible) <= 1:
             raise ValueError('mosaic min_visible must be in [0, 1], got {!r}'.format(min_visible))
-        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, self.multiscale_cfg, (float(prob), int(seed), float(min_visible)),
-                       self.affine_cfg)
+        return self._with(mosaic=(float(prob), int(seed), float(min_visible)))
 
     def affine(self, prob, degrees=10.0, shear=2.0, scale=0.1, translate=0.1, fill=0.0, seed=0, min_visible=0.25):
         """Random affine warp: see the class docstring.  prob: share of warped images, 0 < prob <= 1; degrees in [0, 180]: rotation
@@ -287,8 +318,55 @@ class Dataset:
                             ('fill', fill, np.isfinite), ('min_visible', min_visible, lambda v: 0 <= v <= 1)):
             if isinstance(v, bool) or not ok(float(v)):
                 raise ValueError('affine {} out of range, got {!r}'.format(name, v))
-        return Dataset(self.reader, self.batch_size, self.device, self.prefetch_depth, self.multiscale_cfg, self.mosaic_cfg,
-                       (float(prob), float(degrees), float(shear), float(scale), float(translate), float(fill), int(seed), float(min_visible)))
+        return self._with(affine=(float(prob), float(degrees), float(shear), float(scale), float(translate), float(fill), int(seed), float(min_visible)))
+
+    def photometric(self, prob, hue=0.015, saturation=0.7, value=0.4, gamma=0.0, seed=0, white=None):
+        """Colour / tone jitter: see the class docstring.  prob: share of changed images, 0 < prob <= 1; hue in [0, 0.5]: rotation of
+        the YIQ chroma plane drawn in +-hue turns; saturation, value in [0, 1]: gains drawn in 1 +- saturation, 1 +- value; gamma in
+        [0, 4]: tone exponent 2^(+-gamma) on t / white; white: the top of the stored pixel range (the clamp and the scale of the tone
+        curve), by default 255 for a uint8 and 65535 for a uint16 database -- a float32 database must pass it.  A one-channel
+        database ignores hue and saturation.  The magnitudes are the common recipe's defaults, not tuned values."""
+        if getattr(self.reader, 'augmentation_device', 'cpu') != 'gpu':
+            raise ValueError("photometric() needs a reader with augmentation_device='gpu': the pass runs on the device, after the augmentation")
+        if isinstance(prob, bool) or not 0 < float(prob) <= 1:
+            raise ValueError('photometric prob must be in (0, 1], got {!r}'.format(prob))
+        for name, v, ok in (('hue', hue, lambda v: 0 <= v <= 0.5), ('saturation', saturation, lambda v: 0 <= v <= 1),
+                            ('value', value, lambda v: 0 <= v <= 1), ('gamma', gamma, lambda v: 0 <= v <= 4)):
+            if isinstance(v, bool) or not ok(float(v)):
+                raise ValueError('photometric {} out of range, got {!r}'.format(name, v))
+        if white is None:
+            stored = getattr(self.reader, 'image_dtype', None)
+            white = {'uint8': 255.0, 'uint16': 65535.0}.get(str(stored))
+            if white is None:
+                raise ValueError('photometric() on a {} database needs white: the top of its pixel range is not known'.format(stored))
+        if isinstance(white, bool) or not (np.isfinite(float(white)) and float(white) > 0):
+            raise ValueError('photometric white must be finite and > 0, got {!r}'.format(white))
+        return self._with(photometric=(float(prob), float(hue), float(saturation), float(value), float(gamma), int(seed), float(white)))
+
+    def mixup(self, prob, spread=0.1, seed=0):
+        """MixUp: see the class docstring.  prob: share of mixed images, 0 < prob <= 1; spread in [0, 0.5]: lambda uniform in
+        0.5 +- spread (a uniform window, not the papers' Beta draw: augment.draw_mixup)."""
+        if getattr(self.reader, 'augmentation_device', 'cpu') != 'gpu':
+            raise ValueError("mixup() needs a reader with augmentation_device='gpu': the images are blended on the device, after the augmentation")
+        if getattr(self.reader, 'label_device', 'cpu') != 'gpu':
+            raise ValueError("mixup() needs a reader with label_device='gpu': label tensors built in the workers cannot be merged")
+        if isinstance(prob, bool) or not 0 < float(prob) <= 1:
+            raise ValueError('mixup prob must be in (0, 1], got {!r}'.format(prob))
+        if isinstance(spread, bool) or not 0 <= float(spread) <= 0.5:
+            raise ValueError('mixup spread must be in [0, 0.5], got {!r}'.format(spread))
+        return self._with(mixup=(float(prob), float(spread), int(seed)))
+
+    def _photo_records(self, index, n):
+        """The PHOTO_RECORD [n] of batch `index` (photometric() and / or mixup() on), drawn after the affine's records."""
+        if self.photo_cfg is not None:
+            prob, hue, saturation, value, gamma, seed, white = self.photo_cfg
+            rec = augment.draw_photometric(seed, self.reader.shard_index, index, n, self.reader.image_size[2], prob, hue, saturation, value, gamma, white)
+        else:
+            rec = augment.photo_identity_records(n)
+        if self.mixup_cfg is not None:
+            prob, spread, seed = self.mixup_cfg
+            rec = augment.draw_mixup(rec, seed, self.reader.shard_index, index, prob, spread)
+        return rec
 
     def size_of_batch(self, i):
         """(h, w) of batch i of this dataset: the reader's stored size unless multiscale() is on."""
@@ -302,7 +380,10 @@ class Dataset:
         counts host int32 (NumPy arrays or pinned tensors).  Augments to this batch's size, z-scores, builds the labels; with
         mosaic() on, the records of this batch are drawn here, the boxes remapped on the host and the augmented images recombined
         before the z-score; with affine() on, its records are drawn here too, the boxes go through affine_boxes after mosaic_boxes
-        and the images through y3_affine_batch after the mosaic.  Without affine() no call is added."""
+        and the images through y3_affine_batch after the mosaic.  Without affine() no call is added.  With photometric() or
+        mixup() on, their records are drawn after the affine's, mixup_boxes runs after affine_boxes, and y3_photometric_batch runs
+        after the warp, right before the z-score (a fill region left by the warp goes through the colour transform like any other
+        pixel).  With neither, no call and no allocation is added."""
         crop = tuple(self.reader.image_size[:2])
         index = self.batches
         size = self.size_of_batch(index)
@@ -324,6 +405,12 @@ class Dataset:
             affine, forward = augment.draw_affine(seed, self.reader.shard_index, index, len(records), size, prob, degrees, shear, scale, translate, fill)
             b, c = (x.numpy() if torch.is_tensor(x) else x for x in (boxes, counts))
             boxes, counts = collate_boxes(augment.affine_boxes([b[i, :c[i]] for i in range(len(c))], forward, size, min_visible))
+        photo = None
+        if self.photo_cfg is not None or self.mixup_cfg is not None:
+            photo = self._photo_records(index, len(records))
+            if self.mixup_cfg is not None:
+                b, c = (x.numpy() if torch.is_tensor(x) else x for x in (boxes, counts))
+                boxes, counts = collate_boxes(augment.mixup_boxes([b[i, :c[i]] for i in range(len(c))], photo))
         as_t =lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True)
         labels = format_labels_device(as_t(boxes), as_t(counts), (size[0], size[1], self.reader.image_size[2]), self.reader.anchors,
                                       self.reader.number_classes)
@@ -332,7 +419,16 @@ class Dataset:
             imgs = mosaic_device(imgs, mosaic)
         if affine is not None:
             imgs = affine_device(imgs, affine)
+        if photo is not None:
+            imgs = photometric_device(imgs, photo)
         return (zscore_normalize_device(imgs), *labels)
+
+    def _host_label_photometric(self, imgs):
+        """photometric() on a label_device='cpu' reader (labels built in the workers; no mixup() there): the pass on the augmented
+        batch, records keyed by this object's batch count as _device_batch keys them."""
+        index = self.batches
+        self.batches += 1
+        return photometric_device(imgs, self._photo_records(index, imgs.shape[0]))
 
     def shard(self, num_shards, index):
         """experimental_distribute_dataset (train.py:62,66): every replica reads its own examples.  The reader's
@@ -360,6 +456,10 @@ class Dataset:
                 raise ValueError('mosaic() combines the images of a batch: call batch(n) before iterating')
             if self.affine_cfg is not None:
                 raise ValueError('affine() warps the images of a batch on the device: call batch(n) before iterating')
+            if self.photo_cfg is not None:
+                raise ValueError('photometric() changes the images of a batch on the device: call batch(n) before iterating')
+            if self.mixup_cfg is not None:
+                raise ValueError('mixup() blends the images of a batch: call batch(n) before iterating')
             yield from self.reader.generator()           # z-scored examples, as the reference's unbatched dataset yields them
             return
         dev = self.device or torch.device('cuda', torch.cuda.current_device())
@@ -375,6 +475,8 @@ class Dataset:
                 labels = [torch.from_numpy(np.stack([e[i] for e in ex])).to(dev, non_blocking=True) for i in (1, 2, 3)]
                 if on_gpu:
                     imgs = augment_device(imgs, np.concatenate([e[4] for e in ex]), crop)
+                    if self.photo_cfg is not None:
+                        imgs = self._host_label_photometric(imgs)
                 yield (zscore_normalize_device(imgs), *labels)
             return
         import queue
@@ -444,6 +546,8 @@ class Dataset:
                 ev.record(torch.cuda.current_stream(dev))
                 slot['event'] = ev
                 imgs = augment_device(dev_t[0], slot['records'], crop) if on_gpu else dev_t[0]
+                if on_gpu and self.photo_cfg is not None:
+                    imgs = self._host_label_photometric(imgs)
                 yield (zscore_normalize_device(imgs), dev_t[1], dev_t[2], dev_t[3])
         finally:
             stop.set()          # the consumer walked away (epoch boundary): the producer exits at its next hand-over
@@ -508,6 +612,7 @@ class ImageReader:
                 self.keys[idx].append(key)
         datum = ImageYoloBoxesPair().ParseFromString(env.get(self.keys_flat[0]))
         self.image_size = [datum.img_height, datum.img_width, datum.channels]
+        self.image_dtype = np.dtype(datum.img_type) if datum.img_type else np.dtype(np.uint8)      # of the first record: Dataset.photometric's default white
         env.close()
         self.number_classes = len(self.keys) - 1 if empty_images_flag else len(self.keys)
         print('Found images of shape: {}'.format(self.image_size))
