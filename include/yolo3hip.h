@@ -883,7 +883,7 @@ int y3_affine_batch(const float* src, int n, int c, int h, int w, const y3_affin
                     y3_stream_t stream);
 
 /* ---- colour / tone jitter and MixUp (not in the reference; yolo3/augment.py draw_photometric / draw_mixup / mixup_boxes /
- * photometric_reference, DESIGN §3.24) ------------------------------------------------------------------------------------------
+ * photometric_reference, DESIGN §3.25) ------------------------------------------------------------------------------------------
  * One elementwise pass over an augmented batch, just before the z-score.  The z-score cancels a uniform gain and offset, so what
  * this pass offers is cross-channel (the matrix: hue, saturation) or non-linear (clamp, tone curve), and a blend of two images.
  * P_r(x), the photometric value of the pixel x (all its channels c0, c1, c2) under record r, is evaluated in fp32, every
@@ -1086,6 +1086,32 @@ int y3_eval_ap_ranges(const long long* keys, const unsigned* tp, const unsigned*
                       int* fp_count, int* ign_count, int* best_n, int* best_tp, float* best_score, float* pr_precision, float* pr_score,
                       y3_stream_t stream);
 size_t y3_eval_ap_ranges_workspace_bytes(long long m, int num_ranges, int num_thr);
+
+/* ---- per-class score cuts and the confusion matrix (opt-in: DetectionEvaluator(class_score_thresholds=..., confusion=True),
+ * bbox_utils.cut_keep_lists) ----
+ * y3_keep_cut: keep lists as y3_nms_per_class writes them, nseg = images * num_classes segments.  For segment s of class
+ * c = s % num_classes, with m = min(max(keep_cnt[s], 0), max_keep): keep_cnt[s] = the length of the longest prefix j < m with
+ * keep_score[s * max_keep + j] >= class_thr[c] (fp32 compare; class_thr: DEVICE array of num_classes values, finite or -inf, which
+ * the host validates: -inf leaves the count at m, a NaN would keep nothing).  In keep order the scores do not increase, so the
+ * prefix is every entry at or above the cut; the kernel itself relies on the prefix rule alone.  Writes keep_cnt only.  One
+ * wave per segment, no atomics. */
+int y3_keep_cut(const float* keep_score, int* keep_cnt, int nseg, int num_classes, int max_keep, const float* class_thr,
+                y3_stream_t stream);
+/* y3_eval_confusion: rows, clip, keep lists, max_det, gt, gt_cnt, max_gt, iou_thr_host and offsets as y3_eval_match; total =
+ * offsets[n * num_classes].  Per image the admitted entries of all classes are put in one pooled order (score descending, fp32;
+ * ties: lower class first, then keep rank; the keep lists' scores must not increase) and per threshold t, in that order, a
+ * detection takes the unmatched GT box OF ANY CLASS with the largest IoU if that IoU >= t (y3_eval_match's arithmetic and tie
+ * rule: the highest GT index).  confusion [num_thr][K + 1][K + 1] (int64, rows true, columns predicted, index K = background) is
+ * ADDED to: [t][g][p] += 1 for a detection of class p on a box of class g, [t][K][p] += 1 for an unmatched detection,
+ * [t][g][K] += 1 for a GT box left unmatched; [t][K][K] is never touched.  Integer atomics: two launches give the same bytes.
+ * max_gt_per_image: the host's bound on the GT boxes of one image; all of them are staged in LDS (24 B each), at most 4096
+ * (Y3_EINVAL + message above that, nothing launched).  workspace: y3_eval_confusion_workspace_bytes(total) (may be null for
+ * total 0).  One workgroup per image, one wave per threshold, behind a small kernel that ranks the entries. */
+int y3_eval_confusion(const float* rows, int n, int nb, int ld, int num_classes, float clip_w, float clip_h, const int* keep_idx,
+                      const int* keep_cnt, const float* keep_score, int max_keep, int max_det, const float* gt, const int* gt_cnt,
+                      int max_gt, int max_gt_per_image, const float* iou_thr_host, int num_thr, const int* offsets, long long total,
+                      void* workspace, size_t workspace_bytes, long long* confusion, y3_stream_t stream);
+size_t y3_eval_confusion_workspace_bytes(long long total);
 
 /* ---- gradient exchange: tf.distribute.MirroredStrategy's all-reduce (train.py:38-39, model.py:500,510-515) -------
  * One process per GPU; SUM over the replicas (the loss is already divided by the global batch, model.py:492).  RCCL over

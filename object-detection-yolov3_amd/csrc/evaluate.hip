@@ -758,3 +758,269 @@ extern "C" int y3_eval_ap_ranges(const long long* keys, const unsigned* tp, cons
     Y3_CHECK_LAUNCH("eval_ap_ranges");
     return Y3_OK;
 }
+
+// ---------------------------------------------------------------------------
+// per-class score cut on keep lists: one wave per (image, class) segment
+// ---------------------------------------------------------------------------
+// The lists are in keep order with non-increasing scores, but the kernel takes the longest passing PREFIX and relies on nothing
+// more: per 64-entry chunk a ballot of "inside the list and score >= threshold" and the count of its trailing ones.
+__global__ __launch_bounds__(256) void keep_cut_kernel(const float* __restrict__ keep_score, int* __restrict__ keep_cnt, int nseg, int K,
+                                                       int max_keep, const float* __restrict__ class_thr) {
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (s >= nseg) return;  // wave-uniform
+    int m = keep_cnt[s];
+    m = m < max_keep ? m : max_keep;
+    m = m > 0 ? m : 0;
+    const float thr = class_thr[s % K];
+    const float* sc = keep_score + (long long)s * max_keep;
+    int kept = 0;
+    for (int j0 = 0; j0 < m; j0 += 64) {
+        const int j = j0 + lane;
+        const bool pass = j < m && sc[j] >= thr;
+        const unsigned long long fail = ~__ballot(pass);
+        const int run = fail ? __builtin_ctzll(fail) : 64;
+        kept += run;
+        if (run < 64) break;
+    }
+    if (lane == 0) keep_cnt[s] = kept;
+}
+
+extern "C" int y3_keep_cut(const float* keep_score, int* keep_cnt, int nseg, int num_classes, int max_keep, const float* class_thr,
+                           y3_stream_t stream) {
+    Y3_CHECK_ARG(keep_score && keep_cnt && class_thr, "keep_cut: null pointer");
+    Y3_CHECK_ARG(nseg >= 1 && num_classes >= 1 && max_keep >= 1, "keep_cut: bad sizes (nseg %d, classes %d, max_keep %d)", nseg, num_classes,
+                 max_keep);
+    Y3_CHECK_ARG(nseg % num_classes == 0, "keep_cut: %d segments are not whole images of %d classes", nseg, num_classes);
+    hipLaunchKernelGGL(keep_cut_kernel, dim3((nseg + 3) / 4), dim3(256), 0, (hipStream_t)stream, keep_score, keep_cnt, nseg, num_classes,
+                       max_keep, class_thr);
+    Y3_CHECK_LAUNCH("keep_cut");
+    return Y3_OK;
+}
+
+// ---------------------------------------------------------------------------
+// confusion matrix: class-agnostic matching, one workgroup per image, one wave per IoU threshold
+// ---------------------------------------------------------------------------
+struct EvalConfusionArgs {
+    EvalMatchArgs m;              // pool_key / pool_tp unused; cap: LDS slots per field for the image's GT boxes of ALL classes
+    int* order;                   // [total]: at offsets[img * K] + pooled rank, the entry's class * max_keep + keep rank
+    long long total;
+    unsigned long long* counts;   // [T][K + 1][K + 1], rows true, columns predicted, index K = background; added to
+};
+
+// entries of the non-increasing list a[0..m) that precede score s: those > s, with `ties` also those == s
+__device__ __forceinline__ int eval_count_before(const float* a, int m, float s, bool ties) {
+    int lo = 0, hi = m;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float v = a[mid];
+        if (ties ? v >= s : v > s) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The pooled order of an image's entries: score descending, ties: lower class first, then keep rank.  An entry's rank is its keep
+// rank plus, per other class, the entries of that class's list that precede it (>= for lower classes, > for higher ones).
+__global__ __launch_bounds__(256) void eval_pool_rank_kernel(const EvalConfusionArgs q) {
+    const EvalMatchArgs& p = q.m;
+    const int img = blockIdx.x, K = p.K;
+    const int* off = p.offsets + (long long)img * K;
+    const int first = off[0], count = off[K] - first;
+    for (int e = threadIdx.x; e < count; e += blockDim.x) {
+        // the segment of entry e: the last class c with off[c] <= first + e (empty segments share their successor's offset)
+        int lo = 0, hi = K;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (off[mid] <= first + e) lo = mid;
+            else hi = mid;
+        }
+        const int c = lo, j = first + e - off[c];
+        const float s = p.keep_score[((long long)img * K + c) * p.max_keep + j];
+        int rank = j;
+        for (int o = 0; o < K; ++o) {
+            if (o == c) continue;
+            const int m = off[o + 1] - off[o];
+            if (m > 0) rank += eval_count_before(p.keep_score + ((long long)img * K + o) * p.max_keep, m, s, o < c);
+        }
+        const long long at = (long long)first + rank;
+        if (rank < count && at < q.total) q.order[at] = c * p.max_keep + j;
+    }
+}
+
+__global__ __launch_bounds__(1024) void eval_confusion_kernel(const EvalConfusionArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float sg[];  // SoA [6][cap]: x0, y0, x1, y1, area, class of the image's GT boxes
+    const EvalMatchArgs& p = q.m;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int img = blockIdx.x, K = p.K, K1 = p.K + 1;
+    float* gx0 = sg;
+    float* gy0 = gx0 + p.cap;
+    float* gx1 = gy0 + p.cap;
+    float* gy1 = gx1 + p.cap;
+    float* gar = gy1 + p.cap;
+    int* gcl = (int*)(gar + p.cap);
+
+    // 1. the image's GT boxes of every class into LDS, in GT order
+    int G = p.gt_cnt[img];
+    G = G < p.max_gt ? G : p.max_gt;
+    G = G < p.cap ? G : p.cap;
+    G = G > 0 ? G : 0;
+    const float* gt = p.gt + (long long)img * p.max_gt * 5;
+    for (int i = threadIdx.x; i < G; i += blockDim.x) {
+        const float* b = gt + (long long)i * 5;
+        const float x0 = b[0], y0 = b[1], x1 = b[2], y1 = b[3];
+        const int c = (int)b[4];
+        gx0[i] = x0;
+        gy0[i] = y0;
+        gx1[i] = x1;
+        gy1[i] = y1;
+        gar[i] = (x1 - x0) * (y1 - y0);
+        gcl[i] = c < 0 ? 0 : (c < K ? c : K - 1);
+    }
+    __syncthreads();
+    const int first = p.offsets[(long long)img * K];
+    const int cnt = p.offsets[(long long)img * K + K] - first;
+    const float* rows = p.rows + (long long)img * p.nb * p.ld;
+
+    // 2. greedy matching in pooled order, one wave per threshold; no barriers from here on.  Lane l owns GT boxes l, l + 64, ...;
+    //    their matched flags are the bits of one 64-bit register (G <= 4096 = 64 x 64).
+    for (int t = wave; t < p.T; t += nwaves) {
+        const float thr = p.thr[t];
+        unsigned long long* M = q.counts + (long long)t * K1 * K1;
+        unsigned long long matched = 0ull;
+        for (int j0 = 0; j0 < cnt; j0 += 64) {
+            // lane l stages pooled entry j0 + l (clipped like eval_match_kernel)
+            const int j = j0 + lane;
+            float x0 = 0.f, y0 = 0.f, x1 = 0.f, y1 = 0.f;
+            int cls = -1;  // < 0: an entry the rank kernel did not place (scores out of order); skipped
+            bool ok = false;
+            if (j < cnt && (long long)first + j < q.total) {
+                const int v = q.order[first + j];
+                const int c = v / p.max_keep, slot = v - c * p.max_keep;
+                if (v >= 0 && c < K && slot < eval_kept(p.keep_cnt, img * K + c, p.max_keep, p.max_det)) {
+                    cls = c;
+                    const int r = p.keep_idx[((long long)img * K + c) * p.max_keep + slot];
+                    if (r >= 0 && r < p.nb) {
+                        const float* b = rows + (long long)r * p.ld;
+                        x0 = b[0];
+                        y0 = b[1];
+                        x1 = b[2];
+                        y1 = b[3];
+                        if (p.clip_w > 0.f) {
+                            x0 = fminf(fmaxf(x0, 0.f), p.clip_w);
+                            x1 = fminf(fmaxf(x1, 0.f), p.clip_w);
+                            y0 = fminf(fmaxf(y0, 0.f), p.clip_h);
+                            y1 = fminf(fmaxf(y1, 0.f), p.clip_h);
+                        }
+                        ok = true;
+                    }
+                }
+            }
+            const float ar = (x1 - x0) * (y1 - y0);
+            const unsigned long long okmask = __ballot(ok);
+            const int nj = cnt - j0 < 64 ? cnt - j0 : 64;
+            for (int k = 0; k < nj; ++k) {
+                const int pc = __shfl(cls, k);
+                if (pc < 0) continue;
+                unsigned long long best = 0ull;
+                if ((okmask >> k) & 1ull) {  // a keep row outside the rows is background, as eval_match_kernel never makes it a TP
+                    const float kx0 = __shfl(x0, k), ky0 = __shfl(y0, k), kx1 = __shfl(x1, k), ky1 = __shfl(y1, k), kar = __shfl(ar, k);
+                    // key = (IoU bits << 32) | (g + 1): IoU >= thr > 0 makes the bits monotone; the max takes the highest g on ties
+                    int bit = 0;
+                    for (int g = lane; g < G; g += 64, ++bit) {
+                        if ((matched >> bit) & 1ull) continue;
+                        const float xl = fmaxf(kx0, gx0[g]), yt = fmaxf(ky0, gy0[g]);
+                        const float xr = fminf(kx1, gx1[g]), yb = fminf(ky1, gy1[g]);
+                        const float inter = fmaxf(yb - yt, 0.f) * fmaxf(xr - xl, 0.f);
+                        const float iou = inter / ((kar + gar[g]) - inter);
+                        if (iou >= thr) {
+                            const unsigned long long key = ((unsigned long long)__float_as_uint(iou) << 32) | (unsigned)(g + 1);
+                            best = key > best ? key : best;
+                        }
+                    }
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) {
+                        const unsigned long long other = __shfl_xor(best, o);
+                        best = other > best ? other : best;
+                    }
+                }
+                int row = K;  // background: a false positive
+                if (best) {
+                    const int g = (int)(unsigned)(best & 0xffffffffull) - 1;
+                    if (lane == (g & 63)) matched |= 1ull << (g >> 6);
+                    row = gcl[g];
+                }
+                if (lane == 0) atomicAdd(&M[(long long)row * K1 + pc], 1ull);
+            }
+        }
+        // 3. the GT boxes nobody took: missed
+        int bit = 0;
+        for (int g = lane; g < G; g += 64, ++bit)
+            if (!((matched >> bit) & 1ull)) atomicAdd(&M[(long long)gcl[g] * K1 + K], 1ull);
+    }
+}
+
+extern "C" size_t y3_eval_confusion_workspace_bytes(long long total) { return total > 0 ? (size_t)total * sizeof(int) : 0; }
+
+extern "C" int y3_eval_confusion(const float* rows, int n, int nb, int ld, int num_classes, float clip_w, float clip_h, const int* keep_idx,
+                                 const int* keep_cnt, const float* keep_score, int max_keep, int max_det, const float* gt,
+                                 const int* gt_cnt, int max_gt, int max_gt_per_image, const float* iou_thr_host, int num_thr,
+                                 const int* offsets, long long total, void* workspace, size_t workspace_bytes, long long* confusion,
+                                 y3_stream_t stream) {
+    Y3_CHECK_ARG(rows && keep_idx && keep_cnt && keep_score && gt && gt_cnt && iou_thr_host && offsets && confusion,
+                 "eval_confusion: null pointer");
+    Y3_CHECK_ARG(n >= 1 && nb >= 1 && ld >= 4 && num_classes >= 1 && max_keep >= 1 && max_det >= 1 && max_gt >= 1 && total >= 0,
+                 "eval_confusion: bad sizes (n %d, nb %d, ld %d, classes %d, max_keep %d, max_det %d, max_gt %d, total %lld)", n, nb, ld,
+                 num_classes, max_keep, max_det, max_gt, total);
+    Y3_CHECK_ARG(num_thr >= 1 && num_thr <= Y3_EVAL_MAX_THR, "eval_confusion: %d IoU thresholds (1..%d)", num_thr, Y3_EVAL_MAX_THR);
+    Y3_CHECK_ARG(max_gt_per_image >= 0 && max_gt_per_image <= Y3_EVAL_MAX_GT,
+                 "eval_confusion: %d ground-truth boxes in one image; at most %d fit the LDS stage", max_gt_per_image, Y3_EVAL_MAX_GT);
+    Y3_CHECK_ARG((long long)n * num_classes <= 0x7fffffffLL && (long long)num_classes * max_keep <= 0x7fffffffLL && total <= 0x7fffffffLL,
+                 "eval_confusion: n * classes, classes * max_keep or total overflows");
+    Y3_CHECK_ARG(total == 0 || (workspace && workspace_bytes >= y3_eval_confusion_workspace_bytes(total)),
+                 "eval_confusion: workspace missing or too small");
+    EvalConfusionArgs q = {};
+    EvalMatchArgs& p = q.m;
+    for (int t = 0; t < num_thr; ++t) {
+        const float v = iou_thr_host[t];
+        Y3_CHECK_ARG(v > 0.f && v <= 1.f, "eval_confusion: IoU threshold %d = %g outside (0, 1]", t, (double)v);
+        p.thr[t] = v;
+    }
+    p.rows = rows;
+    p.nb = nb;
+    p.ld = ld;
+    p.K = num_classes;
+    p.clip_w = clip_w;
+    p.clip_h = clip_h;
+    p.keep_idx = keep_idx;
+    p.keep_cnt = keep_cnt;
+    p.keep_score = keep_score;
+    p.max_keep = max_keep;
+    p.max_det = max_det;
+    p.gt = gt;
+    p.gt_cnt = gt_cnt;
+    p.max_gt = max_gt;
+    p.cap = max_gt_per_image < 64 ? 64 : (max_gt_per_image + 63) & ~63;
+    p.T = num_thr;
+    p.offsets = offsets;
+    q.order = (int*)workspace;
+    q.total = total;
+    q.counts = (unsigned long long*)confusion;
+    static bool attr_set = false;
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)eval_confusion_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, Y3_EVAL_MAX_GT * 24) !=
+            hipSuccess) {
+            y3_set_error("eval_confusion: cannot raise the dynamic LDS limit");
+            return Y3_ELAUNCH;
+        }
+        attr_set = true;
+    }
+    if (total > 0) {
+        hipLaunchKernelGGL(eval_pool_rank_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, q);
+        Y3_CHECK_LAUNCH("eval_confusion (pooled order)");
+    }
+    const int waves = num_thr < 16 ? num_thr : 16;
+    hipLaunchKernelGGL(eval_confusion_kernel, dim3(n), dim3(64 * waves), (size_t)p.cap * 24, (hipStream_t)stream, q);
+    Y3_CHECK_LAUNCH("eval_confusion");
+    return Y3_OK;
+}

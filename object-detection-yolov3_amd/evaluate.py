@@ -10,7 +10,9 @@ Under `python -m torch.distributed.run --nproc-per-node N` every rank evaluates 
 the ranks' evaluators are merged (yolo3.metrics.all_gather_evaluator, a collective); rank 0 prints and writes the csv.
 --area-ranges scores every class once per range of box area (COCO's AP small / medium / large with its ignore rule),
 --operating-points and --pr-curves write the best-F1 score threshold and the PR curve per class, range and IoU threshold
-(DESIGN §3.16); they go with every other flag.
+(DESIGN §3.16); they go with every other flag.  --score-thresholds cuts every class's detections at its own score threshold
+(a number, or the csv --operating-points wrote) and --confusion-matrix writes the class-agnostic confusion matrix of the
+detections that are left; they too go with every other flag.
 """
 import argparse
 import math
@@ -47,19 +49,20 @@ def folder_examples(image_folder, csv_folder, image_format, num_shards=1, shard_
 
 def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', batch_size=8, iou_thresholds=metrics.COCO_IOU_THRESHOLDS,
              max_detections=None, distributed=False, nms='hard', nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep',
-             area_ranges=None, area_names=None, curves=False, letterbox=False):
+             area_ranges=None, area_names=None, curves=False, letterbox=False, class_score_thresholds=None, confusion=False):
     """Runs the model over ``examples`` and returns (DetectionEvaluator.result() dict, number of images, seconds).
     distributed: a collective over the default process group; every rank passes its keys[rank::world] share of the
     examples and gets the result over all of them.  nms / nms_sigma: the NMS method (bbox_utils.NMS_METHODS) and its
     Gaussian parameter.  tta / tta_vote_iou / tta_score: test-time augmentation (metrics.evaluate_examples).  area_ranges /
-    area_names / curves: DetectionEvaluator's.  letterbox: images of any size, each letterboxed into the model input (not with
-    tta; metrics.evaluate_examples)."""
+    area_names / curves / class_score_thresholds / confusion: DetectionEvaluator's.  letterbox: images of any size, each
+    letterboxed into the model input (not with tta; metrics.evaluate_examples)."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score)
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision
     ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections, area_ranges=area_ranges, area_names=area_names,
-                                    curves=curves)
+                                    curves=curves, class_score_thresholds=_resolve_cuts(class_score_thresholds, yolo.number_classes),
+                                    confusion=confusion)
     t0 = time.perf_counter()
     metrics.evaluate_examples(yolo, examples, ev, min_box_size, batch_size, nms=nms, nms_sigma=nms_sigma, tta=tta, tta_vote_iou=tta_vote_iou,
                               tta_score=tta_score, letterbox=letterbox)
@@ -72,12 +75,13 @@ def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', bat
 
 def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, precision='fp32', batch_size=None,
                    iou_thresholds=metrics.COCO_IOU_THRESHOLDS, max_detections=None, distributed=False, nms='hard', nms_sigma=0.5,
-                   seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5, area_ranges=None, area_names=None, curves=False):
+                   seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5, area_ranges=None, area_names=None, curves=False,
+                   class_score_thresholds=None, confusion=False):
     """``evaluate`` for the tiled pipeline (inference_tiled.py with --merge-device gpu): every image, of any size, is cut
     into tiles, the tiles' detections are merged on the device (seam_margin) and the pool is matched against the
     whole-image ground truth there (DetectionEvaluator.add_pool with nms=merge_nms).  batch_size: tiles per network launch
-    (None: inference_tiled's default).  area_ranges / area_names / curves: DetectionEvaluator's.  Returns (result dict, number
-    of images, seconds)."""
+    (None: inference_tiled's default).  area_ranges / area_names / curves / class_score_thresholds / confusion:
+    DetectionEvaluator's.  Returns (result dict, number of images, seconds)."""
     import inference_tiled
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args('gpu', seam_margin, merge_nms, merge_nms_sigma, inference_tiled.EDGE_EFFECT_RANGE)
@@ -87,7 +91,8 @@ def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, prec
         raise RuntimeError('tile size {} must equal the size the model was trained at {} (Q18)'.format(list(tile_size), yolo.img_size[:2]))
     model = yolo.get_keras_model()
     ev = metrics.DetectionEvaluator(yolo.number_classes, iou_thresholds, max_detections, area_ranges=area_ranges, area_names=area_names,
-                                    curves=curves)
+                                    curves=curves, class_score_thresholds=_resolve_cuts(class_score_thresholds, yolo.number_classes),
+                                    confusion=confusion)
     t0 = time.perf_counter()
     for _, img, gt in examples:
         pool, count, _ = inference_tiled.tiled_pool_device(model, img, tile_size, min_box_size, batch_size, nms, nms_sigma, seam_margin)
@@ -97,6 +102,12 @@ def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, prec
     res = ev.result()
     torch.cuda.synchronize()
     return res, ev.num_images, time.perf_counter() - t0
+
+
+def _resolve_cuts(spec, num_classes):
+    """class_score_thresholds of evaluate / evaluate_tiled: None, values, or a callable of the model's class count (the command
+    line's: the csv can only be checked once the model is loaded)."""
+    return spec(num_classes) if callable(spec) else spec
 
 
 def _fmt(v):
@@ -143,6 +154,17 @@ def write_pr_curves(res, path):
                                            _fmt(float(res['pr_score'][a, c, t, j]))]) + '\n')
 
 
+def write_confusion_matrix(res, path):
+    """One row per IoU threshold and true class, then a 'background' row (the unmatched detections per predicted class); the last
+    column counts the missed ground-truth boxes of the row's class."""
+    K = res['confusion'].shape[1] - 1
+    with open(path, 'w') as fh:
+        fh.write(','.join(['iou_threshold', 'true'] + ['pred_%d' % c for c in range(K)] + ['missed']) + '\n')
+        for t, thr in enumerate(res['iou_thresholds']):
+            for g in range(K + 1):
+                fh.write(','.join([repr(float(thr)), str(g) if g < K else 'background'] + [str(int(v)) for v in res['confusion'][t, g]]) + '\n')
+
+
 def write_csv(res, path, area_columns=False):
     """One row per class, then a 'mean' row (mean over the classes with ground truth; NaN cells are empty).  area_columns:
     append one ap_<range name> column per area range (the class's mean AP over the thresholds in that range)."""
@@ -178,6 +200,15 @@ def print_table(res):
         lo, hi = res['area_ranges'][a]
         print('area {:>8} [{:g}, {:g}]: npos {:d}  AP = {:.4f}  AP50 = {:.4f}  AR = {:.4f}'.format(
             name, lo, hi, int(res['npos_area'][:, a].sum()), float(np.mean(res['map_area'][a])), res['map50_area'][a], res['ar_area'][a]))
+    if 'class_score_thresholds' in res:
+        print('score thresholds per class: {}'.format(', '.join(repr(float(v)) for v in res['class_score_thresholds'])))
+    if 'confusion_op' in res:
+        cm = res['confusion_op']
+        K = cm.shape[0] - 1
+        print('confusion matrix at IoU {:.2f} (rows: true class, columns: predicted class; class-agnostic matching):'.format(op))
+        print('{:>10} '.format('true') + ' '.join('{:>7}'.format('pred %d' % c) for c in range(K)) + ' {:>7}'.format('missed'))
+        for g in range(K + 1):
+            print('{:>10} '.format(g if g < K else 'background') + ' '.join('{:>7d}'.format(int(v)) for v in cm[g]))
 
 
 if __name__ == '__main__':
@@ -224,6 +255,18 @@ if __name__ == '__main__':
                         help='csv of the score threshold of best F1 per class, area range and IoU threshold')
     parser.add_argument('--pr-curves', dest='pr_curves', type=str, default=None, metavar='FILE',
                         help='csv of the 101-point precision/recall curve per class, area range and IoU threshold')
+    parser.add_argument('--score-thresholds', dest='score_thresholds', type=str, default=None, metavar='S|FILE',
+                        help='keep a detection only if its score >= the threshold of its class: one number for every class, or the csv '
+                        '--operating-points wrote (an empty cell: no cut for that class).  The cut is applied after the NMS: for --nms hard '
+                        'and diou, with every cut at or above the base score threshold 0.1, that equals cutting before the NMS (a dropped box '
+                        'could only have suppressed boxes scoring below it); for the soft methods it applies to the decayed scores')
+    parser.add_argument('--score-thresholds-range', dest='score_thresholds_range', type=str, default='all', metavar='NAME',
+                        help='--score-thresholds FILE: the area range whose rows to take (default all)')
+    parser.add_argument('--score-thresholds-iou', dest='score_thresholds_iou', type=float, default=0.5, metavar='T',
+                        help='--score-thresholds FILE: the IoU threshold whose rows to take (default 0.5)')
+    parser.add_argument('--confusion-matrix', dest='confusion_matrix', type=str, default=None, metavar='FILE',
+                        help='csv of the confusion matrix per IoU threshold: every detection left after --score-thresholds is matched to '
+                        'the ground truth of ANY class; rows true class (+ background), columns predicted class (+ missed)')
     parser.add_argument('--backend', type=str, default='nccl', help='torch.distributed backend under torch.distributed.run: nccl (= RCCL, '
                         'one GPU per rank) or gloo (rehearsal; ranks may share a GPU)')
     a = parser.parse_args()
@@ -270,6 +313,12 @@ if __name__ == '__main__':
         except ValueError as e:
             parser.error(str(e))
     curves = a.operating_points is not None or a.pr_curves is not None
+    cuts = None
+    if a.score_thresholds is not None:
+        def cuts(num_classes):
+            return metrics.load_score_thresholds(a.score_thresholds, num_classes, a.score_thresholds_range, a.score_thresholds_iou)
+    elif a.score_thresholds_range != 'all' or a.score_thresholds_iou != 0.5:
+        parser.error('--score-thresholds-range and --score-thresholds-iou go with --score-thresholds')
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
         import torch.distributed as dist
@@ -291,12 +340,13 @@ if __name__ == '__main__':
         res, count, secs = evaluate_tiled(examples, a.saved_model_filepath, [a.tile_height, a.tile_width], a.min_box_size, a.precision,
                                           a.batch_size, thresholds, a.max_detections, distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma,
                                           seam_margin=a.seam_margin, merge_nms=a.merge_nms, merge_nms_sigma=a.merge_nms_sigma,
-                                          area_ranges=area_ranges, area_names=area_names, curves=curves)
+                                          area_ranges=area_ranges, area_names=area_names, curves=curves, class_score_thresholds=cuts,
+                                          confusion=a.confusion_matrix is not None)
     else:
         res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
                                     distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma, tta=a.tta, tta_vote_iou=a.tta_vote_iou,
                                     tta_score=a.tta_score, area_ranges=area_ranges, area_names=area_names, curves=curves,
-                                    letterbox=a.letterbox)
+                                    letterbox=a.letterbox, class_score_thresholds=cuts, confusion=a.confusion_matrix is not None)
     if rank == 0:
         print('Evaluated {} images in {:.2f} s ({:.1f} images/s)'.format(count, secs, count / secs if secs > 0 else float('nan')))
         print('NMS: {}'.format(a.nms + (' (sigma {:g})'.format(a.nms_sigma) if a.nms == 'soft-gaussian' else '')))
@@ -314,6 +364,8 @@ if __name__ == '__main__':
             write_operating_points(res, a.operating_points)
         if a.pr_curves:
             write_pr_curves(res, a.pr_curves)
+        if a.confusion_matrix:
+            write_confusion_matrix(res, a.confusion_matrix)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

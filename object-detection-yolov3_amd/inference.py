@@ -9,7 +9,7 @@ import os
 import numpy as np
 import torch
 
-from yolo3 import bbox_utils, imagereader
+from yolo3 import bbox_utils, imagereader, metrics
 from yolo3.model import YoloV3
 
 
@@ -34,8 +34,12 @@ def write_detections(group, dets, output_folder, image_format):
 
 
 def inference(image_folder, image_format, saved_model_filepath, output_folder, min_box_size, precision='fp32', batch_size=8, nms='hard',
-              nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep', letterbox=False):
-    """letterbox: the images of the folder may differ in size; each is rescaled with its aspect ratio kept and padded to the model's
+              nms_sigma=0.5, tta='none', tta_vote_iou=None, tta_score='keep', letterbox=False, score_thresholds=None, score_thresholds_range='all',
+              score_thresholds_iou=0.5):
+    """score_thresholds: a number, or the csv evaluate.py --operating-points wrote (its rows of range score_thresholds_range and IoU
+    threshold score_thresholds_iou; metrics.load_score_thresholds): a detection is kept only if its score >= the threshold of its
+    class, cut on the device behind the NMS (bbox_utils.cut_keep_lists; with tta: on the pooled arrays, filter_class_scores).
+    letterbox: the images of the folder may differ in size; each is rescaled with its aspect ratio kept and padded to the model's
     input on the device, and its boxes come back in its own pixels (YoloV3.predict_letterbox); not with tta.
     tta: a view set of bbox_utils.TTA_VIEWS; every image also goes through the network flipped / transposed and the views'
     detections are pooled before the NMS.  tta_vote_iou: box voting over the pool at this IoU (None: the NMS
@@ -56,6 +60,8 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision          # 'bf16': bf16 MFMA convs, fp32 heads / decode / NMS (not in the reference)
     yolo_model = yolo.get_keras_model()
+    cuts = None if score_thresholds is None else metrics.load_score_thresholds(score_thresholds, yolo.number_classes, score_thresholds_range,
+                                                                              score_thresholds_iou)
     print('Starting inference of file list')
     # The reference runs one image per model call (inference.py:40-101).  Here up to `batch_size` images go through the
     # network together; each is still z-scored with its own statistics and clipped / filtered / NMS'ed on its own.
@@ -71,7 +77,7 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
             dets, step = [], yolo.LETTERBOX_MAX_BATCH
             for s0 in range(0, len(group), step):
                 rows, _ = yolo.predict_letterbox(imgs[s0:s0 + step])
-                dets += bbox_utils.detect(rows, min_box_size, clip_wh=None, method=nms, sigma=nms_sigma)
+                dets += bbox_utils.detect(rows, min_box_size, clip_wh=None, method=nms, sigma=nms_sigma, class_score_thresholds=cuts)
             write_detections(group, dets, output_folder, image_format)
             continue
         height, width, channels = imgs[0].shape
@@ -82,7 +88,8 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
         if tta == 'none':
             rows = yolo_model(x, training=False)                              # [B, Nb, 5+K]
             # clip to the image (the intent of inference.py:62-65, Q11), small-box filter (:72), class-wise NMS (:79)
-            dets = bbox_utils.detect(rows, min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma)   # --nms: extension
+            dets = bbox_utils.detect(rows, min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma,   # --nms: extension
+                                     class_score_thresholds=cuts)
         else:
             # --tta (extension): the views of a few images per network call, pooled per image, then the same clip / filter / NMS
             bbox_utils.check_tta_args(tta, tta_vote_iou, tta_score, (height, width))
@@ -91,6 +98,8 @@ def inference(image_folder, image_format, saved_model_filepath, output_folder, m
                 rows = yolo.predict_tta(x[s0:s0 + step], views)              # [b, k * Nb, 5+K], boxes in the image's frame
                 dets += bbox_utils.detect_tta(rows, len(views), min_box_size, clip_wh=(width, height), method=nms, sigma=nms_sigma,
                                               vote_iou=tta_vote_iou, score=tta_score)
+            if cuts is not None:
+                dets = bbox_utils.filter_class_scores(dets, cuts)
         write_detections(group, dets, output_folder, image_format)
 
 
@@ -116,7 +125,19 @@ if __name__ == '__main__':
     parser.add_argument('--letterbox', action='store_true',
                         help='images of any size (extension): rescale each with its aspect ratio kept and pad it to the model input on '
                         'the device; boxes and --min-box-size are in the image\'s own pixels (not with --tta)')
+    parser.add_argument('--score-thresholds', dest='score_thresholds', type=str, default=None, metavar='S|FILE',
+                        help='keep a detection only if its score >= the threshold of its class (extension): one number for every class, or '
+                        'the csv evaluate.py --operating-points wrote (an empty cell: no cut for that class).  The cut is applied after the '
+                        'NMS: for --nms hard and diou, with every cut at or above the base score threshold 0.1, that equals cutting before the '
+                        'NMS (a dropped box could only have suppressed boxes scoring below it); for the soft methods it applies to the '
+                        'decayed scores')
+    parser.add_argument('--score-thresholds-range', dest='score_thresholds_range', type=str, default='all', metavar='NAME',
+                        help='--score-thresholds FILE: the area range whose rows to take (default all)')
+    parser.add_argument('--score-thresholds-iou', dest='score_thresholds_iou', type=float, default=0.5, metavar='T',
+                        help='--score-thresholds FILE: the IoU threshold whose rows to take (default 0.5)')
     a = parser.parse_args()
+    if a.score_thresholds is None and (a.score_thresholds_range != 'all' or a.score_thresholds_iou != 0.5):
+        parser.error('--score-thresholds-range and --score-thresholds-iou go with --score-thresholds')
     if a.letterbox and a.tta != 'none':
         parser.error('--letterbox does not go with --tta')
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
@@ -131,4 +152,4 @@ if __name__ == '__main__':
     for k, v in vars(a).items():
         print('{} = {}'.format(k, v))
     inference(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, a.min_box_size, a.precision, a.batch_size, a.nms, a.nms_sigma,
-              a.tta, a.tta_vote_iou, a.tta_score, a.letterbox)
+              a.tta, a.tta_vote_iou, a.tta_score, a.letterbox, a.score_thresholds, a.score_thresholds_range, a.score_thresholds_iou)

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from yolo3 import bbox_utils, imagereader
+from yolo3 import bbox_utils, imagereader, metrics
 from yolo3.model import YoloV3
 
 BATCH_SIZE = 25                   # tiles per network launch (the reference declares 8 at :25 and never uses it); 25 = a 4k image in 4 launches
@@ -316,7 +316,11 @@ def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_si
 
 
 def inference_image_folder(image_folder, image_format, saved_model_filepath, output_folder, tile_size, min_roi_size, precision='fp32',
-                           batch_size=None, nms='hard', nms_sigma=0.5, merge_device='cpu', seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5):
+                           batch_size=None, nms='hard', nms_sigma=0.5, merge_device='cpu', seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5,
+                           score_thresholds=None, score_thresholds_range='all', score_thresholds_iou=0.5):
+    """score_thresholds: a number, or the csv evaluate.py --operating-points wrote (metrics.load_score_thresholds): of the merged
+    detections of an image only those with score >= the threshold of their class are written (bbox_utils.filter_class_scores, on
+    either merge device; after a soft merge NMS the scores are the decayed ones)."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args(merge_device, seam_margin, merge_nms, merge_nms_sigma, EDGE_EFFECT_RANGE)
     if not os.path.exists(saved_model_filepath):
@@ -335,6 +339,8 @@ def inference_image_folder(image_folder, image_format, saved_model_filepath, out
     if list(tile_size) != list(yolo.img_size[:2]):
         raise RuntimeError('tile size {} must equal the size the model was trained at {} (Q18)'.format(tile_size, yolo.img_size[:2]))
     yolo_model = yolo.get_keras_model()
+    cuts = None if score_thresholds is None else metrics.load_score_thresholds(score_thresholds, yolo.number_classes, score_thresholds_range,
+                                                                              score_thresholds_iou)
     os.makedirs(output_folder, exist_ok=True)
     print('Starting inference of file list')
     for i, img_filepath in enumerate(img_filepath_list):
@@ -345,6 +351,9 @@ def inference_image_folder(image_folder, image_format, saved_model_filepath, out
             img = np.expand_dims(img, -1)
         predictions = inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, merge_device, seam_margin,
                                             merge_nms, merge_nms_sigma)
+        if cuts is not None:
+            predictions = bbox_utils.filter_class_scores(predictions, cuts)
+            print('Kept: {} rois at the class score thresholds'.format(predictions.shape[0]))
         bbox_utils.write_boxes_from_ltrbpc(predictions, os.path.join(output_folder, file_name.replace(image_format, 'csv')))
 
 
@@ -369,7 +378,19 @@ if __name__ == '__main__':
     parser.add_argument('--merge-nms', dest='merge_nms', choices=list(bbox_utils.MERGE_NMS_METHODS), default='none',
                         help='with --merge-device gpu: class-wise NMS over the merged detections of the whole image')
     parser.add_argument('--merge-nms-sigma', dest='merge_nms_sigma', type=float, default=0.5, help='sigma of --merge-nms soft-gaussian (> 0)')
+    parser.add_argument('--score-thresholds', dest='score_thresholds', type=str, default=None, metavar='S|FILE',
+                        help='keep a detection only if its score >= the threshold of its class (extension): one number for every class, or '
+                        'the csv evaluate.py --operating-points wrote (an empty cell: no cut for that class).  The cut is applied after the '
+                        'per-tile NMS and the merge: for --nms hard and diou, with every cut at or above the base score threshold 0.1, that equals cutting before the '
+                        'NMS (a dropped box could only have suppressed boxes scoring below it); for the soft methods it applies to the '
+                        'decayed scores')
+    parser.add_argument('--score-thresholds-range', dest='score_thresholds_range', type=str, default='all', metavar='NAME',
+                        help='--score-thresholds FILE: the area range whose rows to take (default all)')
+    parser.add_argument('--score-thresholds-iou', dest='score_thresholds_iou', type=float, default=0.5, metavar='T',
+                        help='--score-thresholds FILE: the IoU threshold whose rows to take (default 0.5)')
     a = parser.parse_args()
+    if a.score_thresholds is None and (a.score_thresholds_range != 'all' or a.score_thresholds_iou != 0.5):
+        parser.error('--score-thresholds-range and --score-thresholds-iou go with --score-thresholds')
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
         parser.error('--nms-sigma must be > 0')
     try:
@@ -377,4 +398,5 @@ if __name__ == '__main__':
     except ValueError as e:
         parser.error(str(e))
     inference_image_folder(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, [a.tile_height, a.tile_width], a.min_box_size, a.precision, a.batch_size,
-                           a.nms, a.nms_sigma, a.merge_device, a.seam_margin, a.merge_nms, a.merge_nms_sigma)
+                           a.nms, a.nms_sigma, a.merge_device, a.seam_margin, a.merge_nms, a.merge_nms_sigma, a.score_thresholds,
+                           a.score_thresholds_range, a.score_thresholds_iou)

@@ -175,6 +175,10 @@ SIGNATURES = {
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), i32, ip, vp, vp, vp, C.c_longlong, vp]),   # thr, lo, hi: HOST
     'y3_eval_ap_ranges': (i32, [vp, vp, vp, C.c_longlong, i32, i32, i32, ip, vp, sz, fp, fp, ip, ip, ip, ip, ip, fp, fp, fp, vp]),
     'y3_eval_ap_ranges_workspace_bytes': (sz, [C.c_longlong, i32, i32]),
+    'y3_keep_cut': (i32, [fp, ip, i32, i32, i32, fp, vp]),
+    'y3_eval_confusion': (i32, [fp, i32, i32, i32, i32, f32, f32, ip, ip, fp, i32, i32, fp, ip, i32, i32, C.POINTER(C.c_float), i32, ip,
+                                C.c_longlong, vp, sz, vp, vp]),     # iou_thr: HOST array
+    'y3_eval_confusion_workspace_bytes': (sz, [C.c_longlong]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -76,14 +76,71 @@ def nms_device(rows, min_box_size=0.0, iou_threshold=0.3, score_threshold=0.1, c
     return keep_idx, keep_cnt, keep_score
 
 
-def detect_async(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5):
+def check_class_thresholds(thresholds, num_classes):
+    """A number (one cut for every class) or num_classes values -> float32 [num_classes].  Each is finite or -inf (no cut);
+    ValueError on NaN, +inf, or another length."""
+    try:
+        thr = np.asarray(thresholds, np.float32)
+    except (TypeError, ValueError):
+        raise ValueError('class score thresholds: a number or {} numbers, got {!r}'.format(num_classes, thresholds))
+    if thr.ndim == 0:
+        thr = np.full(int(num_classes), thr, np.float32)
+    if thr.ndim != 1 or thr.size != int(num_classes):
+        raise ValueError('class score thresholds: a number or {} numbers, got shape {}'.format(num_classes, thr.shape))
+    if np.any(np.isnan(thr)) or np.any(thr == np.inf):
+        raise ValueError('class score thresholds must be finite or -inf, got {}'.format(thr.tolist()))
+    return np.ascontiguousarray(thr)
+
+
+def cut_keep_lists(keep_cnt, keep_score, class_thr_dev):
+    """Per-class score cut on NMS keep lists, in place on the device (y3_keep_cut, current stream): keep_cnt int32 [..., K] and
+    keep_score float32 [..., K, max_keep] as nms_device / nms_labelled_device return them, class_thr_dev CUDA float32 [K] (the
+    values of check_class_thresholds).  Every count becomes the length of the longest prefix of its list with score >= the class's
+    threshold; nothing else is written.  The caller owns keep_cnt: cut a copy of nms_device's cached buffer."""
+    assert keep_cnt.is_cuda and keep_cnt.dtype == torch.int32 and keep_cnt.is_contiguous()
+    assert keep_score.is_cuda and keep_score.dtype == torch.float32 and keep_score.is_contiguous()
+    assert class_thr_dev.is_cuda and class_thr_dev.dtype == torch.float32 and class_thr_dev.is_contiguous() and class_thr_dev.dim() == 1
+    k = class_thr_dev.numel()
+    if keep_cnt.dim() < 1 or keep_cnt.shape[-1] != k or tuple(keep_score.shape[:-1]) != tuple(keep_cnt.shape):
+        raise ValueError('keep_cnt {} / keep_score {} are not keep lists of {} classes'.format(tuple(keep_cnt.shape), tuple(keep_score.shape), k))
+    check(lib.y3_keep_cut(keep_score.data_ptr(), keep_cnt.data_ptr(), keep_cnt.numel(), k, keep_score.shape[-1], class_thr_dev.data_ptr(),
+                          torch.cuda.current_stream(keep_cnt.device).cuda_stream), 'y3_keep_cut')
+    return keep_cnt
+
+
+def filter_class_scores(dets, thr):
+    """Host twin of cut_keep_lists for pipelines that end in host arrays.  dets: a list of per-image (boxes [M,4], score [M],
+    label [M], keep [M]) tuples or (None,)*4 (``detect`` / ``detect_tta``), or one float [M, 6] array x0, y0, x1, y1, score, class
+    (inference_image_tiled).  thr: check_class_thresholds' float32 [K].  Keeps the rows with np.float32(score) >=
+    np.float32(thr[label]), in their order; an image left empty becomes (None,)*4."""
+    thr = np.asarray(thr, np.float32).reshape(-1)
+    if isinstance(dets, np.ndarray):
+        if dets.ndim != 2 or dets.shape[1] != 6:
+            raise ValueError('a detection array is [M, 6] = x0, y0, x1, y1, score, class, got shape {}'.format(dets.shape))
+        return dets[dets[:, 4].astype(np.float32) >= thr[dets[:, 5].astype(np.int64)]]
+    out = []
+    for det in dets:
+        if det[0] is None:
+            out.append((None, None, None, None))
+            continue
+        keep = np.asarray(det[1]).astype(np.float32).reshape(-1) >= thr[np.asarray(det[2]).astype(np.int64).reshape(-1)]
+        out.append(tuple(None if v is None else np.asarray(v)[keep] for v in det) if keep.any() else (None, None, None, None))
+    return out
+
+
+def detect_async(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5,
+                 class_score_thresholds=None):
     """Enqueue clip -> small-box filter -> class-wise NMS for a batch and return a ``collect()`` callable; nothing
     synchronises until it is called, so the caller can queue the next batch's network first.  ``rows`` must stay
-    untouched until then (pass a clone of a buffer that the next forward overwrites).  method / sigma: see nms_device."""
+    untouched until then (pass a clone of a buffer that the next forward overwrites).  method / sigma: see nms_device.
+    class_score_thresholds: a number or K values (check_class_thresholds); the keep lists are then cut per class on the device
+    (cut_keep_lists) behind the NMS, before the counts are read."""
     keep_idx, keep_cnt, keep_score = nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh, private_outputs=True,
                                                 method=method, sigma=sigma)
     n, nb, d = rows.shape
     k = d - 5
+    if class_score_thresholds is not None:
+        cut_keep_lists(keep_cnt, keep_score, torch.from_numpy(check_class_thresholds(class_score_thresholds, k)).to(rows.device))
     done = torch.cuda.Event()
     done.record(torch.cuda.current_stream(rows.device))
 
@@ -265,10 +322,11 @@ def gather_kept(pool_rows, keep_idx, keep_cnt, keep_score):
     return out
 
 
-def detect(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5):
+def detect(rows, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5, class_score_thresholds=None):
     """inference.py:62-79 for a batch: returns, per image, (boxes[M,4], score[M],
-    label[M] int32, keep[M] row indices) as NumPy arrays, or (None,)*4.  method / sigma: see nms_device."""
-    return detect_async(rows, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma)()
+    label[M] int32, keep[M] row indices) as NumPy arrays, or (None,)*4.  method / sigma: see nms_device;
+    class_score_thresholds: see detect_async."""
+    return detect_async(rows, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma, class_score_thresholds)()
 
 
 # ---- test-time augmentation: pooled views, box voting (y3_box_vote, DESIGN §3.15) -------------------------------------------

@@ -23,7 +23,15 @@ torch.distributed group.  ``evaluate_examples`` is the batching loop evaluate.py
 Opt-in: ``area_ranges`` scores every class once per closed range of box area with COCO's ignore rule
 (``y3_eval_match_ranges``), ``curves`` adds the best-F1 score cut and the 101-point PR curve per (class, range, threshold)
 (``y3_eval_ap_ranges``).  Without them the three kernels above run exactly as before.
+
+Opt-in: ``class_score_thresholds`` cuts every keep list at its class's score threshold on the device before
+matching (``y3_keep_cut``; ``load_score_thresholds`` reads the cuts from an operating-points csv), ``confusion`` also matches
+each image class-agnostically and counts the [T, K+1, K+1] confusion matrix (``y3_eval_confusion``).
 """
+import csv
+import zlib
+
+
 import numpy as np
 import torch
 
@@ -34,6 +42,7 @@ from .isg_ai_pb import ImageYoloBoxesPair
 COCO_IOU_THRESHOLDS = tuple(float(np.float32(0.5) + np.float32(0.05) * np.float32(k)) for k in range(10))
 MAX_GT_PER_CLASS = 4096     # Y3_EVAL_MAX_GT: the GT boxes of one (image, class) are staged in LDS
 MAX_AREA_RANGES = 8         # Y3_EVAL_MAX_RANGES
+MAX_GT_PER_IMAGE = 4096     # with confusion=True the GT boxes of one IMAGE, all classes, are staged in LDS
 COCO_AREA_RANGES = (('all', -np.inf, np.inf), ('small', 0.0, 32.0 ** 2), ('medium', 32.0 ** 2, 96.0 ** 2), ('large', 96.0 ** 2, 1e10))
 
 
@@ -93,10 +102,13 @@ class DetectionEvaluator:
     (lo, hi) closed ranges of box area, area_names their names: AP / recall / TP / FP per range with the ignore rule of DESIGN
     §3.16.  curves: also the best-F1 score cut and the PR curve per (class, range, threshold); without ranges over the one
     range (-inf, inf).  Either option switches matching and AP to the *_ranges kernels; ``state``, ``matches`` and ``result``
-    then carry one TP and one ignore mask per entry and range."""
+    then carry one TP and one ignore mask per entry and range.  class_score_thresholds: a number or K values (finite or -inf):
+    every input path's keep lists are cut to the entries with score >= their class's threshold before matching, so every number
+    is that of the cut lists.  confusion: also count the class-agnostic confusion matrix of the same lists; at
+    most 4096 GT boxes per image then."""
 
     def __init__(self, num_classes, iou_thresholds=COCO_IOU_THRESHOLDS, max_detections=None, device=None, area_ranges=None, area_names=None,
-                 curves=False):
+                 curves=False, class_score_thresholds=None, confusion=False):
         self.num_classes = int(num_classes)
         if self.num_classes < 1:
             raise ValueError('num_classes must be >= 1')
@@ -119,6 +131,10 @@ class DetectionEvaluator:
                 check_area_ranges(area_ranges, area_names)
             self._lo_host = float_array(self.area_ranges[:, 0])
             self._hi_host = float_array(self.area_ranges[:, 1])
+        self.confusion = bool(confusion)
+        self.class_score_thresholds = None if class_score_thresholds is None else \
+            bbox_utils.check_class_thresholds(class_score_thresholds, self.num_classes)
+        self._cut_dev = None if self.class_score_thresholds is None else torch.from_numpy(self.class_score_thresholds).to(self.device)
         self.reset()
 
     def reset(self):
@@ -130,6 +146,8 @@ class DetectionEvaluator:
         self._counts = []         # per batch: int32 device [n] = pool entries each image added (image order)
         self._npos = np.zeros(self.num_classes, np.int64)
         self.num_images = 0
+        self._confusion = torch.zeros(len(self.iou_thresholds), self.num_classes + 1, self.num_classes + 1, dtype=torch.int64,
+                                      device=self.device) if self.confusion else None
 
     # ---- input paths ----------------------------------------------------------------------------------------------
     def add_batch(self, rows, gt_boxes_per_image, min_box_size, clip_wh=None, iou_threshold=0.3, score_threshold=0.1, nms='hard',
@@ -265,6 +283,8 @@ class DetectionEvaluator:
         st = torch.cuda.current_stream(dev).cuda_stream
         K = self.num_classes
         max_det = max_keep if self.max_detections is None else min(self.max_detections, max_keep)
+        if self._cut_dev is not None:                 # a private copy: nms_device's cached buffers belong to the caller
+            keep_cnt = bbox_utils.cut_keep_lists(keep_cnt.clone(), keep_score, self._cut_dev)
         offsets = torch.empty(n * K + 1, dtype=torch.int32, device=dev)
         check(lib.y3_eval_offsets(keep_cnt.data_ptr(), n * K, max_keep, max_det, offsets.data_ptr(), st), 'y3_eval_offsets')
         gt_dev = torch.from_numpy(buf).to(dev)
@@ -272,6 +292,14 @@ class DetectionEvaluator:
         total = int(offsets[n * K].item())                                # the one host read of the batch
         self._reserve(self._used + total)             # only grows capacity: a refused batch below (GT over the LDS cap) adds nothing
         used = self._used
+        if self.confusion:
+            # first: it refuses an image over the LDS cap (which every (image, class) over the cap is too) before anything is counted
+            ws_bytes = int(lib.y3_eval_confusion_workspace_bytes(total))
+            ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.int32, device=dev)
+            check(lib.y3_eval_confusion(rows.data_ptr(), n, nb, ld, K, clip_w, clip_h, keep_idx.data_ptr(), keep_cnt.data_ptr(),
+                                        keep_score.data_ptr(), max_keep, max_det, gt_dev.data_ptr(), cnt_dev.data_ptr(), max_gt,
+                                        int(cnt.max()) if cnt.size else 0, self._thr_host, len(self.iou_thresholds), offsets.data_ptr(), total,
+                                        ws.data_ptr(), ws_bytes, self._confusion.data_ptr(), st), 'y3_eval_confusion')
         if self._ranged:
             A = len(self.area_ranges)
             check(lib.y3_eval_match_ranges(rows.data_ptr(), n, nb, ld, K, clip_w, clip_h, keep_idx.data_ptr(), keep_cnt.data_ptr(),
@@ -316,13 +344,18 @@ class DetectionEvaluator:
         """What ``merge`` / ``all_gather_evaluator`` combine (device tensors are copies): keys int64 [M], tp int32 [M] = the
         pools in (image, class, keep rank) order, image_counts int32 [num_images], npos int64 [K] (NumPy), num_images,
         iou_thresholds (float32), num_classes, max_detections.  With area ranges or curves: tp is [M, A] and the state also
-        holds ign int32 [M, A], npos_area int64 [K, A], area_ranges float32 [A, 2], area_names, curves."""
+        holds ign int32 [M, A], npos_area int64 [K, A], area_ranges float32 [A, 2], area_names, curves.  With
+        class_score_thresholds: those (float32 [K]); with confusion: confusion int64 device [T, K+1, K+1]."""
         st = {'keys': self._keys[:self._used].clone(), 'tp': self._tp[:self._used].clone(), 'image_counts': self.image_counts().clone(),
               'npos': self._npos.copy(), 'num_images': self.num_images, 'iou_thresholds': self.iou_thresholds.copy(),
               'num_classes': self.num_classes, 'max_detections': self.max_detections}
         if self._ranged:
             st.update(ign=self._ign[:self._used].clone(), npos_area=self._npos_area.copy(), area_ranges=self.area_ranges.copy(),
                       area_names=list(self.area_names), curves=self.curves)
+        if self.class_score_thresholds is not None:
+            st['class_score_thresholds'] = self.class_score_thresholds.copy()
+        if self.confusion:
+            st['confusion'] = self._confusion.clone()
         return st
 
     @classmethod
@@ -332,7 +365,7 @@ class DetectionEvaluator:
         inference.py), or an explicit sequence of (state, local image) pairs naming every image once.  ``result()`` sorts
         stably, so equal scores rank by pool position: rebuilding the single-process order makes the merged result
         bit-identical to one evaluator fed all images in that order.  States must share thresholds, classes,
-        max_detections, area ranges and curves."""
+        max_detections, area ranges, curves, class_score_thresholds and the confusion flag; the confusion matrices are summed."""
         states = list(states)
         if not states:
             raise ValueError('merge needs at least one state')
@@ -346,10 +379,14 @@ class DetectionEvaluator:
             if not _same_ranges(s, s0):
                 raise ValueError('state {} does not match state 0: area_ranges {} / {}, curves {} / {}'.format(
                     i, _ranges_list(s), _ranges_list(s0), s.get('curves', False), s0.get('curves', False)))
+            if not _same_cuts(s, s0) or ('confusion' in s) != ('confusion' in s0):
+                raise ValueError('state {} does not match state 0: class_score_thresholds {} / {}, confusion {} / {}'.format(
+                    i, _cuts_list(s), _cuts_list(s0), 'confusion' in s, 'confusion' in s0))
         state_index, local_index = global_image_order([int(s['num_images']) for s in states], order)
         ranged = s0.get('area_ranges') is not None
         ev = cls(s0['num_classes'], thr0, s0['max_detections'], device, area_ranges=s0['area_ranges'] if ranged else None,
-                 area_names=s0['area_names'] if ranged else None, curves=bool(s0.get('curves', False)))
+                 area_names=s0['area_names'] if ranged else None, curves=bool(s0.get('curves', False)),
+                 class_score_thresholds=s0.get('class_score_thresholds'), confusion='confusion' in s0)
         dev = ev.device
         counts = []
         for i, s in enumerate(states):
@@ -373,6 +410,12 @@ class DetectionEvaluator:
         if ranged:
             ev._npos_area = np.sum([np.asarray(s['npos_area'], np.int64) for s in states], axis=0)
         ev.num_images = int(state_index.size)
+        if ev.confusion:
+            for i, s in enumerate(states):
+                if tuple(s['confusion'].shape) != tuple(ev._confusion.shape):
+                    raise ValueError('state {}: confusion matrix of shape {}, expected {}'.format(i, tuple(s['confusion'].shape),
+                                                                                                 tuple(ev._confusion.shape)))
+                ev._confusion += s['confusion'].to(dev, torch.int64)
         return ev
 
     # ---- output ---------------------------------------------------------------------------------------------------
@@ -396,9 +439,19 @@ class DetectionEvaluator:
         range 0, and the dict adds area_ranges [A,2], area_names, ap_area, recall_area, tp_area, fp_area, ign_area [A,K,T],
         npos_area [K,A], map_area [A,T], map50_area, map50_95_area, ar_area [A] (mean final recall over the classes with GT and
         the thresholds); with curves also best_score, best_precision, best_recall, best_f1, best_tp, best_fp [A,K,T] (the best-F1
-        score cut: keep score >= best_score; NaN / 0 without entries or GT) and pr_precision, pr_score [A,K,T,101]."""
-        if self._ranged:
-            return self._result_ranges()
+        score cut: keep score >= best_score; NaN / 0 without entries or GT) and pr_precision, pr_score [A,K,T,101].
+        With class_score_thresholds the dict carries them (float32 [K]); with confusion it adds confusion int64 [T,K+1,K+1] (rows
+        true, columns predicted, index K = background: row K the unmatched detections, column K the missed GT boxes; over all box
+        areas) and confusion_op [K+1,K+1], the matrix at op_threshold."""
+        res = self._result_ranges() if self._ranged else self._result_plain()
+        if self.class_score_thresholds is not None:
+            res['class_score_thresholds'] = self.class_score_thresholds.copy()
+        if self.confusion:
+            res['confusion'] = self._confusion.cpu().numpy()
+            res['confusion_op'] = res['confusion'][int(np.nonzero(self.iou_thresholds == np.float32(res['op_threshold']))[0][0])].copy()
+        return res
+
+    def _result_plain(self):
         dev = self.device
         st = torch.cuda.current_stream(dev).cuda_stream
         K, T, m = self.num_classes, len(self.iou_thresholds), self._used
@@ -446,6 +499,57 @@ class DetectionEvaluator:
 def _ranges_list(state):
     r = state.get('area_ranges')
     return None if r is None else np.asarray(r, np.float32).tolist()
+
+
+def _cuts_list(state):
+    c = state.get('class_score_thresholds')
+    return None if c is None else np.asarray(c, np.float32).tolist()
+
+
+def _same_cuts(s, s0):
+    a, b = s.get('class_score_thresholds'), s0.get('class_score_thresholds')
+    if (a is None) != (b is None):
+        return False
+    return a is None or np.asarray(a, np.float32).tobytes() == np.asarray(b, np.float32).tobytes()
+
+
+def load_score_thresholds(spec, num_classes, range_name='all', iou=0.5):
+    """Per-class score thresholds -> float32 [num_classes].  spec: a number (or its text), one cut for every class, or the path of a
+    csv written by evaluate.py --operating-points: per class the score_threshold cell of the row whose range is ``range_name`` and
+    whose np.float32(iou_threshold) equals np.float32(iou), parsed as np.float32(float(cell)) (the writer prints
+    repr(float(float32)), so the bits round-trip).  An empty cell (a class without entries or ground truth) gives -inf: no cut
+    beyond the pipeline's base threshold.  ValueError names a missing class, range or IoU row, a NaN, or a wrong class count."""
+    K = int(num_classes)
+    if not isinstance(spec, str):
+        return bbox_utils.check_class_thresholds(spec, K)
+    try:
+        value = float(spec)
+    except ValueError:
+        value = None
+    if value is not None:
+        return bbox_utils.check_class_thresholds(value, K)
+    with open(spec, newline='') as fh:
+        rows = list(csv.DictReader(fh))
+    for col in ('class', 'range', 'iou_threshold', 'score_threshold'):
+        if not rows or col not in rows[0]:
+            raise ValueError('{}: not an operating-points csv (no rows or no {!r} column)'.format(spec, col))
+    if not any(r['range'] == range_name for r in rows):
+        raise ValueError('{}: no rows of range {!r} (it has {})'.format(spec, range_name, sorted({r['range'] for r in rows})))
+    rows = [r for r in rows if r['range'] == range_name]
+    if not any(np.float32(float(r['iou_threshold'])) == np.float32(iou) for r in rows):
+        raise ValueError('{}: no rows of IoU threshold {!r} in range {!r} (it has {})'.format(
+            spec, iou, range_name, sorted({float(r['iou_threshold']) for r in rows})))
+    rows = [r for r in rows if np.float32(float(r['iou_threshold'])) == np.float32(iou)]
+    classes = sorted(int(r['class']) for r in rows)
+    if classes != list(range(len(classes))) or len(classes) != K:
+        missing = sorted(set(range(K)) - set(classes))
+        raise ValueError('{}: rows of classes {} for a model of {} classes{}'.format(
+            spec, classes, K, ' (class {} is missing)'.format(missing[0]) if missing else ''))
+    thr = np.empty(K, np.float32)
+    for r in rows:
+        cell = r['score_threshold'].strip()
+        thr[int(r['class'])] = np.float32(float(cell)) if cell else np.float32(-np.inf)
+    return bbox_utils.check_class_thresholds(thr, K)
 
 
 def _same_ranges(s, s0):
@@ -554,6 +658,14 @@ def pool_gather_index(image_counts, state_index, local_index, total):
     return torch.repeat_interleave(first, cnt, output_size=total) + within, cnt
 
 
+def _cut_words(state):
+    """The meta words of all_gather_evaluator behind the existing ones: confusion flag, number of class score thresholds (0: none),
+    CRC-32 of their fp32 bytes; a fixed length whatever the class count."""
+    c = state.get('class_score_thresholds')
+    return [int('confusion' in state), 0 if c is None else int(np.asarray(c).size),
+            0 if c is None else zlib.crc32(np.asarray(c, np.float32).tobytes())]
+
+
 def all_gather_evaluator(ev, group=None):
     """COLLECTIVE over ``group`` (default: the default process group): EVERY rank must call it, with its own evaluator,
     and every rank gets back the merged evaluator (``merge`` of the ranks' states in rank order, order='strided': rank r
@@ -580,12 +692,16 @@ def all_gather_evaluator(ev, group=None):
     if ranged:
         rng[:, :A] = st['area_ranges'].T
     meta = torch.tensor([st['keys'].numel(), st['num_images'], st['num_classes'], md, T] + thr.view(np.int32).tolist() +
-                        [A, int(st.get('curves', False))] + rng.reshape(-1).view(np.int32).tolist(), dtype=torch.int64, device=dev)
+                        [A, int(st.get('curves', False))] + rng.reshape(-1).view(np.int32).tolist() + _cut_words(st),
+                        dtype=torch.int64, device=dev)
     metas = [m.cpu().numpy() for m in gather(meta)]
     for r, m in enumerate(metas):                    # every rank sees every meta row: all raise together, before shapes diverge
-        if not np.array_equal(m[2:], metas[0][2:]):
+        if not np.array_equal(m[2:55], metas[0][2:55]):
             raise ValueError('rank {} evaluates with classes / max_detections / thresholds {} and area ranges / curves {} against rank 0\'s {} '
                              'and {}'.format(r, m[2:5], m[37:39], metas[0][2:5], metas[0][37:39]))
+        if not np.array_equal(m[55:], metas[0][55:]):
+            raise ValueError('rank {} evaluates with confusion / class_score_thresholds (count, checksum) {} against rank 0\'s {}'.format(
+                r, m[55:], metas[0][55:]))
     max_m = max(1, max(int(m[0]) for m in metas))
     max_n = max(1, max(int(m[1]) for m in metas))
 
@@ -608,6 +724,12 @@ def all_gather_evaluator(ev, group=None):
         for r, (s, m) in enumerate(zip(states, metas)):
             s.update(tp=s['tp'].reshape(-1, A), ign=ign[r][:int(m[0]) * A].reshape(-1, A), npos_area=npos_area[r].cpu().numpy(),
                      area_ranges=st['area_ranges'], area_names=st['area_names'], curves=st['curves'])
+    if 'class_score_thresholds' in st:
+        for s in states:
+            s['class_score_thresholds'] = st['class_score_thresholds']
+    if 'confusion' in st:
+        for s, c in zip(states, gather(st['confusion'].to(dev))):
+            s['confusion'] = c
     return DetectionEvaluator.merge(states, 'strided', device=ev.device)
 
 
