@@ -681,6 +681,16 @@ int y3_tile_merge(const float* rows, int n, int nb, int ld, int num_classes, con
                   y3_stream_t stream);
 size_t y3_tile_merge_workspace_bytes(int n, int num_classes);
 
+/* y3_tile_merge for tiles whose kept boxes were replaced by box voting (tile test-time augmentation): voted
+ * [n][K][max_keep][6] is y3_box_vote's out for the batch, and entry e = (t * K + c) * max_keep + j takes its box from
+ * voted[e * 6 + 0 .. 3] and its score from voted[e * 6 + 4] instead of rows[keep_idx[e]] and keep_score[e].  Everything else is
+ * y3_tile_merge's: the ghost test, the shift, the rounding, the centre test, the clamp, the ordered append, the two launches, the
+ * limits and the workspace.  keep_idx is still range-checked against nb (an entry outside 0 .. nb-1 is skipped), so with voted
+ * filled from rows[keep_idx] and keep_score the pool is y3_tile_merge's byte for byte. */
+int y3_tile_merge_voted(const float* voted, int n, int nb, int num_classes, const int* keep_idx, const int* keep_cnt,
+                        int max_keep, const int* table_dev, int tile_h, int tile_w, int img_h, int img_w, int edge, float margin,
+                        float* pool, int cap, int* pool_count, void* workspace, size_t workspace_bytes, y3_stream_t stream);
+
 /* y3_nms_labelled: class-wise NMS over such a pool.  pool [m][6] = x0,y0,x1,y1,score,class; workgroup c takes the rows whose
  * column 5 == (float)c (a label outside 0..K-1 belongs to no class) with score > 0 and score >= score_thr as candidates, the
  * score as is (the order key is the score's bit pattern, so a row with a zero, negative or NaN score is never a candidate,
@@ -783,6 +793,21 @@ int y3_tile_gather(const void* img, int dtype, int height, int width, int channe
 int y3_tile_gather_zscore_nhwc(const void* img, int dtype, int height, int width, int channels, const int* table_dev,
                                int ntiles, int tile_h, int tile_w, float* out, int channel_pitch, void* workspace,
                                y3_stream_t stream);
+
+/* The same tiles again, with their test-time augmentation views: out float32 NHWC
+ * [ntiles * k][tile_h][tile_w][channel_pitch], tile-major and view-minor -- image t * k + v is view views_host[v] of tile t, the
+ * layout y3_tta_views_nhwc gives images.  Bit for bit, view 0 of tile t is what y3_tile_gather_zscore_nhwc writes for tile t and
+ * every other view is that tensor permuted by the view definition above (transpose first, then flip x, flip y); equivalently the
+ * result is y3_tile_gather -> y3_zscore -> y3_tta_views_nhwc.  The statistics are per tile, computed once by the launches of
+ * y3_tile_gather_zscore_nhwc; one 256-thread workgroup per 32 x 32 pixel block of a tile then gathers the block once through
+ * the reflect index, normalises it, stages it in LDS (up to four channel planes, row pitch 33 dwords) and stores it to all k
+ * views as 16-byte pixels along each destination row (straight views read LDS rows, transposed views LDS columns).
+ * views_host: a HOST array, validated as y3_tta_views_nhwc validates it (a transposing code needs tile_h == tile_w).
+ * channels <= 4; channel_pitch >= 4 and a multiple of 4 (every float of a pixel beyond `channels` is written as zero); out
+ * 16-byte aligned; ntiles <= 65535.  workspace: y3_zscore_workspace_bytes(ntiles). */
+int y3_tile_gather_zscore_views_nhwc(const void* img, int dtype, int height, int width, int channels, const int* table_dev,
+                                     int ntiles, int tile_h, int tile_w, const int* views_host, int k, float* out,
+                                     int channel_pitch, void* workspace, y3_stream_t stream);
 
 /* ---- training augmentation on the device: augment.py:30-125, 275-297 at the severities of imagereader.py:369-391 ----------
  * The random decisions of augment_image_box_pair are drawn on the host (yolo3/augment.py draw_augmentation, same np.random

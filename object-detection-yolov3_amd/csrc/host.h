@@ -13,6 +13,14 @@ void y3_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 
+// A checked test-time augmentation view list as a kernel argument (tta.hip; the tile gather of pointwise.hip writes views too)
+struct TtaViews {
+    int k;
+    int code[Y3_TTA_MAX_VIEWS];
+};
+// 1 .. Y3_TTA_MAX_VIEWS distinct codes 0 .. 7, a transposing one only for h == w: Y3_EINVAL + message otherwise (tta.hip)
+int y3_tta_check_views(const int* views, int k, int h, int w, const char* what, TtaViews* out);
+
 static inline int y3_ilog2(int v) {
     int l = 0;
     while ((1 << l) < v) ++l;

@@ -1257,3 +1257,100 @@ extern "C" int y3_tile_gather_zscore_nhwc(const void* img, int dtype, int height
     return Y3_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// y3_tile_gather_zscore_nhwc with the test-time augmentation views of every tile: the statistics launches above,
+// then one 256-thread workgroup per 32 x 32 pixel block of a tile.  The block is gathered ONCE through reflect_index (rows of the
+// image: the lanes of a half wave read neighbouring pixels), normalised with tile_gather_norm_kernel's expressions and staged in LDS
+// as up to four channel planes of row pitch 33 dwords; every view then stores whole 16-byte pixels with thread x walking the
+// DESTINATION row.  A straight view reads an LDS row (forwards or, flipped, backwards), a transposed view an LDS column: at pitch
+// 33 the 32 lanes of a half wave meet 32 different banks either way (tta_views_kernel of tta.hip moves gathered tensors the same
+// way).  A per-view gather would read image COLUMNS for the transposed views instead: C bytes per lane, each from another row.
+// ---------------------------------------------------------------------------
+#define Y3_TV_BLOCK 32                  // pixels per side of a workgroup's block
+#define Y3_TV_PITCH (Y3_TV_BLOCK + 1)   // LDS row pitch in dwords
+template <typename T>
+__global__ __launch_bounds__(256) void tile_gather_views_kernel(const T* __restrict__ img, int W, int C, const int* __restrict__ table, int th, int tw,
+                                                                const float* __restrict__ mvsd, float* __restrict__ out, int cpitch,
+                                                                const TtaViews vw) {
+    __shared__ float blk[4][Y3_TV_BLOCK][Y3_TV_PITCH];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+    const int bx = blockIdx.x * Y3_TV_BLOCK, by = blockIdx.y * Y3_TV_BLOCK, tile = blockIdx.z;
+    const float mv = mvsd[2 * tile], sd = mvsd[2 * tile + 1];
+    const bool divide = !(sd <= 1.0f);
+    const int* row = table + tile * 6;
+    const int y0 = row[0], ny = row[1], pre_y = row[2], x0 = row[3], nx = row[4], pre_x = row[5];
+    const int x = bx + tx;
+    if (x < tw) {
+        const int sx = x0 + reflect_index(x - pre_x, nx);
+#pragma unroll
+        for (int r = ty; r < Y3_TV_BLOCK; r += 8) {
+            const int y = by + r;
+            if (y >= th) break;
+            const T* px = img + ((size_t)(y0 + reflect_index(y - pre_y, ny)) * W + sx) * C;
+            for (int c = 0; c < C; ++c) {
+                const float d = (float)px[c] - mv;
+                blk[c][r][tx] = divide ? d / sd : d;
+            }
+        }
+    }
+    __syncthreads();
+    const long long hw = (long long)th * tw;
+    for (int v = 0; v < vw.k; ++v) {
+        const int code = vw.code[v];
+        const bool tr = code & Y3_TTA_TRANSPOSE, fx = code & Y3_TTA_FLIP_X, fy = code & Y3_TTA_FLIP_Y;
+        float* dst = out + ((long long)tile * vw.k + v) * hw * cpitch;  // a transposing view is square: the view is th x tw as well
+#pragma unroll
+        for (int r = ty; r < Y3_TV_BLOCK; r += 8) {
+            // (ly, lx): the block entry this thread moves; (vy, vx): where it lands in the view before the flips
+            const int ly = tr ? tx : r, lx = tr ? r : tx;
+            const int sy = by + ly, sx = bx + lx;
+            if (sy >= th || sx >= tw) continue;
+            int vy = tr ? sx : sy, vx = tr ? sy : sx;
+            if (fx) vx = tw - 1 - vx;
+            if (fy) vy = th - 1 - vy;
+            float4 px;
+            px.x = blk[0][ly][lx];
+            px.y = C > 1 ? blk[1][ly][lx] : 0.f;
+            px.z = C > 2 ? blk[2][ly][lx] : 0.f;
+            px.w = C > 3 ? blk[3][ly][lx] : 0.f;
+            float* p = dst + ((long long)vy * tw + vx) * cpitch;
+            *reinterpret_cast<float4*>(p) = px;
+            for (int c = 4; c < cpitch; c += 4) *reinterpret_cast<float4*>(p + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+}
+template <typename T>
+static void tile_gather_views_launch(const void* img, int width, int channels, const int* table_dev, int ntiles, int tile_h, int tile_w,
+                                     const TtaViews& vw, float* out, int channel_pitch, void* workspace, hipStream_t st) {
+    double* ws = (double*)workspace;
+    float* mvsd = (float*)(ws + (size_t)ntiles * Y3_ZS_BLOCKS * 2);  // as y3_tile_gather_zscore_nhwc lays the workspace out
+    const double count = (double)channels * (double)tile_h * (double)tile_w;
+    const dim3 grid(y3_cdiv(tile_w, Y3_TV_BLOCK), y3_cdiv(tile_h, Y3_TV_BLOCK), ntiles);
+    hipLaunchKernelGGL(tile_stats_kernel<T>, dim3(Y3_ZS_BLOCKS, ntiles), dim3(256), 0, st, (const T*)img, width, channels, table_dev, tile_h, tile_w, ws);
+    hipLaunchKernelGGL(tile_stats_finalize_kernel, dim3(y3_cdiv(ntiles, 64)), dim3(64), 0, st, (const double*)ws, ntiles, count, mvsd);
+    hipLaunchKernelGGL(tile_gather_views_kernel<T>, grid, dim3(256), 0, st, (const T*)img, width, channels, table_dev, tile_h, tile_w, (const float*)mvsd,
+                       out, channel_pitch, vw);
+}
+extern "C" int y3_tile_gather_zscore_views_nhwc(const void* img, int dtype, int height, int width, int channels, const int* table_dev, int ntiles,
+                                                int tile_h, int tile_w, const int* views_host, int k, float* out, int channel_pitch,
+                                                void* workspace, y3_stream_t stream) {
+    Y3_CHECK_ARG(img && table_dev && views_host && out && workspace, "tile_gather_zscore_views_nhwc: null pointer");
+    Y3_CHECK_ARG(height > 0 && width > 0 && channels > 0 && ntiles > 0 && tile_h > 0 && tile_w > 0, "tile_gather_zscore_views_nhwc: bad dims");
+    Y3_CHECK_ARG(channels <= 4, "tile_gather_zscore_views_nhwc: %d channels (at most 4)", channels);
+    Y3_CHECK_ARG(channel_pitch >= 4 && (channel_pitch & 3) == 0 && ((uintptr_t)out & 15) == 0,
+                 "tile_gather_zscore_views_nhwc: channel pitch %d (a multiple of 4, at least 4), out 16-byte aligned", channel_pitch);
+    Y3_CHECK_ARG(dtype >= 0 && dtype <= 2, "tile_gather_zscore_views_nhwc: dtype %d (0 = u8, 1 = u16, 2 = f32)", dtype);
+    TtaViews vw;
+    if (int e = y3_tta_check_views(views_host, k, tile_h, tile_w, "tile_gather_zscore_views_nhwc", &vw)) return e;
+    Y3_CHECK_ARG(ntiles <= 65535 && y3_cdiv(tile_h, Y3_TV_BLOCK) <= 65535 && (long long)channels * tile_h * tile_w < 0x7fffffffLL,
+                 "tile_gather_zscore_views_nhwc: grid too large");
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case 0: tile_gather_views_launch<unsigned char>(img, width, channels, table_dev, ntiles, tile_h, tile_w, vw, out, channel_pitch, workspace, st); break;
+        case 1: tile_gather_views_launch<unsigned short>(img, width, channels, table_dev, ntiles, tile_h, tile_w, vw, out, channel_pitch, workspace, st); break;
+        default: tile_gather_views_launch<float>(img, width, channels, table_dev, ntiles, tile_h, tile_w, vw, out, channel_pitch, workspace, st); break;
+    }
+    Y3_CHECK_LAUNCH("tile_gather_zscore_views_nhwc");
+    return Y3_OK;
+}

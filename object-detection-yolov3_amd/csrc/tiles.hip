@@ -20,6 +20,7 @@ struct TileMergeArgs {
     int cap;
     int* pool_count;  // {rows written, rows needed}
     int* ws;          // [0] = rows needed before this batch, [1 + s] = survivors of segment s = tile * K + class
+    const float* voted;  // VOTED kernels only: [n][K][max_keep][6], y3_box_vote's out (box and score of entry e at voted + e * 6)
 };
 
 // np.round(...).astype(np.int32) of one float32: half-to-even, then the conversion NumPy performs on x86-64 (cvttss2si: anything
@@ -30,12 +31,14 @@ __device__ __forceinline__ int tile_round_i32(float v) {
 }
 __device__ __forceinline__ int tile_clamp(int v, int lim) { return v < 0 ? 0 : (v >= lim ? lim - 1 : v); }
 
-// Entry j of segment (tile t, class c): does it survive, and as which pool row
+// Entry j of segment (tile t, class c): does it survive, and as which pool row.  VOTED: the box and the score come from p.voted
+// (tile test-time augmentation with box voting) instead of rows[keep_idx] and keep_score; nothing else differs.
+template <bool VOTED>
 __device__ __forceinline__ bool tile_merge_entry(const TileMergeArgs& p, int t, int c, int j, float ty, float tx, float* out) {
     const long long e = ((long long)t * p.K + c) * p.max_keep + j;
     const int row = p.keep_idx[e];
     if (row < 0 || row >= p.nb) return false;  // never produced by the NMS kernels; nothing outside `rows` is read
-    const float* r = p.rows + ((long long)t * p.nb + row) * p.ld;
+    const float* r = VOTED ? p.voted + e * 6 : p.rows + ((long long)t * p.nb + row) * p.ld;
     const float b0 = r[0], b1 = r[1], b2 = r[2], b3 = r[3];
     const float cx = (b2 + b0) / 2.0f, cy = (b3 + b1) / 2.0f;
     const float cxg = cx + tx, cyg = cy + ty;
@@ -50,7 +53,7 @@ __device__ __forceinline__ bool tile_merge_entry(const TileMergeArgs& p, int t, 
     out[1] = (float)tile_clamp(y0, p.img_h);
     out[2] = (float)tile_clamp(x1, p.img_w);
     out[3] = (float)tile_clamp(y1, p.img_h);
-    out[4] = p.keep_score[e];
+    out[4] = VOTED ? r[4] : p.keep_score[e];
     out[5] = (float)c;
     return true;
 }
@@ -59,7 +62,7 @@ __device__ __forceinline__ bool tile_merge_entry(const TileMergeArgs& p, int t, 
 // the rows needed so far into ws[0] (pool_count is only read by this launch).  WRITE == true: the segment starts at ws[0] + the
 // sum of the counts before it and its survivors go out in keep order (ballot prefix inside a wave, the four waves' counts in
 // LDS); workgroup 0 stores the new totals (pool_count is only written by this launch).  No atomics: the positions are sums.
-template <bool WRITE>
+template <bool WRITE, bool VOTED>
 __global__ __launch_bounds__(256) void tile_merge_kernel(const TileMergeArgs p) {
     __shared__ int wave_cnt[4];
     __shared__ int red[4];
@@ -102,7 +105,7 @@ __global__ __launch_bounds__(256) void tile_merge_kernel(const TileMergeArgs p) 
     for (int j0 = 0; j0 < cnt; j0 += 256) {
         const int j = j0 + tid;
         float o[6];
-        const bool keep = j < cnt && tile_merge_entry(p, t, c, j, ty, tx, o);
+        const bool keep = j < cnt && tile_merge_entry<VOTED>(p, t, c, j, ty, tx, o);
         const unsigned long long bal = __ballot(keep);
         if (WRITE) {
             if (lane == 0) wave_cnt[wave] = __popcll(bal);
@@ -133,28 +136,29 @@ extern "C" size_t y3_tile_merge_workspace_bytes(int n, int num_classes) {
     return ((size_t)n * (size_t)num_classes + 1) * sizeof(int);
 }
 
-extern "C" int y3_tile_merge(const float* rows, int n, int nb, int ld, int num_classes, const int* keep_idx, const int* keep_cnt,
-                             const float* keep_score, int max_keep, const int* table_dev, int tile_h, int tile_w, int img_h, int img_w,
-                             int edge, float margin, float* pool, int cap, int* pool_count, void* workspace, size_t workspace_bytes,
+// rows / keep_score (voted == nullptr) or voted (rows == nullptr): the one difference between the two entry points
+static int tile_merge_launch(const char* what, const float* rows, int n, int nb, int ld, int num_classes, const int* keep_idx, const int* keep_cnt,
+                             const float* keep_score, const float* voted, int max_keep, const int* table_dev, int tile_h, int tile_w, int img_h,
+                             int img_w, int edge, float margin, float* pool, int cap, int* pool_count, void* workspace, size_t workspace_bytes,
                              y3_stream_t stream) {
-    Y3_CHECK_ARG(rows && keep_idx && keep_cnt && keep_score && table_dev && pool && pool_count && workspace, "tile_merge: null pointer");
+    Y3_CHECK_ARG((voted || (rows && keep_score)) && keep_idx && keep_cnt && table_dev && pool && pool_count && workspace, "%s: null pointer", what);
     Y3_CHECK_ARG(n >= 1 && nb >= 1 && ld >= 4 && num_classes >= 1 && max_keep >= 1 && cap >= 1,
-                 "tile_merge: bad sizes (n %d, nb %d, ld %d, classes %d, max_keep %d, cap %d)", n, nb, ld, num_classes, max_keep, cap);
+                 "%s: bad sizes (n %d, nb %d, ld %d, classes %d, max_keep %d, cap %d)", what, n, nb, ld, num_classes, max_keep, cap);
     // every workgroup of the write launch adds up the counts before its segment itself: fine for the few hundred segments of a batch
     // of tiles, quadratic beyond
-    Y3_CHECK_ARG((long long)n * num_classes <= Y3_TILE_MERGE_MAX_SEGMENTS, "tile_merge: n * classes = %lld segments (at most %d per call)",
+    Y3_CHECK_ARG((long long)n * num_classes <= Y3_TILE_MERGE_MAX_SEGMENTS, "%s: n * classes = %lld segments (at most %d per call)", what,
                  (long long)n * num_classes, Y3_TILE_MERGE_MAX_SEGMENTS);
-    Y3_CHECK_ARG((long long)n * num_classes * max_keep < (1LL << 31), "tile_merge: n * classes * max_keep overflows");
+    Y3_CHECK_ARG((long long)n * num_classes * max_keep < (1LL << 31), "%s: n * classes * max_keep overflows", what);
     // rounded, clamped coordinates are stored as fp32: exact below 2^24
-    Y3_CHECK_ARG(img_h >= 1 && img_w >= 1 && img_h <= (1 << 24) && img_w <= (1 << 24), "tile_merge: image %d x %d (sides 1 .. 2^24)", img_h,
-                 img_w);
-    Y3_CHECK_ARG(tile_h >= 1 && tile_w >= 1 && tile_h <= (1 << 24) && tile_w <= (1 << 24), "tile_merge: tile %d x %d", tile_h, tile_w);
-    Y3_CHECK_ARG(edge >= 0 && edge <= (1 << 20), "tile_merge: edge %d", edge);
-    Y3_CHECK_ARG((margin >= 0.f && margin < (float)edge) || (edge == 0 && margin == 0.f), "tile_merge: margin %g outside [0, edge = %d)",
+    Y3_CHECK_ARG(img_h >= 1 && img_w >= 1 && img_h <= (1 << 24) && img_w <= (1 << 24), "%s: image %d x %d (sides 1 .. 2^24)", what, img_h, img_w);
+    Y3_CHECK_ARG(tile_h >= 1 && tile_w >= 1 && tile_h <= (1 << 24) && tile_w <= (1 << 24), "%s: tile %d x %d", what, tile_h, tile_w);
+    Y3_CHECK_ARG(edge >= 0 && edge <= (1 << 20), "%s: edge %d", what, edge);
+    Y3_CHECK_ARG((margin >= 0.f && margin < (float)edge) || (edge == 0 && margin == 0.f), "%s: margin %g outside [0, edge = %d)", what,
                  (double)margin, edge);
-    Y3_CHECK_ARG(workspace_bytes >= y3_tile_merge_workspace_bytes(n, num_classes), "tile_merge: workspace too small");
+    Y3_CHECK_ARG(workspace_bytes >= y3_tile_merge_workspace_bytes(n, num_classes), "%s: workspace too small", what);
     TileMergeArgs p = {};
     p.rows = rows;
+    p.voted = voted;
     p.keep_idx = keep_idx;
     p.keep_cnt = keep_cnt;
     p.keep_score = keep_score;
@@ -177,9 +181,33 @@ extern "C" int y3_tile_merge(const float* rows, int n, int nb, int ld, int num_c
     p.pool_count = pool_count;
     p.ws = (int*)workspace;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(tile_merge_kernel<false>, dim3(n * num_classes), dim3(256), 0, st, p);
-    Y3_CHECK_LAUNCH("tile_merge (count)");
-    hipLaunchKernelGGL(tile_merge_kernel<true>, dim3(n * num_classes), dim3(256), 0, st, p);
-    Y3_CHECK_LAUNCH("tile_merge (write)");
+    const dim3 grid(n * num_classes), block(256);
+    if (voted) {
+        hipLaunchKernelGGL((tile_merge_kernel<false, true>), grid, block, 0, st, p);
+        Y3_CHECK_LAUNCH("tile_merge_voted (count)");
+        hipLaunchKernelGGL((tile_merge_kernel<true, true>), grid, block, 0, st, p);
+        Y3_CHECK_LAUNCH("tile_merge_voted (write)");
+    } else {
+        hipLaunchKernelGGL((tile_merge_kernel<false, false>), grid, block, 0, st, p);
+        Y3_CHECK_LAUNCH("tile_merge (count)");
+        hipLaunchKernelGGL((tile_merge_kernel<true, false>), grid, block, 0, st, p);
+        Y3_CHECK_LAUNCH("tile_merge (write)");
+    }
     return Y3_OK;
+}
+
+extern "C" int y3_tile_merge(const float* rows, int n, int nb, int ld, int num_classes, const int* keep_idx, const int* keep_cnt,
+                             const float* keep_score, int max_keep, const int* table_dev, int tile_h, int tile_w, int img_h, int img_w,
+                             int edge, float margin, float* pool, int cap, int* pool_count, void* workspace, size_t workspace_bytes,
+                             y3_stream_t stream) {
+    return tile_merge_launch("tile_merge", rows, n, nb, ld, num_classes, keep_idx, keep_cnt, keep_score, nullptr, max_keep, table_dev, tile_h,
+                             tile_w, img_h, img_w, edge, margin, pool, cap, pool_count, workspace, workspace_bytes, stream);
+}
+
+extern "C" int y3_tile_merge_voted(const float* voted, int n, int nb, int num_classes, const int* keep_idx, const int* keep_cnt, int max_keep,
+                                   const int* table_dev, int tile_h, int tile_w, int img_h, int img_w, int edge, float margin, float* pool,
+                                   int cap, int* pool_count, void* workspace, size_t workspace_bytes, y3_stream_t stream) {
+    Y3_CHECK_ARG(voted, "tile_merge_voted: null pointer");
+    return tile_merge_launch("tile_merge_voted", nullptr, n, nb, 6, num_classes, keep_idx, keep_cnt, nullptr, voted, max_keep, table_dev, tile_h,
+                             tile_w, img_h, img_w, edge, margin, pool, cap, pool_count, workspace, workspace_bytes, stream);
 }

@@ -6,12 +6,7 @@
 #define Y3_TTA_TILE 32                 // source pixels per tile side
 #define Y3_TTA_PITCH (Y3_TTA_TILE + 1)  // LDS row pitch in dwords: a column read (transposed views) walks banks 33 apart
 
-struct TtaViews {
-    int k;
-    int code[Y3_TTA_MAX_VIEWS];
-};
-
-static int tta_check_views(const int* views, int k, int h, int w, const char* what, TtaViews* out) {
+int y3_tta_check_views(const int* views, int k, int h, int w, const char* what, TtaViews* out) {
     Y3_CHECK_ARG(views && k >= 1 && k <= Y3_TTA_MAX_VIEWS, "%s: 1 .. %d views (got %d)", what, Y3_TTA_MAX_VIEWS, k);
     unsigned seen = 0;
     for (int v = 0; v < k; ++v) {
@@ -80,7 +75,7 @@ extern "C" int y3_tta_views_nhwc(const float* src, int n, int c, int h, int w, c
     Y3_CHECK_ARG(src && dst && dst->ptr, "tta_views: null pointer");
     Y3_CHECK_ARG(n >= 1 && c >= 1 && h >= 1 && w >= 1, "tta_views: bad source (n %d, c %d, %d x %d)", n, c, h, w);
     TtaViews vw;
-    if (int e = tta_check_views(views, k, h, w, "tta_views", &vw)) return e;
+    if (int e = y3_tta_check_views(views, k, h, w, "tta_views", &vw)) return e;
     Y3_CHECK_ARG((long long)n * k <= 65535, "tta_views: n * k = %lld images (at most 65535)", (long long)n * k);
     Y3_CHECK_ARG(dst->n == n * k && dst->h == h && dst->w == w, "tta_views: destination %d x %d x %d, expected %d x %d x %d", dst->n, dst->h,
                  dst->w, n * k, h, w);
@@ -132,7 +127,7 @@ extern "C" int y3_tta_unmap(float* rows, int n_views, int nb, int ld, const int*
     Y3_CHECK_ARG(nb >= 1 && ld >= 4 && img_h >= 1 && img_w >= 1 && img_h <= (1 << 24) && img_w <= (1 << 24),
                  "tta_unmap: bad sizes (nb %d, ld %d, image %d x %d)", nb, ld, img_h, img_w);
     TtaViews vw;
-    if (int e = tta_check_views(views, k, img_h, img_w, "tta_unmap", &vw)) return e;
+    if (int e = y3_tta_check_views(views, k, img_h, img_w, "tta_unmap", &vw)) return e;
     Y3_CHECK_ARG(n_views >= k && n_views % k == 0, "tta_unmap: %d images are no multiple of %d views", n_views, k);
     const long long total = (long long)n_views * nb;
     Y3_CHECK_ARG(total < (1LL << 31), "tta_unmap: %lld rows (fewer than 2^31)", total);

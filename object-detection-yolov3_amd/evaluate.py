@@ -76,15 +76,17 @@ def evaluate(examples, saved_model_filepath, min_box_size, precision='fp32', bat
 def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, precision='fp32', batch_size=None,
                    iou_thresholds=metrics.COCO_IOU_THRESHOLDS, max_detections=None, distributed=False, nms='hard', nms_sigma=0.5,
                    seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5, area_ranges=None, area_names=None, curves=False,
-                   class_score_thresholds=None, confusion=False):
+                   class_score_thresholds=None, confusion=False, tile_tta='none', tta_vote_iou=None, tta_score='keep'):
     """``evaluate`` for the tiled pipeline (inference_tiled.py with --merge-device gpu): every image, of any size, is cut
     into tiles, the tiles' detections are merged on the device (seam_margin) and the pool is matched against the
     whole-image ground truth there (DetectionEvaluator.add_pool with nms=merge_nms).  batch_size: tiles per network launch
     (None: inference_tiled's default).  area_ranges / area_names / curves / class_score_thresholds / confusion:
-    DetectionEvaluator's.  Returns (result dict, number of images, seconds)."""
+    DetectionEvaluator's.  tile_tta / tta_vote_iou / tta_score: test-time augmentation of every tile
+    (inference_tiled.inference_image_tiled).  Returns (result dict, number of images, seconds)."""
     import inference_tiled
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args('gpu', seam_margin, merge_nms, merge_nms_sigma, inference_tiled.EDGE_EFFECT_RANGE)
+    bbox_utils.check_tta_args(tile_tta, tta_vote_iou, tta_score, tile_size)
     yolo = load_model(saved_model_filepath)
     yolo.inference_precision = precision
     if list(tile_size) != list(yolo.img_size[:2]):
@@ -95,7 +97,8 @@ def evaluate_tiled(examples, saved_model_filepath, tile_size, min_box_size, prec
                                     confusion=confusion)
     t0 = time.perf_counter()
     for _, img, gt in examples:
-        pool, count, _ = inference_tiled.tiled_pool_device(model, img, tile_size, min_box_size, batch_size, nms, nms_sigma, seam_margin)
+        pool, count, _ = inference_tiled.tiled_pool_device(model, img, tile_size, min_box_size, batch_size, nms, nms_sigma, seam_margin,
+                                                           tile_tta, tta_vote_iou, tta_score)
         ev.add_pool(pool, count, gt, nms=merge_nms, nms_sigma=merge_nms_sigma)
     if distributed:
         ev = metrics.all_gather_evaluator(ev)
@@ -245,6 +248,13 @@ if __name__ == '__main__':
                         help='--tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
     parser.add_argument('--tta-score', dest='tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
                         help='--tta with --tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
+    parser.add_argument('--tile-tta', dest='tile_tta', choices=list(bbox_utils.TTA_VIEWS), default='none',
+                        help='--tiled: test-time augmentation of every tile: also run its flipped (hflip, flips) and transposed (d4: square '
+                        'tiles) views and pool their detections before --nms; --batch-size then counts network inputs')
+    parser.add_argument('--tile-tta-vote-iou', dest='tile_tta_vote_iou', type=float, default=None, metavar='T',
+                        help='--tile-tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
+    parser.add_argument('--tile-tta-score', dest='tile_tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
+                        help='--tile-tta with --tile-tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
     parser.add_argument('--letterbox', action='store_true',
                         help='images of any size (not with --tta or --tiled): rescale each with its aspect ratio kept and pad it to the model '
                         'input on the device; detections are matched in the image\'s own pixels')
@@ -293,6 +303,14 @@ if __name__ == '__main__':
         parser.error('--tta-vote-iou and --tta-score go with --tta')
     if a.tiled and a.tta != 'none':
         parser.error('--tta does not go with --tiled')
+    if not a.tiled and (a.tile_tta != 'none' or a.tile_tta_vote_iou is not None or a.tile_tta_score != 'keep'):
+        parser.error('--tile-tta, --tile-tta-vote-iou and --tile-tta-score go with --tiled')
+    try:
+        bbox_utils.check_tta_args(a.tile_tta, a.tile_tta_vote_iou, a.tile_tta_score, (a.tile_height, a.tile_width) if a.tiled else None)
+    except ValueError as e:
+        parser.error(str(e))
+    if a.tile_tta == 'none' and a.tile_tta_vote_iou is not None:
+        parser.error('--tile-tta-vote-iou and --tile-tta-score go with --tile-tta')
     if a.letterbox and (a.tiled or a.tta != 'none'):
         parser.error('--letterbox does not go with --tta or --tiled')
     if a.batch_size is None and not a.tiled:
@@ -341,7 +359,8 @@ if __name__ == '__main__':
                                           a.batch_size, thresholds, a.max_detections, distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma,
                                           seam_margin=a.seam_margin, merge_nms=a.merge_nms, merge_nms_sigma=a.merge_nms_sigma,
                                           area_ranges=area_ranges, area_names=area_names, curves=curves, class_score_thresholds=cuts,
-                                          confusion=a.confusion_matrix is not None)
+                                          confusion=a.confusion_matrix is not None, tile_tta=a.tile_tta, tta_vote_iou=a.tile_tta_vote_iou,
+                                          tta_score=a.tile_tta_score)
     else:
         res, count, secs = evaluate(examples, a.saved_model_filepath, a.min_box_size, a.precision, a.batch_size, thresholds, a.max_detections,
                                     distributed=world > 1, nms=a.nms, nms_sigma=a.nms_sigma, tta=a.tta, tta_vote_iou=a.tta_vote_iou,
@@ -357,6 +376,9 @@ if __name__ == '__main__':
             print('Letterbox: images of any size into the model input, boxes in their own pixels')
         if a.tiled:
             print('Tiled: {} x {} tiles, seam margin {:g}, merge NMS {}'.format(a.tile_height, a.tile_width, a.seam_margin, a.merge_nms))
+            if a.tile_tta != 'none':
+                print('Tile TTA: {} ({} views), {}'.format(a.tile_tta, len(bbox_utils.TTA_VIEWS[a.tile_tta]), 'no voting' if a.tile_tta_vote_iou is None
+                                                           else 'vote IoU {:g}, score {}'.format(a.tile_tta_vote_iou, a.tile_tta_score)))
         print_table(res)
         if a.output_file:
             write_csv(res, a.output_file, area_columns=area_ranges is not None)

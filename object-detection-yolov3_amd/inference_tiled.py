@@ -169,6 +169,28 @@ def plan_tile_batches(n_tiles, tile_size, compute_units=256, mem_budget_bytes=No
     return out
 
 
+def tta_tile_batches(input_sizes, k, n_tiles):
+    """Tiles per network call under tile test-time augmentation with k views.  input_sizes: the schedule in NETWORK INPUTS, as it
+    is computed without augmentation for n_tiles * k inputs (batch_size, BATCH_SIZE or plan_tile_batches).  A batch of b inputs
+    becomes max(1, b // k) tiles: all views of a tile go into one call, and a call never holds more inputs than its batch was given,
+    except that a batch smaller than k still takes one whole tile.  Rounding b / k down can leave tiles over when the schedule
+    ends; they are dealt out by walking the schedule again from its start.  k = 1 returns the schedule itself."""
+    k, left, out = int(k), int(n_tiles), []
+    input_sizes = [int(b) for b in input_sizes]
+    if k < 1 or (left > 0 and not any(b >= 1 for b in input_sizes)):
+        raise ValueError('tta_tile_batches: {} views, schedule {}'.format(k, input_sizes))
+    i = 0
+    while left > 0:
+        b = input_sizes[i % len(input_sizes)]
+        i += 1
+        if b < 1:
+            continue
+        t = min(max(1, b // k), left)
+        out.append(t)
+        left -= t
+    return out
+
+
 def upload_bands(table, sizes, height):
     """Rows of the image that must be on the device before batch i of the tile table can be gathered: the cumulative maximum of
     y0 + ny over the tiles of batches 0..i (tile_table rows are {y0, ny, pre_y, x0, nx, pre_x}: a tile reads only its crop, the
@@ -185,7 +207,7 @@ def upload_bands(table, sizes, height):
 
 
 def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5, merge_device='cpu',
-                          seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5):
+                          seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5, tile_tta='none', tta_vote_iou=None, tta_score='keep'):
     """inference_tiled.py:185-310.  ``yolo_model(batch, training=False)`` maps CUDA float32 [B,C,h,w] (z-scored) to
     rows [B, Nb, 5+K] (CUDA tensor or ndarray).  batch_size None: BATCH_SIZE tiles per launch on the fp32 path,
     plan_tile_batches() on the bf16 path.  nms / nms_sigma: the per-tile NMS method (bbox_utils.NMS_METHODS) and its
@@ -199,29 +221,49 @@ def inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size=N
     instead of by chance.  merge_nms ('none' or one of bbox_utils.NMS_METHODS, needs 'gpu'; merge_nms_sigma: Gaussian
     parameter): class-wise NMS over the whole image's detections (IoU threshold 0.3; the soft methods drop below the per-tile
     score threshold 0.1 and return decayed scores), which removes those duplicates.  With a merge NMS the rows come back
-    class-major, in keep order (score descending) inside a class, not in tile order."""
+    class-major, in keep order (score descending) inside a class, not in tile order.
+
+    tile_tta (extension; one of bbox_utils.TTA_VIEWS, 'none' by default): every tile also goes through the network
+    flipped ('hflip', 'flips') and transposed ('d4': square tiles), the views' detections are mapped back to the tile and pooled, and
+    the pooled rows of a tile go through ``nms`` as one tile's rows.  tta_vote_iou (0 < T <= 1): every kept box is then replaced by
+    the score-weighted mean of the pooled candidates with IoU >= T; tta_score 'consensus' (needs voting): its score by the mean
+    over the views of the best member score.  The merge -- on either device, with seam_margin and merge_nms -- works on the result
+    as it does on a plain tile's.  batch_size then counts network inputs: a call takes max(1, batch_size // views) tiles
+    (tta_tile_batches).  Needs a model with the fused tile path (``run_tiles``)."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args(merge_device, seam_margin, merge_nms, merge_nms_sigma, EDGE_EFFECT_RANGE)
+    tta = (tile_tta, tta_vote_iou, tta_score)
+    bbox_utils.check_tta_args(tile_tta, tta_vote_iou, tta_score, tile_size)
     if merge_device == 'gpu':
-        pool, count, classes = tiled_pool_device(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, seam_margin)
+        pool, count, classes = tiled_pool_device(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, seam_margin, *tta)
         if merge_nms != 'none':
             pool = bbox_utils.gather_kept(pool, *bbox_utils.nms_labelled_device(pool, classes, merge_nms, sigma=merge_nms_sigma))
         predictions = pool.cpu().numpy().astype(np.float64)
         print('Found: {} rois'.format(predictions.shape[0]))
         return predictions
-    return _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, None)
+    return _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, None, *tta)
 
 
-def tiled_pool_device(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5, seam_margin=0.0):
+def tiled_pool_device(yolo_model, img, tile_size, min_roi_size, batch_size=None, nms='hard', nms_sigma=0.5, seam_margin=0.0, tile_tta='none',
+                      tta_vote_iou=None, tta_score='keep'):
     """The tiled pipeline with the merge on the device: -> (pool CUDA float32 [M, 6] = x0, y0, x1, y1, score, class in the host
-    merge's order, M, number of classes).  One host read (the count) per image; nothing else leaves the device."""
+    merge's order, M, number of classes).  One host read (the count) per image; nothing else leaves the device.  tile_tta /
+    tta_vote_iou / tta_score: inference_image_tiled's; the voted boxes and scores reach the pool through y3_tile_merge_voted."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args('gpu', seam_margin, 'none', 0.5, EDGE_EFFECT_RANGE)
-    return _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, float(seam_margin))
+    bbox_utils.check_tta_args(tile_tta, tta_vote_iou, tta_score, tile_size)
+    return _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, float(seam_margin), tile_tta, tta_vote_iou, tta_score)
 
 
-def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, device_margin):
+def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, device_margin, tile_tta='none', tta_vote_iou=None,
+               tta_score='keep'):
     """device_margin None: the host merge -> predictions; a float: the device merge with that seam margin -> tiled_pool_device's tuple."""
+    views = bbox_utils.check_tta_args(tile_tta, tta_vote_iou, tta_score, tile_size)
+    views = None if tile_tta == 'none' else views          # None: every call below is the one made without augmentation
+    fused = hasattr(yolo_model, 'run_tiles') and not getattr(yolo_model, '_fm', False)
+    if views is not None and not fused:
+        raise ValueError('tile_tta {!r} needs a model with the fused tile path (run_tiles); this one has none'.format(tile_tta))
+    n_views = 1 if views is None else len(views)
     img_size = img.shape
     # the image goes to the GPU once, in its own dtype; cropping, reflect padding, astype(float32) and HWC -> CHW of
     # convert_image_to_tiles (inference_tiled.py:29-100,199-203) happen there, one launch per batch of tiles
@@ -253,7 +295,7 @@ def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_si
         bf16 = getattr(getattr(yolo_model, '_y', None), 'inference_precision', 'fp32') == 'bf16'
         if bf16:
             dev = torch.cuda.current_device()
-            sizes = plan_tile_batches(len(xs), tile_size, compute_units=torch.cuda.get_device_properties(dev).multi_processor_count,
+            sizes = plan_tile_batches(len(xs) * n_views, tile_size, compute_units=torch.cuda.get_device_properties(dev).multi_processor_count,
                                       mem_budget_bytes=torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev))
         else:
             sizes = None
@@ -261,7 +303,9 @@ def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_si
     else:
         sizes = None
     if sizes is None:
-        sizes = [min(batch_size, len(xs) - b0) for b0 in range(0, len(xs), batch_size)]
+        sizes = [min(batch_size, len(xs) * n_views - b0) for b0 in range(0, len(xs) * n_views, batch_size)]
+    if views is not None:          # the schedule above counts network inputs: all views of a tile go into one call
+        sizes = tta_tile_batches(sizes, n_views, len(xs))
     starts = [sum(sizes[:i]) for i in range(len(sizes))]
     # Batches alternate between two streams with their own activation buffers (model slots).  Everything is queued first;
     # detections are copied back and merged at the end.  The image goes up in BANDS: a batch only needs the rows its tiles
@@ -280,7 +324,6 @@ def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_si
     queued = []
     rows_up = 0
     bands = upload_bands(table, sizes, img_size[0])
-    fused = hasattr(yolo_model, 'run_tiles') and not getattr(yolo_model, '_fm', False)
     for bi, (b0, nb) in enumerate(zip(starts, sizes)):
         need = bands[bi]
         if need > rows_up:
@@ -290,19 +333,26 @@ def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_si
         with torch.cuda.stream(streams[bi % slots]):
             if fused:
                 # tiles -> z-scored network input in two passes over the image, then the network (yolo3.model.YoloV3.predict_tiles)
-                rows = yolo_model.run_tiles(img_dev, code, img_size, table_dev.data_ptr() + 24 * b0, nb, tile_size=tile_size, slot=bi % slots)
+                kw = {} if views is None else {'views': views}      # [nb, views * Nb, 5+K]: a tile's views pooled (predict_tiles_tta)
+                rows = yolo_model.run_tiles(img_dev, code, img_size, table_dev.data_ptr() + 24 * b0, nb, tile_size=tile_size, slot=bi % slots, **kw)
             else:
                 x = tiles_to_device(img_dev, code, img_size, table_dev, b0, nb, tile_size)
                 x = imagereader.zscore_normalize_device(x)               # per TILE statistics (inference_tiled.py:205, Q12)
                 rows = yolo_model(x, training=False, slot=bi % slots) if slots > 1 else yolo_model(x, training=False)
             rows = torch.as_tensor(rows, dtype=torch.float32).cuda().clone()   # the slot's output buffer is reused two batches later
-            if pool is None:
+            if pool is None and views is None:
                 queued.append((bbox_utils.detect_async(rows, min_roi_size, method=nms, sigma=nms_sigma), b0))
+            elif pool is None:
+                queued.append((bbox_utils.detect_tta_async(rows, n_views, min_roi_size, method=nms, sigma=nms_sigma, vote_iou=tta_vote_iou,
+                                                           score=tta_score), b0))
             else:
                 keep = bbox_utils.nms_device(rows, min_roi_size, private_outputs=True, method=nms, sigma=nms_sigma)
+                voted = None
+                if views is not None and tta_vote_iou is not None:
+                    voted = bbox_utils.vote_device(rows, *keep, n_views, tta_vote_iou, min_roi_size, score=tta_score, private_output=True)
                 done = torch.cuda.Event()
                 done.record(torch.cuda.current_stream())
-                bbox_utils.merge_tiles_device(pool, rows, *keep, table_dev[b0:b0 + nb], done)
+                bbox_utils.merge_tiles_device(pool, rows, *keep, table_dev[b0:b0 + nb], done, voted=voted)
                 classes = rows.shape[2] - 5
     for item in queued:
         merge(*item)
@@ -317,12 +367,15 @@ def _run_tiles(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_si
 
 def inference_image_folder(image_folder, image_format, saved_model_filepath, output_folder, tile_size, min_roi_size, precision='fp32',
                            batch_size=None, nms='hard', nms_sigma=0.5, merge_device='cpu', seam_margin=0.0, merge_nms='none', merge_nms_sigma=0.5,
-                           score_thresholds=None, score_thresholds_range='all', score_thresholds_iou=0.5):
+                           score_thresholds=None, score_thresholds_range='all', score_thresholds_iou=0.5, tile_tta='none', tta_vote_iou=None,
+                           tta_score='keep'):
     """score_thresholds: a number, or the csv evaluate.py --operating-points wrote (metrics.load_score_thresholds): of the merged
     detections of an image only those with score >= the threshold of their class are written (bbox_utils.filter_class_scores, on
-    either merge device; after a soft merge NMS the scores are the decayed ones)."""
+    either merge device; after a soft merge NMS the scores are the decayed ones).  tile_tta / tta_vote_iou / tta_score:
+    inference_image_tiled's."""
     bbox_utils.check_nms_args(nms, nms_sigma)
     bbox_utils.check_merge_args(merge_device, seam_margin, merge_nms, merge_nms_sigma, EDGE_EFFECT_RANGE)
+    bbox_utils.check_tta_args(tile_tta, tta_vote_iou, tta_score, tile_size)
     if not os.path.exists(saved_model_filepath):
         raise RuntimeError('Missing saved_model_filepath File')
     if image_format.startswith('.'):
@@ -350,7 +403,7 @@ def inference_image_folder(image_folder, image_format, saved_model_filepath, out
         if len(img.shape) == 2:
             img = np.expand_dims(img, -1)
         predictions = inference_image_tiled(yolo_model, img, tile_size, min_roi_size, batch_size, nms, nms_sigma, merge_device, seam_margin,
-                                            merge_nms, merge_nms_sigma)
+                                            merge_nms, merge_nms_sigma, tile_tta, tta_vote_iou, tta_score)
         if cuts is not None:
             predictions = bbox_utils.filter_class_scores(predictions, cuts)
             print('Kept: {} rois at the class score thresholds'.format(predictions.shape[0]))
@@ -388,7 +441,21 @@ if __name__ == '__main__':
                         help='--score-thresholds FILE: the area range whose rows to take (default all)')
     parser.add_argument('--score-thresholds-iou', dest='score_thresholds_iou', type=float, default=0.5, metavar='T',
                         help='--score-thresholds FILE: the IoU threshold whose rows to take (default 0.5)')
+    parser.add_argument('--tile-tta', dest='tile_tta', choices=list(bbox_utils.TTA_VIEWS), default='none',
+                        help='test-time augmentation of every tile (extension): also run its flipped (hflip, flips) and transposed (d4: '
+                        'square tiles) views and pool their detections before --nms; none (default) runs each tile once.  --batch-size '
+                        'then counts network inputs: a launch takes batch-size // views tiles')
+    parser.add_argument('--tile-tta-vote-iou', dest='tile_tta_vote_iou', type=float, default=None, metavar='T',
+                        help='--tile-tta: replace every kept box by the score-weighted mean of the pooled candidates with IoU >= T (0 < T <= 1)')
+    parser.add_argument('--tile-tta-score', dest='tile_tta_score', choices=list(bbox_utils.TTA_SCORES), default='keep',
+                        help='--tile-tta with --tile-tta-vote-iou: keep the NMS score (default) or the mean over the views of the best member score')
     a = parser.parse_args()
+    try:
+        bbox_utils.check_tta_args(a.tile_tta, a.tile_tta_vote_iou, a.tile_tta_score, (a.tile_height, a.tile_width))
+    except ValueError as e:
+        parser.error(str(e))
+    if a.tile_tta == 'none' and a.tile_tta_vote_iou is not None:
+        parser.error('--tile-tta-vote-iou and --tile-tta-score go with --tile-tta')
     if a.score_thresholds is None and (a.score_thresholds_range != 'all' or a.score_thresholds_iou != 0.5):
         parser.error('--score-thresholds-range and --score-thresholds-iou go with --score-thresholds')
     if a.nms == 'soft-gaussian' and not a.nms_sigma > 0:
@@ -399,4 +466,4 @@ if __name__ == '__main__':
         parser.error(str(e))
     inference_image_folder(a.image_folder, a.image_format, a.saved_model_filepath, a.output_folder, [a.tile_height, a.tile_width], a.min_box_size, a.precision, a.batch_size,
                            a.nms, a.nms_sigma, a.merge_device, a.seam_margin, a.merge_nms, a.merge_nms_sigma, a.score_thresholds,
-                           a.score_thresholds_range, a.score_thresholds_iou)
+                           a.score_thresholds_range, a.score_thresholds_iou, a.tile_tta, a.tile_tta_vote_iou, a.tile_tta_score)

@@ -104,6 +104,7 @@ SIGNATURES = {
     'y3_conv2d_first_bf16': (i32, [TP, fp, fp, TP, u32, f32, fp, fp, vp]),
     'y3_tile_gather': (i32, [vp, i32, i32, i32, i32, ip, i32, i32, i32, fp, vp]),
     'y3_tile_gather_zscore_nhwc': (i32, [vp, i32, i32, i32, i32, ip, i32, i32, i32, fp, i32, vp, vp]),
+    'y3_tile_gather_zscore_views_nhwc': (i32, [vp, i32, i32, i32, i32, ip, i32, i32, i32, C.POINTER(C.c_int), i32, fp, i32, vp, vp]),     # views: HOST array
     'y3_upsample_sum2x_fwd_bf16': (i32, [TP, TP, vp]),
     'y3_add_inplace': (i32, [TP, TP, vp]),
     'y3_fill': (i32, [fp, sz, f32, vp]),
@@ -136,6 +137,7 @@ SIGNATURES = {
     'y3_nms_labelled': (i32, [fp, i32, i32, i32, f32, f32, f32, ip, ip, fp, i32, vp, sz, vp]),
     'y3_tile_merge': (i32, [fp, i32, i32, i32, i32, ip, ip, fp, i32, ip, i32, i32, i32, i32, i32, f32, fp, i32, ip, vp, sz, vp]),
     'y3_tile_merge_workspace_bytes': (sz, [i32, i32]),
+    'y3_tile_merge_voted': (i32, [fp, i32, i32, i32, ip, ip, i32, ip, i32, i32, i32, i32, i32, f32, fp, i32, ip, vp, sz, vp]),
     'y3_tta_views_nhwc': (i32, [fp, i32, i32, i32, i32, C.POINTER(C.c_int), i32, TP, vp]),     # views: HOST array
     'y3_tta_unmap': (i32, [fp, i32, i32, i32, C.POINTER(C.c_int), i32, i32, i32, vp]),
     'y3_box_vote': (i32, [fp, i32, i32, i32, ip, ip, fp, i32, f32, f32, f32, f32, f32, i32, i32, i32, fp, vp, sz, vp]),

@@ -217,7 +217,7 @@ class TilePool:
         self.img_size = (int(img_size[0]), int(img_size[1]))
         self.margin, self.edge = float(margin), int(edge)
         self.stream = torch.cuda.current_stream(self.device) if stream is None else stream
-        self.batches = []             # (rows, keep_idx, keep_cnt, keep_score, table slice): kept for the retry and alive until finish
+        self.batches = []             # (rows, keep_idx, keep_cnt, keep_score, table slice, voted or None): kept for the retry and alive until finish
         self.ws = None
         self._alloc(max(1, int(TILE_POOL_ROWS if cap is None else cap)))
 
@@ -232,13 +232,19 @@ class TilePool:
             self.count.record_stream(self.stream)
 
     def _launch(self, batch):
-        rows, keep_idx, keep_cnt, keep_score, table = batch
+        rows, keep_idx, keep_cnt, keep_score, table, voted = batch
         n, nb, ld = rows.shape
         k, max_keep = keep_idx.shape[1], keep_idx.shape[2]
         ws_bytes = int(lib.y3_tile_merge_workspace_bytes(n, k))
         if self.ws is None or self.ws.numel() * 4 < ws_bytes:
             with torch.cuda.stream(self.stream):          # a larger one replaces it behind the launches that use the old one
                 self.ws = torch.empty(ws_bytes // 4 + 1, dtype=torch.int32, device=self.device)
+        if voted is not None:         # the boxes and scores of box voting instead of rows[keep_idx] and keep_score (tile TTA)
+            check(lib.y3_tile_merge_voted(voted.data_ptr(), n, nb, k, keep_idx.data_ptr(), keep_cnt.data_ptr(), max_keep, table.data_ptr(),
+                                          self.tile_size[0], self.tile_size[1], self.img_size[0], self.img_size[1], self.edge, self.margin,
+                                          self.rows.data_ptr(), self.cap, self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 4,
+                                          self.stream.cuda_stream), 'y3_tile_merge_voted')
+            return
         check(lib.y3_tile_merge(rows.data_ptr(), n, nb, ld, k, keep_idx.data_ptr(), keep_cnt.data_ptr(), keep_score.data_ptr(), max_keep,
                                 table.data_ptr(), self.tile_size[0], self.tile_size[1], self.img_size[0], self.img_size[1], self.edge,
                                 self.margin, self.rows.data_ptr(), self.cap, self.count.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 4,
@@ -256,7 +262,7 @@ class TilePool:
             # on the current stream: the batch tensors and the workspace were allocated on the slot streams and the merge stream, so
             # they are recorded on this one before its launches use them (they may be freed while those are still pending)
             self.stream = cur
-            for t in [t for batch in self.batches for t in batch] + ([self.ws] if self.ws is not None else []):
+            for t in [t for batch in self.batches for t in batch if t is not None] + ([self.ws] if self.ws is not None else []):
                 t.record_stream(cur)
             self._alloc(need)
             for batch in self.batches:
@@ -265,18 +271,23 @@ class TilePool:
         return self.rows[:need], need
 
 
-def merge_tiles_device(pool, rows, keep_idx, keep_cnt, keep_score, table_dev, done=None):
+def merge_tiles_device(pool, rows, keep_idx, keep_cnt, keep_score, table_dev, done=None, voted=None):
     """Append one batch of tiles to ``pool`` (y3_tile_merge): rows CUDA float32 [n, Nb, 5+K] and nms_device(...,
     private_outputs=True)'s outputs for them, table_dev int32 [n, 6] = this batch's rows of the device tile table.
-    done: an event recorded behind the batch's NMS; the pool's stream waits for it.  Nothing is read back."""
+    done: an event recorded behind the batch's NMS; the pool's stream waits for it.  Nothing is read back.
+    voted: vote_device(..., private_output=True)'s [n, K, max_keep, 6] for the batch; the kept entries then take their boxes and
+    scores from it (y3_tile_merge_voted), and the pool retains it for its retry."""
     assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 3 and rows.is_contiguous()
     assert table_dev.dtype == torch.int32 and table_dev.is_contiguous() and table_dev.shape == (rows.shape[0], 6)
     assert keep_idx.shape[0] == rows.shape[0] and keep_cnt.shape == keep_idx.shape[:2] and keep_score.shape == keep_idx.shape
     if done is not None:
         pool.stream.wait_event(done)
-    batch = (rows, keep_idx, keep_cnt, keep_score, table_dev)
+    if voted is not None:
+        assert voted.is_cuda and voted.dtype == torch.float32 and voted.is_contiguous() and tuple(voted.shape) == tuple(keep_idx.shape) + (6,)
+    batch = (rows, keep_idx, keep_cnt, keep_score, table_dev, voted)
     for t in batch:
-        t.record_stream(pool.stream)
+        if t is not None:
+            t.record_stream(pool.stream)
     pool.batches.append(batch)
     pool._launch(batch)
 
@@ -418,6 +429,13 @@ def detect_tta_pools(rows, views, min_box_size, iou_threshold=0.3, score_thresho
         if score != 'keep':
             raise ValueError('a consensus score needs box voting (give a vote_iou)')
         out = None
+    return _tta_pools(rows, (keep_idx, keep_cnt, keep_score), out, clip_wh, with_rows)
+
+
+def _tta_pools(rows, keep, out, clip_wh, with_rows):
+    """detect_tta_pools behind its launches: the keep lists (and the voted array, or None) of rows -> the per-image pools."""
+    keep_idx, keep_cnt, keep_score = keep
+    n, k = keep_cnt.shape
     cnt = keep_cnt.cpu().numpy().astype(np.int64)                       # the one host read: everything below is sized from it
     per_image = cnt.sum(1)
     max_keep = keep_idx.shape[2]
@@ -443,13 +461,44 @@ def detect_tta_pools(rows, views, min_box_size, iou_threshold=0.3, score_thresho
     return pools
 
 
+def detect_tta_async(rows, views, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5, vote_iou=None,
+                     score='keep'):
+    """detect_async for the pooled views: enqueues the NMS (and, with vote_iou, the box voting) of detect_tta_pools on the current
+    stream and returns a ``collect()`` callable that gives what detect_tta returns for the same rows; nothing synchronises until
+    it is called.  ``rows`` must stay untouched until then.  Every output is private to the call, so any number may be pending."""
+    rows = rows.contiguous()
+    keep = nms_device(rows, min_box_size, iou_threshold, score_threshold, clip_wh, private_outputs=True, method=method, sigma=sigma)
+    if vote_iou is not None:
+        out = vote_device(rows, *keep, views, vote_iou, min_box_size, score_threshold, clip_wh, score, private_output=True)
+    else:
+        if score != 'keep':
+            raise ValueError('a consensus score needs box voting (give a vote_iou)')
+        out = None
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(rows.device))
+
+    def collect():
+        cs = _copy_streams.get(str(rows.device))        # behind the event, not behind what the caller has queued since: detect_async
+        if cs is None:
+            cs = _copy_streams[str(rows.device)] = torch.cuda.Stream(device=rows.device)
+        cs.wait_event(done)
+        with torch.cuda.stream(cs):
+            return _tta_host(_tta_pools(rows, keep, out, clip_wh, True))
+    return collect
+
+
 def detect_tta(rows, views, min_box_size, iou_threshold=0.3, score_threshold=0.1, clip_wh=None, method='hard', sigma=0.5, vote_iou=None,
                score='keep'):
     """``detect`` for the pooled views of YoloV3.predict_tta (see detect_tta_pools): per image (boxes [M,4], score [M],
     label [M] int32, keep [M] row indices into the image's k * Nb rows) as NumPy arrays, or (None,)*4."""
+    return _tta_host(detect_tta_pools(rows, views, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma, vote_iou, score,
+                                      with_rows=True))
+
+
+def _tta_host(pools):
+    """Pools with their kept rows -> detect's per-image tuples."""
     out = []
-    for pool, m, kept in detect_tta_pools(rows, views, min_box_size, iou_threshold, score_threshold, clip_wh, method, sigma, vote_iou, score,
-                                          with_rows=True):
+    for pool, m, kept in pools:
         if m == 0:
             out.append((None, None, None, None))
             continue

@@ -1019,8 +1019,11 @@ class _CallableModel:
             return self._y.feature_maps(batch, training=training)
         return self._y.predict(batch, slot=slot)
 
-    def run_tiles(self, img_dev, dtype_code, img_shape, table_ptr, count, tile_size=None, slot=0):
-        """inference_tiled's fast path: gather + z-score + forward + decode of `count` tiles (YoloV3.predict_tiles)."""
+    def run_tiles(self, img_dev, dtype_code, img_shape, table_ptr, count, tile_size=None, slot=0, views=None):
+        """inference_tiled's fast path: gather + z-score + forward + decode of `count` tiles (YoloV3.predict_tiles).  views: the
+        test-time augmentation view codes; the rows of all views of a tile then come back pooled (YoloV3.predict_tiles_tta)."""
+        if views is not None:
+            return self._y.predict_tiles_tta(img_dev, dtype_code, img_shape, table_ptr, count, views, tile_size=tile_size, slot=slot)
         return self._y.predict_tiles(img_dev, dtype_code, img_shape, table_ptr, count, tile_size=tile_size, slot=slot)
 
     @property
@@ -1662,6 +1665,37 @@ class YoloV3:
         else:
             plan.run_inference(st, skip_input=True)
         return plan.boxes
+
+    def predict_tiles_tta(self, img_dev, dtype_code, img_shape, table_ptr, count, views, tile_size=None, precision=None, slot=0):
+        """predict_tiles under test-time augmentation: the views (distinct 3-bit codes, bbox_utils.TTA_VIEWS) of tiles
+        `table_ptr[0:count]` are gathered, z-scored per tile and written straight into the NHWC input of a plan of count * k network
+        inputs, tile-major and view-minor (y3_tile_gather_zscore_views_nhwc; the same bits as tiles_to_device ->
+        zscore_normalize_device -> predict_tta's views), go through the network as one batch, and every view's decode rows are mapped
+        back to the tile's frame in place (y3_tta_unmap).  Returns [count, k * Nb, 5+K]: view v of a tile in rows v * Nb ..
+        (v + 1) * Nb - 1, as predict_tta returns them for images."""
+        h, w, c = (int(v) for v in img_shape)
+        if c != self.img_size[2] or (tile_size is not None and [int(tile_size[0]), int(tile_size[1])] != self.img_size[:2]):
+            raise ValueError('tiles %s x %d channels do not match the model input (H,W,C)=%s (Q18: fixed at construction)' % (tile_size, c, self.img_size))
+        views = [int(v) for v in views]
+        count, k = int(count), len(views)
+        if count < 1 or k < 1:
+            raise ValueError('predict_tiles_tta: {} tiles x {} views (at least one of each)'.format(count, k))
+        plan = self._plan(count * k, False, (precision or self.inference_precision) == 'bf16', slot)
+        st = self._stream()
+        if plan.zs_ws is None:      # sized for the plan's count * k inputs, so predict_tiles can share it
+            plan.zs_ws = torch.empty(int(lib.y3_zscore_workspace_bytes(count * k)) // 8 + 1, dtype=torch.float64, device=self.device)
+        codes = int_array(views)
+        th, tw = self.img_size[0], self.img_size[1]
+        check(lib.y3_tile_gather_zscore_views_nhwc(img_dev.data_ptr(), int(dtype_code), h, w, c, table_ptr, count, th, tw, codes, k,
+                                                   plan.x0.buf.data_ptr(), plan.x0.ld, plan.zs_ws.data_ptr(), st), 'y3_tile_gather_zscore_views_nhwc')
+        if self.use_graph:
+            if plan.infer_graph_tiles is None:      # forward without the input transpose: the gather above wrote x0
+                plan.infer_graph_tiles = self._graph_of(functools.partial(plan.run_inference, skip_input=True))
+            plan.infer_graph_tiles.replay()
+        else:
+            plan.run_inference(st, skip_input=True)
+        check(lib.y3_tta_unmap(plan.boxes.data_ptr(), count * k, plan.nb, plan.boxes.shape[2], codes, k, th, tw, st), 'y3_tta_unmap')
+        return plan.boxes.view(count, k * plan.nb, plan.boxes.shape[2])
 
     TTA_MAX_BATCH = 16     # images x views per network call: the conv routes are tested for batches 1..16
 
