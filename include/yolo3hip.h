@@ -1027,6 +1027,37 @@ int y3_letterbox_unmap(float* rows, int n, int nb, int ld, const y3_letterbox_re
 int y3_format_labels(const int* boxes, const int* counts, int n, int max_boxes, const float* anchors_host, int num_anchors,
                      int num_classes, int img_h, int img_w, float* out1, float* out2, float* out3, y3_stream_t stream);
 
+/* ---- opt-in per-scale anchor assignment: each anchor owned by one scale (not in the reference) --------------------
+ * The reference puts every anchor on every scale (Q5).  YOLOv3 partitions them: anchor_scale_host, a HOST array [A], gives each
+ * anchor's scale, 0 = stride 32 (coarse), 1 = stride 16, 2 = stride 8 (fine).  A_s is the number of anchors of scale s, an anchor's
+ * SLOT its rank among the anchors of its scale in index order.  Every scale owns at least one anchor and 3 <= A <= 16; an entry
+ * outside 0..2, an empty scale, or any argument its all-scales counterpart refuses: Y3_EINVAL + message, nothing launched.
+ *
+ * y3_format_labels_scales: y3_format_labels with out_s = float32 [n][G_s][G_s][A_s][5+K].  The arithmetic is y3_format_labels',
+ * word for word (centre, IoU against ALL A anchors with the first maximum winning, the float32 cell index, no contraction); the
+ * row is written only on the scale that owns the best anchor, at that anchor's slot.  So out_s equals y3_format_labels' tensor of
+ * scale s with its anchor axis gathered at the anchors scale s owns, bit for bit, collisions included (coordinates of the last
+ * box in input order, class bits of all).  Every output word is written by this one launch, zeros included; no atomics, each
+ * word is owned by one workgroup (a run of whole cells, whose length follows A_s (5+K) and so differs per scale).
+ *
+ * y3_decode_fwd_scales: y3_decode_fwd for three feature maps with fm[s].c == A_s (5+K) (ld >= c).  out: [N][Nb][5+K], rows run
+ * scales coarse -> fine, then row, column, slot; Nb = sum of G_s^2 A_s.  Each row uses its own anchor's (w, h); the expression
+ * order and the stride quirk Q6 are y3_decode_fwd's, so the rows equal y3_decode_fwd(nscales = 1) of each scale with that scale's
+ * anchors in slot order.
+ *
+ * y3_truth_boxes_scales: the per-image box lists of y3_truth_boxes gathered from the three label tensors gt_s
+ * [n][cells_anchors_s][d], coarse -> fine, each in index order (here a box lives on one scale only, so the fine tensor alone does
+ * not hold the list).  One launch, one workgroup per image, the ordered append of y3_truth_boxes with its running base carried
+ * across the tensors.  counts[i] is the TRUE total, also above cap; only the first cap boxes are stored. */
+int y3_format_labels_scales(const int* boxes, const int* counts, int n, int max_boxes, const float* anchors_host,
+                            const int* anchor_scale_host, int num_anchors, int num_classes, int img_h, int img_w,
+                            float* out1, float* out2, float* out3, y3_stream_t stream);
+int y3_decode_fwd_scales(const y3_tensor* fm, const float* anchors_host, const int* anchor_scale_host, int num_anchors,
+                         int num_classes, int img_h, int img_w, float* out, y3_stream_t stream);
+int y3_truth_boxes_scales(const float* gt1, const float* gt2, const float* gt3, int n, long long cells_anchors1,
+                          long long cells_anchors2, long long cells_anchors3, int d, float* boxes, int* counts, int cap,
+                          y3_stream_t stream);
+
 /* ---- anchor fitting: P candidate anchor sets scored against n box sizes (opt-in, not in the reference: yolo3/anchors.py,
  * find_anchor_sizes.py --metric iou, train.py --auto_anchors) -------------------------------------------------------
  * wh_dev: DEVICE int32 [n][2] = (w, h) in pixels, 8-byte aligned (16-byte loads are used at either alignment); cand_dev: DEVICE

@@ -76,7 +76,8 @@ def find_anchors_iou(wh, k, seed=0, evolve=1000, population=64, thr=0.5, scale=1
     for line in anchors.format_fit(fit):
         print(line)
     if output:
-        anchors.save_anchors(output, fit)
+        # with at least one anchor per scale the file also records which scale owns each (train.py --anchor_assignment scale)
+        anchors.save_anchors(output, fit, anchors.default_anchor_scales(fit['anchors']) if len(fit['anchors']) >= 3 else None)
         print('anchors written to {}'.format(output))
     return fit
 

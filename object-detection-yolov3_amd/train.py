@@ -61,6 +61,10 @@ reference's pair of anchors; at most one of the three.  --auto_a
 database before the readers start (yolo3.anchors.fit_anchors; --auto_anchors_evolve, --auto_anchors_seed), on the host or, with
 --auto_anchors_device gpu, in a child process that runs find_anchor_sizes.py --device gpu (this process must not touch the GPU before
 its readers are forked); every rank computes the same anchors, rank 0 writes <out>/anchors.json.  The weight files carry the anchors.
+--anchor_assignment scale, or --anchor_masks "6,7,8 3,4,5 0,1,2" (the anchors of stride 32, 16, 8; implies scale), gives each anchor
+to ONE scale as YOLOv3 / Darknet do: a box is a positive only on the scale that owns its best anchor and head s has
+A_s (5 + K) channels; needs at least 3 anchors; rank 0 writes <out>/anchor_scales.json, the weight files carry the table.  The default
+(all) is the reference's network, every anchor on every scale.
 Changed: MirroredStrategy -> one process per GPU + RCCL (yolo3.parallel); TF checkpoint / SavedModel -> .npz weight
 files (<out>/checkpoint/ckpt.npz, <out>/saved_model/yolov3.npz); TensorBoard event files -> <out>/scalars-<ts>/{train,test}.csv.
 """
@@ -329,6 +333,45 @@ def resolve_anchors(anchors, anchors_file, auto_anchors, train_database_filepath
     return [tuple(a) for a in fit['anchors']]
 
 
+def check_anchor_assignment(anchor_assignment, anchor_masks):
+    """--anchor_assignment {all, scale} and --anchor_masks "6,7,8 3,4,5 0,1,2"  -> 'all' or 'scale'.  Masks imply
+    'scale' and contradict an explicit 'all'; the masks themselves are checked once the anchors are known (resolve_anchor_scale)."""
+    if anchor_assignment not in (None, 'all', 'scale'):
+        raise ValueError("--anchor_assignment must be 'all' or 'scale', got {!r}".format(anchor_assignment))
+    if anchor_masks is not None:
+        if anchor_assignment == 'all':
+            raise ValueError('--anchor_masks gives every anchor to one scale: it contradicts --anchor_assignment all')
+        masks = anchor_masks.split() if isinstance(anchor_masks, str) else list(anchor_masks)
+        if len(masks) != 3:
+            raise ValueError('--anchor_masks takes three comma-separated index lists (stride 32, 16, 8), e.g. "6,7,8 3,4,5 0,1,2"; got {!r}'
+                             .format(anchor_masks))
+        return 'scale'
+    return anchor_assignment or 'all'
+
+
+def resolve_anchor_scale(anchor_assignment, anchor_masks, anchors, output_folder=None, rank=0, anchors_file=None):
+    """The owner table of a run (one scale per anchor), or None for the reference's assignment of every anchor to every scale:
+    --anchor_masks, else the table an --anchors_file records, else yolo3.anchors.default_anchor_scales of the anchors.
+    With an output folder, rank 0 writes <out>/anchor_scales.json next to anchors.json."""
+    if check_anchor_assignment(anchor_assignment, anchor_masks) == 'all':
+        return None
+    from yolo3 import anchors as fitting
+    table = None
+    if anchor_masks is not None:
+        table = fitting.parse_anchor_masks(anchor_masks, len(anchors))
+    elif anchors_file is not None:
+        table = fitting.load_anchor_scale(anchors_file)
+    if table is None:
+        table = fitting.default_anchor_scales(anchors)
+    if output_folder is not None and rank == 0:
+        import json
+        with open(os.path.join(output_folder, 'anchor_scales.json'), 'w') as f:
+            json.dump(dict(anchors=[[float(w), float(h)] for w, h in anchors], anchor_scale=table, anchor_masks=fitting.scale_masks(table)), f,
+                      indent=1, sort_keys=True)
+            f.write('\n')
+    return table
+
+
 def describe_freeze(specs, freeze_layers, freeze_bn):
     """The line train_model prints about a fine-tuning run: how many layers and parameters are frozen and how many train."""
     count = lambda sp: sp.k * sp.k * sp.cin * sp.cout + sp.cout * (3 if sp.bn else 1)
@@ -352,8 +395,9 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
                 affine_min_visible=0.25, init_weights=None, init_optimizer=False, freeze_layers=0, freeze_bn=False, anchors=None, anchors_file=None,
                 auto_anchors=None, auto_anchors_evolve=1000, auto_anchors_seed=0, auto_anchors_device='cpu', photo_prob=0.0, photo_hue=0.015,
                 photo_saturation=0.7, photo_value=0.4, photo_gamma=0.0, photo_white=None, photo_seed=0, mixup_prob=0.0, mixup_spread=0.1,
-                mixup_seed=0):
+                mixup_seed=0, anchor_assignment=None, anchor_masks=None):
     check_anchor_flags(anchors, anchors_file, auto_anchors)
+    check_anchor_assignment(anchor_assignment, anchor_masks)
     spp_kw = dict(spp=True) if spp else {}
     from yolo3.model import check_freeze_args
     check_freeze_args(freeze_layers, freeze_bn)
@@ -404,6 +448,13 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     # the reference's pair unless a flag says otherwise; before the readers, which take the anchors and fork
     anchors = resolve_anchors(anchors, anchors_file, auto_anchors, train_database_filepath, output_folder, rank, auto_anchors_evolve,
                               auto_anchors_seed, auto_anchors_device)
+    # every anchor on every scale unless a flag gives each to one; the readers and the model take the same table
+    anchor_scale = resolve_anchor_scale(anchor_assignment, anchor_masks, anchors, output_folder, rank, anchors_file)
+    scale_reader_kw = dict(anchor_scale=anchor_scale) if anchor_scale is not None else {}
+    scale_model_kw = dict(anchor_scales=anchor_scale) if anchor_scale is not None else {}
+    if anchor_scale is not None and rank == 0:
+        print('Per-scale anchor assignment: anchors of stride 32 / 16 / 8 = {} (anchor_scales.json)'.format(
+            ' / '.join(','.join(str(i) for i, s in enumerate(anchor_scale) if s == t) for t in range(3))))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
     global_batch_size = batch_size * world
     local_world = int(os.environ.get('LOCAL_WORLD_SIZE', str(world)))
@@ -418,11 +469,12 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
     # one reader per rank: the unshuffled test reader takes this rank's stride of the key list (the reference splits one
     # global test batch over its replicas, train.py:64-66)
     test_reader = imagereader.ImageReader(test_database_filepath, anchors, use_augmentation=False, shuffle=False, num_workers=reader_count,
-                                          num_shards=world, shard_index=rank, augmentation_device=augmentation_device)
+                                          num_shards=world, shard_index=rank, augmentation_device=augmentation_device, **scale_reader_kw)
     print('Test Reader has {} images'.format(test_reader.get_image_count()))
     print('Setting up training image reader')
     train_reader = imagereader.ImageReader(train_database_filepath, anchors, use_augmentation=use_augmentation, shuffle=True,
                                            num_workers=reader_count, balance_classes=True, augmentation_device=augmentation_device,
+                                           **scale_reader_kw,
                                            **(dict(label_device='gpu') if train_sizes is not None or mosaic_prob or affine_prob or mixup_prob else {}),
                                            # (a shuffled reader ignores its shard when it picks keys; the mosaic, affine, photometric and
                                            # mixup draws are keyed by it)
@@ -489,7 +541,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         yolo = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate, ema_decay=ema_decay,
                             box_loss=box_loss, box_loss_weight=box_loss_weight, accumulate_steps=accumulate_steps,
                             grad_clip_norm=grad_clip_norm, **(dict(train_sizes=train_sizes) if train_sizes is not None else {}), **mask_args,
-                            **focal_kw, **spp_kw, **optim_kw, **(dict(lr_schedule=schedule) if schedule is not None else {}), **freeze_kw)
+                            **focal_kw, **spp_kw, **optim_kw, **(dict(lr_schedule=schedule) if schedule is not None else {}), **freeze_kw, **scale_model_kw)
         if init_weights:
             # every rank reads the same file, so the replicas start equal (the broadcast below then changes nothing)
             if init_optimizer:
@@ -702,7 +754,7 @@ def train_model(batch_size, test_every_n_steps, train_database_filepath, test_da
         print('Converting checkpoint into Saved_Model')
         from yolo3 import model
         best = model.YoloV3(global_batch_size, train_reader.get_image_size(), number_classes, anchors, learning_rate,
-                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw, **spp_kw, **optim_kw)
+                            box_loss=box_loss, box_loss_weight=box_loss_weight, **mask_args, **focal_kw, **spp_kw, **optim_kw, **scale_model_kw)
         best.load_weights(training_checkpoint_filepath)
         os.makedirs(os.path.join(output_folder, 'saved_model'), exist_ok=True)
         best.save_weights(os.path.join(output_folder, 'saved_model', 'yolov3.npz'))
@@ -938,6 +990,10 @@ class _Parser(argparse.ArgumentParser):
             check_anchor_flags(a.anchors, a.anchors_file, a.auto_anchors)
         except ValueError as e:
             self.error(str(e))
+        try:
+            check_anchor_assignment(a.anchor_assignment, a.anchor_masks)
+        except ValueError as e:
+            self.error(str(e))
         if a.auto_anchors is None and (a.auto_anchors_evolve != 1000 or a.auto_anchors_seed != 0 or a.auto_anchors_device != 'cpu'):
             self.error('--auto_anchors_evolve / --auto_anchors_seed / --auto_anchors_device need --auto_anchors K')
         try:
@@ -1124,6 +1180,14 @@ def build_parser():
     parser.add_argument('--auto_anchors_device', dest='auto_anchors_device', choices=('cpu', 'gpu'), default='cpu',
                         help='(addition) where --auto_anchors scores its candidates: cpu (in this process) or gpu (a child process running the '
                              'HIP kernel); the same anchors either way')
+    parser.add_argument('--anchor_assignment', dest='anchor_assignment', choices=('all', 'scale'), default=None,
+                        help='(addition) all (default): every anchor on every scale, the reference\'s network; scale: each anchor is owned by '
+                             'one scale as in YOLOv3 / Darknet (by area: the largest third on stride 32, the smallest on stride 8), a box is a '
+                             'positive only on the scale of its best anchor, and head s has A_s (5 + K) channels; needs at least 3 anchors; '
+                             'the weight files carry the table, <output_dir>/anchor_scales.json records it')
+    parser.add_argument('--anchor_masks', dest='anchor_masks', type=str, default=None, metavar='"I,.. I,.. I,.."',
+                        help='(addition) the anchors of stride 32, 16 and 8 as three comma-separated index lists, e.g. "6,7,8 3,4,5 0,1,2": a '
+                             'partition of the anchors with no empty part; implies --anchor_assignment scale')
     return parser
 
 
@@ -1144,4 +1208,4 @@ if __name__ == "__main__":
                 a.anchors, a.anchors_file, a.auto_anchors, a.auto_anchors_evolve, a.auto_anchors_seed, a.auto_anchors_device,
                 photo_prob=a.photo_prob, photo_hue=a.photo_hue, photo_saturation=a.photo_saturation, photo_value=a.photo_value,
                 photo_gamma=a.photo_gamma, photo_white=a.photo_white, photo_seed=a.photo_seed, mixup_prob=a.mixup_prob,
-                mixup_spread=a.mixup_spread, mixup_seed=a.mixup_seed)
+                mixup_spread=a.mixup_spread, mixup_seed=a.mixup_seed, anchor_assignment=a.anchor_assignment, anchor_masks=a.anchor_masks)

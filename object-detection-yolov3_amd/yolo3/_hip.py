@@ -166,6 +166,9 @@ SIGNATURES = {
     'y3_letterbox_unmap': (i32, [fp, i32, i32, i32, vp, i32, vp]),
     'y3_photometric_batch': (i32, [fp, i32, i32, i32, i32, vp, fp, vp]),     # records: HOST pointer (augment.PHOTO_RECORD)
     'y3_format_labels': (i32, [ip, ip, i32, i32, C.POINTER(C.c_float), i32, i32, i32, i32, fp, fp, fp, vp]),
+    'y3_format_labels_scales': (i32, [ip, ip, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_int), i32, i32, i32, i32, fp, fp, fp, vp]),   # table: HOST
+    'y3_decode_fwd_scales': (i32, [TP, C.POINTER(C.c_float), C.POINTER(C.c_int), i32, i32, i32, i32, fp, vp]),
+    'y3_truth_boxes_scales': (i32, [fp, fp, fp, i32, C.c_longlong, C.c_longlong, C.c_longlong, i32, fp, ip, i32, vp]),
     'y3_anchor_stats_workspace_bytes': (sz, [i32, i32]),
     'y3_anchor_stats': (i32, [ip, C.c_longlong, fp, i32, i32, i32, i32, vp, vp, vp, vp]),
     'y3_eval_offsets':(i32, [ip, i32, i32, i32, ip, vp]),

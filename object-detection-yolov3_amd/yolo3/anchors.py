@@ -351,8 +351,11 @@ def load_sizes_lmdb(path):
 
 # ---- files and flags -------------------------------------------------------------------------------------------------------------
 
-def save_anchors(path, fit):
-    """The dict fit_anchors returns, as JSON (settings and results only)."""
+def save_anchors(path, fit, anchor_scale=None):
+    """The dict fit_anchors returns, as JSON (settings and results only).  anchor_scale: an owner table to record beside it
+    (find_anchor_sizes.py --output records default_anchor_scales of its anchors); load_anchor_scale reads it back."""
+    if anchor_scale is not None:
+        fit = dict(fit, anchor_scale=check_anchor_scales(anchor_scale, len(fit['anchors'])))
     with open(path, 'w') as f:
         json.dump(fit, f, indent=1, sort_keys=True)
         f.write('\n')
@@ -365,7 +368,20 @@ def load_anchors(path):
     if not isinstance(fit, dict) or 'anchors' not in fit:
         raise ValueError('{}: not an anchors file (no "anchors" entry)'.format(path))
     fit['anchors'] = [list(a) for a in check_anchors(fit['anchors'])]
+    if 'anchor_scale' in fit:      # a file with the table reads like one without it; load_anchor_scale hands the table out
+        check_anchor_scales(fit.pop('anchor_scale'), len(fit['anchors']))
     return fit
+
+
+def load_anchor_scale(path):
+    """-> the owner table an anchors file records (checked against its anchors), or None for a file without one."""
+    with open(path) as f:
+        fit = json.load(f)
+    if not isinstance(fit, dict) or 'anchors' not in fit:
+        raise ValueError('{}: not an anchors file (no "anchors" entry)'.format(path))
+    if 'anchor_scale' not in fit:
+        return None
+    return check_anchor_scales(fit['anchor_scale'], len(check_anchors(fit['anchors'])))
 
 
 def check_anchors(anchors):
@@ -380,6 +396,97 @@ def check_anchors(anchors):
         if not (math.isfinite(w) and math.isfinite(h) and w > 0 and h > 0):
             raise ValueError('anchor sizes must be positive and finite, got {},{}'.format(w, h))
     return out
+
+
+# ---- per-scale anchor assignment -----------------------------------------------------------------------------------
+# An owner table anchor_scale[A] gives each anchor's scale: 0 = stride 32 (coarse), 1 = stride 16, 2 = stride 8 (fine).
+
+def default_anchor_scales(anchors):
+    """The owner table YOLOv3 / Darknet use: anchors ranked by area ascending (ties: the lower index first), the anchor of rank r
+    goes to scale 2 - (3 r) // A, so the smallest third sits on the fine grid.  Nine anchors give 3 / 3 / 3.  A < 3 raises."""
+    anchors = check_anchors(anchors)
+    A = len(anchors)
+    if A < 3:
+        raise ValueError('per-scale anchor assignment needs at least 3 anchors (one per scale), got {}'.format(A))
+    area = np.array([float(w) * float(h) for w, h in anchors], np.float64)
+    order = np.argsort(area, kind='stable')
+    table = [0] * A
+    for r, a in enumerate(order):
+        table[int(a)] = 2 - (3 * r) // A
+    return table
+
+
+def check_anchor_scales(table, A):
+    """-> [scale of anchor a] as ints; refuses a table of another length, entries outside 0..2 and a scale that owns no anchor."""
+    try:
+        out = [int(s) for s in table]
+        exact = all(float(s) == int(s) for s in table)
+    except (TypeError, ValueError):
+        raise ValueError('anchor_scale must be a list of integers, got {!r}'.format(table))
+    if not exact:
+        raise ValueError('anchor_scale must be a list of integers, got {!r}'.format(table))
+    if not 3 <= int(A) <= MAX_ANCHORS:
+        raise ValueError('per-scale anchor assignment needs 3..{} anchors, got {}'.format(MAX_ANCHORS, A))
+    if len(out) != int(A):
+        raise ValueError('anchor_scale has {} entries for {} anchors'.format(len(out), A))
+    if any(s not in (0, 1, 2) for s in out):
+        raise ValueError('anchor_scale entries must be 0 (stride 32), 1 (stride 16) or 2 (stride 8), got {!r}'.format(out))
+    for s in range(3):
+        if s not in out:
+            raise ValueError('scale {} owns no anchor in anchor_scale {!r}: every scale needs at least one'.format(s, out))
+    return out
+
+
+def parse_anchor_masks(masks, A):
+    """Explicit masks, coarse -> fine, e.g. [[6, 7, 8], [3, 4, 5], [0, 1, 2]] (or the flag's text '6,7,8 3,4,5 0,1,2') -> the owner
+    table.  The masks must partition 0..A-1 with no empty part."""
+    if isinstance(masks, str):
+        masks = masks.split()
+    masks = list(masks)
+    if len(masks) != 3:
+        raise ValueError('anchor masks are three index lists (stride 32, 16, 8), got {}'.format(len(masks)))
+    A = int(A)
+    table = [None] * A
+    for s, m in enumerate(masks):
+        if isinstance(m, str):
+            m = m.split(',')
+        try:
+            idx = [int(str(i).strip()) for i in m]      # '1.5' and 1.5 are refused, 3 and numpy integers pass
+        except (TypeError, ValueError):
+            raise ValueError('an anchor mask is a list of anchor indices, got {!r}'.format(m))
+        if not idx:
+            raise ValueError('anchor mask {} is empty: every scale needs at least one anchor'.format(s))
+        for i in idx:
+            if not 0 <= i < A:
+                raise ValueError('anchor index {} outside 0..{}'.format(i, A - 1))
+            if table[i] is not None:
+                raise ValueError('anchor {} appears in more than one mask'.format(i))
+            table[i] = s
+    missing = [i for i, s in enumerate(table) if s is None]
+    if missing:
+        raise ValueError('anchors {} appear in no mask'.format(missing))
+    return check_anchor_scales(table, A)
+
+
+def scale_masks(table):
+    """Owner table -> the three masks, coarse -> fine, each in index (= slot) order."""
+    return [[a for a, s in enumerate(table) if s == t] for t in range(3)]
+
+
+def resolve_anchor_scales(spec, anchors):
+    """What YoloV3(anchor_scales=...) and ImageReader(anchor_scale=...) accept -> owner table or None: None, 'auto' (the default
+    table), an owner table [A], or three masks."""
+    if spec is None:
+        return None
+    A = len(anchors)
+    if isinstance(spec, str):
+        if spec != 'auto':
+            raise ValueError("anchor_scales must be None, 'auto', an owner table or three index lists, got {!r}".format(spec))
+        return default_anchor_scales(anchors)
+    spec = list(spec)
+    if len(spec) == 3 and all(isinstance(m, (list, tuple, np.ndarray)) for m in spec):
+        return parse_anchor_masks(spec, A)
+    return check_anchor_scales(spec, A)
 
 
 def parse_anchor_args(args):

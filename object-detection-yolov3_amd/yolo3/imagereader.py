@@ -26,7 +26,8 @@ import traceback
 import numpy as np
 import torch
 
-from ._hip import lib, check, float_array
+from ._hip import lib, check, float_array, int_array
+from .anchors import check_anchor_scales
 from . import augment
 from . import lmdbio
 from .isg_ai_pb import ImageYoloBoxesPair
@@ -122,10 +123,10 @@ def photometric_device(x, records):
     return out
 
 
-def format_labels_device(boxes, counts, image_size, anchors, number_classes):
+def format_labels_device(boxes, counts, image_size, anchors, number_classes, anchor_scale=None):
     """y3_format_labels: boxes CUDA int32 [B, M, 5] (x, y, w, h, class; top-left corner; M may be 0), counts CUDA int32 [B] ->
     the three float32 label tensors [B, G, G, A, 5+K] of format_boxes (bit-identical per image), written completely by one
-    launch on the current stream."""
+    launch on the current stream.  anchor_scale (an owner table [A]): y3_format_labels_scales, [B, G, G, A_s, 5+K]."""
     assert boxes.is_cuda and boxes.dtype == torch.int32 and boxes.dim() == 3 and boxes.shape[2] == 5, (boxes.dtype, tuple(boxes.shape))
     assert counts.is_cuda and counts.dtype == torch.int32 and counts.shape == (boxes.shape[0],), (counts.dtype, tuple(counts.shape))
     boxes, counts = boxes.contiguous(), counts.contiguous()
@@ -133,9 +134,15 @@ def format_labels_device(boxes, counts, image_size, anchors, number_classes):
     h, w = int(image_size[0]), int(image_size[1])
     a, k = len(anchors), int(number_classes)
     f = NETWORK_DOWNSAMPLE_FACTOR
-    out = [torch.empty((b, h // (f >> s), w // (f >> s), a, 5 + k), dtype=torch.float32, device=boxes.device) for s in range(3)]
     anchors_c = float_array([float(v) for an in anchors for v in an])
     st = torch.cuda.current_stream(boxes.device).cuda_stream
+    if anchor_scale is not None:
+        owner = check_anchor_scales(anchor_scale, a)
+        out = [torch.empty((b, h // (f >> s), w // (f >> s), owner.count(s), 5 + k), dtype=torch.float32, device=boxes.device) for s in range(3)]
+        check(lib.y3_format_labels_scales(boxes.data_ptr() if m else None, counts.data_ptr(), b, m, anchors_c, int_array(owner), a, k, h, w,
+                                          out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st), 'y3_format_labels_scales')
+        return out
+    out = [torch.empty((b, h // (f >> s), w // (f >> s), a, 5 + k), dtype=torch.float32, device=boxes.device) for s in range(3)]
     check(lib.y3_format_labels(boxes.data_ptr() if m else None, counts.data_ptr(), b, m, anchors_c, a, k, h, w,
                                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st), 'y3_format_labels')
     return out
@@ -171,13 +178,19 @@ def format_image(image_data):
     return np.transpose(image_data, [2, 0, 1])
 
 
-def format_boxes(boxes, image_size, anchors, number_classes):
+def format_boxes(boxes, image_size, anchors, number_classes, anchor_scale=None):
     """ImageReader.__format_boxes (imagereader.py:252-324).
 
     boxes [n,5] = [x, y, w, h, class] with (x, y) the top-left corner.  Returns
     three float32 label tensors [G, G, A, 5+K] (G = size/32, /16, /8).  The box
     centre is floor(xy + (wh-1)/2); the best anchor (IoU of co-centred w,h) is
-    written at the SAME anchor slot of all three scales (Q5)."""
+    written at the SAME anchor slot of all three scales (Q5).
+
+    anchor_scale (addition): an owner table [A] of scales 0..2 gives [G, G, A_s, 5+K] instead: the box goes only to
+    the scale that owns its best anchor (still the best of ALL anchors), at that anchor's slot (its rank among the scale's
+    anchors).  None runs the reference's code."""
+    if anchor_scale is not None:
+        return _format_boxes_scales(boxes, image_size, anchors, number_classes, anchor_scale)
     anchors = np.asarray(anchors, dtype=np.float32)
     num_anchors = len(anchors)
     f = NETWORK_DOWNSAMPLE_FACTOR
@@ -203,6 +216,39 @@ def format_boxes(boxes, image_size, anchors, number_classes):
             label[l][i, j, n, 0:4] = boxes[t, 0:4]
             label[l][i, j, n, 4] = 1.0
             label[l][i, j, n, 5 + c] = 1.0
+    return label
+
+
+def _format_boxes_scales(boxes, image_size, anchors, number_classes, anchor_scale):
+    """format_boxes with every anchor owned by one scale: the same float32 arithmetic, line for line; only the scale loop and the
+    slot differ."""
+    anchors = np.asarray(anchors, dtype=np.float32)
+    owner = check_anchor_scales(anchor_scale, len(anchors))
+    slot = [owner[:a].count(owner[a]) for a in range(len(owner))]
+    f = NETWORK_DOWNSAMPLE_FACTOR
+    grid_sizes = [(int(image_size[0] / f), int(image_size[1] / f)),
+                  (int(image_size[0] / (f / 2)), int(image_size[1] / (f / 2))),
+                  (int(image_size[0] / (f / 4)), int(image_size[1] / (f / 4)))]
+    label = [np.zeros((g[0], g[1], owner.count(l), 5 + number_classes), dtype=np.float32) for l, g in enumerate(grid_sizes)]
+    if boxes is None or boxes.shape[0] == 0:
+        return label
+    boxes = boxes.astype(np.float32)
+    box_wh = boxes[:, 2:4]
+    boxes[:, 0:2] = np.floor(boxes[:, 0:2] + ((box_wh - 1) / 2.0))
+    wh = np.expand_dims(box_wh, -2)
+    inter_wh = np.maximum(np.minimum(wh / 2.0, anchors / 2.0) - np.maximum(-wh / 2.0, -anchors / 2.0), 0.0)
+    inter = inter_wh[..., 0] * inter_wh[..., 1]
+    iou = inter / (wh[..., 0] * wh[..., 1] + anchors[:, 0] * anchors[:, 1] - inter)
+    best_anchor = np.argmax(iou, axis=-1)
+    for t, n in enumerate(best_anchor):
+        l = owner[n]
+        g = grid_sizes[l]
+        i = np.floor(boxes[t, 1] / image_size[0] * g[0]).astype('int32')
+        j = np.floor(boxes[t, 0] / image_size[1] * g[1]).astype('int32')
+        c = boxes[t, 4].astype('int32')
+        label[l][i, j, slot[n], 0:4] = boxes[t, 0:4]
+        label[l][i, j, slot[n], 4] = 1.0
+        label[l][i, j, slot[n], 5 + c] = 1.0
     return label
 
 
@@ -413,7 +459,7 @@ class Dataset:
                 boxes, counts = collate_boxes(augment.mixup_boxes([b[i, :c[i]] for i in range(len(c))], photo))
         as_t =lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True)
         labels = format_labels_device(as_t(boxes), as_t(counts), (size[0], size[1], self.reader.image_size[2]), self.reader.anchors,
-                                      self.reader.number_classes)
+                                      self.reader.number_classes, **getattr(self.reader, '_label_kw', {}))
         imgs = augment_device(imgs, records, size)
         if mosaic is not None:
             imgs = mosaic_device(imgs, mosaic)
@@ -558,7 +604,7 @@ class ImageReader:
     get_number_classes / get_image_count / get_example / generator; get_tf_dataset() returns a ``Dataset``."""
 
     def __init__(self, img_db, anchors, use_augmentation=True, balance_classes=False, shuffle=True, num_workers=1, num_shards=1, shard_index=0,
-                 augmentation_device='cpu', label_device='cpu'):
+                 augmentation_device='cpu', label_device='cpu', anchor_scale=None):
         """num_shards / shard_index (addition): with one process per GPU every rank owns a reader; an unshuffled reader
         (the test set) then serves every num_shards-th stride of the key list, so the ranks evaluate disjoint images like
         the replicas of the reference's one distributed test batch.
@@ -567,7 +613,9 @@ class ImageReader:
         the stored pixels, which the batches then augment on the device (augment_device, csrc/augment.hip).
         label_device (addition): 'cpu' builds the three label tensors in the worker processes (format_boxes, the reference's
         design); 'gpu' (needs augmentation_device='gpu') has the workers hand out the transformed boxes, [k, 5] int32, and the
-        batches build the labels on the device (format_labels_device): the same tensors, a few dozen boxes over PCIe instead."""
+        batches build the labels on the device (format_labels_device): the same tensors, a few dozen boxes over PCIe instead.
+        anchor_scale (addition): an owner table [A] (yolo3.anchors.default_anchor_scales / parse_anchor_masks); the
+        label builder in use, host or device, then writes [G, G, A_s, 5+K] tensors.  None: the reference's labels."""
         assert augmentation_device in ('cpu', 'gpu'), augmentation_device
         if label_device not in ('cpu', 'gpu'):
             raise ValueError("label_device must be 'cpu' or 'gpu', got {!r}".format(label_device))
@@ -583,6 +631,8 @@ class ImageReader:
         self.balance_classes = balance_classes
         self.anchors = anchors
         self.number_anchors = len(anchors)
+        self.anchor_scale = None if anchor_scale is None else check_anchor_scales(anchor_scale, len(anchors))
+        self._label_kw = {} if self.anchor_scale is None else {'anchor_scale': self.anchor_scale}
         if not os.path.exists(self.image_db):
             print('Could not load database file: ')
             print(self.image_db)
@@ -704,14 +754,14 @@ class ImageReader:
             if self.label_device == 'gpu':
                 boxes = np.zeros((0, 5), np.int32) if boxes is None else np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 5)
                 return (np.ascontiguousarray(img), boxes, rec)
-            labels = format_boxes(boxes, self.image_size, self.anchors, self.number_classes)
+            labels = format_boxes(boxes, self.image_size, self.anchors, self.number_classes, **self._label_kw)
             return (np.ascontiguousarray(img), labels[0], labels[1], labels[2], rec)
         if self.use_augmentation:                               # severities of imagereader.py:369-391
             img, boxes = augment.augment_image_box_pair(img.astype(np.float32), boxes, crop_to=crop_to, **TRAIN_AUGMENTATION)
         if img.shape[0] != self.image_size[0] or img.shape[1] != self.image_size[1]:
             img, boxes = augment.crop_to_size(img, boxes, crop_to)
         img = np.ascontiguousarray(format_image(img)).astype(np.float32)
-        labels = format_boxes(boxes, self.image_size, self.anchors, self.number_classes)
+        labels = format_boxes(boxes, self.image_size, self.anchors, self.number_classes, **self._label_kw)
         return (img, labels[0], labels[1], labels[2])
 
     def _image_loader(self, worker_id):
@@ -757,7 +807,7 @@ class ImageReader:
             img = zscore_normalize_device(augment_device(src, example[2], self.image_size[:2]))[0].cpu().numpy()
             boxes, counts = collate_boxes([example[1]])
             labels = format_labels_device(torch.from_numpy(boxes).cuda(), torch.from_numpy(counts).cuda(), self.image_size, self.anchors,
-                                          self.number_classes)
+                                          self.number_classes, **self._label_kw)
             return (img,) + tuple(l[0].cpu().numpy() for l in labels)
         if self.augmentation_device == 'gpu':                  # a batch of one through the device path
             src = torch.from_numpy(example[0][None]).cuda()

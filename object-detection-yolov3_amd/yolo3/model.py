@@ -25,6 +25,7 @@ import torch
 from . import _hip
 from . import letterbox
 from . import streams
+from .anchors import resolve_anchor_scales, scale_masks
 from ._hip import lib, check, view, int_array, EPI_LRELU, EPI_ACCUM, CONV_X3, BF16_NO_PATCH
 
 BN_EPS = 1e-3          # Keras BatchNormalization defaults
@@ -247,11 +248,12 @@ class LayerSpec:
     __slots__ = ('cin', 'cin_pad', 'cout', 'k', 's', 'bn', 'w_off', 'b_off', 'g_off', 'be_off', 'end_off', 'bn_idx', 'ch_off', 'mv_off')
 
 
-def build_layer_specs(in_channels, num_anchors, num_classes, spp=False):
+def build_layer_specs(in_channels, num_anchors, num_classes, spp=False, head_anchors=None):
     """Conv layers in Keras creation order (model.py:356-421); see the walk in
     ``_Plan._build`` which consumes them in the same order.  spp: the YOLOv3-SPP variant, one more 1x1 layer
     (4 * 512 -> 512) behind the third layer of the coarsest scale's block; everything else, and with spp off every offset, is
-    the reference's network."""
+    the reference's network.  head_anchors: the anchors per head, coarse -> fine (per-scale anchor assignment):
+    head s has A_s * (5 + K) output channels; None gives every head all num_anchors, and every offset is the reference's."""
     L = []
 
     def conv(cin, cout, k, s=1, bn=True):
@@ -279,7 +281,11 @@ def build_layer_specs(in_channels, num_anchors, num_classes, spp=False):
     c = feature_block(c, YoloV3.BLOCK_COUNT)
     c = conv(c, FC, 3, 2)
     c = feature_block(c, YoloV3.BLOCK_COUNT // 2)
-    D = num_anchors * (5 + num_classes)
+    if head_anchors is None:
+        head_anchors = [num_anchors] * 3
+    if len(head_anchors) != 3 or any(int(a) < 1 for a in head_anchors):
+        raise ValueError('head_anchors must be three counts >= 1 (coarse -> fine), got {!r}'.format(head_anchors))
+    D = [int(a) * (5 + num_classes) for a in head_anchors]
 
     def yolo_block(cin, fc, spp=False):
         for i in range(3):
@@ -289,13 +295,13 @@ def build_layer_specs(in_channels, num_anchors, num_classes, spp=False):
             conv(fc // 2, fc, 3)
 
     yolo_block(FC, FC, spp)
-    conv(FC, D, 1, 1, bn=False)
+    conv(FC, D[0], 1, 1, bn=False)
     conv(FC // 2, FC // 2, 1)
     yolo_block(FC, FC // 2)
-    conv(FC // 2, D, 1, 1, bn=False)
+    conv(FC // 2, D[1], 1, 1, bn=False)
     conv(FC // 4, FC // 4, 1)
     yolo_block(FC // 2, FC // 4)
-    conv(FC // 4, D, 1, 1, bn=False)
+    conv(FC // 4, D[2], 1, 1, bn=False)
     # arena offsets (floats)
     off = 0
     bn_idx = 0
@@ -511,8 +517,10 @@ class _Plan:
         N = self.n
         (H, W), C = self.size, mdl.img_size[2]
         A, K = mdl.number_anchors, mdl.number_classes
-        D = A * (5 + K)
-        Dld = _round_up(D, 4)
+        # anchors per scale: all of them on every scale unless the model has an owner table
+        As = mdl.scale_anchor_counts
+        Ds = [a * (5 + K) for a in As]
+        Dlds = [_round_up(d, 4) for d in Ds]
         specs = mdl.specs
         P = mdl.params
         tr = self.training
@@ -535,7 +543,7 @@ class _Plan:
 
         # shared workspaces.  The largest M*Cout of the net is conv1's (full resolution, FILTER_COUNT/32
         # channels); BN partial statistics need <= 2*Cout floats per row tile of >= 64 rows.
-        max_mc = N * H * W * max(YoloV3.FILTER_COUNT // 32, Dld)
+        max_mc = N * H * W * max(YoloV3.FILTER_COUNT // 32, max(Dlds))
         self.stats_ws = torch.empty(max_mc // 16 + 8192, dtype=torch.float32, device=dev)
         # split-K slabs of the small-spatial layers (y3_conv2d_fwd_workspace / _dgrad_workspace); 64 MiB covers every layer
         # of the 416 / 608 configurations, the exact need is checked per layer below
@@ -655,7 +663,7 @@ class _Plan:
             i = li[0]
             li[0] += 1
             sp = specs[i]
-            fm = self._new(N, src.h, src.w, D, Dld, zero=True)
+            fm = self._new(N, src.h, src.w, Ds[g], Dlds[g], zero=True)
             if bf:      # bf16 operands, fp32 feature map: decode / loss / NMS stay fp32
                 self._conv_call(self.fwd, lib.y3_conv2d_fwd_bf16_ws, src.v, self._at(mdl.params_t_bf16, sp.w_off), ptr(sp.b_off), 1, 1, fm.v, 1, 0, 0.0,
                                 None, None, None)
@@ -704,13 +712,16 @@ class _Plan:
         self.fms = [fm1, fm2, fm3]
 
         # decode (model.py:169-212)
-        self.nb = sum(f.h * f.w * A for f in self.fms)
+        self.nb = sum(f.h * f.w * a for f, a in zip(self.fms, As))
         self.boxes = torch.empty(N, self.nb, 5 + K, dtype=torch.float32, device=dev)
         self.fm_arr = (_hip.Tensor * 3)(*[f.v for f in self.fms])
-        self.decode_call = (lib.y3_decode_fwd, (self.fm_arr, 3, mdl.anchors_c, A, K, H, W, self.boxes.data_ptr()))
+        if mdl.anchor_scale is None:
+            self.decode_call = (lib.y3_decode_fwd, (self.fm_arr, 3, mdl.anchors_c, A, K, H, W, self.boxes.data_ptr()))
+        else:      # rows coarse -> fine, then row, column, slot; each with its own anchor
+            self.decode_call = (lib.y3_decode_fwd_scales, (self.fm_arr, mdl.anchors_c, mdl.anchor_scale_c, A, K, H, W, self.boxes.data_ptr()))
 
         # loss (model.py:214-354): always available (test_step needs it in inference mode too)
-        self.gt = [torch.zeros(N, f.h, f.w, A, 5 + K, dtype=torch.float32, device=dev) for f in self.fms]
+        self.gt = [torch.zeros(N, f.h, f.w, a, 5 + K, dtype=torch.float32, device=dev) for f, a in zip(self.fms, As)]
         self.loss4 = torch.zeros(4, dtype=torch.float32, device=dev)
         # one workspace PER SCALE (anchor-present flags + block partials): the three calls of a step then share no word that one
         # clears while another has set or reads it (round 3: a shared flag array cleared by a memset node was mis-ordered in a replayed graph)
@@ -727,34 +738,40 @@ class _Plan:
             self.truth_counts = torch.zeros(N, dtype=torch.int32, device=dev)
             self.ignored = torch.zeros(1, dtype=torch.float32, device=dev)
             fine, gfine = self.fms[-1], self.gt[-1]
-            self.truth_call = (lib.y3_truth_boxes, (gfine.data_ptr(), N, fine.h * fine.w * A, 5 + K, self.truth_boxes.data_ptr(),
-                                                    self.truth_counts.data_ptr(), cap))
+            if mdl.anchor_scale is None:
+                self.truth_call = (lib.y3_truth_boxes, (gfine.data_ptr(), N, fine.h * fine.w * A, 5 + K, self.truth_boxes.data_ptr(),
+                                                        self.truth_counts.data_ptr(), cap))
+            else:      # a box lives on one scale only: the list is gathered from all three label tensors, coarse -> fine
+                self.truth_call = (lib.y3_truth_boxes_scales, tuple(g.data_ptr() for g in self.gt) + (N,) +
+                                   tuple(f.h * f.w * a for f, a in zip(self.fms, As)) +
+                                   (5 + K, self.truth_boxes.data_ptr(), self.truth_counts.data_ptr(), cap))
             ws_floats = (int(lib.y3_loss_truth_workspace_bytes(N)) // 4 + 63) // 64 * 64
             self.loss_ws = torch.zeros(3 * ws_floats, dtype=torch.float32, device=dev)
         focal = mdl.focal_args()                 # None: no focal setting, the call list of a model built without one
         for si, (f, g) in enumerate(zip(self.fms, self.gt)):
-            f.grad = self._new(N, f.h, f.w, D, Dld, zero=True)
+            f.grad = self._new(N, f.h, f.w, Ds[si], Dlds[si], zero=True)
+            anc, As_i = mdl.scale_anchors_c[si], As[si]      # this scale's anchors in slot order (all of them without a table)
             ws = self._at(self.loss_ws, si * ws_floats)
             if focal is not None:
                 # focal objectness / class terms and label smoothing over either mask: null lists select the reference's
                 truth = mdl.ignore_mask == 'truth'
-                self.loss_calls.append((lib.y3_loss_fwd_bwd_focal, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                self.loss_calls.append((lib.y3_loss_fwd_bwd_focal, (f.v, g.data_ptr(), anc, As_i, K, H, W, float(mdl.global_batch_size),
                                                                     BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
                                                                     self.truth_boxes.data_ptr() if truth else None,
                                                                     self.truth_counts.data_ptr() if truth else None,
                                                                     cap if truth else 1, mdl.ignore_thresh, self.loss4.data_ptr(),
                                                                     self.ignored.data_ptr() if truth else None, f.grad.v, ws) + focal))
             elif mdl.ignore_mask == 'truth':
-                self.loss_calls.append((lib.y3_loss_fwd_bwd_truth, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                self.loss_calls.append((lib.y3_loss_fwd_bwd_truth, (f.v, g.data_ptr(), anc, As_i, K, H, W, float(mdl.global_batch_size),
                                                                     BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
                                                                     self.truth_boxes.data_ptr(), self.truth_counts.data_ptr(), cap,
                                                                     mdl.ignore_thresh, self.loss4.data_ptr(), self.ignored.data_ptr(),
                                                                     f.grad.v, ws)))
             elif mdl.box_loss == 'mse':    # the reference's loss: the call list of a model built without box-loss arguments
-                self.loss_calls.append((lib.y3_loss_fwd_bwd, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                self.loss_calls.append((lib.y3_loss_fwd_bwd, (f.v, g.data_ptr(), anc, As_i, K, H, W, float(mdl.global_batch_size),
                                                               self.loss4.data_ptr(), f.grad.v, ws)))
             else:                        # IoU box term in loss4[0], loss4[1] stays 0
-                self.loss_calls.append((lib.y3_loss_fwd_bwd_ex, (f.v, g.data_ptr(), mdl.anchors_c, A, K, H, W, float(mdl.global_batch_size),
+                self.loss_calls.append((lib.y3_loss_fwd_bwd_ex, (f.v, g.data_ptr(), anc, As_i, K, H, W, float(mdl.global_batch_size),
                                                                  BOX_LOSSES.index(mdl.box_loss), mdl.box_loss_weight,
                                                                  self.loss4.data_ptr(), f.grad.v, ws)))
             f.gw = True
@@ -983,7 +1000,7 @@ class _Plan:
 
     def run_decode(self, stream):
         fn, args = self.decode_call
-        check(fn(*args, stream), 'y3_decode_fwd')
+        check(fn(*args, stream), fn.__name__)
 
     def run_inference(self, stream, skip_input=False):
         self.run_forward(stream, skip_input)
@@ -995,7 +1012,7 @@ class _Plan:
         if self.truth_call is not None:
             check(lib.y3_fill(self.ignored.data_ptr(), 1, 0.0, stream), 'y3_fill')
             fn, args = self.truth_call
-            check(fn(*args, stream), 'y3_truth_boxes')
+            check(fn(*args, stream), fn.__name__)
         for fn, args in self.loss_calls:
             check(fn(*args, stream), fn.__name__)
 
@@ -1044,9 +1061,15 @@ class YoloV3:
                  box_loss='mse', box_loss_weight=1.0, accumulate_steps=1, grad_clip_norm=None, train_sizes=None,
                  ignore_mask='reference', ignore_thresh=DEFAULT_IGNORE_THRESH, max_truth_boxes=DEFAULT_MAX_TRUTH_BOXES,
                  focal_gamma=0.0, focal_alpha=0.0, focal_terms='both', label_smoothing=0.0, spp=False, optimizer='adam', momentum=0.9,
-                 nesterov=False, weight_decay=0.0, lr_schedule=None, freeze_layers=0, freeze_bn=False):
+                 nesterov=False, weight_decay=0.0, lr_schedule=None, freeze_layers=0, freeze_bn=False, anchor_scales=None):
         """freeze_layers / freeze_bn are settings of a training run, not of the network: save_weights does not
-        record them (inference does not care), from_file builds a model without them, and every run names them again."""
+        record them (inference does not care), from_file builds a model without them, and every run names them again.
+        anchor_scales: None = every anchor on every scale, the reference's network; 'auto'
+        (anchors.default_anchor_scales), an owner table [A] or three index lists coarse -> fine give each anchor to one scale:
+        head s has A_s (5 + K) channels and the labels are [N, G, G, A_s, 5+K].  Part of the network: weight files record it."""
+        # per-scale anchor assignment: checked before the device is needed
+        given = [(32, 32), (128, 128), (256, 256)] if anchors is None else [tuple(a) for a in anchors]
+        self.anchor_scale = resolve_anchor_scales(anchor_scales, given)
         # the optimiser (DESIGN §3.19): 'adam' without decay = the reference's Keras Adam and its launches; 'adamw' / 'sgd' run
         # y3_optim_step; lr_schedule: None or an object with factor(t) (schedule.LrSchedule); checked before the device is needed
         check_optimizer_args(optimizer, momentum, nesterov, weight_decay, lr_schedule)
@@ -1062,8 +1085,7 @@ class YoloV3:
         # fine-tuning: layers 0 .. freeze_layers - 1 are not trainable (Keras layer.trainable = False, BatchNorm
         # included: they run as in inference); freeze_bn: the BatchNorm of the trainable layers normalises with the moving
         # statistics, which then stay.  0 / False = every layer trains, today's launches; checked before the device is needed
-        check_freeze_args(freeze_layers, freeze_bn, len(build_layer_specs(int(img_size[2]), 3 if anchors is None else len(anchors),
-                                                                          int(number_classes), self.spp)[0]))
+        check_freeze_args(freeze_layers, freeze_bn, len(build_layer_specs(int(img_size[2]), len(given), int(number_classes), self.spp)[0]))
         self.freeze_layers = int(freeze_layers)
         self.freeze_bn = bool(freeze_bn)
         # input sizes train_step / test_step accept: None = img_size only; checked before the device is needed
@@ -1110,15 +1132,28 @@ class YoloV3:
         self.anchors = [(32, 32), (128, 128), (256, 256)] if anchors is None else [tuple(a) for a in anchors]
         self.number_anchors = len(self.anchors)
         self.anchors_c = _hip.float_array([v for a in self.anchors for v in a])
+        # what each scale's loss call and head see: all anchors, or with an owner table the anchors the scale owns, in slot order
+        if self.anchor_scale is None:
+            self.anchor_scale_c = None
+            self.scale_anchor_counts = [self.number_anchors] * 3
+            self.scale_anchors_c = [self.anchors_c] * 3
+        else:
+            self.anchor_scale_c = _hip.int_array(self.anchor_scale)
+            masks = scale_masks(self.anchor_scale)
+            self.scale_anchor_counts = [len(m) for m in masks]
+            self.scale_anchors_c = [_hip.float_array([v for a in m for v in self.anchors[a]]) for m in masks]
         H, W, C = self.img_size
         f = YoloV3.NETWORK_DOWNSAMPLE_FACTOR
         self.box_count_fm1 = (H / f) * (W / f)
         self.box_count_fm2 = (H / (f / 2)) * (W / (f / 2))
         self.box_count_fm3 = (H / (f / 4)) * (W / (f / 4))
         self.number_output_boxes = self.number_anchors * (self.box_count_fm1 + self.box_count_fm2 + self.box_count_fm3)
+        if self.anchor_scale is not None:
+            self.number_output_boxes = sum(a * c for a, c in zip(self.scale_anchor_counts, (self.box_count_fm1, self.box_count_fm2, self.box_count_fm3)))
         self.output_shape = [self.number_output_boxes, 5 + self.number_classes]
 
-        self.specs, self.arena_floats, chan_floats, self.moving_stride = build_layer_specs(C, self.number_anchors, self.number_classes, self.spp)
+        self.specs, self.arena_floats, chan_floats, self.moving_stride = build_layer_specs(
+            C, self.number_anchors, self.number_classes, self.spp, None if self.anchor_scale is None else self.scale_anchor_counts)
         # the part of the arenas a step touches: everything with no layer frozen (trainable_suffix)
         self.train_off, self.train_floats = trainable_suffix(self.specs, self.arena_floats, self.freeze_layers)
         dev = self.device
@@ -1362,6 +1397,8 @@ class YoloV3:
             flat['meta_focal_terms'] = np.asarray(self.focal_terms)
         if self.spp:                              # likewise: a file of the reference's network has no such entry
             flat['meta_spp'] = np.asarray(1, np.int64)
+        if getattr(self, 'anchor_scale', None) is not None:       # likewise: the owner table, one scale per anchor
+            flat['meta_anchor_scale'] = np.asarray(self.anchor_scale, np.int64)
         if getattr(self, 'optimizer_kind', 'adam') != 'adam':       # likewise: a file of the reference's Adam has no such entry
             flat['meta_optimizer'] = np.asarray(self.optimizer_kind)
             flat['meta_optimizer_args'] = np.asarray([self.momentum, float(self.nesterov), self.weight_decay], np.float64)
@@ -1396,6 +1433,10 @@ class YoloV3:
                              'transfer=True loads a plain file into an SPP model)'.format(path, theirs, self.spp))
         else:
             mapping = list(range(len(self.specs)))
+        mine_scale = getattr(self, 'anchor_scale', None)
+        if YoloV3._anchor_scale_meta(z) != mine_scale:
+            raise ValueError('load_weights: {} was written with anchor_scale {}, this model has {} (None: every anchor on every scale); '
+                             'the heads differ'.format(path, YoloV3._anchor_scale_meta(z), mine_scale))
         mine = dict(focal_gamma=self.focal_gamma, focal_alpha=self.focal_alpha, focal_terms=self.focal_terms,
                     label_smoothing=self.label_smoothing) if self.focal_args() is not None else {}
         if YoloV3._focal_meta(z) != mine:          # the weights load all the same; the losses of the two settings are not comparable
@@ -1462,13 +1503,18 @@ class YoloV3:
         return bool(int(z['meta_spp'])) if 'meta_spp' in z else False
 
     @staticmethod
+    def _anchor_scale_meta(z):
+        """The owner table a weight file carries (save_weights); None for a file without one: every anchor on every scale."""
+        return [int(v) for v in z['meta_anchor_scale']] if 'meta_anchor_scale' in z else None
+
+    @staticmethod
     def from_file(path, device=None, lr_schedule=None):
         """The model a weight file describes, with its weights.  The file records the network, the focal setting and the optimiser;
         the learning-rate schedule is the caller's to pass, like box_loss to the constructor."""
         z = np.load(path, allow_pickle=False)
         y = YoloV3(int(z['meta_global_batch_size']), [int(v) for v in z['meta_img_size']], int(z['meta_number_classes']),
                    [tuple(float(v) for v in a) for a in z['meta_anchors']], float(z['meta_learning_rate']), device=device, spp=YoloV3._spp_meta(z), **YoloV3._focal_meta(z),
-                   **YoloV3._optimizer_meta(z), lr_schedule=lr_schedule)
+                   **YoloV3._optimizer_meta(z), lr_schedule=lr_schedule, anchor_scales=YoloV3._anchor_scale_meta(z))
         y.load_weights(path)
         return y
 
